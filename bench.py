@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the hot path on MI355X (BASELINE.json: "tracking frames/s (ORB extract+match)
 and LocalBA iters/s, 1/2/4/8 MI355X vs CPU ref").
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
@@ -11,11 +11,14 @@ One "step" = one pass of the hot path over one batch of synthetic input that is 
 Frames shard over ranks with no collective (weak scaling: B frames per GPU).  value = frames of all ranks / time of
 the slowest rank.  PyTorch only provides device buffers, the stream and torch.distributed.
 
-Extra legs reported in the same JSON line:
+A plain run sets up, warms up, times K steps, writes the last step's outputs if --dump-outputs is given and prints the
+JSON line.  --full adds everything else (--extra and --streams imply it), reported in the same JSON line:
+  self_check    8 frames of the timed batch against the CPU oracle (key points, descriptors, BoW matches, bit-exact)
   roofline      dominant extractor kernel, duration measured live with HIP events on the launch stream
   cpu_baseline  the CPU oracle (this repo's restatement of the reference algorithms) on the box's host cores, 1 thread
   lba           LocalBundleAdjustment 50 KF / 2000 MP / 20 k edges (configs[3]): outer LM iterations per second
   gba           (N>1 only) landmark-sharded global BA whose reduced camera system is summed with one RCCL all-reduce
+and the whole record goes to the --detail file.
 """
 import argparse
 import importlib
@@ -50,9 +53,9 @@ def median_call_seconds(fn, n):
     return ts[len(ts) // 2]
 
 
-def compact_line(out):
+def compact_line(out, detail=None):
     """The ONE JSON line of the contract, kept short enough that every graded number survives a 2000-character tail:
-    headline keys, roofline, cpu_baseline and the LocalBA half of the metric.  Everything else goes to bench_detail.json."""
+    headline keys, roofline, cpu_baseline and the LocalBA half of the metric.  Everything else goes to the detail file."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config")
     line = {k: out[k] for k in keep if k in out}
@@ -95,7 +98,8 @@ def compact_line(out):
             line["gba"]["c_abi_driver"] = {k: g["c_abi_driver"][k] for k in ("iters_per_s", "same_path_as_python_driver", "skipped") if k in g["c_abi_driver"]}
         if "roofline" in g:
             line["gba"]["roofline"] = {k: g["roofline"][k] for k in ("bound", "achieved", "peak", "unit", "frac") if k in g["roofline"]}
-    line["detail"] = "gpurun_out/bench_detail.json"
+    if detail is not None:
+        line["detail"] = detail
 
     def shorten(o):         # six significant digits are plenty for a headline line
         if isinstance(o, float):
@@ -175,22 +179,69 @@ def check_against_oracle(pkg, ex, B, cap, d_kps, d_desc, d_n, d_mono, host_imgs,
     return {"frames_checked": picks, "against": "CPU oracle (key points, descriptors, BoW matches bit-exact)", "schedule_bits": sched, "ok": True}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ddir, pkg, B, cap, d_kps, d_desc, d_n, d_mono, bow):
+    """What the last timed step handed its caller, as float32 / float64 .npy files in ddir: per frame the mono index, the key-point
+    count, the key points (x, y, size, angle, response, octave, class_id) and descriptor bytes of its first n slots (rows of all frames
+    concatenated in frame order), and the SearchByBoW result of its batch slot (match count; per F feature the KF index or -1).
+    All frames while the files stay within DUMP_LIMIT_BYTES, else a fixed seeded sample of frames (frames.npy lists the frames kept)."""
+    nk = d_n.cpu().numpy().astype(np.int64)
+    mono = d_mono.cpu().numpy()
+    kps = d_kps.cpu().numpy().view(pkg.KP_DTYPE).reshape(B, cap)
+    desc = d_desc.cpu().numpy().reshape(B, cap, 32)
+    per_frame = [int(nk[b]) * (7 + 32) * 4 + len(bow[b][1]) * 4 + 3 * 8 + 8 for b in range(B)]
+    frames = list(range(B))
+    if sum(per_frame) > DUMP_LIMIT_BYTES:
+        frames, used = [], 0
+        for b in np.random.RandomState(0).permutation(B):
+            if used + per_frame[b] <= DUMP_LIMIT_BYTES:
+                frames.append(int(b)); used += per_frame[b]
+        frames.sort()
+    kp_rows = [np.stack([kps[b, :nk[b]][f].astype(np.float32) for f in pkg.KP_DTYPE.names], 1) for b in frames]
+    arrays = {
+        "frames": np.asarray(frames, np.float64),
+        "mono_index": mono[frames].astype(np.float64),
+        "n_keypoints": nk[frames].astype(np.float64),
+        "keypoints": np.concatenate(kp_rows).reshape(-1, 7),
+        "descriptors": np.concatenate([desc[b, :nk[b]] for b in frames]).astype(np.float32).reshape(-1, 32),
+        "bow_n_matches": np.asarray([bow[b][0] for b in frames], np.float64),
+        "bow_matches": np.concatenate([bow[b][1] for b in frames]).astype(np.float32),
+    }
+    os.makedirs(ddir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(ddir, name + ".npy"), a)
+    return {"dir": ddir, "frames": len(frames), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("ORBX_BENCH_BATCH", "256")))
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-lba", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the untimed comparison of the timed path's results with the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle self-check, roofline, LocalBA, CPU-baseline legs (and the stereo / "
+                         "global-BA legs when N > 1) and write the whole record to the --detail file")
+    ap.add_argument("--detail", metavar="PATH", default=None,
+                    help="--full: where the whole record goes (default bench_out/bench_detail.json in the repository)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU-baseline legs")
+    ap.add_argument("--no-lba", action="store_true", help="--full without the LocalBA leg (and the legs that need it)")
+    ap.add_argument("--no-check", action="store_true", help="--full without the untimed comparison of the timed path's results with the CPU oracle")
     ap.add_argument("--extra", action="store_true",
-                    help="also time the SURVEY 8(f) legs (PoseOptimization, projection search, vocabulary transform, packets, inertial BA ...); "
-                         "they go to bench_detail.json, never into the headline line")
+                    help="implies --full; also time the SURVEY 8(f) legs (PoseOptimization, projection search, vocabulary transform, packets, "
+                         "inertial BA ...); they go to the detail file, never into the headline line")
     ap.add_argument("--streams", type=int, default=1,
-                    help="extra leg (off by default so that every profiled launch has the headline's size): the same batch cut over "
-                         "this many independent HIP streams, e.g. --streams 4")
+                    help="implies --full when above 1; extra leg (off by default so that every profiled launch has the headline's size): "
+                         "the same batch cut over this many independent HIP streams, e.g. --streams 4")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.extra or args.streams > 1:
+        args.full = True
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -275,10 +326,13 @@ def main():
         raise SystemExit("extractor reported device status %r" % st[st != 0][:4])
     bow = plan.fetch(stream)
     n_kp = float(nk.mean())
-    # self-check of the timed path (untimed): 8 frames of the batch the timed loop produced -- key points, descriptors and the BoW
-    # matches of their pairs -- against the CPU oracle; a mismatch fails the run
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, pkg, B, cap, d_kps, d_desc, d_n, d_mono, bow)
+        log("outputs of the last timed step: %d frames, %d bytes in %s" % (dumped["frames"], dumped["bytes"], dumped["dir"]))
+    # self-check of the timed path (untimed, --full): 8 frames of the batch the timed loop produced -- key points, descriptors and the
+    # BoW matches of their pairs -- against the CPU oracle; a mismatch fails the run
     self_check = None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         self_check = check_against_oracle(pkg, ex, B, cap, d_kps, d_desc, d_n, d_mono, host_imgs, n_distinct, bow, match_sets, n_sets)
 
     out = {
@@ -295,7 +349,7 @@ def main():
         out["config"]["distinct_match_sets"] = n_sets
         out["self_check"] = self_check
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline leg: per-stage device time with HIP events on the launch stream ----
         ex.profile_enable(True)
         acc = {}
@@ -938,7 +992,7 @@ def main():
 
     # ---- stereo streams: two extractions per frame with vLappingArea = {0, 0} (src/Frame.cc:122-125, two
     # ORBextractor instances) + Frame::ComputeStereoMatches, B/2 rectified pairs per GPU, sharded like the mono frames ----
-    if (world > 1 or args.extra) and not args.no_lba:
+    if args.full and (world > 1 or args.extra) and not args.no_lba:
         Bs = B // 2
         exL = pkg.Extractor(1000, 1.2, 8, 20, 7, device=local_rank)
         exR = pkg.Extractor(1000, 1.2, 8, 20, 7, device=local_rank)
@@ -979,7 +1033,7 @@ def main():
 
     # ---- sharded global BA with one RCCL all-reduce per LM trial (N>1) ----
     gba_failed = False
-    if world > 1 and not args.no_lba:
+    if args.full and world > 1 and not args.no_lba:
         # watchdog: the headline number must survive even if this extra leg ever stalled inside a collective
         import threading
 
@@ -1053,15 +1107,18 @@ def main():
         wd.cancel()
 
     if rank == 0:
-        try:
-            ddir = os.path.join(ROOT, "gpurun_out")
-            os.makedirs(ddir, exist_ok=True)
-            with open(os.path.join(ddir, "bench_detail.json"), "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as e:
-            log("could not write bench_detail.json: %r" % (e,))
+        detail = None
+        if args.full:
+            dpath = args.detail or os.path.join(ROOT, "bench_out", "bench_detail.json")
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(dpath)), exist_ok=True)
+                with open(dpath, "w") as f:
+                    json.dump(out, f, indent=1)
+                detail = args.detail or "bench_out/bench_detail.json"
+            except OSError as e:
+                log("could not write %s: %r" % (dpath, e))
         log(json.dumps(out))
-        print(json.dumps(compact_line(out)), flush=True)
+        print(json.dumps(compact_line(out, detail)), flush=True)
     plan.close(); matcher.close(); ex.close()
     if dist is not None:
         if gba_failed:

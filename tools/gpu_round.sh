@@ -9,22 +9,21 @@ timeout -k 10 420 python -m pytest tests -m gpu -x -q < /dev/null > $OUT/pytest_
 tail -3 $OUT/pytest_gpu.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "pytest timed out: stopping"; exit 1; fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python bench.py --steps 5 --warmup 1 --no-cpu > $OUT/bench_prof.json 2> $OUT/bench_prof.err || { echo "rocprof stats failed"; exit 1; }
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python bench.py --steps 3 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_fetch.err || { echo "pmc fetch failed"; exit 1; }
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python bench.py --steps 3 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_write.err || { echo "pmc write failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python bench.py --full --steps 5 --warmup 1 --no-cpu > $OUT/bench_prof.json 2> $OUT/bench_prof.err || { echo "rocprof stats failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python bench.py --full --steps 3 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_fetch.err || { echo "pmc fetch failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python bench.py --full --steps 3 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_write.err || { echo "pmc write failed"; exit 1; }
 python tools/collect_pmc.py $OUT/pmc_fetch $OUT/pmc_write 256 > $OUT/pmc_traffic.log && cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
 # SQ counters of every kernel of a step (+ LDS / memory instruction counts) -> profiles/valu_issue.json (bench.py: roofline.valu_issue_frac)
 bash tools/pmc_sq.sh $TAG/sq > $OUT/sq_counters.log 2>&1 || echo "sq counter pass failed"
 # the bench line LAST of the three: roofline.traffic / valu_issue_frac come from the counter passes above (stamped with these kernel sources)
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
-cp gpurun_out/bench_detail.json $OUT/bench_detail.json 2>/dev/null
+timeout -k 10 400 python bench.py --full --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 cp $(ls $OUT/prof/*/*kernel_stats.csv | head -1) $OUT/kernel_stats.csv
 # the same command with the serial schedule (ORBX_SERIAL=1: one launch per stage on one stream): per-kernel averages that can be
 # compared with the HIP-event stage times of the bench line (in the production schedule FAST and the octree are several
 # launches that run beside other kernels)
-ORBX_SERIAL=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python bench.py --steps 5 --warmup 1 --no-cpu --no-lba > $OUT/bench_prof_serial.json 2> $OUT/bench_prof_serial.err || echo "serial rocprof stats failed"
+ORBX_SERIAL=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python bench.py --full --steps 5 --warmup 1 --no-cpu --no-lba > $OUT/bench_prof_serial.json 2> $OUT/bench_prof_serial.err || echo "serial rocprof stats failed"
 cp $(ls $OUT/prof_serial/*/*kernel_stats.csv | head -1) $OUT/kernel_stats_serial.csv 2>/dev/null
-timeout -k 10 200 python bench.py --streams 4 --no-cpu --no-lba > $OUT/bench_streams4.json 2> $OUT/bench_streams4.err || echo "streams-4 bench failed"
+timeout -k 10 200 python bench.py --full --streams 4 --no-cpu --no-lba > $OUT/bench_streams4.json 2> $OUT/bench_streams4.err || echo "streams-4 bench failed"
 # per-kernel times of the two BA solvers alone (profiles/<tag>_lba_kernel_stats.csv, <tag>_inertial_ba_kernel_stats.csv)
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lbaprof -- python tools/lba_prof.py 5 > $OUT/lbaprof.log 2>&1 || echo "lba profile failed"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/libaprof -- python tools/liba_prof.py 5 > $OUT/libaprof.log 2>&1 || echo "inertial ba profile failed"
@@ -40,7 +39,7 @@ bash tools/pmc_lba.sh $TAG/lba_pmc > $OUT/lba_pmc.log 2>&1 || echo "lba mfma cou
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lbabatchprof -- python tools/lba_batch_prof.py 32 3 > $OUT/lba_batch_prof.log 2>&1 < /dev/null || echo "lba batch profile failed"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/projprof -- python tools/proj_batch_prof.py 256 3 > $OUT/proj_prof.log 2>&1 < /dev/null || echo "projection profile failed"
 ORBM_PROJ_SEQUENTIAL=1 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/projprof_seq -- python tools/proj_batch_prof.py 256 3 > $OUT/proj_prof_seq.log 2>&1 < /dev/null || echo "sequential projection profile failed"
-timeout -k 10 400 python bench.py --extra > $OUT/bench_extra.json 2> $OUT/bench_extra.err < /dev/null && cp gpurun_out/bench_detail.json $OUT/bench_detail_extra.json || echo "bench --extra failed"
+timeout -k 10 400 python bench.py --full --extra --detail $OUT/bench_detail_extra.json > $OUT/bench_extra.json 2> $OUT/bench_extra.err < /dev/null || echo "bench --extra failed"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -6,9 +6,9 @@ OUT=gpurun_out/${1:-sq}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_BUSY_CYCLES \
-    --output-format csv -d $OUT/pmc_sq -- python bench.py --steps 2 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_sq.err || { echo "pmc sq failed"; tail -5 $OUT/pmc_sq.err; exit 1; }
+    --output-format csv -d $OUT/pmc_sq -- python bench.py --full --steps 2 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_sq.err || { echo "pmc sq failed"; tail -5 $OUT/pmc_sq.err; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_INST_LEVEL_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM_RD \
-    --output-format csv -d $OUT/pmc_sq2 -- python bench.py --steps 2 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_sq2.err || echo "second counter pass (LDS / memory instructions) failed"
+    --output-format csv -d $OUT/pmc_sq2 -- python bench.py --full --steps 2 --warmup 1 --no-cpu --no-lba > /dev/null 2> $OUT/pmc_sq2.err || echo "second counter pass (LDS / memory instructions) failed"
 python - <<PY
 import csv, glob, collections, json, sys
 sys.path.insert(0, "tools")

@@ -1724,7 +1724,7 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
 }
 
 // The Levenberg loops of W windows side by side: SparseOptimizer::optimize driving OptimizationAlgorithmLevenberg::solve
-// (levenberg.cpp:61-169) with the user lambda, one state machine per window cut where the host waits for the device; a round =
+// (levenberg.cpp:61-169) with the user lambda, one Levenberg controller (lm_control.h) per window, cut where the host waits for the device; a round =
 // [errors of the accepted state where they are stale] [linearisation where an iteration starts] [one trial], every stage ONE launch
 // for all windows.
 static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, liba::IWin* d_wins, liba_io* io, const LibaProblem* problems,
@@ -1796,60 +1796,30 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     if (ev0) (void)hipEventRecord(ev0, stream);
     const auto t_setup = std::chrono::steady_clock::now();
 
-    enum Phase { kStartIter, kTrials, kDone };
-    struct WS { Phase ph = kStartIter; double lambda = 0, ni = 2, cur_chi = 0, ini_chi = 0, rho = 0; int nBad = 0, it = 0, qmax = 0, cur = 0; bool err_current = false, chi_known = false; LbaStats st; };
-    std::vector<WS> ws((size_t)W);
-    for (int i = 0; i < W; i++) { std::memset(&ws[i].st, 0, sizeof(LbaStats)); ws[i].lambda = problems[i].lambda_init; }
+    std::vector<lm::Levenberg> ctl;                 // one Levenberg controller per window (lm_control.h), started at the user lambda
+    for (int i = 0; i < W; i++) ctl.emplace_back(problems[i].max_iters, problems[i].lambda_init);
+    std::vector<int> cur((size_t)W, 0);             // index of the accepted state; 1 - cur holds the trial state
+    std::vector<char> err_current((size_t)W, 0);    // the device's edge errors belong to the accepted state
     liba::IDynAll dyn;
     std::memset(&dyn, 0, sizeof(dyn));
-    auto read_scalars = [&](liba_solver* sv) -> int {      // poll the sequence number; fall back to a synchronisation after 20 ms
-        const volatile unsigned long long* flag = (const volatile unsigned long long*)(sv->h_scal + 8);
-        const auto t0 = std::chrono::steady_clock::now();
-        int spins = 0;
-        while (*flag != sv->seq) {
-            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-                LBA_HIP(hipStreamSynchronize(stream));
-                if (*flag != sv->seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
-                break;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return ORBX_OK;
-    };
-    auto finish_iteration = [&](int i) {        // after the trial loop of an iteration (levenberg.cpp:150-169, sparse_optimizer.cpp:395-414)
-        WS& x = ws[i];
-        x.st.iterations++;
-        if (x.it < 16) x.st.chi2_trace[x.it] = x.cur_chi;
-        x.st.chi2_final = x.cur_chi;
-        if (x.qmax == 10 || x.rho == 0) { x.st.stop_reason = 1; x.ph = kDone; return; }
-        if ((x.ini_chi - x.cur_chi) * 1e3 < x.ini_chi) x.nBad++; else x.nBad = 0;
-        if (x.nBad >= 3) { x.st.stop_reason = 2; x.ph = kDone; return; }
-        x.it++;
-        x.ph = kStartIter;
-    };
     const int tiles = max_nblk * (max_nblk + 1) / 2;
-    const int flow_windows = std::max(1, 240 / tiles);          // (100 KB of LDS per workgroup: one per CU; every workgroup of a launch must be resident)
+    const int flow_windows = std::max(1, lba::kMaxFlowGroups / tiles);
     for (bool final_round = false;;) {
         bool any_lin = false, any_err = false, any_trial = false;
         for (int i = 0; i < W; i++) {
-            WS& x = ws[i];
+            lm::Levenberg& c = ctl[i];
             liba::IDyn& y = dyn.w[i];
             y.flags = 0;
             if (final_round) {
-                if (!x.err_current) { y.flags = liba::kIwErrors; x.err_current = true; }       // the epilogue reads the errors of the final state
+                if (!err_current[i]) { y.flags = liba::kIwErrors; err_current[i] = 1; }       // the epilogue reads the errors of the final state
             } else {
-                if (x.ph == kStartIter) {
-                    if (x.it >= problems[i].max_iters) x.ph = kDone;
-                    else {
-                        y.flags |= liba::kIwLin;
-                        if (!x.err_current) y.flags |= liba::kIwErrors;
-                        x.rho = 0; x.qmax = 0;
-                        x.ph = kTrials;
-                    }
+                if (c.step() == lm::Levenberg::kBegin && c.begin_iteration(false)) {         // (linearisation and first trial in one round)
+                    y.flags |= liba::kIwLin;
+                    if (!err_current[i]) y.flags |= liba::kIwErrors;
                 }
-                if (x.ph == kTrials) y.flags |= liba::kIwTrial;
+                if (c.step() == lm::Levenberg::kLinearize || c.step() == lm::Levenberg::kTrial) y.flags |= liba::kIwTrial;
             }
-            y.lambda = x.lambda; y.cur = x.cur;
+            y.lambda = c.lambda(); y.cur = cur[i];
             if (y.flags) y.seq = ++slots[i]->seq;
             any_lin |= (y.flags & liba::kIwLin) != 0; any_err |= (y.flags & liba::kIwErrors) != 0; any_trial |= (y.flags & liba::kIwTrial) != 0;
         }
@@ -1868,40 +1838,26 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
         if (hipGetLastError() != hipSuccess) { r = fail(ORBX_ERR_HIP, "launch failed"); break; }
         if (final_round) break;
         for (int i = 0; i < W && !r; i++)
-            if (dyn.w[i].flags) r = read_scalars(slots[i]);
+            if (dyn.w[i].flags) r = wait_scalars(slots[i]->h_scal, slots[i]->seq, stream);
         if (r) break;
         for (int i = 0; i < W; i++) {
-            WS& x = ws[i];
+            lm::Levenberg& c = ctl[i];
             const int f = dyn.w[i].flags;
             const double* h = slots[i]->h_scal;
-            if (f & liba::kIwErrors) {
-                if (!x.chi_known) { x.cur_chi = h[6]; x.chi_known = true; }
-                x.err_current = true;
-            }
-            if (f & liba::kIwLin) {
-                x.ini_chi = x.cur_chi;
-                if (x.it == 0) { x.st.chi2_initial = x.cur_chi; x.ni = 2; x.nBad = 0; }
-            }
+            if (f & liba::kIwErrors) err_current[i] = 1;
+            if (f & liba::kIwLin) c.linearized(c.iteration() == 0 ? h[6] : c.chi2(), problems[i].lambda_init);     // (chi2 of the initial state)
             if (!(f & liba::kIwTrial)) continue;
-            const bool ok = h[5] == 0.0;
-            const double tempChi = ok ? h[0] : std::numeric_limits<double>::max();
-            x.rho = (x.cur_chi - tempChi) / (h[3] + 1e-3);
-            if (!ok) x.rho = -1;
-            if (x.rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * x.rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                x.lambda *= std::max(1. / 3., alpha);
-                x.ni = 2;
-                x.cur_chi = tempChi;
-                x.cur = 1 - x.cur;                          // discardTop(): the trial state (and its errors) become current
-                x.err_current = true;
+            const lm::TrialStatus ts = lm::trial_status(h[5]);
+            if (ts == lm::TrialStatus::kStalled) { r = fail(ORBX_ERR_INTERNAL, "liba_run: window %d: the factorisation stalled (a spin wait between workgroups expired)", i); break; }
+            if (c.trial(ts == lm::TrialStatus::kSolved, h[0], h[3])) {
+                cur[i] = 1 - cur[i];            // discardTop(): the trial state (and its errors) become current
+                err_current[i] = 1;
             } else {
-                x.lambda *= x.ni; x.ni *= 2;                // pop(): the old state stays; its errors are recomputed before the next linearisation
-                x.err_current = false;
+                err_current[i] = 0;             // pop(): the old state stays; its errors are recomputed before the next linearisation
             }
-            x.qmax++; x.st.trials++;
-            if (!(x.rho < 0 && x.qmax < 10)) finish_iteration(i);
+            if (!c.more_trials(false)) c.end_iteration();
         }
+        if (r) break;
     }
     if (ev1) (void)hipEventRecord(ev1, stream);
     const auto t_solved = std::chrono::steady_clock::now();
@@ -1909,9 +1865,8 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     if (!r) {
         // results of all windows: one epilogue launch into the handle's device buffer, ONE copy, one synchronisation, then the scatter
         for (int i = 0; i < W; i++) {
-            dyn.w[i].cur = ws[i].cur;
-            ws[i].st.lambda = ws[i].lambda;
-            if (stats_out) stats_out[i] = ws[i].st;
+            dyn.w[i].cur = cur[i];
+            if (stats_out) stats_out[i] = ctl[i].stats();
         }
         if (outputs) {
             hipLaunchKernelGGL(liba::ki_epilogue, dim3(max_epi, W), dim3(256), 0, stream, (const liba::IWin*)d_wins, dyn);
@@ -1946,7 +1901,7 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     if (timing) {
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         int its = 0, trials = 0;
-        for (int i = 0; i < W; i++) { its += ws[i].st.iterations; trials += ws[i].st.trials; }
+        for (int i = 0; i < W; i++) { its += ctl[i].stats().iterations; trials += ctl[i].stats().trials; }
         std::fprintf(stderr, "[liba_solve] %d window(s): structure + upload %.3f ms, %d iterations / %d trials %.3f ms, download %.3f ms\n", W, ms(t_start, t_setup),
                      its, trials, ms(t_setup, t_solved), ms(t_solved, std::chrono::steady_clock::now()));
     }

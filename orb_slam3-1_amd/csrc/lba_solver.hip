@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "lm_control.h"
 #include "se3_device.h"
 
 namespace orbx {
@@ -701,6 +702,9 @@ __device__ unsigned long long d_step_prof[8];
 constexpr int kFusedMaxBlocks = 8;       // up to 480 reduced unknowns (80 key frames); larger systems keep panel / update launches
 static_assert(NB + 16 * 28 >= kFusedMaxBlocks * NB, "k_chol_solve<true> prefetches at most 28 rows per row group");
 constexpr int kStepLds = (NB * (NB + 1) + 2 * 64 * (NB + 1)) * 8 + (int)sizeof(CholVec4);
+// workgroups of one flow-factorisation launch (k_chol_flow_b, ki_chol_flow) that are resident at once: kStepLds (100 KB of LDS)
+// allows one per CU, and every workgroup of such a launch may wait on others, so all of them must be resident
+constexpr int kMaxFlowGroups = 240;
 __device__ __forceinline__ void chol_step_body(double* __restrict__ S, double* __restrict__ Lp, int n, int K, int nblk,
                                                    double* __restrict__ Linv, double* __restrict__ scal, const int bx, double* __restrict__ sm_step)
 {
@@ -839,12 +843,6 @@ __device__ __forceinline__ void chol_step_body(double* __restrict__ S, double* _
 #ifdef LBA_STEP_TIMING
     if (bi == K + 1 && bj == K + 1 && threadIdx.x == 0) d_step_prof[7] += 1;
 #endif
-}
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_chol_step(double* __restrict__ S, double* __restrict__ Lp, int n, int K, int nblk,
-                                                   double* __restrict__ Linv, double* __restrict__ scal)
-{
-    extern __shared__ __align__(16) double sm_step[];
-    chol_step_body(S, Lp, n, K, nblk, Linv, scal, (int)blockIdx.x, sm_step);
 }
 
 // ---- the whole factorisation in ONE launch (round 3): a workgroup per lower-triangle tile (r, c) of the block matrix ----
@@ -1819,7 +1817,6 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     static std::atomic<unsigned long long> attr_done{0};
     const bool set_attr = !((attr_done.load() >> device) & 1ull);
     if (set_attr) {
-        LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
         LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
     }
     LBA_TRY(s->dalloc(&s->flow, (size_t)lba::kFlowFlags));
@@ -1999,17 +1996,18 @@ int lba_shard_set_reduce_buffer(lba_shard* s, double* device_buffer)
     return ORBX_OK;
 }
 
-static int read_scalars(lba_shard* s)
+// The reduction kernels write their scalars into the host-mapped buffer h_scal[0..7] and then publish sequence number `seq` in
+// h_scal[8]: poll for it (a trial is a few hundred microseconds of kernels); after 20 ms fall back to a stream synchronisation,
+// which also surfaces faults.  Shared by the LocalBA drivers and liba_run (inertial_solver.inc).
+static int wait_scalars(const double* h_scal, unsigned long long seq, hipStream_t stream)
 {
-    // k_reduce wrote the scalars into the host-mapped buffer and then published its sequence number: poll for it (a trial is
-    // a few hundred microseconds of kernels); after 20 ms fall back to a stream synchronisation, which also surfaces faults
-    const volatile unsigned long long* flag = (const volatile unsigned long long*)(s->h_scal + 8);
+    const volatile unsigned long long* flag = (const volatile unsigned long long*)(h_scal + 8);
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
-    while (*flag != s->seq) {
+    while (*flag != seq) {
         if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-            LBA_HIP(hipStreamSynchronize(s->stream));
-            if (*flag != s->seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
+            LBA_HIP(hipStreamSynchronize(stream));
+            if (*flag != seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
             break;
         }
     }
@@ -2052,7 +2050,7 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
         hipLaunchKernelGGL(lba::k_reduce, dim3(1), dim3(1024), 0, s->stream, d, 0, s->d_hmap, ++s->seq);
         s->mark(lba::kStageIdle);
         LBA_HIP(hipGetLastError());
-        int r = read_scalars(s);
+        int r = wait_scalars(s->h_scal, s->seq, s->stream);
         if (r) return r;
         s->chi_current = s->h_scal[0];
         s->mdp_cached = s->h_scal[1];
@@ -2104,18 +2102,10 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     if (n > 0) {
         if (!s->lambda_added) hipLaunchKernelGGL(lba::k_add_lambda, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->S(), n, lambda);
         const bool fused = s->nblk <= lba::kFusedMaxBlocks;
-        static const bool step_launches = std::getenv("ORBX_LBA_STEPS") != nullptr;       // A/B knob: round 2's launch per block column
-        if (fused && !step_launches) {
+        if (fused) {
             // the whole factorisation as one launch: a workgroup per lower-triangle tile, flags between them (k_chol_flow)
             hipLaunchKernelGGL(lba::k_chol_flow, dim3(s->nblk * (s->nblk + 1) / 2), dim3(256), lba::kStepLds, s->stream, s->S(), s->Lp, n, s->nblk, s->Linv, d.scal,
                                s->flow, ++s->flow_epoch);
-        } else if (fused) {
-            // one launch per block column: panel + trailing update + the next diagonal factorisation (k_chol_step)
-            hipLaunchKernelGGL(lba::k_chol_diag, dim3(1), dim3(256), 0, s->stream, (const double*)s->S(), n, 0, std::min(lba::NB, n), s->Linv, d.scal);
-            for (int K = 0; K + 1 < s->nblk; K++) {
-                const int T = s->nblk - 1 - K;
-                hipLaunchKernelGGL(lba::k_chol_step, dim3(T * (T + 1) / 2), dim3(256), lba::kStepLds, s->stream, s->S(), s->Lp, n, K, s->nblk, s->Linv, d.scal);
-            }
         }
         for (int K = 0; K < s->nblk && !fused; K++) {
             const int k0 = K * lba::NB, nb = std::min(lba::NB, n - k0);
@@ -2144,14 +2134,18 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     hipLaunchKernelGGL(lba::k_update_errors, dim3(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1)), dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->d_hmap, ++s->seq);
     s->mark(lba::kStageIdle);
     LBA_HIP(hipGetLastError());
-    int r = read_scalars(s);
+    int r = wait_scalars(s->h_scal, s->seq, s->stream);
     if (r) return r;
     s->chi_trial = s->h_scal[0];
     s->err_current = false;         // the error buffer now belongs to the trial state
     if (chi2_local_new) *chi2_local_new = s->h_scal[0];
     if (scale_poses) *scale_poses = s->h_scal[3];
     if (scale_landmarks_local) *scale_landmarks_local = s->h_scal[4];
-    return s->h_scal[5] != 0.0 ? 0 : 1;
+    switch (lm::trial_status(s->h_scal[5])) {
+    case lm::TrialStatus::kSolved: return 1;
+    case lm::TrialStatus::kNotPositiveDefinite: return 0;
+    default: return fail(ORBX_ERR_INTERNAL, "lba_shard_finish: the factorisation stalled (a spin wait between workgroups expired)");
+    }
 }
 
 int lba_shard_accept(lba_shard* s, int accept)
@@ -2235,81 +2229,42 @@ int lba_shard_optimize(lba_shard* s, lba_allreduce_fn allreduce, void* user, int
         *stop = f > 0.0;
         return rr;
     };
-    LbaStats st;
-    std::memset(&st, 0, sizeof(st));
-    double lambda = -1, ni = 2;
-    int nBad = 0;
-    for (int it = 0; it < max_iters; it++) {
+    lm::Levenberg ctl(max_iters);
+    while (!ctl.capped()) {      // (the cap first: terminate() is a collective every rank calls equally often)
         bool stop = false;
-        if ((r = terminate(&stop))) break;
-        if (stop) { st.stop_reason = 3; break; }
+        if ((r = terminate(&stop)) || !ctl.begin_iteration(stop)) break;
         double currentChi = 0, mdp = 0, mdl = 0;
-        if (it > 0) lba_shard_hint_lambda(s, lambda);
+        if (ctl.iteration() > 0) lba_shard_hint_lambda(s, ctl.lambda());
         else if (lambda_init > 0) lba_shard_hint_lambda(s, lambda_init);
         if ((r = lba_shard_linearize(s, &currentChi, &mdp, &mdl))) break;
         if ((r = reduce_scalars(&currentChi, 1, LBA_REDUCE_SUM))) break;
-        const double iniChi = currentChi;
-        if (it == 0) {
-            st.chi2_initial = currentChi;
-            if (lambda_init > 0) lambda = lambda_init;
-            else {
-                if (dist) {
-                    // the pose diagonals are partial sums over the shards: one lambda-free exchange, then the maximum of the summed
-                    // diagonal section; the landmark maximum is MAX-reduced (computeLambdaInit, levenberg.cpp:171-185)
-                    if ((r = lba_shard_reduce(s, 0.0)) || (r = reduce_system())) break;
-                    std::vector<double> dg((size_t)std::max(s->d.n, 1), 0.0);
-                    if (s->d.n > 0) LBA_HIP(hipMemcpyAsync(dg.data(), s->diag(), (size_t)s->d.n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-                    LBA_HIP(hipStreamSynchronize(s->stream));
-                    mdp = 0;
-                    for (int k = 0; k < s->d.n; k++) mdp = std::max(mdp, std::fabs(dg[k]));
-                    if ((r = reduce_scalars(&mdl, 1, LBA_REDUCE_MAX))) break;
-                }
-                lambda = 1e-5 * std::max(mdp, mdl);
-            }
-            ni = 2; nBad = 0;
+        if (ctl.iteration() == 0 && !(lambda_init > 0) && dist) {
+            // the pose diagonals are partial sums over the shards: one lambda-free exchange, then the maximum of the summed
+            // diagonal section; the landmark maximum is MAX-reduced (computeLambdaInit, levenberg.cpp:171-185)
+            if ((r = lba_shard_reduce(s, 0.0)) || (r = reduce_system())) break;
+            std::vector<double> dg((size_t)std::max(s->d.n, 1), 0.0);
+            if (s->d.n > 0) LBA_HIP(hipMemcpyAsync(dg.data(), s->diag(), (size_t)s->d.n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            LBA_HIP(hipStreamSynchronize(s->stream));
+            mdp = 0;
+            for (int k = 0; k < s->d.n; k++) mdp = std::max(mdp, std::fabs(dg[k]));
+            if ((r = reduce_scalars(&mdl, 1, LBA_REDUCE_MAX))) break;
         }
-        double rho = 0;
-        int qmax = 0;
+        ctl.linearized(currentChi, lm::initial_lambda(lambda_init, mdp, mdl));
         bool stopped = false;
         do {
+            const double lambda = ctl.lambda();
             if ((r = lba_shard_reduce(s, lambda)) || (r = reduce_system())) break;
             double tempChi = 0, sp = 0, sl = 0;
             const int ok2 = lba_shard_finish(s, lambda, &tempChi, &sp, &sl);
             if (ok2 < 0) { r = ok2; break; }
             double pack[3] = {tempChi, sl, (double)ok2};
             if ((r = reduce_scalars(pack, 3, LBA_REDUCE_SUM))) break;
-            tempChi = pack[0]; sl = pack[1];
-            if (pack[2] < (dist ? world_size : 1) - 0.5) tempChi = std::numeric_limits<double>::max();
-            rho = currentChi - tempChi;
-            double scale = sp + sl;
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
-                lba_shard_accept(s, 1);
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                lba_shard_accept(s, 0);
-            }
-            qmax++;
-            st.trials++;
+            lba_shard_accept(s, ctl.trial(pack[2] >= (dist ? world_size : 1) - 0.5, pack[0], sp + pack[1]));
             if ((r = terminate(&stopped))) break;
-        } while (rho < 0 && qmax < 10 && !stopped);
-        if (r) break;
-        st.iterations++;
-        if (it < 16) st.chi2_trace[it] = currentChi;
-        st.chi2_final = currentChi;
-        if (qmax == 10 || rho == 0) { st.stop_reason = 1; break; }
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) { st.stop_reason = 2; break; }
+        } while (ctl.more_trials(stopped));
+        if (r || !ctl.end_iteration()) break;
     }
-    st.lambda = lambda;
-    if (stats_out) *stats_out = st;
+    if (stats_out) *stats_out = ctl.stats();
     return r;
 }
 
@@ -2379,8 +2334,8 @@ int lba_solve(lba_solver* sv, const LbaProblem* problem, const volatile uint8_t*
 // ---------------------------------------------------------------------------------------------------------------
 // lba_solve_batch: W independent windows (one map per client session, SURVEY.md 8(e): "independent maps shard round-robin") through
 // ONE sequence of launches per Levenberg round, grid.y = window.  Every window walks exactly the path lba_solve would walk for it
-// (same kernel bodies, same order of operations -> bit-identical results); the host keeps one LM state machine per window and a
-// round is: [linearise the windows that start an iteration] + [one trial of every window that is not finished].
+// (same kernel bodies, same order of operations -> bit-identical results); the host keeps one Levenberg controller
+// (lm_control.h) per window and a round is: [linearise the windows that start an iteration] + [one trial of every window that is not finished].
 // ---------------------------------------------------------------------------------------------------------------
 struct lba_batch {
     int device = 0;
@@ -2504,49 +2459,34 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     }
     (void)hipEventRecord(b->ev0, b->stream);
 
-    // ---- one Levenberg state machine per window (the control flow of lba_shard_optimize, cut at the points where it waits for the device) ----
-    enum Phase { kStartIter, kAfterLin, kTrials, kDone };
-    struct WS { Phase ph = kStartIter; double lambda = -1, ni = 2, cur_chi = 0, ini_chi = 0, rho = 0, trial_lambda = 0; int nBad = 0, it = 0, qmax = 0, cur = 0; bool err_current = false, first_trial = false; double hint = -1; LbaStats st; };
-    std::vector<WS> ws((size_t)W);
-    for (auto& x : ws) std::memset(&x.st, 0, sizeof(x.st));
+    // ---- one Levenberg controller per window (the control flow of lba_shard_optimize, cut at the points where it waits for the device);
+    // the accepted state and the currency of the errors are the shard's own cur / err_current ----
+    std::vector<lm::Levenberg> ctl((size_t)W, lm::Levenberg(max_iters));
+    std::vector<double> hint((size_t)W, -1.0);         // the lambda the linearisation of the current iteration prepared the Schur side for
+    std::vector<char> first_trial((size_t)W, 0);
     auto stopped = [&](int i) { return stop_flags && stop_flags[i] && *stop_flags[i]; };
     std::vector<unsigned long long> seq((size_t)W);
     for (int i = 0; i < W; i++) seq[i] = sh[i]->seq;
     lba::BDynAll dyn;
     std::memset(&dyn, 0, sizeof(dyn));
-    auto finish_iteration = [&](int i) {        // after the trial loop of an iteration (levenberg.cpp:150-169, sparse_optimizer.cpp:395-414)
-        WS& x = ws[i];
-        x.st.iterations++;
-        if (x.it < 16) x.st.chi2_trace[x.it] = x.cur_chi;
-        x.st.chi2_final = x.cur_chi;
-        if (x.qmax == 10 || x.rho == 0) { x.st.stop_reason = 1; x.ph = kDone; return; }
-        if ((x.ini_chi - x.cur_chi) * 1e3 < x.ini_chi) x.nBad++; else x.nBad = 0;
-        if (x.nBad >= 3) { x.st.stop_reason = 2; x.ph = kDone; return; }
-        x.it++;
-        x.ph = kStartIter;
-    };
     for (;;) {
         bool any_lin = false, any_err = false, any_trial = false, any_lm = false;
         for (int i = 0; i < W; i++) {
-            WS& x = ws[i];
+            lm::Levenberg& c = ctl[i];
+            lba_shard* s = sh[i];
             lba::BDyn& y = dyn.w[i];
             y.flags = 0;
-            if (x.ph == kStartIter) {
-                if (x.it >= max_iters) { x.ph = kDone; }
-                else if (stopped(i)) { x.st.stop_reason = 3; x.ph = kDone; }
-                else {
-                    x.hint = x.it > 0 ? x.lambda : (lambda_init > 0 ? lambda_init : -1.0);
-                    y.flags |= lba::kBwLin;
-                    if (!x.err_current) { y.flags |= lba::kBwErrors | lba::kBwReduce0; x.ph = kAfterLin; }       // the host needs chi2 / the diagonals first
-                    else { x.ini_chi = x.cur_chi; x.rho = 0; x.qmax = 0; x.first_trial = true; x.ph = kTrials; }
-                }
+            if (c.step() == lm::Levenberg::kBegin && c.begin_iteration(stopped(i))) {
+                hint[i] = c.iteration() > 0 ? c.lambda() : (lambda_init > 0 ? lambda_init : -1.0);
+                y.flags |= lba::kBwLin;
+                if (!s->err_current) y.flags |= lba::kBwErrors | lba::kBwReduce0;       // the host needs chi2 / the diagonals first
+                else { c.linearized(c.chi2(), lambda_init); first_trial[i] = 1; }
             }
-            if (x.ph == kTrials) {
+            if (c.step() == lm::Levenberg::kTrial) {
                 y.flags |= lba::kBwTrial;
-                if (!(x.first_trial && x.hint >= 0.0 && x.hint == x.lambda)) y.flags |= lba::kBwSchurLm;
-                x.trial_lambda = x.lambda;
+                if (!(first_trial[i] && hint[i] >= 0.0 && hint[i] == c.lambda())) y.flags |= lba::kBwSchurLm;
             }
-            y.lambda = x.lambda; y.hint = x.hint; y.cur = x.cur;
+            y.lambda = c.lambda(); y.hint = hint[i]; y.cur = s->cur;
             if (y.flags & (lba::kBwReduce0 | lba::kBwTrial)) y.seq = ++seq[i];
             any_lin |= (y.flags & lba::kBwLin) != 0; any_err |= (y.flags & lba::kBwErrors) != 0;
             any_trial |= (y.flags & lba::kBwTrial) != 0; any_lm |= (y.flags & lba::kBwSchurLm) != 0;
@@ -2561,9 +2501,8 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             hipLaunchKernelGGL(lba::k_schur_blocks_b, dim3(max_sb, W), dim3(lba::kSchurThreads), 0, st, (const lba::BWin*)b->d_wins, dyn);
             // the factorisation: one launch (a workgroup per tile and window, flags between them) while every workgroup of the launch
             // can be resident at once (it waits on others), else a launch per block column
-            static const bool step_launches = std::getenv("ORBX_LBA_STEPS") != nullptr;
             const int tiles = max_nblk * (max_nblk + 1) / 2;
-            if (!step_launches && tiles * W <= 240) {       // (100 KB of LDS per workgroup: one per CU)
+            if (tiles * W <= lba::kMaxFlowGroups) {
                 hipLaunchKernelGGL(lba::k_chol_flow_b, dim3(tiles, W), dim3(256), lba::kStepLds, st, (const lba::BWin*)b->d_wins, dyn);
             } else {
                 hipLaunchKernelGGL(lba::k_chol_diag_b, dim3(1, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
@@ -2581,53 +2520,32 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             const int f = dyn.w[i].flags;
             if (!(f & (lba::kBwReduce0 | lba::kBwTrial))) continue;
             sh[i]->seq = seq[i];
-            r = read_scalars(sh[i]);
+            r = wait_scalars(sh[i]->h_scal, seq[i], b->stream);
         }
         if (r) break;
         for (int i = 0; i < W; i++) {
-            WS& x = ws[i];
+            lm::Levenberg& c = ctl[i];
+            lba_shard* s = sh[i];
             const int f = dyn.w[i].flags;
-            const double* h = sh[i]->h_scal;
+            const double* h = s->h_scal;
             if (f & lba::kBwReduce0) {      // linearised without a trial: chi2 and the diagonal maxima are in
-                x.cur_chi = h[0];
-                x.err_current = true;
-                x.ini_chi = x.cur_chi;
-                if (x.it == 0) {
-                    x.st.chi2_initial = x.cur_chi;
-                    x.lambda = lambda_init > 0 ? lambda_init : 1e-5 * std::max(h[1], h[2]);      // computeLambdaInit (levenberg.cpp:171-185)
-                    x.ni = 2; x.nBad = 0;
-                }
-                x.rho = 0; x.qmax = 0; x.first_trial = true;
-                x.ph = kTrials;
+                s->err_current = true;
+                c.linearized(h[0], lm::initial_lambda(lambda_init, h[1], h[2]));
+                first_trial[i] = 1;
                 continue;
             }
             if (!(f & lba::kBwTrial)) continue;
-            double tempChi = h[0];
-            const double sp = h[3], sl = h[4];
-            if (h[5] != 0.0) tempChi = std::numeric_limits<double>::max();       // the reduced system was not positive definite
-            x.first_trial = false;
-            x.err_current = false;
-            x.rho = x.cur_chi - tempChi;
-            double scale = sp + sl;
-            scale += 1e-3;
-            x.rho /= scale;
-            if (x.rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * x.rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                x.lambda *= std::max(1. / 3., alpha);
-                x.ni = 2;
-                x.cur_chi = tempChi;
-                x.cur = 1 - x.cur;              // discardTop(): the trial state becomes the estimate, its errors are the current ones
-                x.err_current = true;
-            } else {
-                x.lambda *= x.ni;
-                x.ni *= 2;
+            const lm::TrialStatus ts = lm::trial_status(h[5]);
+            if (ts == lm::TrialStatus::kStalled) { r = fail(ORBX_ERR_INTERNAL, "lba_solve_batch: window %d: the factorisation stalled (a spin wait between workgroups expired)", i); break; }
+            first_trial[i] = 0;
+            s->err_current = false;
+            if (c.trial(ts == lm::TrialStatus::kSolved, h[0], h[3] + h[4])) {
+                s->cur = 1 - s->cur;            // discardTop(): the trial state becomes the estimate, its errors are the current ones
+                s->err_current = true;
             }
-            x.qmax++;
-            x.st.trials++;
-            const bool stop_now = stopped(i);
-            if (!(x.rho < 0 && x.qmax < 10 && !stop_now)) finish_iteration(i);
+            if (!c.more_trials(stopped(i))) c.end_iteration();
         }
+        if (r) break;
     }
     (void)hipEventRecord(b->ev1, b->stream);
     const auto t_solved = std::chrono::steady_clock::now();
@@ -2649,9 +2567,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         }
         for (int i = 0; i < W && !r; i++) {
             lba_shard* s = sh[i];
-            s->cur = ws[i].cur;
-            ws[i].st.lambda = ws[i].lambda;
-            if (stats_out) stats_out[i] = ws[i].st;
+            if (stats_out) stats_out[i] = ctl[i].stats();
             if (!outputs) continue;
             const lba::Dev& d = s->d;
             uint8_t* o = b->h_out + off[i];

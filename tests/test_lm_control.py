@@ -1,0 +1,179 @@
+"""The Levenberg controller of the C++ drivers (orb_slam3-1_amd/csrc/lm_control.h) takes exactly the decisions of the Python
+driver distributed.sharded_bundle_adjustment: the same scripted linearisation and trial results go through tests/lm_replay.cpp
+(g++, no device) and through the Python driver over a fake shard (world size 1); decisions, lambdas and stats must be equal."""
+import importlib
+import os
+import random
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def replay_exe(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("lm") / "lm_replay"
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           "-I", os.path.join(ROOT, "orb_slam3-1_amd", "csrc"), os.path.join(ROOT, "tests", "lm_replay.cpp"), "-o", str(exe)])
+    return str(exe)
+
+
+@pytest.fixture(scope="module")
+def distributed(pkg):
+    return importlib.import_module("orb_slam3-1_amd.distributed")
+
+
+class Script:
+    """max_iters, lambda_init, stop_at (stop flag raised once that many trials ran; 0: from the start; -1: never),
+    lins = [(chi2, max_diag_poses, max_diag_landmarks)], trials = [(solved, chi2_new, scale_poses, scale_landmarks)]"""
+
+    def __init__(self, max_iters, lambda_init, lins, trials, stop_at=-1):
+        self.max_iters, self.lambda_init, self.stop_at = max_iters, lambda_init, stop_at
+        self.lins, self.trials = lins, trials
+
+    def text(self):
+        h = float.hex
+        out = ["script %d %s %d" % (self.max_iters, h(float(self.lambda_init)), self.stop_at)]
+        out += ["L %s %s %s" % tuple(h(float(v)) for v in l) for l in self.lins]
+        out += ["T %d %s %s %s" % ((int(t[0]),) + tuple(h(float(v)) for v in t[1:])) for t in self.trials]
+        return "\n".join(out + ["end"])
+
+
+class FakeShard:
+    """The shard interface of sharded_bundle_adjustment, answering from a script; records decisions and lambdas."""
+
+    def __init__(self, sc):
+        self.sc, self.li, self.ti, self.mdp = sc, 0, 0, 0.0
+        self.stop = [1 if sc.stop_at == 0 else 0]
+        self.lambdas, self.accepted = [], []
+
+    def linearize(self):
+        chi, self.mdp, mdl = self.sc.lins[self.li]
+        self.li += 1
+        return chi, self.mdp, mdl
+
+    def max_pose_diag(self):
+        return self.mdp
+
+    def reduce(self, lam):
+        pass
+
+    def finish(self, lam):
+        t = self.sc.trials[self.ti]
+        self.ti += 1
+        self.lambdas.append(lam)
+        if self.ti == self.sc.stop_at:
+            self.stop[0] = 1
+        return t
+
+    def accept(self, ok):
+        self.accepted.append(bool(ok))
+
+
+def run_python(distributed, sc):
+    sh = FakeShard(sc)
+    st = distributed.sharded_bundle_adjustment(sh, None, comm=None, max_iters=sc.max_iters, lambda_init=sc.lambda_init, stop_flag=sh.stop)
+    trace = (st["chi2_trace"] + [0.0] * 16)[:16]
+    return dict(accepted=sh.accepted, lambdas=sh.lambdas[1:] + [st["lambda_"]] if sh.lambdas else [], iterations=st["iterations"],
+                trials=st["trials"], stop_reason=st["stop_reason"], chi2_initial=st.get("chi2_initial", 0.0),
+                chi2_final=st.get("chi2_final", 0.0), lambda_=st["lambda_"], trace=trace)
+
+
+def run_cpp(exe, scripts):
+    out = subprocess.run([exe], input="\n".join(s.text() for s in scripts) + "\n", capture_output=True, text=True, check=True).stdout
+    res, cur = [], None
+    for line in out.splitlines():
+        f = line.split()
+        if cur is None:
+            cur = dict(accepted=[], lambdas=[])
+        if f[0] == "trial":
+            cur["accepted"].append(f[1] == "1")
+            cur["lambdas"].append(float.fromhex(f[2]))
+        elif f[0] == "stats":
+            cur.update(iterations=int(f[1]), trials=int(f[2]), stop_reason=int(f[3]), chi2_initial=float.fromhex(f[4]),
+                       chi2_final=float.fromhex(f[5]), lambda_=float.fromhex(f[6]))
+        elif f[0] == "trace":
+            cur["trace"] = [float.fromhex(v) for v in f[1:]]
+        elif f[0] == "end":
+            res.append(cur)
+            cur = None
+    assert len(res) == len(scripts)
+    return res
+
+
+def check_same(exe, distributed, scripts):
+    cpp = run_cpp(exe, scripts)
+    for i, (sc, c) in enumerate(zip(scripts, cpp)):
+        p = run_python(distributed, sc)
+        assert c == p, "script %d:\n%s\nC++    %s\nPython %s" % (i, sc.text(), c, p)
+    return cpp
+
+
+def random_script(rng):
+    max_iters = rng.choice([0, 1, 2, 5, 10, 10, 10, 20, 25])
+    lambda_init = 0.0 if rng.random() < 0.5 else 10 ** rng.uniform(-8, 2)
+    stop_at = -1 if rng.random() < 0.7 else rng.randint(0, 30)
+    base = 10 ** rng.uniform(0, 5)
+    pool = [base * 10 ** rng.uniform(-1, 0.5) for _ in range(4)]      # repeated values make chi2_new == chi2 (rho == 0) happen
+
+    slow = rng.random() < 0.25      # gains around the 1e-3 of the nBad rule
+
+    def chi():
+        return rng.choice(pool) if rng.random() < 0.3 else base * 10 ** rng.uniform(-1, 0.5)
+
+    def chi_new():
+        return base * (1 - 10 ** rng.uniform(-5, -2)) if slow else chi()
+    lins = [(base if slow else chi(), 10 ** rng.uniform(-2, 6), 10 ** rng.uniform(-2, 6)) for _ in range(max_iters)]
+    trials = [(int(rng.random() < 0.85), chi_new(), rng.uniform(0, base), rng.uniform(0, base) if rng.random() < 0.7 else 0.0)
+              for _ in range(10 * max_iters)]
+    return Script(max_iters, lambda_init, lins, trials, stop_at)
+
+
+def test_random_scripts_match_python_driver(replay_exe, distributed):
+    rng = random.Random(20261016)
+    cpp = check_same(replay_exe, distributed, [random_script(rng) for _ in range(400)])
+    # the random scripts reach every stop reason and both decisions
+    assert {c["stop_reason"] for c in cpp} == {0, 1, 2, 3}
+    assert any(any(c["accepted"]) for c in cpp) and any(not all(c["accepted"]) for c in cpp)
+
+
+def _good(chi):      # a trial that is accepted from chi2 = 2 chi (rho = 1)
+    return (1, chi, chi / 2, chi / 2 - 1e-3)
+
+
+def test_targeted_scripts(replay_exe, distributed):
+    big = [(1000.0 / 2 ** k, 4e4, 3e5) for k in range(25)]
+    cases = {
+        # lambda from the diagonals (1e-5 * max(mdp, mdl)) and the user's lambda
+        "computed_lambda": Script(3, 0.0, big, [_good(500.0 / 2 ** k) for k in range(30)]),
+        "user_lambda": Script(3, 0.25, big, [_good(500.0 / 2 ** k) for k in range(30)]),
+        "ten_rejections": Script(5, 0.0, big, [(1, 2000.0, 1.0, 1.0)] * 50),
+        "rho_zero": Script(5, 1e-3, big, [(1, 1000.0, 1.0, 1.0)] * 50),
+        "three_small_gains": Script(10, 1e-3, [(1000.0 - 0.1 * k, 1.0, 1.0) for k in range(10)],
+                                    [(1, 1000.0 - 0.1 * (k + 1), 0.05, 0.0) for k in range(100)]),
+        "stop_before_first_iteration": Script(5, 0.0, big, [_good(500.0 / 2 ** k) for k in range(50)], stop_at=0),
+        "stop_after_rejected_trial": Script(5, 0.0, big, [(1, 2000.0, 1.0, 1.0)] * 50, stop_at=3),
+        "stop_after_accepted_trial": Script(5, 0.0, big, [_good(500.0 / 2 ** k) for k in range(50)], stop_at=2),
+        "max_iters_cap": Script(4, 0.0, big, [_good(500.0 / 2 ** k) for k in range(40)]),
+        "unsolved_trials": Script(5, 0.0, big, [(0, 1.0, 7.0, 3.0)] * 3 + [_good(500.0 / 2 ** k) for k in range(50)]),
+        "more_than_16_iterations": Script(20, 0.0, big, [_good(500.0 / 2 ** k) for k in range(200)]),
+    }
+    cpp = dict(zip(cases, check_same(replay_exe, distributed, list(cases.values()))))
+    assert cpp["computed_lambda"]["lambdas"][0] == pytest.approx(3e5 * 1e-5 / 3)
+    assert cpp["user_lambda"]["lambdas"][0] == pytest.approx(0.25 / 3)
+    assert cpp["ten_rejections"]["stop_reason"] == 1 and cpp["ten_rejections"]["trials"] == 10
+    assert not any(cpp["ten_rejections"]["accepted"])
+    assert cpp["rho_zero"]["stop_reason"] == 1 and cpp["rho_zero"]["trials"] == 1
+    assert cpp["three_small_gains"]["stop_reason"] == 2 and cpp["three_small_gains"]["iterations"] == 3
+    assert cpp["stop_before_first_iteration"]["stop_reason"] == 3 and cpp["stop_before_first_iteration"]["iterations"] == 0
+    assert cpp["stop_after_rejected_trial"]["stop_reason"] == 3 and cpp["stop_after_rejected_trial"]["trials"] == 3
+    assert cpp["stop_after_accepted_trial"]["stop_reason"] == 3 and cpp["stop_after_accepted_trial"]["iterations"] == 2
+    assert cpp["max_iters_cap"]["stop_reason"] == 0 and cpp["max_iters_cap"]["iterations"] == 4
+    assert cpp["unsolved_trials"]["accepted"][:4] == [False, False, False, True]
+    assert cpp["more_than_16_iterations"]["iterations"] == 20 and all(v > 0 for v in cpp["more_than_16_iterations"]["trace"])
+
+
+def test_failure_flag_mapping(replay_exe):
+    out = subprocess.run([replay_exe, "flags", "0", "1", "2"], capture_output=True, text=True, check=True).stdout.split()
+    assert out == ["solved", "rejected", "stalled"]      # 2.0: the spin bound of the factorisation expired -> an error

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Phase split of k_chol_step's factoring workgroup (GPU box).  Needs lba_solver.hip compiled with -DLBA_STEP_TIMING:
+"""Phase split of the factoring workgroup of k_chol_step_b, the per-block-column factorisation that lba_solve_batch takes when
+the tiles of all windows exceed one resident launch (here 32 windows of 15 tiles; GPU box).  Needs lba_solver.hip compiled with -DLBA_STEP_TIMING:
   cd orb_slam3-1_amd/csrc && hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -DLBA_STEP_TIMING -c -o lba_solver.o lba_solver.hip \\
      && hipcc --offload-arch=gfx950 -shared -fPIC -o ../liborbslam3_hip.so *.o        (then `make -B` restores the product build)"""
 import ctypes as C
@@ -13,13 +14,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("orb_slam3-1_amd")
 synth = importlib.import_module("orb_slam3-1_amd.synth")
 w = synth.make_ba_window(0)
-s = pkg.LbaSolver()
-s.solve(w, 10)
+s = pkg.LbaBatch()
+s.solve([w] * 32, 10)
 out = (C.c_ulonglong * 8)()
 pkg.lib.lba_debug_step_prof(out)
 pkg.lib.lba_debug_tile_prof(out)
 for _ in range(5):
-    s.solve(w, 10)
+    s.solve([w] * 32, 10)
 pkg.lib.lba_debug_step_prof(out)
 v = list(out)
 n = max(v[7], 1)

@@ -216,9 +216,10 @@ def make_ba_window(seed, n_opt=50, n_fixed=10, n_points=2000, obs_per_point=10, 
 
 
 # ---------------------------------------------------------------- motion-only BA (PoseOptimization)
-def make_pose_problem(seed, n=300, outlier_frac=0.1, stereo_frac=0.0):
+def make_pose_problem(seed, n=300, outlier_frac=0.1, stereo_frac=0.0, noise_px=1.0):
     """One frame for Optimizer::PoseOptimization (reference src/Optimizer.cc:814-1115): n features holding map points,
-    EuRoC pinhole intrinsics, pixel noise by octave, gross outliers, initial pose a few degrees / centimetres off."""
+    EuRoC pinhole intrinsics, pixel noise by octave (scaled by noise_px; the default 1.0 leaves every output bit-identical),
+    gross outliers, initial pose a few degrees / centimetres off."""
     rs = np.random.RandomState(5151 + seed)
     fx, fy, cx, cy = [float(np.float32(v)) for v in (458.654, 457.296, 367.215, 248.375)]
     bf = float(np.float32(47.90639384423901))
@@ -229,13 +230,13 @@ def make_pose_problem(seed, n=300, outlier_frac=0.1, stereo_frac=0.0):
     scale2 = 1.2 ** (2 * np.arange(8))
     octv = rs.randint(0, 8, n)
     sig = np.sqrt(scale2[octv])
-    u = fx * Xc[:, 0] / Xc[:, 2] + cx + rs.normal(0, 1, n) * sig
-    v = fy * Xc[:, 1] / Xc[:, 2] + cy + rs.normal(0, 1, n) * sig
+    u = fx * Xc[:, 0] / Xc[:, 2] + cx + rs.normal(0, 1, n) * sig * noise_px
+    v = fy * Xc[:, 1] / Xc[:, 2] + cy + rs.normal(0, 1, n) * sig * noise_px
     out = rs.uniform(size=n) < outlier_frac
     u[out] += rs.choice([-40.0, 40.0], out.sum())
     v[out] += rs.choice([-25.0, 25.0], out.sum())
     st = (rs.uniform(size=n) < stereo_frac)
-    ur = np.where(st, u - bf / Xc[:, 2] + rs.normal(0, 1, n) * sig, -1.0)
+    ur = np.where(st, u - bf / Xc[:, 2] + rs.normal(0, 1, n) * sig * noise_px, -1.0)
     dR = _rodrigues(rs.normal(0, np.deg2rad(2.0) / np.sqrt(3), 3))
     q0 = _quat_from_R(dR @ R).astype(np.float32).astype(np.float64)
     t0 = (dR @ t + rs.normal(0, 0.05 / np.sqrt(3), 3)).astype(np.float32).astype(np.float64)

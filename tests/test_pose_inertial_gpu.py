@@ -1,5 +1,6 @@
 """PoseInertialOptimizationLastKeyFrame on the device (liba_pose_optimize_batch; reference src/Optimizer.cc:4491-4873) against the
-oracle: identical outlier flags / counters, states and the prior Hessian within 1e-4 relative (observed far tighter).  PARITY UNPINNED."""
+oracle: identical outlier flags / counters, states within 1e-4 relative (observed far tighter), the prior Hessian within 1e-10 of each
+3 x 3 block's own scale.  PARITY UNPINNED."""
 import numpy as np
 import pytest
 
@@ -15,7 +16,20 @@ def _check(r0, r1, pr, tag):
         d0, d1 = r0[k] - ini, r1[k] - ini
         assert np.abs(d0 - d1).max() <= 1e-4 * max(np.abs(d0).max(), 1e-9), (tag, k)
     assert np.abs(r0["Rwb"] - r1["Rwb"]).max() < 1e-7 and np.abs(r0["bg"] - r1["bg"]).max() < 1e-9 and np.abs(r0["ba"] - r1["ba"]).max() < 1e-9, tag
-    assert np.abs(r0["H"] - r1["H"]).max() <= 1e-6 * np.abs(r0["H"]).max(), tag
+    _check_hessian_blocks(r0["H"], r1["H"], tag)
+
+
+def _check_hessian_blocks(H0, H1, tag, rel=1e-10):
+    """H per 3 x 3 block (rotation, translation, velocity, gyro bias, acc bias of each frame): relative to the block's own largest
+    entry, so the visual 6 x 6 block is not measured against info_gyro ~ 1e6 / dt.  1e-10: two f64 sums of the same terms in a
+    different order (observed <= 2e-14); never looser than the former 1e-6 * max|H|, and a block that is zero in the oracle may
+    differ only by rounding far below any entry of H"""
+    hmax = np.abs(H0).max()
+    for i in range(0, H0.shape[0], 3):
+        for j in range(0, H0.shape[1], 3):
+            b0, b1 = H0[i:i + 3, j:j + 3], H1[i:i + 3, j:j + 3]
+            tol = min(rel * hmax, rel * np.abs(b0).max() + 1e-15 * hmax)
+            assert np.abs(b0 - b1).max() <= tol, (tag, "H block", i // 3, j // 3, np.abs(b0 - b1).max(), np.abs(b0).max())
 
 
 def test_pose_inertial_batch_matches_oracle(pkg, oracle, synth):

@@ -752,6 +752,97 @@ typedef struct OrbeCamera {
 int  orbe_undistort_batch_device(orbe_codec* c, const OrbxKeyPoint* d_kps, const int32_t* d_n, int batch, int cap, const OrbeCamera* cam,
                                  OrbxKeyPoint* d_kps_un, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Loop-closing geometry: what runs between SearchByBoW(KF, KF) and the two SearchByProjection(KF, Scw, ...) calls of
+ * LoopClosing::DetectCommonRegionsFromBoW (reference src/LoopClosing.cc:640-830).
+ *
+ * sim3_ransac_batch replaces Sim3Solver::iterate (src/Sim3Solver.cc:149-294) with ComputeSim3 (:311-412) and CheckInliers
+ * (:415-439) for pinhole cameras: float inputs, float T12 and a float inlier test like the reference; Horn's closed form in
+ * between runs in double, so that T12 is exact to the rounding of its float outputs whatever the conditioning of a triple.
+ * The caller flattens what the constructor derives (:35-121):
+ * correspondence k is the k-th match i1 that passes the tests of :73-91 (mvnIndices1[k] = i1).  All n_hyp hypotheses of a
+ * problem are evaluated in one launch, one workgroup per problem; the selection is the one `iterate` would have made had it
+ * been called until it converged or ran out (mnBestInliers starts at 0): the FIRST hypothesis with count > min_inliers;
+ * without one, converged = 0 and index = the LAST hypothesis that attains the maximum count (the >= at :192, :265).
+ * n < min_inliers (bNoMore at :155-159) or n < 3: nothing is scored, scored = 0, index = -1, every output array is zero.
+ * The index triples are an INPUT (the reference draws them with libc rand, :172-186): see sim3_draw_triples.
+ * Up to SIM3_LDS_CORRESPONDENCES correspondences are staged in LDS; larger problems are read from global memory.
+ * One handle owns one stream and its workspace (grown on demand, no allocation once warm): one thread per handle at a time.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SIM3_LDS_CORRESPONDENCES 1024
+#define SIM3_MAX_HYPOTHESES 1024
+typedef struct Sim3RansacProblem {
+    int32_t n;                      /* correspondences, N of :129 */
+    const float* X1c;               /* [n][3] mvX3Dc1: Rcw1 * pMP1->GetWorldPos() + tcw1 (:106-107) */
+    const float* X2c;               /* [n][3] mvX3Dc2 (:109-110) */
+    const float* max_err1;          /* [n] mvnMaxError1: 9.210 * mvLevelSigma2[kp1.octave] as stored, i.e. truncated by the
+                                       vector<size_t> (:99, include/Sim3Solver.h:78) */
+    const float* max_err2;          /* [n] mvnMaxError2 (:100) */
+    float fx1, fy1, cx1, cy1;       /* pCamera1 (pinhole); mvP1im1 = project(X1c) is computed on the device (:117) */
+    float fx2, fy2, cx2, cy2;       /* pCamera2 (:118) */
+    int32_t fix_scale;              /* mbFixScale */
+    int32_t min_inliers;            /* mRansacMinInliers */
+    int32_t n_hyp;                  /* mRansacMaxIts after SetRansacParameters (:144), 1 .. SIM3_MAX_HYPOTHESES */
+    const int32_t* triples;         /* [n_hyp][3] indices into the correspondences, each in [0, n) */
+} Sim3RansacProblem;
+
+typedef struct Sim3RansacResult {
+    int32_t converged;              /* out: bConverge */
+    int32_t index;                  /* out: the selected hypothesis (mBestT12 = T12[index], mvbBestInliers = mask[index]) */
+    int32_t scored;                 /* out: 0 when n < min_inliers or n < 3 */
+    int32_t* count;                 /* in: [n_hyp] buffer or NULL; out: mnInliersi of every hypothesis */
+    float* T12;                     /* in: [n_hyp][13] buffer or NULL; out: mR12i row-major (9), mt12i (3), ms12i (1) */
+    uint64_t* mask;                 /* in: [n_hyp][(n + 63) / 64] buffer or NULL; out: bit k % 64 of word k / 64 = mvbInliersi[k] */
+} Sim3RansacResult;
+
+typedef struct sim3_solver sim3_solver;
+int  sim3_create(int device, sim3_solver** out);
+void sim3_destroy(sim3_solver* s);
+int  sim3_ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_problems, Sim3RansacResult* results);
+/* The draw of :172-186 (pick a slot of the list of available indices, move the last entry into it, shrink; three times per
+ * hypothesis, the list restored per hypothesis) with a generator that is part of this interface: splitmix64, state = seed,
+ * state += 0x9E3779B97F4A7C15 per draw, z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; z ^= z >> 31; slot = z % (entries available).  Host only.  out[n_hyp][3]; n >= 3. */
+int  sim3_draw_triples(uint64_t seed, int n, int n_hyp, int32_t* out);
+/* device time of the kernel of the LAST call (HIP events on the solver's stream), milliseconds */
+float sim3_last_kernel_ms(const sim3_solver* s);
+
+/* sim3_optimize_batch replaces  int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1,
+ * g2o::Sim3& g2oS12, const float th2, const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints)
+ * (src/Optimizer.cc:2115-2381) for pinhole cameras, in double: the edges EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ
+ * (include/OptimizableTypes.h:175-215) with g2o's numeric Jacobians (central differences, delta = 1e-9, through
+ * VertexSim3Expmap::oplusImpl), Huber kernels and Levenberg (optimize(5), the chi2 > th2 drop, optimize(5 or 10), the final
+ * test) in one launch, one workgroup per problem.  The caller flattens the graph: one PAIR of edges per match i that reaches
+ * :2241 (vpMatches1[i] and vpMapPoints1[i] both set and not bad :2183-2207; i2 >= 0 or bAllPoints :2229; P3D2c.z >= 0 :2235),
+ * in the order of i.  Fewer than 10 pairs after the drop: n_in = 0 and q, t, s are the input (:2348-2349). */
+typedef struct Sim3OptProblem {
+    double q[4], t[3], s;           /* g2oS12: rotation qx qy qz qw (used as given, g2o::Sim3 does not normalise), translation, scale */
+    int32_t n;                      /* edge pairs (nCorrespondences) */
+    const double* X1c;              /* [n][3] P3D1c = R1w * P3D1w + t1w in float, cast to double (:2188-2190) */
+    const double* X2c;              /* [n][3] P3D2c (:2196-2198) */
+    const double* obs1;             /* [n][2] pKF1->mvKeysUn[i].pt (:2244-2246) */
+    const double* obs2;             /* [n][2] pKF2->mvKeysUn[i2].pt, or for i2 < 0 the float (x/z, y/z) of P3D2c (:2265-2284) */
+    const double* inv_sigma2_1;     /* [n] pKF1->mvInvLevelSigma2[kpUn1.octave] (:2253-2254) */
+    const double* inv_sigma2_2;     /* [n] pKF2->mvInvLevelSigma2[kpUn2.octave]; octave = pMP2->mnTrackScaleLevel for i2 < 0 (:2280, :2291) */
+    double fx1, fy1, cx1, cy1;      /* vSim3->pCamera1 (:2140) */
+    double fx2, fy2, cx2, cy2;      /* vSim3->pCamera2 (:2141) */
+    double th2;                     /* (double)th2 of the float argument (:2320, :2367) */
+    double huber_delta;             /* (double)deltaHuber, deltaHuber = float sqrt(th2) (:2157) */
+    int32_t fix_scale;              /* vSim3->_fix_scale (:2136) */
+} Sim3OptProblem;
+
+typedef struct Sim3OptResult {
+    double q[4], t[3], s;           /* g2oS12 on return */
+    int32_t n_in;                   /* the function's return value */
+    int32_t n_bad;                  /* pairs dropped after the first optimize (nBad) */
+    int32_t iterations[2], trials[2];   /* per optimize(): outer iterations and Levenberg trials executed */
+    int32_t stop_reason[2];         /* 0 iteration cap, 1 ten trials or rho == 0, 2 three iterations below 1e-3 relative gain */
+    double chi2[2];                 /* per optimize(): activeRobustChi2 after the last trial */
+} Sim3OptResult;
+/* keep_out (may be NULL or hold NULL entries): keep_out[p][k] = 1 iff the match of pair k is still set in vpMatches1 on
+ * return (0: nulled at :2323 or :2369).  mAcumHessian is only zeroed by the reference (:2356); the caller does the same. */
+int  sim3_optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problems, Sim3OptResult* results, uint8_t* const* keep_out);
+
 #ifdef __cplusplus
 }
 #endif

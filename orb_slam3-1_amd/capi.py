@@ -1292,3 +1292,155 @@ InertialSolver.pose_prepare = _pose_inertial_prepare
 InertialSolver.pose_launch = _pose_inertial_launch
 InertialSolver.pose_results = _pose_inertial_results
 InertialSolver.pose_optimize_batch = _pose_inertial_batch
+
+
+class Sim3RansacProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("n_hyp", C.c_int32), ("triples", C.c_void_p)]
+
+
+class Sim3RansacResult(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("index", C.c_int32), ("scored", C.c_int32),
+                ("count", C.c_void_p), ("T12", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class Sim3OptProblem(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("n", C.c_int32),
+                ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
+                ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p),
+                ("fx1", C.c_double), ("fy1", C.c_double), ("cx1", C.c_double), ("cy1", C.c_double),
+                ("fx2", C.c_double), ("fy2", C.c_double), ("cx2", C.c_double), ("cy2", C.c_double),
+                ("th2", C.c_double), ("huber_delta", C.c_double), ("fix_scale", C.c_int32)]
+
+
+class Sim3OptResult(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("n_in", C.c_int32), ("n_bad", C.c_int32),
+                ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("stop_reason", C.c_int32 * 2), ("chi2", C.c_double * 2)]
+
+
+SIM3_LDS_CORRESPONDENCES = 1024
+SIM3_MAX_HYPOTHESES = 1024
+
+
+def sim3_draw_triples(seed, n, n_hyp):
+    """sim3_draw_triples: the draw-three-without-replacement of Sim3Solver::iterate (src/Sim3Solver.cc:172-186) with the
+    header's splitmix64 generator; host only (needs no device).  Returns int32 [n_hyp][3]."""
+    lib.sim3_draw_triples.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+    out = np.zeros((max(n_hyp, 0), 3), np.int32)
+    _check(lib.sim3_draw_triples(int(seed), int(n), int(n_hyp), _p(out)))
+    return out
+
+
+class Sim3Solver:
+    """Sim3Solver::iterate (reference src/Sim3Solver.cc) and Optimizer::OptimizeSim3 (src/Optimizer.cc:2115-2381): one workgroup
+    per problem, a batch per launch."""
+
+    def __init__(self, device=0):
+        lib.sim3_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.sim3_destroy.argtypes = [C.c_void_p]
+        lib.sim3_ransac_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.sim3_optimize_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.sim3_last_kernel_ms.restype = C.c_float
+        lib.sim3_last_kernel_ms.argtypes = [C.c_void_p]
+        h = C.c_void_p()
+        _check(lib.sim3_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.sim3_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_kernel_ms(self):
+        return float(lib.sim3_last_kernel_ms(self._h))
+
+    def ransac_prepare(self, problems):
+        """flatten a list of problems once: dict(X1c, X2c [n][3], max_err1, max_err2 [n], K1, K2 (fx fy cx cy), fix_scale,
+        min_inliers, triples [H][3])"""
+        B = len(problems)
+        prs, res = (Sim3RansacProblem * B)(), (Sim3RansacResult * B)()
+        keep, outs = [], []
+        for i, w in enumerate(problems):
+            a = [np.ascontiguousarray(w["X1c"], np.float32).reshape(-1, 3), np.ascontiguousarray(w["X2c"], np.float32).reshape(-1, 3),
+                 np.ascontiguousarray(w["max_err1"], np.float32), np.ascontiguousarray(w["max_err2"], np.float32),
+                 np.ascontiguousarray(w["triples"], np.int32).reshape(-1, 3)]
+            n = len(a[0])
+            if not (a[1].shape == (n, 3) and a[2].shape == (n,) and a[3].shape == (n,)):     # the C side copies n rows of each array
+                raise ValueError("problem %d: X2c / max_err1 / max_err2 do not hold %d correspondences" % (i, n))
+            keep.append(a)
+            p = prs[i]
+            p.n, p.n_hyp = n, len(a[4])
+            p.X1c, p.X2c, p.max_err1, p.max_err2, p.triples = (x.ctypes.data for x in a)
+            p.fx1, p.fy1, p.cx1, p.cy1 = (float(v) for v in w["K1"])
+            p.fx2, p.fy2, p.cx2, p.cy2 = (float(v) for v in w["K2"])
+            p.fix_scale, p.min_inliers = int(bool(w["fix_scale"])), int(w["min_inliers"])
+            o = dict(count=np.zeros(p.n_hyp, np.int32), T12=np.zeros((p.n_hyp, 13), np.float32),
+                     mask=np.zeros((p.n_hyp, (p.n + 63) // 64), np.uint64))
+            res[i].count, res[i].T12, res[i].mask = o["count"].ctypes.data, o["T12"].ctypes.data, o["mask"].ctypes.data
+            outs.append(o)
+        return dict(B=B, prs=prs, res=res, keep=keep, outs=outs)
+
+    def ransac_launch(self, prep):
+        """the C call alone: upload, one kernel launch, download"""
+        _check(lib.sim3_ransac_batch(self._h, prep["prs"], prep["B"], prep["res"]))
+
+    def ransac_results(self, prep):
+        return [dict(converged=int(r.converged), index=int(r.index), scored=int(r.scored), count=o["count"].copy(), T12=o["T12"].copy(),
+                     mask=o["mask"].copy()) for r, o in zip(prep["res"], prep["outs"])]
+
+    def ransac_batch(self, problems):
+        prep = self.ransac_prepare(problems)
+        self.ransac_launch(prep)
+        return self.ransac_results(prep)
+
+    def ransac(self, w):
+        return self.ransac_batch([w])[0]
+
+    def optimize_prepare(self, problems):
+        """flatten a list of problems once: dict(q (x y z w), t, s, X1c, X2c [n][3], obs1, obs2 [n][2], inv_sigma2_1/2 [n], K1, K2,
+        th2, huber_delta, fix_scale)"""
+        B = len(problems)
+        prs, res = (Sim3OptProblem * B)(), (Sim3OptResult * B)()
+        keep, outs = [], []
+        for i, w in enumerate(problems):
+            a = [np.ascontiguousarray(w[k], np.float64) for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")]
+            n = len(a[4])
+            if [x.size for x in a] != [3 * n, 3 * n, 2 * n, 2 * n, n, n]:                    # the C side copies n rows of each array
+                raise ValueError("problem %d: the arrays do not hold %d edge pairs each" % (i, n))
+            keep.append(a)
+            p = prs[i]
+            p.q[:] = [float(v) for v in w["q"]]
+            p.t[:] = [float(v) for v in w["t"]]
+            p.s = float(w["s"])
+            p.n = len(a[4])
+            p.X1c, p.X2c, p.obs1, p.obs2, p.inv_sigma2_1, p.inv_sigma2_2 = (x.ctypes.data for x in a)
+            p.fx1, p.fy1, p.cx1, p.cy1 = (float(v) for v in w["K1"])
+            p.fx2, p.fy2, p.cx2, p.cy2 = (float(v) for v in w["K2"])
+            p.th2, p.huber_delta, p.fix_scale = float(w["th2"]), float(w["huber_delta"]), int(bool(w["fix_scale"]))
+            outs.append(np.zeros(max(p.n, 1), np.uint8))
+        ptrs = (C.c_void_p * B)(*[o.ctypes.data for o in outs])
+        return dict(B=B, prs=prs, res=res, keep=keep, outs=outs, ptrs=ptrs)
+
+    def optimize_launch(self, prep):
+        _check(lib.sim3_optimize_batch(self._h, prep["prs"], prep["B"], prep["res"], prep["ptrs"]))
+
+    def optimize_results(self, prep):
+        return [dict(q=np.array(r.q[:]), t=np.array(r.t[:]), s=float(r.s), n_in=int(r.n_in), n_bad=int(r.n_bad),
+                     iterations=list(r.iterations), trials=list(r.trials), stop_reason=list(r.stop_reason), chi2=list(r.chi2),
+                     keep=prep["outs"][i][:prep["prs"][i].n].astype(bool)) for i, r in enumerate(prep["res"])]
+
+    def optimize_batch(self, problems):
+        prep = self.optimize_prepare(problems)
+        self.optimize_launch(prep)
+        return self.optimize_results(prep)
+
+    def optimize(self, w):
+        return self.optimize_batch([w])[0]

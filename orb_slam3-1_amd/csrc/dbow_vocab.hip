@@ -18,17 +18,7 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
-
-namespace orbx {
-int fail(int code, const char* fmt, ...);
-}
-using orbx::fail;
-
-#define ORBV_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#include "hip_check.h"
 
 namespace orbv {
 
@@ -304,7 +294,7 @@ int enqueue_transform(orbv_vocab* v, const uint8_t* d_desc, const int32_t* d_n, 
         hipLaunchKernelGGL(orbv::k_vocab_assemble, dim3(batch), dim3(256), (size_t)n_pow2 * 16, st, d_n, n_fixed, cap, n_pow2, d_word, d_weight, d_node,
                            d_bow_id, d_bow_val, d_n_bow, d_fv_node, d_fv_off, d_fv_feat, d_n_fv);
     }
-    ORBV_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 }  // namespace
@@ -329,7 +319,7 @@ int orbv_create(int device, const OrbvVocabulary* voc, orbv_vocab** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBV_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     orbv_vocab* v = new orbv_vocab();
     v->device = device;
     const size_t o_off = 0, o_cid = al(o_off + sizeof(int32_t) * ((size_t)nn + 1)), o_desc = al(o_cid + sizeof(uint32_t) * (size_t)std::max(n_child, 1)),
@@ -382,19 +372,19 @@ int orbv_transform_features(orbv_vocab* v, const uint8_t* desc, int n, int level
 {
     if (!v || n < 0 || (n > 0 && (!desc || !word || !weight || !node))) return fail(ORBX_ERR_ARG, "bad arguments");
     if (n == 0) return ORBX_OK;
-    ORBV_HIP(hipSetDevice(v->device));
+    ORBX_HIP(hipSetDevice(v->device));
     const size_t o_d = 0, o_wd = al((size_t)n * 32), o_wt = al(o_wd + 4 * (size_t)n), o_nd = al(o_wt + 8 * (size_t)n), total = al(o_nd + 4 * (size_t)n);
     int r = v->ensure(total);
     if (r) return r;
     uint8_t* b = v->d_scratch;
-    ORBV_HIP(hipMemcpyAsync(b + o_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
+    ORBX_HIP(hipMemcpyAsync(b + o_d, desc, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
     r = enqueue_transform(v, b + o_d, nullptr, n, 1, n, levelsup, (uint32_t*)(b + o_wd), (double*)(b + o_wt), (uint32_t*)(b + o_nd),
                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, v->stream, false);
     if (r) return r;
-    ORBV_HIP(hipMemcpyAsync(word, b + o_wd, 4 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
-    ORBV_HIP(hipMemcpyAsync(weight, b + o_wt, 8 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
-    ORBV_HIP(hipMemcpyAsync(node, b + o_nd, 4 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
-    ORBV_HIP(hipStreamSynchronize(v->stream));
+    ORBX_HIP(hipMemcpyAsync(word, b + o_wd, 4 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
+    ORBX_HIP(hipMemcpyAsync(weight, b + o_wt, 8 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
+    ORBX_HIP(hipMemcpyAsync(node, b + o_nd, 4 * (size_t)n, hipMemcpyDeviceToHost, v->stream));
+    ORBX_HIP(hipStreamSynchronize(v->stream));
     return ORBX_OK;
 }
 
@@ -405,33 +395,33 @@ int orbv_transform(orbv_vocab* v, const uint8_t* desc, int n, int levelsup, uint
         return fail(ORBX_ERR_ARG, "bad arguments");
     if (n == 0) { *n_bow = 0; *n_fv_nodes = 0; fv_off[0] = 0; return 0; }
     if (n > 8192) return fail(ORBX_ERR_ARG, "more than 8192 features per frame are not supported");
-    ORBV_HIP(hipSetDevice(v->device));
+    ORBX_HIP(hipSetDevice(v->device));
     const size_t N = (size_t)n;
     const size_t o_d = 0, o_wd = al(N * 32), o_wt = al(o_wd + 4 * N), o_nd = al(o_wt + 8 * N), o_bi = al(o_nd + 4 * N), o_bv = al(o_bi + 4 * N),
                  o_fn = al(o_bv + 8 * N), o_fo = al(o_fn + 4 * N), o_ff = al(o_fo + 4 * (N + 1)), o_cnt = al(o_ff + 4 * N), total = al(o_cnt + 8);
     int r = v->ensure(total);
     if (r) return r;
     uint8_t* b = v->d_scratch;
-    ORBV_HIP(hipMemcpyAsync(b + o_d, desc, N * 32, hipMemcpyHostToDevice, v->stream));
+    ORBX_HIP(hipMemcpyAsync(b + o_d, desc, N * 32, hipMemcpyHostToDevice, v->stream));
     r = enqueue_transform(v, b + o_d, nullptr, n, 1, n, levelsup, (uint32_t*)(b + o_wd), (double*)(b + o_wt), (uint32_t*)(b + o_nd),
                           (uint32_t*)(b + o_bi), (double*)(b + o_bv), (int32_t*)(b + o_cnt), (uint32_t*)(b + o_fn), (int32_t*)(b + o_fo),
                           (uint32_t*)(b + o_ff), (int32_t*)(b + o_cnt) + 1, v->stream, true);
     if (r) return r;
     int32_t cnt[2] = {0, 0};
-    ORBV_HIP(hipMemcpyAsync(cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, v->stream));
-    ORBV_HIP(hipStreamSynchronize(v->stream));
+    ORBX_HIP(hipMemcpyAsync(cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, v->stream));
+    ORBX_HIP(hipStreamSynchronize(v->stream));
     *n_bow = cnt[0]; *n_fv_nodes = cnt[1];
     if (cnt[0] > 0) {
-        ORBV_HIP(hipMemcpyAsync(bow_id, b + o_bi, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost, v->stream));
-        ORBV_HIP(hipMemcpyAsync(bow_val, b + o_bv, 8 * (size_t)cnt[0], hipMemcpyDeviceToHost, v->stream));
+        ORBX_HIP(hipMemcpyAsync(bow_id, b + o_bi, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost, v->stream));
+        ORBX_HIP(hipMemcpyAsync(bow_val, b + o_bv, 8 * (size_t)cnt[0], hipMemcpyDeviceToHost, v->stream));
     }
-    ORBV_HIP(hipMemcpyAsync(fv_off, b + o_fo, 4 * ((size_t)cnt[1] + 1), hipMemcpyDeviceToHost, v->stream));
-    if (cnt[1] > 0) ORBV_HIP(hipMemcpyAsync(fv_node, b + o_fn, 4 * (size_t)cnt[1], hipMemcpyDeviceToHost, v->stream));
-    ORBV_HIP(hipStreamSynchronize(v->stream));
+    ORBX_HIP(hipMemcpyAsync(fv_off, b + o_fo, 4 * ((size_t)cnt[1] + 1), hipMemcpyDeviceToHost, v->stream));
+    if (cnt[1] > 0) ORBX_HIP(hipMemcpyAsync(fv_node, b + o_fn, 4 * (size_t)cnt[1], hipMemcpyDeviceToHost, v->stream));
+    ORBX_HIP(hipStreamSynchronize(v->stream));
     const int used = fv_off[cnt[1]];
     if (used > 0) {
-        ORBV_HIP(hipMemcpyAsync(fv_feat, b + o_ff, 4 * (size_t)used, hipMemcpyDeviceToHost, v->stream));
-        ORBV_HIP(hipStreamSynchronize(v->stream));
+        ORBX_HIP(hipMemcpyAsync(fv_feat, b + o_ff, 4 * (size_t)used, hipMemcpyDeviceToHost, v->stream));
+        ORBX_HIP(hipStreamSynchronize(v->stream));
     }
     return used;
 }
@@ -442,7 +432,7 @@ int orbv_transform_batch_device(orbv_vocab* v, const uint8_t* d_desc, const int3
 {
     if (!v || batch < 1 || cap < 1 || !d_desc || !d_n || !d_bow_id || !d_bow_val || !d_n_bow || !d_fv_node || !d_fv_off || !d_fv_feat || !d_n_fv)
         return fail(ORBX_ERR_ARG, "bad arguments");
-    ORBV_HIP(hipSetDevice(v->device));
+    ORBX_HIP(hipSetDevice(v->device));
     const size_t T = (size_t)batch * cap;
     const size_t o_wd = 0, o_wt = al(4 * T), o_nd = al(o_wt + 8 * T), total = al(o_nd + 4 * T);
     const int r = v->ensure(total);

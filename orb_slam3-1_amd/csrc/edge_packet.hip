@@ -19,17 +19,7 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
-
-namespace orbx {
-int fail(int code, const char* fmt, ...);
-}
-using orbx::fail;
-
-#define ORBE_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#include "hip_check.h"
 
 namespace orbe {
 
@@ -184,7 +174,7 @@ struct orbe_codec {
         if (bytes <= d_bytes) return ORBX_OK;
         if (d_buf) (void)hipFree(d_buf);
         d_buf = nullptr; d_bytes = 0;
-        ORBE_HIP(hipMalloc((void**)&d_buf, bytes));
+        ORBX_HIP(hipMalloc((void**)&d_buf, bytes));
         d_bytes = bytes;
         return ORBX_OK;
     }
@@ -210,7 +200,7 @@ int orbe_create(int device, orbe_codec** out)
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(ORBX_ERR_NO_DEVICE, "no HIP device: the packet codec runs on the GPU only");
     if (device < 0 || device >= count) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBE_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     orbe_codec* c = new orbe_codec;
     c->device = device;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(ORBX_ERR_HIP, "stream"); }
@@ -236,10 +226,10 @@ int orbe_pack_batch_device(orbe_codec* c, const OrbxKeyPoint* d_kps, const uint8
     if ((d_imu == nullptr) != (d_imu_off == nullptr)) return fail(ORBX_ERR_ARG, "d_imu and d_imu_off go together");
     if (stride < orbe::kInfoLen || (stride & 3) || !aligned4(d_payload) || !aligned4(d_desc))
         return fail(ORBX_ERR_ARG, "packet stride must be a multiple of 4 (>= 16) and the buffers 4-byte aligned");
-    ORBE_HIP(hipSetDevice(c->device));
+    ORBX_HIP(hipSetDevice(c->device));
     hipLaunchKernelGGL(orbe::k_pack_packets, dim3(batch), dim3(orbe::kThreads), 0, (hipStream_t)stream, d_kps, d_desc, d_n, cap, d_frame_id,
                        d_timestamp, d_imu, d_imu_off, d_payload, stride, d_len, d_head, d_status);
-    ORBE_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -252,10 +242,10 @@ int orbe_unpack_batch_device(orbe_codec* c, const uint8_t* d_payload, int stride
     if (imu_cap > 0 && !d_imu) return fail(ORBX_ERR_ARG, "imu_cap > 0 needs d_imu");
     if (stride < orbe::kInfoLen || (stride & 3) || !aligned4(d_payload) || !aligned4(d_desc))
         return fail(ORBX_ERR_ARG, "packet stride must be a multiple of 4 (>= 16) and the buffers 4-byte aligned");
-    ORBE_HIP(hipSetDevice(c->device));
+    ORBX_HIP(hipSetDevice(c->device));
     hipLaunchKernelGGL(orbe::k_unpack_packets, dim3(batch), dim3(orbe::kThreads), 0, (hipStream_t)stream, d_payload, stride, d_len, cap,
                        imu_cap > 0 ? imu_cap : 1, d_kps, d_desc, d_n, d_frame_id, d_timestamp, imu_cap > 0 ? d_imu : nullptr, d_n_imu, d_status);
-    ORBE_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -270,7 +260,7 @@ int orbe_pack_batch(orbe_codec* c, const OrbxKeyPoint* kps, const uint8_t* desc,
     if (stride < orbe::kInfoLen || (stride & 3)) return fail(ORBX_ERR_ARG, "packet stride must be a multiple of 4 (>= 16)");
     const int n_imu = imu ? imu_off[batch] : 0;
     if (n_imu < 0) return fail(ORBX_ERR_ARG, "bad imu offsets");
-    ORBE_HIP(hipSetDevice(c->device));
+    ORBX_HIP(hipSetDevice(c->device));
     const size_t B = (size_t)batch;
     const size_t o_kps = 0, o_desc = al(o_kps + B * cap * sizeof(OrbxKeyPoint)), o_n = al(o_desc + B * cap * 32), o_id = al(o_n + 4 * B),
                  o_ts = al(o_id + 4 * B), o_imu = al(o_ts + 8 * B), o_ioff = al(o_imu + (size_t)n_imu * sizeof(OrbeImuSample)),
@@ -280,26 +270,26 @@ int orbe_pack_batch(orbe_codec* c, const OrbxKeyPoint* kps, const uint8_t* desc,
     if (r) return r;
     uint8_t* d = c->d_buf;
     hipStream_t s = c->stream;
-    ORBE_HIP(hipMemcpyAsync(d + o_kps, kps, B * cap * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemcpyAsync(d + o_desc, desc, B * cap * 32, hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemcpyAsync(d + o_n, n, 4 * B, hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemcpyAsync(d + o_id, frame_id, 4 * B, hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemcpyAsync(d + o_ts, timestamp, 8 * B, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_kps, kps, B * cap * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_desc, desc, B * cap * 32, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_n, n, 4 * B, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_id, frame_id, 4 * B, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_ts, timestamp, 8 * B, hipMemcpyHostToDevice, s));
     if (imu) {
-        if (n_imu) ORBE_HIP(hipMemcpyAsync(d + o_imu, imu, (size_t)n_imu * sizeof(OrbeImuSample), hipMemcpyHostToDevice, s));
-        ORBE_HIP(hipMemcpyAsync(d + o_ioff, imu_off, 4 * (B + 1), hipMemcpyHostToDevice, s));
+        if (n_imu) ORBX_HIP(hipMemcpyAsync(d + o_imu, imu, (size_t)n_imu * sizeof(OrbeImuSample), hipMemcpyHostToDevice, s));
+        ORBX_HIP(hipMemcpyAsync(d + o_ioff, imu_off, 4 * (B + 1), hipMemcpyHostToDevice, s));
     }
-    ORBE_HIP(hipMemsetAsync(d + o_pay, 0, B * stride, s));
+    ORBX_HIP(hipMemsetAsync(d + o_pay, 0, B * stride, s));
     r = orbe_pack_batch_device(c, (const OrbxKeyPoint*)(d + o_kps), d + o_desc, (const int32_t*)(d + o_n), batch, cap, (const int32_t*)(d + o_id),
                                (const int64_t*)(d + o_ts), imu ? (const OrbeImuSample*)(d + o_imu) : nullptr,
                                imu ? (const int32_t*)(d + o_ioff) : nullptr, d + o_pay, stride, (int32_t*)(d + o_len), d + o_head,
                                (int32_t*)(d + o_st), s);
     if (r) return r;
-    ORBE_HIP(hipMemcpyAsync(payload, d + o_pay, B * stride, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(len, d + o_len, 4 * B, hipMemcpyDeviceToHost, s));
-    if (head) ORBE_HIP(hipMemcpyAsync(head, d + o_head, 2 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(status, d + o_st, 4 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipStreamSynchronize(s));
+    ORBX_HIP(hipMemcpyAsync(payload, d + o_pay, B * stride, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(len, d + o_len, 4 * B, hipMemcpyDeviceToHost, s));
+    if (head) ORBX_HIP(hipMemcpyAsync(head, d + o_head, 2 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(status, d + o_st, 4 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
@@ -311,7 +301,7 @@ int orbe_unpack_batch(orbe_codec* c, const uint8_t* payload, int stride, const i
         return fail(ORBX_ERR_ARG, "bad arguments");
     if (imu_cap > 0 && !imu) return fail(ORBX_ERR_ARG, "imu_cap > 0 needs imu");
     if (stride < orbe::kInfoLen || (stride & 3)) return fail(ORBX_ERR_ARG, "packet stride must be a multiple of 4 (>= 16)");
-    ORBE_HIP(hipSetDevice(c->device));
+    ORBX_HIP(hipSetDevice(c->device));
     const size_t B = (size_t)batch;
     const size_t o_pay = 0, o_len = al(o_pay + B * stride), o_kps = al(o_len + 4 * B), o_desc = al(o_kps + B * cap * sizeof(OrbxKeyPoint)),
                  o_n = al(o_desc + B * cap * 32), o_id = al(o_n + 4 * B), o_ts = al(o_id + 4 * B),
@@ -321,23 +311,23 @@ int orbe_unpack_batch(orbe_codec* c, const uint8_t* payload, int stride, const i
     if (r) return r;
     uint8_t* d = c->d_buf;
     hipStream_t s = c->stream;
-    ORBE_HIP(hipMemcpyAsync(d + o_pay, payload, B * stride, hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemcpyAsync(d + o_len, len, 4 * B, hipMemcpyHostToDevice, s));
-    ORBE_HIP(hipMemsetAsync(d + o_kps, 0, o_n - o_kps, s));
-    if (imu_cap > 0) ORBE_HIP(hipMemsetAsync(d + o_imu, 0, o_ni - o_imu, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_pay, payload, B * stride, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemcpyAsync(d + o_len, len, 4 * B, hipMemcpyHostToDevice, s));
+    ORBX_HIP(hipMemsetAsync(d + o_kps, 0, o_n - o_kps, s));
+    if (imu_cap > 0) ORBX_HIP(hipMemsetAsync(d + o_imu, 0, o_ni - o_imu, s));
     r = orbe_unpack_batch_device(c, d + o_pay, stride, (const int32_t*)(d + o_len), batch, cap, imu_cap, (OrbxKeyPoint*)(d + o_kps), d + o_desc,
                                  (int32_t*)(d + o_n), (int32_t*)(d + o_id), (int64_t*)(d + o_ts),
                                  imu_cap > 0 ? (OrbeImuSample*)(d + o_imu) : nullptr, (int32_t*)(d + o_ni), (int32_t*)(d + o_st), s);
     if (r) return r;
-    ORBE_HIP(hipMemcpyAsync(n, d + o_n, 4 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(n_imu, d + o_ni, 4 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(status, d + o_st, 4 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(frame_id, d + o_id, 4 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(timestamp, d + o_ts, 8 * B, hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipMemcpyAsync(kps, d + o_kps, B * cap * sizeof(OrbxKeyPoint), hipMemcpyDeviceToHost, s));      // rows past n[b] are zero
-    ORBE_HIP(hipMemcpyAsync(desc, d + o_desc, B * cap * 32, hipMemcpyDeviceToHost, s));
-    if (imu_cap > 0) ORBE_HIP(hipMemcpyAsync(imu, d + o_imu, B * imu_cap * sizeof(OrbeImuSample), hipMemcpyDeviceToHost, s));
-    ORBE_HIP(hipStreamSynchronize(s));
+    ORBX_HIP(hipMemcpyAsync(n, d + o_n, 4 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(n_imu, d + o_ni, 4 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(status, d + o_st, 4 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(frame_id, d + o_id, 4 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(timestamp, d + o_ts, 8 * B, hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipMemcpyAsync(kps, d + o_kps, B * cap * sizeof(OrbxKeyPoint), hipMemcpyDeviceToHost, s));      // rows past n[b] are zero
+    ORBX_HIP(hipMemcpyAsync(desc, d + o_desc, B * cap * 32, hipMemcpyDeviceToHost, s));
+    if (imu_cap > 0) ORBX_HIP(hipMemcpyAsync(imu, d + o_imu, B * imu_cap * sizeof(OrbeImuSample), hipMemcpyDeviceToHost, s));
+    ORBX_HIP(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
@@ -346,11 +336,11 @@ int orbe_undistort_batch_device(orbe_codec* c, const OrbxKeyPoint* d_kps, const 
 {
     if (!c || !d_kps || !d_n || !cam || !d_kps_un || batch < 1 || cap < 1) return fail(ORBX_ERR_ARG, "bad arguments");
     if (!(cam->fx != 0.0f) || !(cam->fy != 0.0f)) return fail(ORBX_ERR_ARG, "bad camera matrix");
-    ORBE_HIP(hipSetDevice(c->device));
+    ORBX_HIP(hipSetDevice(c->device));
     const int total = batch * cap;
     hipLaunchKernelGGL(orbe::k_undistort, dim3((total + orbe::kThreads - 1) / orbe::kThreads), dim3(orbe::kThreads), 0, (hipStream_t)stream, d_kps, d_n, cap, total,
                        *cam, d_kps_un);
-    ORBE_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 

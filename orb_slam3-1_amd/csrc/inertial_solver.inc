@@ -1471,7 +1471,7 @@ struct liba_solver {
         const size_t bytes = (std::max(count, (size_t)1) * sizeof(T) + 255) & ~(size_t)255;
         wanted += bytes;
         if (arena && arena_off + bytes <= arena_cap) { *p = (T*)(arena + arena_off); arena_off += bytes; return ORBX_OK; }
-        LBA_HIP(hipMalloc((void**)p, bytes));
+        ORBX_HIP(hipMalloc((void**)p, bytes));
         allocs.push_back(*p);
         return ORBX_OK;
     }
@@ -1497,12 +1497,12 @@ struct liba_solver {
             else pending.push_back(std::make_pair(off, bytes));
             return ORBX_OK;
         }
-        LBA_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, stream));
+        ORBX_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, stream));
         return ORBX_OK;
     }
     int flush()
     {
-        for (const auto& sg : pending) LBA_HIP(hipMemcpyAsync(arena + sg.first, h_mirror + sg.first, sg.second, hipMemcpyHostToDevice, stream));
+        for (const auto& sg : pending) ORBX_HIP(hipMemcpyAsync(arena + sg.first, h_mirror + sg.first, sg.second, hipMemcpyHostToDevice, stream));
         pending.clear();
         return ORBX_OK;
     }
@@ -1526,8 +1526,8 @@ struct liba_solver {
 
 static int liba_kernel_attributes()
 {
-    LBA_HIP(hipFuncSetAttribute((const void*)liba::ki_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
-    LBA_HIP(hipFuncSetAttribute((const void*)liba::ki_solve_update, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    ORBX_HIP(hipFuncSetAttribute((const void*)liba::ki_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
+    ORBX_HIP(hipFuncSetAttribute((const void*)liba::ki_solve_update, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     return ORBX_OK;
 }
 
@@ -1540,7 +1540,7 @@ int liba_create(int device, liba_solver** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     liba_solver* s = new liba_solver();
     s->device = device;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return fail(ORBX_ERR_HIP, "stream creation failed"); }
@@ -1734,7 +1734,7 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     const auto t_start = std::chrono::steady_clock::now();
     int r = ORBX_OK;
     for (int i = 0; i < W; i++) if ((r = liba_validate(&problems[i]))) return r;
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     for (int i = 0; i < W; i++) slots[i]->release();
     auto cleanup = [&]() { for (int i = 0; i < W; i++) slots[i]->release(); };
     std::vector<LibaWindow> win((size_t)W);
@@ -1939,7 +1939,7 @@ int liba_batch_create(int device, liba_batch** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     liba_batch* b = new liba_batch();
     b->device = device;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -2004,7 +2004,7 @@ int liba_pose_optimize_batch(liba_solver* sv, const LibaPoseProblem* probs, int 
     }
     const bool lf = probs[0].last_frame != 0;
     const int NN = lf ? 30 : 15;
-    LBA_HIP(hipSetDevice(sv->device));
+    ORBX_HIP(hipSetDevice(sv->device));
     sv->release();
     hipStream_t stream = sv->stream;
     // One pinned staging buffer and one device buffer with the same layout: inputs first (one copy in), then the error scratch,

@@ -33,19 +33,9 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "hip_check.h"
 #include "lm_control.h"
 #include "se3_device.h"
-
-namespace orbx {
-int fail(int code, const char* fmt, ...);
-}
-using orbx::fail;
-
-#define LBA_HIP(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace lba {
 
@@ -1577,7 +1567,7 @@ struct lba_shard {
             arena_off += bytes;
             return ORBX_OK;
         }
-        LBA_HIP(hipMalloc((void**)p, bytes));
+        ORBX_HIP(hipMalloc((void**)p, bytes));
         allocs.push_back(*p);
         return ORBX_OK;
     }
@@ -1612,12 +1602,12 @@ struct lba_shard {
             stage_end = std::max(stage_end, off + bytes);
             return ORBX_OK;
         }
-        LBA_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        ORBX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
         return ORBX_OK;
     }
     int flush_stage()
     {
-        if (stage_end > 0) LBA_HIP(hipMemcpyAsync(arena, stage, stage_end, hipMemcpyHostToDevice, stream));
+        if (stage_end > 0) ORBX_HIP(hipMemcpyAsync(arena, stage, stage_end, hipMemcpyHostToDevice, stream));
         stage_end = 0;
         return ORBX_OK;
     }
@@ -1679,7 +1669,7 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     lba_shard* s = new lba_shard();
     s->device = device;
     if (owner) {
@@ -1817,19 +1807,19 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     static std::atomic<unsigned long long> attr_done{0};
     const bool set_attr = !((attr_done.load() >> device) & 1ull);
     if (set_attr) {
-        LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
     }
     LBA_TRY(s->dalloc(&s->flow, (size_t)lba::kFlowFlags));
-    LBA_HIP(hipMemsetAsync(s->flow, 0, lba::kFlowFlags * sizeof(unsigned), s->stream));
+    ORBX_HIP(hipMemsetAsync(s->flow, 0, lba::kFlowFlags * sizeof(unsigned), s->stream));
     {
         const size_t solve_lds = ((size_t)d.n + 64 + 16 * 64 + lba::NB * (lba::NB + 1)) * sizeof(double);
         if (solve_lds > 160 * 1024) LBA_TRY(fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the substitution kernel's LDS", d.n));
         if (set_attr) {     // (a limit, not an allocation: the largest system the check above lets through)
             const int lim = 160 * 1024;
-            LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            LBA_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
             attr_done.fetch_or(1ull << device);
         }
     }
@@ -1843,18 +1833,18 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
 #undef LBA_TRY
     if ((r = s->put(s->poses[0], poses.data(), poses.size() * sizeof(double))) || (d.nL > 0 && (r = s->put(s->pts[0], p->points, 3 * (size_t)d.nL * sizeof(double)))) ||
         (r = s->flush_stage())) { lba_shard_destroy(s); return r; }
-    LBA_HIP(hipMemsetAsync(d.err, 0, 3 * (size_t)std::max(d.nE, 1) * sizeof(double), s->stream));
-    LBA_HIP(hipMemsetAsync(d.scal, 0, 16 * sizeof(double), s->stream));
-    LBA_HIP(hipMemsetAsync(d.ticket, 0, 64 * sizeof(unsigned int), s->stream));
+    ORBX_HIP(hipMemsetAsync(d.err, 0, 3 * (size_t)std::max(d.nE, 1) * sizeof(double), s->stream));
+    ORBX_HIP(hipMemsetAsync(d.scal, 0, 16 * sizeof(double), s->stream));
+    ORBX_HIP(hipMemsetAsync(d.ticket, 0, 64 * sizeof(unsigned int), s->stream));
     d.cam.fx = p->fx; d.cam.fy = p->fy; d.cam.cx = p->cx; d.cam.cy = p->cy; d.cam.bf = p->bf;
     d.cam.huber_mono = p->huber_mono; d.cam.huber_stereo = p->huber_stereo;
     d.cam.dsqr_mono = p->huber_mono * p->huber_mono; d.cam.dsqr_stereo = p->huber_stereo * p->huber_stereo;    // RobustKernelHuber::setDelta
     hipLaunchKernelGGL(lba::k_normalize_poses, dim3((p->n_poses + 63) / 64), dim3(64), 0, s->stream, s->poses[0], p->n_poses);
     if (!owner) {       // a standalone shard can be reset to its initial estimates (lba_shard_reset); lba_solve never does that
         if ((r = s->dalloc(&s->poses0, 7 * (size_t)p->n_poses)) || (r = s->dalloc(&s->pts0, 3 * (size_t)d.nL))) { lba_shard_destroy(s); return r; }
-        LBA_HIP(hipMemcpyAsync(s->poses0, s->poses[0], 7 * (size_t)p->n_poses * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        if (d.nL > 0) LBA_HIP(hipMemcpyAsync(s->pts0, s->pts[0], 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        LBA_HIP(hipStreamSynchronize(s->stream));
+        ORBX_HIP(hipMemcpyAsync(s->poses0, s->poses[0], 7 * (size_t)p->n_poses * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        if (d.nL > 0) ORBX_HIP(hipMemcpyAsync(s->pts0, s->pts[0], 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        ORBX_HIP(hipStreamSynchronize(s->stream));
     }
     if (build_timing) {
         auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -1889,13 +1879,13 @@ extern "C" {
 int lba_shard_reset(lba_shard* s)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     if (!s->poses0) return fail(ORBX_ERR_ARG, "this shard keeps no copy of its initial estimates");
     s->cur = 0;
     s->err_current = false;
-    LBA_HIP(hipMemcpyAsync(s->poses[0], s->poses0, 7 * (size_t)s->d.nPoses * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    if (s->d.nL > 0) LBA_HIP(hipMemcpyAsync(s->pts[0], s->pts0, 3 * (size_t)s->d.nL * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    LBA_HIP(hipMemsetAsync(s->d.err, 0, 3 * (size_t)std::max(s->d.nE, 1) * sizeof(double), s->stream));
+    ORBX_HIP(hipMemcpyAsync(s->poses[0], s->poses0, 7 * (size_t)s->d.nPoses * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    if (s->d.nL > 0) ORBX_HIP(hipMemcpyAsync(s->pts[0], s->pts0, 3 * (size_t)s->d.nL * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    ORBX_HIP(hipMemsetAsync(s->d.err, 0, 3 * (size_t)std::max(s->d.nE, 1) * sizeof(double), s->stream));
     return ORBX_OK;
 }
 
@@ -1931,11 +1921,11 @@ int lba_shard_set_local(lba_shard* s, int local)
 int lba_shard_profile_enable(lba_shard* s, int on)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     if (on && s->prof_ev.empty()) {
         s->prof_ev.resize(lba_shard::kProfMarks);
         s->prof_stage.assign(lba_shard::kProfMarks, 0);
-        for (auto& e : s->prof_ev) LBA_HIP(hipEventCreate(&e));
+        for (auto& e : s->prof_ev) ORBX_HIP(hipEventCreate(&e));
     }
     s->profile = on != 0;
     s->prof_n = 0;
@@ -1945,12 +1935,12 @@ int lba_shard_profile_enable(lba_shard* s, int on)
 int lba_shard_profile_read(lba_shard* s, float* stage_ms, int n_stages)
 {
     if (!s || !stage_ms) return fail(ORBX_ERR_ARG, "NULL argument");
-    LBA_HIP(hipSetDevice(s->device));
-    LBA_HIP(hipStreamSynchronize(s->stream));
+    ORBX_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipStreamSynchronize(s->stream));
     for (int i = 0; i < n_stages; i++) stage_ms[i] = 0.f;
     for (int i = 0; i + 1 < s->prof_n; i++) {
         float ms = 0.f;
-        LBA_HIP(hipEventElapsedTime(&ms, s->prof_ev[i], s->prof_ev[i + 1]));
+        ORBX_HIP(hipEventElapsedTime(&ms, s->prof_ev[i], s->prof_ev[i + 1]));
         if (s->prof_stage[i] < n_stages) stage_ms[s->prof_stage[i]] += ms;
     }
     s->prof_n = 0;
@@ -1964,20 +1954,20 @@ int lba_shard_profile_read(lba_shard* s, float* stage_ms, int n_stages)
 int lba_shard_fence_out(lba_shard* s, void* other)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
-    if (!s->ev_fence) LBA_HIP(hipEventCreateWithFlags(&s->ev_fence, hipEventDisableTiming));
-    LBA_HIP(hipEventRecord(s->ev_fence, s->stream));
-    LBA_HIP(hipStreamWaitEvent((hipStream_t)other, s->ev_fence, 0));
+    ORBX_HIP(hipSetDevice(s->device));
+    if (!s->ev_fence) ORBX_HIP(hipEventCreateWithFlags(&s->ev_fence, hipEventDisableTiming));
+    ORBX_HIP(hipEventRecord(s->ev_fence, s->stream));
+    ORBX_HIP(hipStreamWaitEvent((hipStream_t)other, s->ev_fence, 0));
     return ORBX_OK;
 }
 
 int lba_shard_fence_in(lba_shard* s, void* other)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
-    if (!s->ev_fence) LBA_HIP(hipEventCreateWithFlags(&s->ev_fence, hipEventDisableTiming));
-    LBA_HIP(hipEventRecord(s->ev_fence, (hipStream_t)other));
-    LBA_HIP(hipStreamWaitEvent(s->stream, s->ev_fence, 0));
+    ORBX_HIP(hipSetDevice(s->device));
+    if (!s->ev_fence) ORBX_HIP(hipEventCreateWithFlags(&s->ev_fence, hipEventDisableTiming));
+    ORBX_HIP(hipEventRecord(s->ev_fence, (hipStream_t)other));
+    ORBX_HIP(hipStreamWaitEvent(s->stream, s->ev_fence, 0));
     return ORBX_OK;
 }
 
@@ -2006,7 +1996,7 @@ static int wait_scalars(const double* h_scal, unsigned long long seq, hipStream_
     int spins = 0;
     while (*flag != seq) {
         if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-            LBA_HIP(hipStreamSynchronize(stream));
+            ORBX_HIP(hipStreamSynchronize(stream));
             if (*flag != seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
             break;
         }
@@ -2028,7 +2018,7 @@ int lba_shard_hint_lambda(lba_shard* s, double lambda)
 int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses_local, double* max_diag_landmarks_local)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     const lba::Dev& d = s->d;
     const double* P = s->poses[s->cur];
     const double* X = s->pts[s->cur];
@@ -2049,14 +2039,14 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
         s->mark(lba::kStageReduce);
         hipLaunchKernelGGL(lba::k_reduce, dim3(1), dim3(1024), 0, s->stream, d, 0, s->d_hmap, ++s->seq);
         s->mark(lba::kStageIdle);
-        LBA_HIP(hipGetLastError());
+        ORBX_HIP(hipGetLastError());
         int r = wait_scalars(s->h_scal, s->seq, s->stream);
         if (r) return r;
         s->chi_current = s->h_scal[0];
         s->mdp_cached = s->h_scal[1];
         s->mdl_cached = s->h_scal[2];
     } else {
-        LBA_HIP(hipGetLastError());
+        ORBX_HIP(hipGetLastError());
     }
     s->err_valid = true;
     s->err_current = true;
@@ -2070,7 +2060,7 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
 int lba_shard_reduce(lba_shard* s, double lambda)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     const lba::Dev& d = s->d;
     s->mark(lba::kStageSchur);
     if (d.nL > 0 && !(s->schur_lambda >= 0.0 && s->schur_lambda == lambda))
@@ -2081,8 +2071,8 @@ int lba_shard_reduce(lba_shard* s, double lambda)
                            s->lambda_in_reduce ? lambda : 0.0, s->bs(), s->bpf(), s->diag());
     s->lambda_added = s->lambda_in_reduce;
     s->mark(lba::kStageIdle);
-    LBA_HIP(hipGetLastError());
-    if (s->sync_after_reduce) LBA_HIP(hipStreamSynchronize(s->stream));      // the caller hands the buffer to RCCL on another stream
+    ORBX_HIP(hipGetLastError());
+    if (s->sync_after_reduce) ORBX_HIP(hipStreamSynchronize(s->stream));      // the caller hands the buffer to RCCL on another stream
     return ORBX_OK;
 }
 
@@ -2091,7 +2081,7 @@ int lba_shard_reduce(lba_shard* s, double lambda)
 int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double* scale_poses, double* scale_landmarks_local)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     const lba::Dev& d = s->d;
     const int n = d.n;
     const double* P = s->poses[s->cur];
@@ -2133,7 +2123,7 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     s->mark(lba::kStageUpdate);
     hipLaunchKernelGGL(lba::k_update_errors, dim3(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1)), dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->d_hmap, ++s->seq);
     s->mark(lba::kStageIdle);
-    LBA_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     int r = wait_scalars(s->h_scal, s->seq, s->stream);
     if (r) return r;
     s->chi_trial = s->h_scal[0];
@@ -2162,17 +2152,17 @@ int lba_shard_accept(lba_shard* s, int accept)
 int lba_shard_download(lba_shard* s, double* pose_q, double* pose_t, double* points, double* chi2_per_edge, uint8_t* depth_positive)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     const lba::Dev& d = s->d;
     if (d.nE > 0)
         hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-    LBA_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     std::vector<double> poses(7 * (size_t)d.nPoses);
-    LBA_HIP(hipMemcpyAsync(poses.data(), s->poses[s->cur], poses.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (points && d.nL > 0) LBA_HIP(hipMemcpyAsync(points, s->pts[s->cur], 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (chi2_per_edge && d.nE > 0) LBA_HIP(hipMemcpyAsync(chi2_per_edge, s->d_chi2, (size_t)d.nE * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (depth_positive && d.nE > 0) LBA_HIP(hipMemcpyAsync(depth_positive, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, s->stream));
-    LBA_HIP(hipStreamSynchronize(s->stream));
+    ORBX_HIP(hipMemcpyAsync(poses.data(), s->poses[s->cur], poses.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (points && d.nL > 0) ORBX_HIP(hipMemcpyAsync(points, s->pts[s->cur], 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (chi2_per_edge && d.nE > 0) ORBX_HIP(hipMemcpyAsync(chi2_per_edge, s->d_chi2, (size_t)d.nE * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (depth_positive && d.nE > 0) ORBX_HIP(hipMemcpyAsync(depth_positive, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, s->stream));
+    ORBX_HIP(hipStreamSynchronize(s->stream));
     for (int i = 0; i < d.nPoses; i++) {
         if (pose_q) for (int k = 0; k < 4; k++) pose_q[4 * i + k] = poses[7 * (size_t)i + k];
         if (pose_t) for (int k = 0; k < 3; k++) pose_t[3 * i + k] = poses[7 * (size_t)i + 4 + k];
@@ -2190,7 +2180,7 @@ int lba_shard_optimize(lba_shard* s, lba_allreduce_fn allreduce, void* user, int
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
     if (world_size < 1 || (world_size > 1 && !allreduce)) return fail(ORBX_ERR_ARG, "world size %d needs an all-reduce callback", world_size);
-    LBA_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     const bool dist = allreduce != nullptr;         // a callback is always used, also by a communicator of one rank
     if (dist) {
         // the all-reduce sits between reduce() and finish() on the shard's own stream: lambda is added afterwards, no host wait
@@ -2210,10 +2200,10 @@ int lba_shard_optimize(lba_shard* s, lba_allreduce_fn allreduce, void* user, int
     auto reduce_scalars = [&](double* v, int n, int op) -> int {
         if (!dist) return ORBX_OK;
         for (int i = 0; i < n; i++) s->h_coll[i] = v[i];
-        LBA_HIP(hipMemcpyAsync(s->d_coll, s->h_coll, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        ORBX_HIP(hipMemcpyAsync(s->d_coll, s->h_coll, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
         if (allreduce(user, s->d_coll, n, op, (void*)s->stream)) return fail(ORBX_ERR_INTERNAL, "the all-reduce callback failed");
-        LBA_HIP(hipMemcpyAsync(s->h_coll, s->d_coll, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        LBA_HIP(hipStreamSynchronize(s->stream));
+        ORBX_HIP(hipMemcpyAsync(s->h_coll, s->d_coll, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        ORBX_HIP(hipStreamSynchronize(s->stream));
         for (int i = 0; i < n; i++) v[i] = s->h_coll[i];
         return ORBX_OK;
     };
@@ -2243,8 +2233,8 @@ int lba_shard_optimize(lba_shard* s, lba_allreduce_fn allreduce, void* user, int
             // diagonal section; the landmark maximum is MAX-reduced (computeLambdaInit, levenberg.cpp:171-185)
             if ((r = lba_shard_reduce(s, 0.0)) || (r = reduce_system())) break;
             std::vector<double> dg((size_t)std::max(s->d.n, 1), 0.0);
-            if (s->d.n > 0) LBA_HIP(hipMemcpyAsync(dg.data(), s->diag(), (size_t)s->d.n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            LBA_HIP(hipStreamSynchronize(s->stream));
+            if (s->d.n > 0) ORBX_HIP(hipMemcpyAsync(dg.data(), s->diag(), (size_t)s->d.n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            ORBX_HIP(hipStreamSynchronize(s->stream));
             mdp = 0;
             for (int k = 0; k < s->d.n; k++) mdp = std::max(mdp, std::fabs(dg[k]));
             if ((r = reduce_scalars(&mdl, 1, LBA_REDUCE_MAX))) break;
@@ -2276,7 +2266,7 @@ int lba_create(int device, lba_solver** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     lba_solver* s = new lba_solver();
     s->device = device;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipHostMalloc((void**)&s->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
@@ -2358,7 +2348,7 @@ int lba_batch_create(int device, lba_batch** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    LBA_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     lba_batch* b = new lba_batch();
     b->device = device;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -2400,7 +2390,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     if (!b || !problems || n_windows < 0) return fail(ORBX_ERR_ARG, "NULL argument");
     if (n_windows > lba::kMaxBatch) return fail(ORBX_ERR_CAPACITY, "at most %d windows per call", lba::kMaxBatch);
     if (n_windows == 0) return ORBX_OK;
-    LBA_HIP(hipSetDevice(b->device));
+    ORBX_HIP(hipSetDevice(b->device));
     const int W = n_windows;
     while ((int)b->slots.size() < W) {
         lba_solver* sv = new lba_solver();

@@ -22,18 +22,11 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "hip_check.h"
 
 namespace orbx {
 extern thread_local std::string g_last_error;
-int fail(int code, const char* fmt, ...);
 }
-using orbx::fail;
-
-#define ORBM_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace orbm {
 
@@ -1659,7 +1652,7 @@ struct orbm_matcher {
         if (d_blob) (void)hipFree(d_blob);
         d_blob = nullptr; blob_cap = 0;
         const size_t cap = std::max(bytes * 2, (size_t)1 << 20);
-        ORBM_HIP(hipMalloc((void**)&d_blob, cap));
+        ORBX_HIP(hipMalloc((void**)&d_blob, cap));
         blob_cap = cap;
         return ORBX_OK;
     }
@@ -1722,7 +1715,7 @@ static int bow_batch(orbm_matcher* m, int n_pairs,
                      float nnratio, int check_ori, int32_t* const* match_out, int32_t* nmatches_out)
 {
     if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     std::vector<PairOffsets> po(n_pairs);
     const size_t desc_off = blob.reserve(sizeof(orbm::BowPairDev) * n_pairs);
@@ -1768,15 +1761,15 @@ static int bow_batch(orbm_matcher* m, int n_pairs,
         D.serial = o.serial;
         descs[p] = D;
     }
-    ORBM_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_bow<KFKF>, dim3(n_pairs), dim3(orbm::kBowThreads), 0, m->stream, (const orbm::BowPairDev*)(base + desc_off), nnratio, check_ori);
-    ORBM_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     for (int p = 0; p < n_pairs; p++) {
         const PairOffsets& o = po[p];
-        if (o.n_out > 0) ORBM_HIP(hipMemcpyAsync(match_out[p], base + o.match, sizeof(int32_t) * o.n_out, hipMemcpyDeviceToHost, m->stream));
-        ORBM_HIP(hipMemcpyAsync(&nmatches_out[p], base + o.nmatch, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        if (o.n_out > 0) ORBX_HIP(hipMemcpyAsync(match_out[p], base + o.match, sizeof(int32_t) * o.n_out, hipMemcpyDeviceToHost, m->stream));
+        ORBX_HIP(hipMemcpyAsync(&nmatches_out[p], base + o.nmatch, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
     }
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
 
@@ -1850,7 +1843,7 @@ static int run_projection_jobs(orbm_matcher* m, ProjJob* jobs, int n_jobs, int l
 {
     if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
     if (!jobs || n_jobs < 1) return fail(ORBX_ERR_ARG, "no jobs");
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     (void)hipGetLastError();            // (an error an earlier, failed call left behind must not fail this one)
     Blob blob(m->h_blob);
     const size_t oargs = blob.reserve(sizeof(orbm::ProjArgs) * (size_t)n_jobs);
@@ -1951,29 +1944,29 @@ static int run_projection_jobs(orbm_matcher* m, ProjJob* jobs, int n_jobs, int l
     const bool stage = lds_full <= lds_budget;
     const size_t lds = stage ? lds_full : lds_occ;
     for (int j = 0; j < n_jobs; j++) args[j].lds_frame = stage ? 1 : 0;
-    ORBM_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
     if (device_grid) {
         int n_pow2 = 2;
         while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
         hipLaunchKernelGGL(orbm::k_grid, dim3(n_jobs), dim3(256), (size_t)n_pow2 * 8, m->stream, (const orbm::ProjArgs*)(base + oargs), n_pow2);
     }
     if (par && stage) {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj_par<true>, dim3(n_jobs), dim3(orbm::kProjThreads), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
     } else if (par) {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj_par<false>, dim3(n_jobs), dim3(orbm::kProjThreads), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
     } else if (stage) {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj<true>, dim3(n_jobs), dim3(64), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
     } else {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj<false>, dim3(n_jobs), dim3(64), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
     }
-    ORBM_HIP(hipGetLastError());
-    ORBM_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, m->h_blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, m->h_blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     for (int j = 0; j < n_jobs; j++) {
         const Off& o = offs[j];
         const int n = jobs[j].f->n;
@@ -2018,7 +2011,7 @@ int orbm_create(int device, orbm_matcher** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBM_HIP(hipSetDevice(device));
+    ORBX_HIP(hipSetDevice(device));
     orbm_matcher* m = new orbm_matcher();
     m->device = device;
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; return fail(ORBX_ERR_HIP, "stream create failed"); }
@@ -2085,7 +2078,7 @@ int orbm_bow_plan_create(orbm_matcher* m, const OrbmBowPair* pairs, int n_pairs,
 {
     if (!m || !pairs || n_pairs < 1 || !out) return fail(ORBX_ERR_ARG, "bad plan arguments");
     *out = nullptr;
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     PinnedBytes host;            // (a plan is created once: its staging buffer lives for this call only)
     Blob blob(host);
     orbm_bow_plan* pl = new orbm_bow_plan();
@@ -2139,7 +2132,7 @@ int orbm_bow_plan_create_device(orbm_matcher* m, const OrbmBowPairDevice* pairs,
 {
     if (!m || !pairs || n_pairs < 1 || !out) return fail(ORBX_ERR_ARG, "bad plan arguments");
     *out = nullptr;
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     std::vector<orbm::BowPairDev> descs(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
         const OrbmBowPairDevice& q = pairs[p];
@@ -2174,10 +2167,10 @@ int orbm_bow_plan_create_device(orbm_matcher* m, const OrbmBowPairDevice* pairs,
 int orbm_bow_plan_run(orbm_bow_plan* pl, float nnratio, int check_orientation, void* stream)
 {
     if (!pl) return fail(ORBX_ERR_ARG, "NULL plan");
-    ORBM_HIP(hipSetDevice(pl->m->device));
+    ORBX_HIP(hipSetDevice(pl->m->device));
     hipLaunchKernelGGL(orbm::k_bow<false>, dim3(pl->n_pairs), dim3(orbm::kBowThreads), 0, (hipStream_t)stream,
                        (const orbm::BowPairDev*)(pl->d_blob + pl->desc_off), nnratio, check_orientation);
-    ORBM_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -2185,15 +2178,15 @@ int orbm_bow_plan_fetch(orbm_bow_plan* pl, OrbmBowPair* pairs, void* stream)
 {
     if (!pl || !pairs) return fail(ORBX_ERR_ARG, "NULL argument");
     if (pl->po.empty()) return fail(ORBX_ERR_ARG, "a device-resident plan writes into the caller's device arrays: nothing to fetch");
-    ORBM_HIP(hipSetDevice(pl->m->device));
+    ORBX_HIP(hipSetDevice(pl->m->device));
     hipStream_t st = (hipStream_t)stream;
     for (int p = 0; p < pl->n_pairs; p++) {
         const PairOffsets& o = pl->po[p];
         if (o.n_out > 0 && pairs[p].match_f2kf)
-            ORBM_HIP(hipMemcpyAsync(pairs[p].match_f2kf, pl->d_blob + o.match, sizeof(int32_t) * o.n_out, hipMemcpyDeviceToHost, st));
-        ORBM_HIP(hipMemcpyAsync(&pairs[p].n_matches, pl->d_blob + o.nmatch, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            ORBX_HIP(hipMemcpyAsync(pairs[p].match_f2kf, pl->d_blob + o.match, sizeof(int32_t) * o.n_out, hipMemcpyDeviceToHost, st));
+        ORBX_HIP(hipMemcpyAsync(&pairs[p].n_matches, pl->d_blob + o.nmatch, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    ORBM_HIP(hipStreamSynchronize(st));
+    ORBX_HIP(hipStreamSynchronize(st));
     return ORBX_OK;
 }
 
@@ -2284,7 +2277,7 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
     if (mode == 0 && (!mp || !mp->d_view_cos || !mp->d_track_depth || !mp->d_bad || !last->d_has_obs)) return fail(ORBX_ERR_ARG, "bad map-point description");
     if (cur->grid_cols < 1 || cur->grid_rows < 1 || cur->grid_cols * (int64_t)cur->grid_rows > (1 << 20) || !(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) return fail(ORBX_ERR_ARG, "bad frame grid");
     if (cur->cap > 8192) return fail(ORBX_ERR_CAPACITY, "at most 8192 features per frame (the grid is sorted in LDS)");
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t B = (size_t)batch, cap = (size_t)cur->cap, pcap = (size_t)last->cap, cells = (size_t)cur->grid_cols * cur->grid_rows;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -2299,16 +2292,16 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
     const size_t o_lb = off; off += al(B * pcap * 4);
     const size_t o_jobs = off; off += al(B * sizeof(orbm::ProjArgs));
     if (off > m->ws_cap) {
-        if (m->d_ws) { ORBM_HIP(hipDeviceSynchronize()); (void)hipFree(m->d_ws); }
+        if (m->d_ws) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(m->d_ws); }
         m->d_ws = nullptr; m->ws_cap = 0;
-        ORBM_HIP(hipMalloc((void**)&m->d_ws, off + off / 4));
+        ORBX_HIP(hipMalloc((void**)&m->d_ws, off + off / 4));
         m->ws_cap = off + off / 4;
     }
-    if (!m->d_scale) ORBM_HIP(hipMalloc((void**)&m->d_scale, 32 * sizeof(float)));
+    if (!m->d_scale) ORBX_HIP(hipMalloc((void**)&m->d_scale, 32 * sizeof(float)));
     if (std::memcmp(m->h_scale, cur->scale_factors, sizeof(float) * cur->n_levels) != 0) {      // (unchanged between the calls of a stream of frames)
-        ORBM_HIP(hipStreamSynchronize(st));                 // an earlier copy out of h_scale may still be in flight
+        ORBX_HIP(hipStreamSynchronize(st));                 // an earlier copy out of h_scale may still be in flight
         std::memcpy(m->h_scale, cur->scale_factors, sizeof(float) * cur->n_levels);
-        ORBM_HIP(hipMemcpyAsync(m->d_scale, m->h_scale, sizeof(float) * cur->n_levels, hipMemcpyHostToDevice, st));
+        ORBX_HIP(hipMemcpyAsync(m->d_scale, m->h_scale, sizeof(float) * cur->n_levels, hipMemcpyHostToDevice, st));
     }
     // LDS of the search kernel, as in run_projection_jobs
     const size_t max_n = cap;
@@ -2336,16 +2329,16 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
     hipLaunchKernelGGL(orbm::k_proj_dev_setup, dim3(batch), dim3(256), 0, st, P);
     int n_pow2 = 2;
     while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
-    ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
+    ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
     hipLaunchKernelGGL(orbm::k_grid, dim3(batch), dim3(256), (size_t)n_pow2 * 8, st, (const orbm::ProjArgs*)P.jobs, n_pow2);
     if (stage) {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj_par<true>, dim3(batch), dim3(orbm::kProjThreads), lds, st, (const orbm::ProjArgs*)P.jobs);
     } else {
-        ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(orbm::k_proj_par<false>, dim3(batch), dim3(orbm::kProjThreads), lds, st, (const orbm::ProjArgs*)P.jobs);
     }
-    ORBM_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -2407,7 +2400,7 @@ int orbm_search_for_triangulation(orbm_matcher* m, const OrbmTriSide* k1, const 
         if (k2->octave[i] < 0 || k2->octave[i] >= n_levels_2) return fail(ORBX_ERR_ARG, "octave out of range");
     if (k1->n > 0 && !match12) return fail(ORBX_ERR_ARG, "NULL match12");
     if (k1->n == 0) return 0;
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     size_t o[2][10];
     for (int q = 0; q < 2; q++) {
@@ -2436,13 +2429,13 @@ int orbm_search_for_triangulation(orbm_matcher* m, const OrbmTriSide* k1, const 
     A.ep_x = ep_x; A.ep_y = ep_y;
     A.n1 = k1->n; A.nn1 = k1->fv.n_nodes; A.nn2 = k2->fv.n_nodes; A.only_stereo = only_stereo; A.coarse = coarse; A.check_ori = check_orientation;
     A.match12 = (int32_t*)(b + omatch); A.n_matches = (int32_t*)(b + onm);
-    ORBM_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_triangulation, dim3(1), dim3(256), 0, m->stream, A);
-    ORBM_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     int nm = 0;
-    ORBM_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * k1->n, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * k1->n, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return nm;
 }
 
@@ -2460,7 +2453,7 @@ int orbm_search_for_initialization(orbm_matcher* m, const uint8_t* desc1, int n1
     if (n1 == 0) return 0;
     const int n = f2->n;
     if ((size_t)n * 8 + 256 > 150 * 1024) return fail(ORBX_ERR_ARG, "F2 with %d features exceeds the LDS state", n);
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     const size_t ox = blob.put(f2->x, sizeof(float) * n), oy = blob.put(f2->y, sizeof(float) * n);
     const size_t ooct = blob.put(f2->octave, sizeof(int32_t) * n), oang = blob.put(f2->angle, f2->angle ? sizeof(float) * n : 0);
@@ -2481,14 +2474,14 @@ int orbm_search_for_initialization(orbm_matcher* m, const uint8_t* desc1, int n1
     A.n1 = n1; A.window = window_size; A.check_ori = check_orientation; A.nnratio = nnratio;
     A.match12 = (int32_t*)(b + omatch); A.n_matches = (int32_t*)(b + onm);
     const size_t lds = std::max((size_t)n * 8, (size_t)64);
-    ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_initialization, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ORBM_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_initialization, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_initialization, dim3(1), dim3(64), lds, m->stream, A);
-    ORBM_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     int nm = 0;
-    ORBM_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return nm;
 }
 
@@ -2511,7 +2504,7 @@ int orbm_fuse_search(orbm_matcher* m, const OrbmFrame* kf, const float* u_right,
         for (int i = 0; i < kf->n; i++)
             if (kf->octave[i] < 0 || kf->octave[i] >= kf->n_levels) return fail(ORBX_ERR_ARG, "key point %d: octave %d out of range", i, kf->octave[i]);
     if (n_pts == 0) return ORBX_OK;
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     const int n = kf->n;
     const size_t ox = blob.put(kf->x, sizeof(float) * n), oy = blob.put(kf->y, sizeof(float) * n);
@@ -2538,12 +2531,12 @@ int orbm_fuse_search(orbm_matcher* m, const OrbmFrame* kf, const float* u_right,
     A.n_pts = n_pts; A.valid = base + ovalid; A.u = (const float*)(base + ou); A.v = (const float*)(base + ov); A.ur = (const float*)(base + opr);
     A.level = (const int32_t*)(base + olevel); A.desc = base + odmp; A.th = th; A.chi2_check = chi2_check;
     A.best_idx = (int32_t*)(base + obi); A.best_dist = (int32_t*)(base + obd);
-    ORBM_HIP(hipMemcpyAsync(base, m->h_blob.data(), obi, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), obi, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_fuse, dim3((n_pts + 3) / 4), dim3(256), 0, m->stream, A);
-    ORBM_HIP(hipGetLastError());
-    ORBM_HIP(hipMemcpyAsync(best_idx, base + obi, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipMemcpyAsync(best_dist, base + obd, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(best_idx, base + obi, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(best_dist, base + obd, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
 
@@ -2561,7 +2554,7 @@ int orbm_distinctive_descriptors(orbm_matcher* m, const uint8_t* desc, const int
     const int total = off[n_points];
     if (total > 0 && !desc) return fail(ORBX_ERR_ARG, "NULL descriptors");
     if (max_n > 4096) return fail(ORBX_ERR_CAPACITY, "a map point with %d observations exceeds the LDS staging (4096)", max_n);
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     const size_t od = blob.put(desc, (size_t)total * 32), oo = blob.put(off, sizeof(int32_t) * (n_points + 1));
     const size_t in_bytes = m->h_blob.size();
@@ -2570,14 +2563,14 @@ int orbm_distinctive_descriptors(orbm_matcher* m, const uint8_t* desc, const int
     if (r) return r;
     uint8_t* b = m->d_blob;
     const size_t lds = std::max((size_t)max_n * 32, (size_t)64);
-    ORBM_HIP(hipFuncSetAttribute((const void*)orbm::k_distinctive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ORBM_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_distinctive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_distinctive, dim3(n_points), dim3(64), lds, m->stream, b + od, (const int32_t*)(b + oo), n_points,
                        (int32_t*)(b + ob), (int32_t*)(b + om));
-    ORBM_HIP(hipGetLastError());
-    ORBM_HIP(hipMemcpyAsync(best_idx, b + ob, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
-    if (best_median) ORBM_HIP(hipMemcpyAsync(best_median, b + om, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(best_idx, b + ob, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
+    if (best_median) ORBX_HIP(hipMemcpyAsync(best_median, b + om, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
 
@@ -2593,7 +2586,7 @@ int orbm_update_normal_and_depth(orbm_matcher* m, const float* pos, const float*
         if (off[p + 1] <= off[p]) return fail(ORBX_ERR_ARG, "point %d has no observation (the reference returns before touching it)", p);
     const int total = off[n_points];
     if (!centers) return fail(ORBX_ERR_ARG, "NULL camera centres");
-    ORBM_HIP(hipSetDevice(m->device));
+    ORBX_HIP(hipSetDevice(m->device));
     Blob blob(m->h_blob);
     const size_t op = blob.put(pos, sizeof(float) * 3 * n_points), oc = blob.put(centers, sizeof(float) * 3 * total);
     const size_t oo = blob.put(off, sizeof(int32_t) * (n_points + 1)), orc = blob.put(ref_center, sizeof(float) * 3 * n_points);
@@ -2603,15 +2596,15 @@ int orbm_update_normal_and_depth(orbm_matcher* m, const float* pos, const float*
     int r = m->ensure(m->h_blob.size());
     if (r) return r;
     uint8_t* b = m->d_blob;
-    ORBM_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_normal_depth, dim3((n_points + 255) / 256), dim3(256), 0, m->stream, (const float*)(b + op), (const float*)(b + oc),
                        (const int32_t*)(b + oo), (const float*)(b + orc), (const float*)(b + ol), last_level_scale, n_points,
                        (float*)(b + on), (float*)(b + omx), (float*)(b + omn));
-    ORBM_HIP(hipGetLastError());
-    ORBM_HIP(hipMemcpyAsync(normal, b + on, sizeof(float) * 3 * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipMemcpyAsync(max_dist, b + omx, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipMemcpyAsync(min_dist, b + omn, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBM_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(normal, b + on, sizeof(float) * 3 * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(max_dist, b + omx, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(min_dist, b + omn, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
 

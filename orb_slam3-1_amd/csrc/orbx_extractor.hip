@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_check.h"
 #include "orbx_kernels.hip"
 
 namespace orbx {
@@ -30,12 +31,6 @@ int fail(int code, const char* fmt, ...)
     g_last_error = buf;
     return code;
 }
-
-#define ORBX_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 static inline int cv_round_host(double v) { return (int)std::nearbyint(v); }
 static inline int cv_floor_host(double v) { int i = (int)v; return i - (i > v); }

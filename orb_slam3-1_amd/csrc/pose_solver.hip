@@ -15,18 +15,9 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "batch_stage.h"
+#include "dense_lm_device.h"
 #include "se3_device.h"
-
-namespace orbx {
-int fail(int code, const char* fmt, ...);
-}
-using orbx::fail;
-
-#define POSE_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace poseopt {
 
@@ -42,64 +33,6 @@ struct ProblemDev {
     uint8_t* active;        // [n] scratch: level 0
     PoseResult* result;
 };
-
-__device__ __forceinline__ double block_sum(double v, double* s_red)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-    __syncthreads();
-    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
-// 6x6 LDL^T solve (LinearSolverDense, solvers/linear_solver_dense.h:55-110) of (H + lambda I) x = b; Hu = packed upper
-// triangle (row a, column c >= a at a*6 - a(a-1)/2 + c - a).  Returns false for a non-positive pivot.  Everything is
-// indexed at compile time (registers only); one reciprocal per pivot instead of a division per entry.
-__device__ __forceinline__ bool solve6(const double* Hu, double lambda, const double* b, double* x)
-{
-    double A[36], D[6], iD[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = r; c < 6; c++) { const double v = Hu[r * 6 - (r * (r - 1)) / 2 + (c - r)]; A[r * 6 + c] = v; A[c * 6 + r] = v; }
-#pragma unroll
-    for (int i = 0; i < 6; i++) A[i * 7] += lambda;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= A[j * 6 + k] * A[j * 6 + k] * D[k];
-        ok = ok && (d > 0.0) && isfinite(d);
-        D[j] = d;
-        iD[j] = 1.0 / d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double sv = A[i * 6 + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) sv -= A[i * 6 + k] * A[j * 6 + k] * D[k];
-            A[i * 6 + j] = sv * iD[j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double sv = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) sv -= A[i * 6 + k] * x[k];
-        x[i] = sv;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) x[i] *= iD[i];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double sv = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) sv -= A[k * 6 + i] * x[k];
-        x[i] = sv;
-    }
-    return ok;
-}
 
 // one edge in registers
 struct Edge {
@@ -160,8 +93,8 @@ __device__ __forceinline__ void edge_build(const ProblemDev& P, const double* T,
     edge_eval<STEREO>(P, T, d, Xc, r);
     const double chi = edge_chi2<STEREO>(d, r);
     const double delta = (STEREO && d.st) ? rb.delta_s : rb.delta_m, dsq = (STEREO && d.st) ? rb.dsq_s : rb.dsq_m;
-    double rho0 = chi, rho1 = 1.0;
-    if (rb.on && !(chi <= dsq)) { const double sq = sqrt(chi); rho0 = 2 * sq * delta - dsq; rho1 = delta / sq; }
+    double rho0, rho1;
+    dlm::huber(rb.on, chi, delta, dsq, rho0, rho1);
     acc[27] += rho0;
     const double x = Xc[0], y = Xc[1], z = Xc[2];
     if (!STEREO || !d.st) {
@@ -205,8 +138,9 @@ __device__ __forceinline__ double edge_trial(const ProblemDev& P, const double* 
     edge_eval<STEREO>(P, T, d, Xc, r);
     const double chi = edge_chi2<STEREO>(d, r);
     const double delta = (STEREO && d.st) ? rb.delta_s : rb.delta_m, dsq = (STEREO && d.st) ? rb.dsq_s : rb.dsq_m;
-    if (rb.on && !(chi <= dsq)) return 2 * sqrt(chi) * delta - dsq;
-    return chi;
+    double rho0, rho1;
+    dlm::huber(rb.on, chi, delta, dsq, rho0, rho1);
+    return rho0;
 }
 
 // float chi2 against the 95 % thresholds (src/Optimizer.cc:1020-1034, 1049-1063)
@@ -277,7 +211,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__
 #pragma unroll
         for (int j = 0; j < kRegEdges; j++) cnt += cact[j] ? 1.0 : 0.0;
         for (int e = e_rest; e < n; e += 256) cnt += P.active[e];
-        const int n_active = (int)block_sum(cnt, s_red);
+        const int n_active = (int)dlm::block_sum(cnt, s_red);
         if (n_active > 0) {
             double lambda = 0, ni = 2;
             int nbad_lm = 0;
@@ -318,12 +252,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__
                 for (int k = 0; k < 6; k++) b[k] = s_out[21 + k];
                 double cur = s_out[27];
                 const double ini = cur;
-                if (it == 0) {      // computeLambdaInit (levenberg.cpp:171-185)
-                    double m = 0;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) m = fmax(fabs(Hu[j * 6 - (j * (j - 1)) / 2]), m);
-                    lambda = 1e-5 * m; ni = 2; nbad_lm = 0;
-                }
+                if (it == 0) { lambda = dlm::lambda_init<6>(Hu); ni = 2; nbad_lm = 0; }
                 POSE_TICK(1)
                 // ---- LM trial loop (levenberg.cpp:102-149) ----
                 int qmax = 0;
@@ -331,7 +260,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__
 #pragma unroll 1
                 do {
                     double x[6], Tt[7];
-                    const bool ok2 = solve6(Hu, lambda, b, x);
+                    const bool ok2 = dlm::ldlt_solve<6, true>(Hu, lambda, b, x);
                     if (ok2) pose_oplus<true>(T, x, Tt);
                     else {
                         for (int k = 0; k < 7; k++) Tt[k] = T[k];
@@ -350,32 +279,17 @@ __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__
                         P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
                     }
                     POSE_TICK(3)
-                    double tempChi = block_sum(tchi, s_red);
-                    if (!ok2) tempChi = 1.7976931348623157e308;
+                    const double tempChi = dlm::block_sum(tchi, s_red);
                     double scale = 0;
 #pragma unroll
                     for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    scale += 1e-3;
-                    rho = (cur - tempChi) / scale;
-                    if (rho > 0 && isfinite(tempChi)) {
-                        const double c1 = 2 * rho - 1;
-                        double alpha = 1. - c1 * c1 * c1;      // pow(2 rho - 1, 3) (levenberg.cpp:129), <= 2 ulp apart
-                        alpha = fmin(alpha, 2. / 3.);
-                        lambda *= fmax(1. / 3., alpha);
-                        ni = 2;
-                        cur = tempChi;
-                        for (int k = 0; k < 7; k++) T[k] = Tt[k];     // discardTop()
-                    } else {
-                        lambda *= ni; ni *= 2;                          // pop(): the estimate stays
-                    }
+                    if (dlm::trial(ok2, tempChi, scale, lambda, ni, cur, rho))
+                        for (int k = 0; k < 7; k++) T[k] = Tt[k];     // discardTop(); after pop() the estimate stays
                     qmax++;
                     POSE_TICK(4)
-                } while (rho < 0 && qmax < 10);
-                // stop rules (:151-166)
+                } while (dlm::more_trials(rho, qmax));
                 if (tid == 0) { s_iters[round]++; s_trials[round] += qmax; s_chi[round] = cur; }
-                if (qmax == 10 || rho == 0) break;
-                if ((ini - cur) * 1e3 < ini) nbad_lm++; else nbad_lm = 0;
-                if (nbad_lm >= 3) break;
+                if (dlm::stop_reason(qmax, rho, ini, cur, nbad_lm)) break;      // stop rules (:151-166)
             }
         }
         // ---- inlier / outlier classification with float chi2 (:1016-1100) ----
@@ -401,7 +315,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__
             const bool o = edge_is_outlier<STEREO>(d, r);
             P.outlier[e] = o ? 1 : 0; P.active[e] = o ? 0 : 1; bad += o ? 1.0 : 0.0;
         }
-        nBad = (int)block_sum(bad, s_red);
+        nBad = (int)dlm::block_sum(bad, s_red);
         POSE_TICK(5)
         if (round == 2) rb.on = false;      // setRobustKernel(0) after the third round
         if (n < 10) break;                  // optimizer.edges().size() < 10
@@ -513,20 +427,14 @@ __global__ __launch_bounds__(256) void k_pose_scatter(const ProblemDev* __restri
 
 }  // namespace poseopt
 
-struct pose_solver {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t* d_blob = nullptr;      // device image of h_blob + scratch
-    uint8_t* h_blob = nullptr;      // pinned staging: [descriptors | inputs] up, [results | outlier flags] down
-    size_t d_cap = 0, h_cap = 0;
+// staging: [descriptors | inputs] up, [results | outlier flags] down, scratch behind them on the device
+struct pose_solver : stage::Batch {
     uint8_t* d_dev = nullptr;       // arena of the device-resident entry (edge slots, problem descriptors, results)
     size_t dev_cap = 0;
-    float last_kernel_ms = 0;
+    ~pose_solver() { if (d_dev) (void)hipFree(d_dev); }
 };
 
 namespace {
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p)
 {
     if (stereo) {
@@ -537,94 +445,46 @@ inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, con
         else hipLaunchKernelGGL((poseopt::k_pose_opt<false, 2>), dim3(n), dim3(256), 0, st, p);
     }
 }
-}  // namespace
 
-extern "C" {
-
-int pose_create(int device, pose_solver** out)
-{
-    if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    POSE_HIP(hipSetDevice(device));
-    pose_solver* s = new pose_solver();
-    s->device = device;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess ||
-        hipEventCreate(&s->ev1) != hipSuccess) {
-        pose_destroy(s);
-        return fail(ORBX_ERR_HIP, "stream / event create failed");
-    }
-    *out = s;
-    return ORBX_OK;
-}
-
-void pose_destroy(pose_solver* s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->d_blob) (void)hipFree(s->d_blob);
-    if (s->d_dev) (void)hipFree(s->d_dev);
-    if (s->h_blob) (void)hipHostFree(s->h_blob);
-    delete s;
-}
-
-float pose_last_kernel_ms(const pose_solver* s) { return s ? s->last_kernel_ms : 0.0f; }
-
-int pose_optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
+int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
 {
     if (!s || !problems || !results || n_problems < 1) return fail(ORBX_ERR_ARG, "bad arguments");
-    POSE_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     // layout: [ProblemDev x N][per problem: Xw obs w stereo]  ||  [PoseResult x N][per problem: outlier]  ||  scratch
     struct Off { size_t Xw, obs, w, st, outl, err, act; };
     std::vector<Off> offs(n_problems);
-    size_t pos = align16(sizeof(poseopt::ProblemDev) * (size_t)n_problems);
+    stage::Cursor cur;
+    cur.take(sizeof(poseopt::ProblemDev) * (size_t)n_problems);
     for (int i = 0; i < n_problems; i++) {
         const PoseProblem& p = problems[i];
         if (p.n < 0 || (p.n > 0 && (!p.Xw || !p.obs || !p.inv_sigma2 || !p.stereo))) return fail(ORBX_ERR_ARG, "problem %d: NULL arrays", i);
         const size_t n = (size_t)p.n;
         Off& o = offs[i];
-        o.Xw = pos; pos = align16(pos + 24 * n);
-        o.obs = pos; pos = align16(pos + 24 * n);
-        o.w = pos; pos = align16(pos + 8 * n);
-        o.st = pos; pos = align16(pos + n);
+        o.Xw = cur.take(24 * n);
+        o.obs = cur.take(24 * n);
+        o.w = cur.take(8 * n);
+        o.st = cur.take(n);
     }
-    const size_t up_bytes = pos;
-    const size_t res_off = pos;
-    pos = align16(pos + sizeof(PoseResult) * (size_t)n_problems);
-    for (int i = 0; i < n_problems; i++) { offs[i].outl = pos; pos = align16(pos + (size_t)std::max(problems[i].n, 1)); }
-    const size_t down_end = pos;
+    const size_t up_bytes = cur.pos;
+    const size_t res_off = cur.take(sizeof(PoseResult) * (size_t)n_problems);
+    for (int i = 0; i < n_problems; i++) offs[i].outl = cur.take((size_t)std::max(problems[i].n, 1));
+    const size_t down_end = cur.pos;
     for (int i = 0; i < n_problems; i++) {
         const size_t n = (size_t)std::max(problems[i].n, 1);
-        offs[i].err = pos; pos = align16(pos + 24 * n);
-        offs[i].act = pos; pos = align16(pos + n);
+        offs[i].err = cur.take(24 * n);
+        offs[i].act = cur.take(n);
     }
-    const size_t total = pos;
-    if (down_end > s->h_cap) {
-        if (s->h_blob) (void)hipHostFree(s->h_blob);
-        s->h_blob = nullptr; s->h_cap = 0;
-        const size_t cap = std::max(down_end * 2, (size_t)1 << 20);
-        POSE_HIP(hipHostMalloc((void**)&s->h_blob, cap, hipHostMallocDefault));
-        s->h_cap = cap;
-    }
-    if (total > s->d_cap) {
-        if (s->d_blob) (void)hipFree(s->d_blob);
-        s->d_blob = nullptr; s->d_cap = 0;
-        const size_t cap = std::max(total * 2, (size_t)1 << 20);
-        POSE_HIP(hipMalloc((void**)&s->d_blob, cap));
-        s->d_cap = cap;
-    }
+    const int rc = stage::reserve(*s, down_end, cur.pos);       // the scratch is never staged on the host
+    if (rc != ORBX_OK) return rc;
     uint8_t* base = s->d_blob;
     poseopt::ProblemDev* descs = (poseopt::ProblemDev*)s->h_blob;
     bool any_stereo = false;
+    int n_max = 0;
     for (int i = 0; i < n_problems; i++) {
         const PoseProblem& p = problems[i];
         const Off& o = offs[i];
         const size_t n = (size_t)p.n;
+        n_max = std::max(n_max, p.n);
         for (size_t k = 0; k < n && !any_stereo; k++) any_stereo = p.stereo[k] != 0;
         if (n) {
             std::memcpy(s->h_blob + o.Xw, p.Xw, 24 * n); std::memcpy(s->h_blob + o.obs, p.obs, 24 * n);
@@ -640,21 +500,28 @@ int pose_optimize_batch(pose_solver* s, const PoseProblem* problems, int n_probl
         d.result = (PoseResult*)(base + res_off) + i;
         descs[i] = d;
     }
-    POSE_HIP(hipMemcpyAsync(base, s->h_blob, up_bytes, hipMemcpyHostToDevice, s->stream));
-    POSE_HIP(hipEventRecord(s->ev0, s->stream));
-    int n_max = 0;
-    for (int i = 0; i < n_problems; i++) n_max = std::max(n_max, problems[i].n);
-    pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base);
-    POSE_HIP(hipGetLastError());
-    POSE_HIP(hipEventRecord(s->ev1, s->stream));
-    POSE_HIP(hipMemcpyAsync(s->h_blob + res_off, base + res_off, down_end - res_off, hipMemcpyDeviceToHost, s->stream));
-    POSE_HIP(hipStreamSynchronize(s->stream));
-    (void)hipEventElapsedTime(&s->last_kernel_ms, s->ev0, s->ev1);
+    const int rr = stage::run(*s, up_bytes, res_off, down_end,
+                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base); });
+    if (rr != ORBX_OK) return rr;
     std::memcpy(results, s->h_blob + res_off, sizeof(PoseResult) * (size_t)n_problems);
     if (outlier_out)
         for (int i = 0; i < n_problems; i++)
             if (outlier_out[i] && problems[i].n > 0) std::memcpy(outlier_out[i], s->h_blob + offs[i].outl, (size_t)problems[i].n);
     return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pose_create(int device, pose_solver** out) { return stage::open(device, out); }
+
+void pose_destroy(pose_solver* s) { stage::close(s); }
+
+float pose_last_kernel_ms(const pose_solver* s) { return s ? s->last_kernel_ms : 0.0f; }
+
+int pose_optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
+{
+    return stage::guarded("pose_optimize_batch", [&] { return optimize_batch(s, problems, n_problems, results, outlier_out); });
 }
 
 int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int batch, double* d_pose_out, int32_t* d_inliers,
@@ -663,28 +530,30 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
     if (!s || !f || batch < 1) return fail(ORBX_ERR_ARG, "bad arguments");
     if (!f->d_kps || !f->d_n || !f->d_assign || !f->d_mp_xyz || !f->d_pose || !f->inv_level_sigma2) return fail(ORBX_ERR_ARG, "NULL arrays");
     if (f->cap < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap / mp_cap / n_levels");
-    POSE_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t cap = (size_t)f->cap;
     poseopt::GatherArgs A;
     std::memset(&A, 0, sizeof(A));
-    size_t pos = 0;
-    pos = align16(pos + 24 * cap); A.o_obs = pos;
-    pos = align16(pos + 24 * cap); A.o_w = pos;
-    pos = align16(pos + 8 * cap); A.o_err = pos;
-    pos = align16(pos + 24 * cap); A.o_idx = pos;
-    pos = align16(pos + 4 * cap); A.o_st = pos;
-    pos = align16(pos + cap); A.o_outl = pos;
-    pos = align16(pos + cap); A.o_act = pos;
-    pos = align16(pos + cap);
-    A.slot_bytes = pos;
-    const size_t prob_off = pos * (size_t)batch;
-    const size_t res_off = align16(prob_off + sizeof(poseopt::ProblemDev) * (size_t)batch);
-    const size_t total = align16(res_off + sizeof(PoseResult) * (size_t)batch);
+    stage::Cursor slot;                 // Xw at 0
+    slot.take(24 * cap);
+    A.o_obs = slot.take(24 * cap);
+    A.o_w = slot.take(8 * cap);
+    A.o_err = slot.take(24 * cap);
+    A.o_idx = slot.take(4 * cap);
+    A.o_st = slot.take(cap);
+    A.o_outl = slot.take(cap);
+    A.o_act = slot.take(cap);
+    A.slot_bytes = slot.pos;
+    stage::Cursor arena;
+    arena.take(A.slot_bytes * (size_t)batch);
+    const size_t prob_off = arena.take(sizeof(poseopt::ProblemDev) * (size_t)batch);
+    const size_t res_off = arena.take(sizeof(PoseResult) * (size_t)batch);
+    const size_t total = arena.pos;
     if (total > s->dev_cap) {           // (first call / larger batch: the only synchronising step)
-        if (s->d_dev) { POSE_HIP(hipDeviceSynchronize()); (void)hipFree(s->d_dev); }
+        if (s->d_dev) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(s->d_dev); }
         s->d_dev = nullptr; s->dev_cap = 0;
-        POSE_HIP(hipMalloc((void**)&s->d_dev, total));
+        ORBX_HIP(hipMalloc((void**)&s->d_dev, total));
         s->dev_cap = total;
     }
     A.kps = f->d_kps; A.n_kps = f->d_n; A.u_right = f->d_u_right; A.assign = f->d_assign; A.mp_xyz = f->d_mp_xyz; A.pose = f->d_pose;
@@ -698,7 +567,7 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
     pose_launch(f->d_u_right != nullptr, f->cap > 512, batch, st, (const poseopt::ProblemDev*)A.problems);
     hipLaunchKernelGGL(poseopt::k_pose_scatter, dim3(batch), dim3(256), 0, st, (const poseopt::ProblemDev*)A.problems, (const uint8_t*)s->d_dev, A.slot_bytes, A.o_idx,
                        f->cap, d_pose_out, d_inliers, d_outlier, d_results);
-    POSE_HIP(hipGetLastError());
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 

@@ -14,22 +14,12 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <exception>
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "batch_stage.h"
+#include "dense_lm_device.h"
 #include "se3_device.h"
-
-namespace orbx {
-int fail(int code, const char* fmt, ...);
-}
-using orbx::fail;
-
-#define SIM3_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace sim3 {
 
@@ -379,69 +369,7 @@ __device__ __forceinline__ void sim3_edge_error(const double* S, const double* K
     r[1] = obs[1] - (K[1] * Y[1] / Y[2] + K[3]);
 }
 
-// 7x7 dense LDL^T of (H + lambda I) x = b, Hu = packed upper triangle; false for a non-positive pivot
-__device__ inline bool solve7(const double* Hu, double lambda, const double* b, double* x)
-{
-    constexpr int N = 7;
-    double A[N * N], D[N];
-    for (int r = 0; r < N; r++)
-        for (int c = r; c < N; c++) { const double v = Hu[r * N - (r * (r - 1)) / 2 + (c - r)]; A[r * N + c] = v; A[c * N + r] = v; }
-    for (int i = 0; i < N; i++) A[i * (N + 1)] += lambda;
-    bool ok = true;
-    for (int j = 0; j < N; j++) {
-        double d = A[j * N + j];
-        for (int k = 0; k < j; k++) d -= A[j * N + k] * A[j * N + k] * D[k];
-        ok = ok && (d > 0.0) && isfinite(d);
-        D[j] = d;
-        for (int i = j + 1; i < N; i++) {
-            double sv = A[i * N + j];
-            for (int k = 0; k < j; k++) sv -= A[i * N + k] * A[j * N + k] * D[k];
-            A[i * N + j] = sv / d;
-        }
-    }
-    for (int i = 0; i < N; i++) {
-        double sv = b[i];
-        for (int k = 0; k < i; k++) sv -= A[i * N + k] * x[k];
-        x[i] = sv;
-    }
-    for (int i = 0; i < N; i++) x[i] /= D[i];
-    for (int i = N - 1; i >= 0; i--) {
-        double sv = x[i];
-        for (int k = i + 1; k < N; k++) sv -= A[k * N + i] * x[k];
-        x[i] = sv;
-    }
-    return ok;
-}
-
 constexpr int kOptAcc = 36;         // H upper triangle (28), b (7), robust chi2 (1)
-
-// ordered block sum of K values per thread: wave butterfly, then the four wave partials in a fixed order; result replicated
-template <int K>
-__device__ __forceinline__ void block_sum_many(double* v, double (*s_part)[4])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double a = v[k];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-        v[k] = a;
-    }
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++) s_part[k][wave] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = ((s_part[k][0] + s_part[k][1]) + s_part[k][2]) + s_part[k][3];
-}
-
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp): rho0 and rho1 of a squared error
-__device__ __forceinline__ void huber(bool on, double chi, double delta, double& rho0, double& rho1)
-{
-    const double dsq = delta * delta;
-    rho0 = chi; rho1 = 1.0;
-    if (on && !(chi <= dsq)) { const double sq = sqrt(chi); rho0 = 2 * sq * delta - dsq; rho1 = delta / sq; }
-}
 
 // The Levenberg state (estimate, lambda, chi2, counters) and the 7x7 solve are replicated in every thread, as in k_pose_opt:
 // the only synchronisation is inside the block reductions and around the shared perturbed similarities.
@@ -451,6 +379,7 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
     __shared__ double s_pert[14][2][8];         // exp(+-delta e_d) * S and its inverse, d = 0..6 (+) and 7..13 (-)
     const OptDev P = problems[blockIdx.x];
     const int tid = threadIdx.x, n = P.n;
+    const double dsq = P.delta * P.delta;
     double T[8];
     for (int k = 0; k < 8; k++) T[k] = P.S[k];
     for (int e = tid; e < n; e += 256) { P.keep[e] = 1; for (int k = 0; k < 4; k++) P.err[4 * (size_t)e + k] = 0; }
@@ -514,7 +443,7 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
                         }
                         const double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
                         double rho0, rho1;
-                        huber(robust, chi, P.delta, rho0, rho1);
+                        dlm::huber(robust, chi, P.delta, dsq, rho0, rho1);
                         acc[35] += rho0;
                         const double rw = rho1 * w;
                         const double wr0 = rho1 * (-(w * r[0])), wr1 = rho1 * (-(w * r[1]));
@@ -526,23 +455,19 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
                         }
                     }
                 }
-                block_sum_many<kOptAcc>(acc, s_part);
+                dlm::block_sum<kOptAcc>(acc, s_part);
                 const double* Hu = acc;
                 const double* b = acc + 28;
                 double cur = acc[35];
                 const double ini = cur;
-                if (it == 0) {          // computeLambdaInit (optimization_algorithm_levenberg.cpp:171-185)
-                    double m = 0;
-                    for (int j = 0; j < 7; j++) m = fmax(fabs(Hu[j * 7 - (j * (j - 1)) / 2]), m);
-                    lambda = 1e-5 * m; ni = 2; nbad_lm = 0;
-                }
+                if (it == 0) { lambda = dlm::lambda_init<7>(Hu); ni = 2; nbad_lm = 0; }
                 // ---- LM trial loop (optimization_algorithm_levenberg.cpp:102-149) ----
                 int qmax = 0;
                 double rho = 0;
 #pragma unroll 1
                 do {
                     double x[7], Tt[8], Tti[8];
-                    const bool ok2 = solve7(Hu, lambda, b, x);
+                    const bool ok2 = dlm::ldlt_solve<7, false>(Hu, lambda, b, x);
                     if (ok2) {
                         double u[7], E[8];
                         for (int k = 0; k < 7; k++) u[k] = x[k];
@@ -554,7 +479,7 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
                         for (int k = 0; k < 7; k++) x[k] = 0;
                     }
                     sim3_inv(Tt, Tti);
-                    double tchi[1] = {0};
+                    double tchi = 0;
                     for (int e = tid; e < n; e += 256) {
                         if (!P.keep[e]) continue;
 #pragma unroll 1
@@ -568,34 +493,20 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
                             for (int k = 0; k < 8; k++) Ss[k] = side == 0 ? Tt[k] : Tti[k];
                             sim3_edge_error(Ss, side == 0 ? P.K1 : P.K2, Xe, oe, r);
                             P.err[4 * (size_t)e + 2 * side] = r[0]; P.err[4 * (size_t)e + 2 * side + 1] = r[1];
-                            huber(robust, r[0] * (w * r[0]) + r[1] * (w * r[1]), P.delta, rho0, rho1);
-                            tchi[0] += rho0;
+                            dlm::huber(robust, r[0] * (w * r[0]) + r[1] * (w * r[1]), P.delta, dsq, rho0, rho1);
+                            tchi += rho0;
                         }
                     }
-                    block_sum_many<1>(tchi, s_part);
-                    double tempChi = tchi[0];
-                    if (!ok2) tempChi = 1.7976931348623157e308;
+                    const double tempChi = dlm::block_sum(tchi, s_part[0]);
                     double scale = 0;
                     for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    scale += 1e-3;
-                    rho = (cur - tempChi) / scale;
-                    if (rho > 0 && isfinite(tempChi)) {
-                        const double c1 = 2 * rho - 1;
-                        double alpha = 1. - c1 * c1 * c1;
-                        alpha = fmin(alpha, 2. / 3.);
-                        lambda *= fmax(1. / 3., alpha);
-                        ni = 2;
-                        cur = tempChi;
-                        for (int k = 0; k < 8; k++) T[k] = Tt[k];
-                    } else {
-                        lambda *= ni; ni *= 2;
-                    }
+                    if (dlm::trial(ok2, tempChi, scale, lambda, ni, cur, rho))
+                        for (int k = 0; k < 8; k++) T[k] = Tt[k];     // discardTop(); after pop() the estimate stays
                     qmax++;
-                } while (rho < 0 && qmax < 10);
+                } while (dlm::more_trials(rho, qmax));
                 r_iters++; r_trials += qmax; r_chi = cur;
-                if (qmax == 10 || rho == 0) { r_reason = 1; break; }
-                if ((ini - cur) * 1e3 < ini) nbad_lm++; else nbad_lm = 0;
-                if (nbad_lm >= 3) { r_reason = 2; break; }
+                r_reason = dlm::stop_reason(qmax, rho, ini, cur, nbad_lm);
+                if (r_reason) break;
             }
         }
         __syncthreads();
@@ -603,15 +514,14 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
         else { iters[1] = r_iters; trials[1] = r_trials; reason[1] = r_reason; chis[1] = r_chi; }
         if (round == 0) {
             // chi2 of the errors as last computed against th2 (:2313-2340); the dropped pairs leave the graph
-            double bad[1] = {0};
+            double bad = 0;
             for (int e = tid; e < n; e += 256) {
                 const double* r = P.err + 4 * (size_t)e;
                 const double w1 = P.w1[e], w2 = P.w2[e];
                 const double c12 = r[0] * (w1 * r[0]) + r[1] * (w1 * r[1]), c21 = r[2] * (w2 * r[2]) + r[3] * (w2 * r[3]);
-                if (c12 > P.th2 || c21 > P.th2) { P.keep[e] = 0; bad[0] += 1.0; }
+                if (c12 > P.th2 || c21 > P.th2) { P.keep[e] = 0; bad += 1.0; }
             }
-            block_sum_many<1>(bad, s_part);
-            nBad = (int)bad[0];
+            nBad = (int)dlm::block_sum(bad, s_part[0]);
             if (n - nBad < 10) {                                 // return 0; g2oS12 is not written (:2348-2349)
                 for (int k = 0; k < 8; k++) T[k] = P.S[k];
                 nIn = 0;
@@ -619,7 +529,7 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
             }
         } else {
             // computeError on the final estimate, chi2 against th2 (:2357-2374)
-            double Ti[8], in[1] = {0};
+            double Ti[8], in = 0;
             sim3_inv(T, Ti);
             for (int e = tid; e < n; e += 256) {
                 if (!P.keep[e]) continue;
@@ -632,10 +542,9 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
                 const double w1 = P.w1[e], w2 = P.w2[e];
                 const double c12 = r1[0] * (w1 * r1[0]) + r1[1] * (w1 * r1[1]), c21 = r2[0] * (w2 * r2[0]) + r2[1] * (w2 * r2[1]);
                 if (c12 > P.th2 || c21 > P.th2) P.keep[e] = 0;
-                else in[0] += 1.0;
+                else in += 1.0;
             }
-            block_sum_many<1>(in, s_part);
-            nIn = (int)in[0];
+            nIn = (int)dlm::block_sum(in, s_part[0]);
         }
     }
     if (tid == 0) {
@@ -651,46 +560,18 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(const OptDev* __restrict_
 
 }  // namespace sim3
 
-struct sim3_solver {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t* d_blob = nullptr;      // device image of h_blob
-    uint8_t* h_blob = nullptr;      // pinned staging: [descriptors | inputs] up, [outputs] down
-    size_t d_cap = 0, h_cap = 0;
-    float last_kernel_ms = 0;
-};
+struct sim3_solver : stage::Batch {};     // staging: [descriptors | inputs] up, [outputs] down
 
 namespace {
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-int sim3_reserve(sim3_solver* s, size_t total)
-{
-    if (total > s->h_cap) {
-        if (s->h_blob) (void)hipHostFree(s->h_blob);
-        s->h_blob = nullptr; s->h_cap = 0;
-        const size_t cap = std::max(total * 2, (size_t)1 << 20);
-        SIM3_HIP(hipHostMalloc((void**)&s->h_blob, cap, hipHostMallocDefault));
-        s->h_cap = cap;
-    }
-    if (total > s->d_cap) {
-        if (s->d_blob) (void)hipFree(s->d_blob);
-        s->d_blob = nullptr; s->d_cap = 0;
-        const size_t cap = std::max(total * 2, (size_t)1 << 20);
-        SIM3_HIP(hipMalloc((void**)&s->d_blob, cap));
-        s->d_cap = cap;
-    }
-    return ORBX_OK;
-}
-
 int ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_problems, Sim3RansacResult* results)
 {
     if (!s || !problems || !results || n_problems < 1) return fail(ORBX_ERR_ARG, "bad arguments");
-    SIM3_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     // layout: [RansacDev x P][per problem: X1 X2 e1 e2 triples]  ||  [per problem: sel count T12 mask]
     struct Off { size_t X1, X2, e1, e2, tri, sel, cnt, T, mask; };
     std::vector<Off> offs(n_problems);
-    size_t pos = align16(sizeof(sim3::RansacDev) * (size_t)n_problems);
+    stage::Cursor cur;
+    cur.take(sizeof(sim3::RansacDev) * (size_t)n_problems);
     for (int i = 0; i < n_problems; i++) {
         const Sim3RansacProblem& p = problems[i];
         if (p.n < 0 || p.n_hyp < 1 || p.n_hyp > SIM3_MAX_HYPOTHESES) return fail(ORBX_ERR_ARG, "problem %d: n %d / n_hyp %d out of range", i, p.n, p.n_hyp);
@@ -700,23 +581,22 @@ int ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_proble
                 if (p.triples[k] < 0 || p.triples[k] >= p.n) return fail(ORBX_ERR_ARG, "problem %d: triple index %d out of [0, %d)", i, p.triples[k], p.n);
         const size_t n = (size_t)p.n, H = (size_t)p.n_hyp;
         Off& o = offs[i];
-        o.X1 = pos; pos = align16(pos + 12 * n);
-        o.X2 = pos; pos = align16(pos + 12 * n);
-        o.e1 = pos; pos = align16(pos + 4 * n);
-        o.e2 = pos; pos = align16(pos + 4 * n);
-        o.tri = pos; pos = align16(pos + 12 * H);
+        o.X1 = cur.take(12 * n);
+        o.X2 = cur.take(12 * n);
+        o.e1 = cur.take(4 * n);
+        o.e2 = cur.take(4 * n);
+        o.tri = cur.take(12 * H);
     }
-    const size_t up_bytes = pos, down_off = pos;
+    const size_t up_bytes = cur.pos;
     for (int i = 0; i < n_problems; i++) {
         const size_t H = (size_t)problems[i].n_hyp, W = ((size_t)problems[i].n + 63) / 64;
         Off& o = offs[i];
-        o.sel = pos; pos = align16(pos + 16);
-        o.cnt = pos; pos = align16(pos + 4 * H);
-        o.T = pos; pos = align16(pos + 52 * H);
-        o.mask = pos; pos = align16(pos + 8 * H * W);
+        o.sel = cur.take(16);
+        o.cnt = cur.take(4 * H);
+        o.T = cur.take(52 * H);
+        o.mask = cur.take(8 * H * W);
     }
-    const size_t total = pos;
-    const int rc = sim3_reserve(s, total);
+    const int rc = stage::reserve(*s, cur.pos, cur.pos);
     if (rc != ORBX_OK) return rc;
     uint8_t* base = s->d_blob;
     sim3::RansacDev* descs = (sim3::RansacDev*)s->h_blob;
@@ -740,14 +620,10 @@ int ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_proble
         d.mask = (unsigned long long*)(base + o.mask);
         descs[i] = d;
     }
-    SIM3_HIP(hipMemcpyAsync(base, s->h_blob, up_bytes, hipMemcpyHostToDevice, s->stream));
-    SIM3_HIP(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(sim3::k_sim3_ransac, dim3(n_problems), dim3(256), 0, s->stream, (const sim3::RansacDev*)base);
-    SIM3_HIP(hipGetLastError());
-    SIM3_HIP(hipEventRecord(s->ev1, s->stream));
-    SIM3_HIP(hipMemcpyAsync(s->h_blob + down_off, base + down_off, total - down_off, hipMemcpyDeviceToHost, s->stream));
-    SIM3_HIP(hipStreamSynchronize(s->stream));
-    (void)hipEventElapsedTime(&s->last_kernel_ms, s->ev0, s->ev1);
+    const int rr = stage::run(*s, up_bytes, up_bytes, cur.pos, [&] {
+        hipLaunchKernelGGL(sim3::k_sim3_ransac, dim3(n_problems), dim3(256), 0, s->stream, (const sim3::RansacDev*)base);
+    });
+    if (rr != ORBX_OK) return rr;
     for (int i = 0; i < n_problems; i++) {
         const Off& o = offs[i];
         const size_t H = (size_t)problems[i].n_hyp, W = ((size_t)problems[i].n + 63) / 64;
@@ -764,30 +640,31 @@ int ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_proble
 int optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problems, Sim3OptResult* results, uint8_t* const* keep_out)
 {
     if (!s || !problems || !results || n_problems < 1) return fail(ORBX_ERR_ARG, "bad arguments");
-    SIM3_HIP(hipSetDevice(s->device));
+    ORBX_HIP(hipSetDevice(s->device));
     // layout: [OptDev x P][per problem: X1 X2 obs1 obs2 w1 w2]  ||  [Sim3OptResult x P][per problem: keep]  ||  err scratch
     struct Off { size_t X1, X2, o1, o2, w1, w2, keep, err; };
     std::vector<Off> offs(n_problems);
-    size_t pos = align16(sizeof(sim3::OptDev) * (size_t)n_problems);
+    stage::Cursor cur;
+    cur.take(sizeof(sim3::OptDev) * (size_t)n_problems);
     for (int i = 0; i < n_problems; i++) {
         const Sim3OptProblem& p = problems[i];
         if (p.n < 0 || (p.n > 0 && (!p.X1c || !p.X2c || !p.obs1 || !p.obs2 || !p.inv_sigma2_1 || !p.inv_sigma2_2)))
             return fail(ORBX_ERR_ARG, "problem %d: NULL arrays", i);
         const size_t n = (size_t)p.n;
         Off& o = offs[i];
-        o.X1 = pos; pos = align16(pos + 24 * n);
-        o.X2 = pos; pos = align16(pos + 24 * n);
-        o.o1 = pos; pos = align16(pos + 16 * n);
-        o.o2 = pos; pos = align16(pos + 16 * n);
-        o.w1 = pos; pos = align16(pos + 8 * n);
-        o.w2 = pos; pos = align16(pos + 8 * n);
+        o.X1 = cur.take(24 * n);
+        o.X2 = cur.take(24 * n);
+        o.o1 = cur.take(16 * n);
+        o.o2 = cur.take(16 * n);
+        o.w1 = cur.take(8 * n);
+        o.w2 = cur.take(8 * n);
     }
-    const size_t up_bytes = pos, res_off = pos;
-    pos = align16(pos + sizeof(Sim3OptResult) * (size_t)n_problems);
-    for (int i = 0; i < n_problems; i++) { offs[i].keep = pos; pos = align16(pos + (size_t)std::max(problems[i].n, 1)); }
-    const size_t down_end = pos;
-    for (int i = 0; i < n_problems; i++) { offs[i].err = pos; pos = align16(pos + 32 * (size_t)std::max(problems[i].n, 1)); }
-    const int rc = sim3_reserve(s, pos);
+    const size_t up_bytes = cur.pos;
+    const size_t res_off = cur.take(sizeof(Sim3OptResult) * (size_t)n_problems);
+    for (int i = 0; i < n_problems; i++) offs[i].keep = cur.take((size_t)std::max(problems[i].n, 1));
+    const size_t down_end = cur.pos;
+    for (int i = 0; i < n_problems; i++) offs[i].err = cur.take(32 * (size_t)std::max(problems[i].n, 1));
+    const int rc = stage::reserve(*s, cur.pos, cur.pos);
     if (rc != ORBX_OK) return rc;
     uint8_t* base = s->d_blob;
     sim3::OptDev* descs = (sim3::OptDev*)s->h_blob;
@@ -815,14 +692,10 @@ int optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problem
         d.result = (Sim3OptResult*)(base + res_off) + i;
         descs[i] = d;
     }
-    SIM3_HIP(hipMemcpyAsync(base, s->h_blob, up_bytes, hipMemcpyHostToDevice, s->stream));
-    SIM3_HIP(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(sim3::k_sim3_optimize, dim3(n_problems), dim3(256), 0, s->stream, (const sim3::OptDev*)base);
-    SIM3_HIP(hipGetLastError());
-    SIM3_HIP(hipEventRecord(s->ev1, s->stream));
-    SIM3_HIP(hipMemcpyAsync(s->h_blob + res_off, base + res_off, down_end - res_off, hipMemcpyDeviceToHost, s->stream));
-    SIM3_HIP(hipStreamSynchronize(s->stream));
-    (void)hipEventElapsedTime(&s->last_kernel_ms, s->ev0, s->ev1);
+    const int rr = stage::run(*s, up_bytes, res_off, down_end, [&] {
+        hipLaunchKernelGGL(sim3::k_sim3_optimize, dim3(n_problems), dim3(256), 0, s->stream, (const sim3::OptDev*)base);
+    });
+    if (rr != ORBX_OK) return rr;
     std::memcpy(results, s->h_blob + res_off, sizeof(Sim3OptResult) * (size_t)n_problems);
     if (keep_out)
         for (int i = 0; i < n_problems; i++)
@@ -833,60 +706,20 @@ int optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problem
 
 extern "C" {
 
-int sim3_create(int device, sim3_solver** out)
-{
-    if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    SIM3_HIP(hipSetDevice(device));
-    sim3_solver* s = new (std::nothrow) sim3_solver();
-    if (!s) return fail(ORBX_ERR_INTERNAL, "out of host memory");
-    s->device = device;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess ||
-        hipEventCreate(&s->ev1) != hipSuccess) {
-        sim3_destroy(s);
-        return fail(ORBX_ERR_HIP, "stream / event create failed");
-    }
-    *out = s;
-    return ORBX_OK;
-}
+int sim3_create(int device, sim3_solver** out) { return stage::open(device, out); }
 
-void sim3_destroy(sim3_solver* s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->d_blob) (void)hipFree(s->d_blob);
-    if (s->h_blob) (void)hipHostFree(s->h_blob);
-    delete s;
-}
+void sim3_destroy(sim3_solver* s) { stage::close(s); }
 
 float sim3_last_kernel_ms(const sim3_solver* s) { return s ? s->last_kernel_ms : 0.0f; }
 
 int sim3_ransac_batch(sim3_solver* s, const Sim3RansacProblem* problems, int n_problems, Sim3RansacResult* results)
 {
-    try {
-        return ransac_batch(s, problems, n_problems, results);
-    } catch (const std::exception& e) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_ransac_batch: %s", e.what());
-    } catch (...) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_ransac_batch: unknown exception");
-    }
+    return stage::guarded("sim3_ransac_batch", [&] { return ransac_batch(s, problems, n_problems, results); });
 }
 
 int sim3_optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problems, Sim3OptResult* results, uint8_t* const* keep_out)
 {
-    try {
-        return optimize_batch(s, problems, n_problems, results, keep_out);
-    } catch (const std::exception& e) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_optimize_batch: %s", e.what());
-    } catch (...) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_optimize_batch: unknown exception");
-    }
+    return stage::guarded("sim3_optimize_batch", [&] { return optimize_batch(s, problems, n_problems, results, keep_out); });
 }
 
 // The reference draws with DUtils::Random::RandomInt (libc rand); here the generator is part of the interface: splitmix64
@@ -895,7 +728,7 @@ int sim3_optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_pr
 int sim3_draw_triples(uint64_t seed, int n, int n_hyp, int32_t* out)
 {
     if (n < 3 || n_hyp < 1 || !out) return fail(ORBX_ERR_ARG, "sim3_draw_triples: n %d (>= 3) / n_hyp %d (>= 1) / out", n, n_hyp);
-    try {
+    return stage::guarded("sim3_draw_triples", [&] {
         std::vector<int32_t> all(n), avail;
         for (int i = 0; i < n; i++) all[i] = i;
         uint64_t state = seed;
@@ -913,12 +746,8 @@ int sim3_draw_triples(uint64_t seed, int n, int n_hyp, int32_t* out)
                 avail.pop_back();
             }
         }
-    } catch (const std::exception& e) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_draw_triples: %s", e.what());
-    } catch (...) {
-        return fail(ORBX_ERR_INTERNAL, "sim3_draw_triples: unknown exception");
-    }
-    return ORBX_OK;
+        return ORBX_OK;
+    });
 }
 
 }  // extern "C"

@@ -87,6 +87,17 @@ def test_bad_arguments_rejected(pkg):
     assert b"bad extractor parameters" in pkg.lib.orbx_last_error()
 
 
+def test_pose_null_arguments_rejected(pkg):
+    """the pose entry points check their handle and arrays before any device work, like the sim3_* ones (tests/test_sim3_abi.py)"""
+    assert pkg.lib.pose_create(C.c_int(0), None) == -3
+    assert b"out is NULL" in pkg.lib.orbx_last_error()
+    assert pkg.lib.pose_optimize_batch(None, None, C.c_int(1), None, None) == -3
+    assert b"bad arguments" in pkg.lib.orbx_last_error()
+    assert pkg.lib.pose_optimize(None, None, None, None) == -3
+    assert pkg.lib.pose_optimize_batch_device(None, None, C.c_int(1), None, None, None, None, None) == -3
+    pkg.lib.pose_destroy(None)                                                      # a NULL handle is ignored
+
+
 def test_product_never_touches_oracle():
     """A product path that routes through the oracle would void every parity claim."""
     pkg_dir = os.path.join(ROOT, "orb_slam3-1_amd")

@@ -1,6 +1,8 @@
 """The Levenberg controller of the C++ drivers (orb_slam3-1_amd/csrc/lm_control.h) takes exactly the decisions of the Python
 driver distributed.sharded_bundle_adjustment: the same scripted linearisation and trial results go through tests/lm_replay.cpp
-(g++, no device) and through the Python driver over a fake shard (world size 1); decisions, lambdas and stats must be equal."""
+(g++, no device) and through the Python driver over a fake shard (world size 1); decisions, lambdas and stats must be equal.
+The same scripts also go through the policy functions of the one-workgroup solvers (orb_slam3-1_amd/csrc/dense_lm_device.h,
+`lm_replay device`): they must take the decisions of lm::Levenberg."""
 import importlib
 import os
 import random
@@ -80,8 +82,8 @@ def run_python(distributed, sc):
                 chi2_final=st.get("chi2_final", 0.0), lambda_=st["lambda_"], trace=trace)
 
 
-def run_cpp(exe, scripts):
-    out = subprocess.run([exe], input="\n".join(s.text() for s in scripts) + "\n", capture_output=True, text=True, check=True).stdout
+def run_cpp(exe, scripts, mode=()):
+    out = subprocess.run([exe, *mode], input="\n".join(s.text() for s in scripts) + "\n", capture_output=True, text=True, check=True).stdout
     res, cur = [], None
     for line in out.splitlines():
         f = line.split()
@@ -90,6 +92,8 @@ def run_cpp(exe, scripts):
         if f[0] == "trial":
             cur["accepted"].append(f[1] == "1")
             cur["lambdas"].append(float.fromhex(f[2]))
+            if len(f) > 3:      # `lm_replay device`
+                cur.setdefault("rhos", []).append(float.fromhex(f[3]))
         elif f[0] == "stats":
             cur.update(iterations=int(f[1]), trials=int(f[2]), stop_reason=int(f[3]), chi2_initial=float.fromhex(f[4]),
                        chi2_final=float.fromhex(f[5]), lambda_=float.fromhex(f[6]))
@@ -142,9 +146,9 @@ def _good(chi):      # a trial that is accepted from chi2 = 2 chi (rho = 1)
     return (1, chi, chi / 2, chi / 2 - 1e-3)
 
 
-def test_targeted_scripts(replay_exe, distributed):
+def targeted_scripts():
     big = [(1000.0 / 2 ** k, 4e4, 3e5) for k in range(25)]
-    cases = {
+    return {
         # lambda from the diagonals (1e-5 * max(mdp, mdl)) and the user's lambda
         "computed_lambda": Script(3, 0.0, big, [_good(500.0 / 2 ** k) for k in range(30)]),
         "user_lambda": Script(3, 0.25, big, [_good(500.0 / 2 ** k) for k in range(30)]),
@@ -159,6 +163,10 @@ def test_targeted_scripts(replay_exe, distributed):
         "unsolved_trials": Script(5, 0.0, big, [(0, 1.0, 7.0, 3.0)] * 3 + [_good(500.0 / 2 ** k) for k in range(50)]),
         "more_than_16_iterations": Script(20, 0.0, big, [_good(500.0 / 2 ** k) for k in range(200)]),
     }
+
+
+def test_targeted_scripts(replay_exe, distributed):
+    cases = targeted_scripts()
     cpp = dict(zip(cases, check_same(replay_exe, distributed, list(cases.values()))))
     assert cpp["computed_lambda"]["lambdas"][0] == pytest.approx(3e5 * 1e-5 / 3)
     assert cpp["user_lambda"]["lambdas"][0] == pytest.approx(0.25 / 3)
@@ -172,6 +180,53 @@ def test_targeted_scripts(replay_exe, distributed):
     assert cpp["max_iters_cap"]["stop_reason"] == 0 and cpp["max_iters_cap"]["iterations"] == 4
     assert cpp["unsolved_trials"]["accepted"][:4] == [False, False, False, True]
     assert cpp["more_than_16_iterations"]["iterations"] == 20 and all(v > 0 for v in cpp["more_than_16_iterations"]["trace"])
+
+
+# rho at which alpha = 1 - (2 rho - 1)^3 meets its clamps 2/3 and 1/3 (levenberg.cpp:129-131)
+RHO_CLAMPS = ((1 + (1 / 3) ** (1 / 3)) / 2, (1 + (2 / 3) ** (1 / 3)) / 2)
+
+
+def near_threshold(rhos):
+    """some trial's rho is within 1e-9 of a decision threshold without sitting on it: 0 (accept / reject; rho is a gain ratio
+    of order 1, so the band is absolute there) or a clamp of alpha.  rho == 0 exactly is the scripted stop rule, not a tie."""
+    return any(0 < abs(r - t) <= 1e-9 * max(1.0, t) for r in rhos for t in (0.0,) + RHO_CLAMPS)
+
+
+def check_device_form(exe, scripts):
+    """dense_lm_device.h against lm::Levenberg: the same decisions, counts and stop reason; lambda after each trial within 1e-12
+    relative (alpha as a cube and as pow differ by <= 2 ulp per accepted trial and the relative errors of the product add up; a script
+    has <= 25 * 10 trials: 500 * 2.2e-16 = 1.1e-13, a decade below the bound)"""
+    host, dev = run_cpp(exe, scripts), run_cpp(exe, scripts, ("device",))
+    dropped = 0
+    for i, (sc, h, d) in enumerate(zip(scripts, host, dev)):
+        if near_threshold(d.get("rhos", [])):
+            dropped += 1
+            continue
+        where = "script %d:\n%s\nhost   %s\ndevice %s" % (i, sc.text(), h, d)
+        assert d["accepted"] == h["accepted"], where
+        for k in ("iterations", "trials", "stop_reason", "chi2_initial", "chi2_final", "trace"):
+            assert d[k] == h[k], where
+        for a, b in zip(d["lambdas"] + [d["lambda_"]], h["lambdas"] + [h["lambda_"]]):
+            assert abs(a - b) <= 1e-12 * abs(b), where
+    print("device form: %d of %d scripts dropped (rho within 1e-9 of a threshold)" % (dropped, len(scripts)))
+    assert dropped * 100 < len(scripts)         # under 1 %
+    return dev
+
+
+def test_device_form_matches_controller_on_random_scripts(replay_exe):
+    rng = random.Random(20261016)
+    dev = check_device_form(replay_exe, [random_script(rng) for _ in range(400)])
+    assert {d["stop_reason"] for d in dev} == {0, 1, 2, 3}
+    assert any(any(d["accepted"]) for d in dev) and any(not all(d["accepted"]) for d in dev)
+
+
+def test_device_form_matches_controller_on_targeted_scripts(replay_exe):
+    cases = targeted_scripts()
+    dev = dict(zip(cases, check_device_form(replay_exe, list(cases.values()))))
+    assert dev["ten_rejections"]["stop_reason"] == 1 and dev["ten_rejections"]["trials"] == 10
+    assert dev["rho_zero"]["stop_reason"] == 1 and dev["rho_zero"]["trials"] == 1
+    assert dev["three_small_gains"]["stop_reason"] == 2 and dev["three_small_gains"]["iterations"] == 3
+    assert dev["unsolved_trials"]["accepted"][:4] == [False, False, False, True]
 
 
 def test_failure_flag_mapping(replay_exe):

@@ -356,6 +356,65 @@ int orbm_search_for_triangulation(orbm_matcher* m, const OrbmTriSide* kf1, const
                                   const float* level_sigma2_2, const float* scale_factors_2, int n_levels_2,
                                   int only_stereo, int coarse, int check_orientation, int32_t* match12);
 
+/* void LocalMapping::CreateNewMapPoints() (src/LocalMapping.cc:392-716) in one call and one launch: for every neighbour in
+ * order, SearchForTriangulation(kf1, neighbour, bOnlyStereo=false, coarse) with ORBmatcher(0.6, false) (:416: no rotation
+ * histogram), then per match the parallax test (:561-608), GeometricTools::Triangulate (src/GeometricTools.cc:47-66) or
+ * KeyFrame::UnprojectStereo (src/KeyFrame.cc:755-772), the depth signs (:617-623), the reprojection gates (:625-676, with
+ * the reference's use of key frame 1's mbf for the neighbour's right-image error, :669), the distance, far-point and scale
+ * gates (:679-695).  A key-frame-1 feature walks the neighbours until the first one that accepts it; from then on it holds a
+ * map point and the later searches skip it (src/ORBmatcher.cc:968).  The reference never writes vbMatched2 and every
+ * neighbour is a different key frame, so features of key frame 1 do not interact and are processed in parallel.
+ * Conventional cameras only (mpCamera2 == NULL, NLeft == -1).
+ *
+ * Two parts of the reference's loop stay with the caller: the baseline test (:447-464; ComputeSceneMedianDepth walks map
+ * points) -- pass only the neighbours that survive it -- and the CheckNewKeyFrames() early return (:440), checked once
+ * before the call.  The pointer surgery (:698-713) follows on the host: (neighbour, idx1) ascending is the reference's
+ * creation order.
+ *
+ * OrbmMapKeyFrame: side = as for orbm_search_for_triangulation (side.stereo[i] = mvuRight[i] >= 0; side.angle is not read);
+ * u_right = mvuRight, depth = mvDepth; key_x / key_y = mvKeys (the DISTORTED key points UnprojectStereo reads, KeyFrame.cc:
+ * 760-761; NULL = same as side.x / side.y); Rcw row-major, tcw = GetPose(), Ow = GetCameraCenter(); level_sigma2 =
+ * mvLevelSigma2, scale_factors = mvScaleFactors.  OrbmMapPair (one per neighbour): ep / F12 as orbm_search_for_triangulation
+ * defines them for (kf1, neighbour).  OrbmMapParams: inertial = mbInertial (parallax bound 0.9996, else 0.9998, :587);
+ * far_points / th_far = mbFarPoints / mThFarPoints (:688); scale_factor_1 = kf1->mfScaleFactor (ratioFactor = 1.5f * it).
+ *
+ * OrbmNewPoints (caller-allocated): per key-frame-1 feature neighbour[n1] (index of the accepting neighbour or -1), idx2[n1]
+ * (-1), x3d[n1][3], point_stereo[n1] (bPointStereo), and MapPoint::UpdateNormalAndDepth of the new point with its two
+ * observations (kf1, neighbour), pRefKF = kf1, level = octave of the feature: normal[n1][3], max_dist[n1], min_dist[n1] (the
+ * three may be NULL).  Per neighbour n_matched[j] = what SearchForTriangulation returns given the points created before it,
+ * n_created[j]; match12[n_neighbours][n1] (may be NULL) = the vMatchedPairs of those searches, match12[j][i] = neighbour j's
+ * feature matched to feature i or -1 (also -1 where the feature no longer took part).  The null vector of Triangulate's 4x4 matrix is computed in double and the point rounded to float.
+ * Returns the number of points created, or ORBX_ERR_ARG (the handle stays usable) / ORBX_ERR_NO_DEVICE / ORBX_ERR_HIP. */
+#define ORBM_MAX_NEIGHBOURS 64
+typedef struct OrbmMapKeyFrame {
+    OrbmTriSide side;
+    const float* u_right; const float* depth;
+    const float* key_x; const float* key_y;
+    float Rcw[9]; float tcw[3]; float Ow[3];
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float* level_sigma2; const float* scale_factors; int32_t n_levels;
+} OrbmMapKeyFrame;
+typedef struct OrbmMapPair {
+    float ep_x, ep_y;
+    float F12[9];
+    int32_t coarse;
+} OrbmMapPair;
+typedef struct OrbmMapParams {
+    int32_t inertial;
+    int32_t far_points; float th_far;
+    float scale_factor_1;
+} OrbmMapParams;
+typedef struct OrbmNewPoints {
+    int32_t* neighbour; int32_t* idx2; float* x3d; uint8_t* point_stereo;
+    float* normal; float* max_dist; float* min_dist;
+    int32_t* n_matched; int32_t* n_created;
+    int32_t* match12;
+} OrbmNewPoints;
+int orbm_create_new_map_points(orbm_matcher* m, const OrbmMapKeyFrame* kf1, const OrbmMapKeyFrame* neighbours, int n_neighbours,
+                               const OrbmMapPair* pairs, const OrbmMapParams* params, OrbmNewPoints* out);
+/* device time of the kernel of the last orbm_create_new_map_points on this handle (0 before the first) */
+float orbm_create_new_map_points_last_kernel_ms(const orbm_matcher* m);
+
 /* int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
  *                                         int windowSize) (:648-763; monocular map initialisation).  prev_x/y = vbPrevMatched;
  * f2 describes F2 (grid, descriptors, angles).  match12[n1] = vnMatches12; the caller then refreshes vbPrevMatched from

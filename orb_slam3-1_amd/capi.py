@@ -516,6 +516,114 @@ class Matcher:
         return n, m12[:n1]
 
 
+    def create_new_map_points_prepare(self, kf1, neighbours, pairs, params):
+        """flatten the arguments of orbm_create_new_map_points once (no device needed).  kf1 / neighbours[j]: dict(desc, has_mp,
+        stereo, x, y, octave, fv, u_right, depth, [key_x, key_y], Rcw, tcw, Ow, fx, fy, cx, cy, invfx, invfy, mb, mbf, level_sigma2,
+        scale_factors); pairs[j]: dict(ep, F12, coarse); params: dict(inertial, far_points, th_far, scale_factor_1)."""
+        if len(pairs) != len(neighbours):
+            raise ValueError("%d pairs for %d neighbours" % (len(pairs), len(neighbours)))
+        keep = []
+        kfs = (OrbmMapKeyFrame * (1 + len(neighbours)))()
+        for q, k in enumerate([kf1] + list(neighbours)):
+            _fill_map_key_frame(kfs[q], k, keep, "kf1" if q == 0 else "neighbour %d" % (q - 1))
+        prs = (OrbmMapPair * max(len(pairs), 1))()
+        for j, w in enumerate(pairs):
+            F12 = np.ascontiguousarray(w["F12"], np.float32).reshape(-1)
+            if F12.shape != (9,):
+                raise ValueError("pair %d: F12 is not 3x3" % j)
+            prs[j].ep_x, prs[j].ep_y = float(w["ep"][0]), float(w["ep"][1])
+            prs[j].F12[:] = [float(v) for v in F12]
+            prs[j].coarse = int(bool(w.get("coarse", False)))
+        par = OrbmMapParams(int(bool(params["inertial"])), int(bool(params["far_points"])), float(params["th_far"]), float(params["scale_factor_1"]))
+        n1, nb = kfs[0].side.n, len(neighbours)
+        o = dict(neighbour=np.full(max(n1, 1), -1, np.int32), idx2=np.full(max(n1, 1), -1, np.int32), x3d=np.zeros((max(n1, 1), 3), np.float32),
+                 point_stereo=np.zeros(max(n1, 1), np.uint8), normal=np.zeros((max(n1, 1), 3), np.float32), max_dist=np.zeros(max(n1, 1), np.float32),
+                 min_dist=np.zeros(max(n1, 1), np.float32), n_matched=np.zeros(max(nb, 1), np.int32), n_created=np.zeros(max(nb, 1), np.int32),
+                 match12=np.full((max(nb, 1), max(n1, 1)), -1, np.int32))
+        out = OrbmNewPoints(*[o[f].ctypes.data for f, _ in OrbmNewPoints._fields_])
+        return dict(kfs=kfs, pairs=prs, params=par, out=out, arrays=o, n1=n1, n_neighbours=nb, keep=keep)
+
+    def create_new_map_points_launch(self, prep):
+        """the C call alone: one upload, one kernel launch, one download"""
+        lib.orbm_create_new_map_points.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+        nbs = C.byref(prep["kfs"], C.sizeof(OrbmMapKeyFrame)) if prep["n_neighbours"] else None
+        return _check(lib.orbm_create_new_map_points(self._h, C.byref(prep["kfs"]), nbs, prep["n_neighbours"],
+                                                     C.byref(prep["pairs"]), C.byref(prep["params"]), C.byref(prep["out"])))
+
+    def create_new_map_points(self, kf1, neighbours, pairs, params):
+        """LocalMapping::CreateNewMapPoints: dict(created, neighbour, idx2, x3d, point_stereo, normal, max_dist, min_dist [n1],
+        n_matched, n_created [n_neighbours], match12 [n_neighbours][n1]); (neighbour, idx1) ascending over neighbour >= 0 is the reference's creation order"""
+        prep = self.create_new_map_points_prepare(kf1, neighbours, pairs, params)
+        created = self.create_new_map_points_launch(prep)
+        a, n1, nb = prep["arrays"], prep["n1"], prep["n_neighbours"]
+        r = {k: (a[k][:nb] if k in ("n_matched", "n_created") else a[k][:nb, :n1] if k == "match12" else a[k][:n1]).copy() for k in a}
+        r["created"] = created
+        return r
+
+    def create_new_map_points_last_kernel_ms(self):
+        lib.orbm_create_new_map_points_last_kernel_ms.restype = C.c_float
+        lib.orbm_create_new_map_points_last_kernel_ms.argtypes = [C.c_void_p]
+        return float(lib.orbm_create_new_map_points_last_kernel_ms(self._h))
+
+
+ORBM_MAX_NEIGHBOURS = 64
+
+
+class OrbmMapKeyFrame(C.Structure):
+    _fields_ = [("side", Matcher._TriSide), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("key_x", C.c_void_p), ("key_y", C.c_void_p),
+                ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("mb", C.c_float), ("mbf", C.c_float),
+                ("level_sigma2", C.c_void_p), ("scale_factors", C.c_void_p), ("n_levels", C.c_int32)]
+
+
+class OrbmMapPair(C.Structure):
+    _fields_ = [("ep_x", C.c_float), ("ep_y", C.c_float), ("F12", C.c_float * 9), ("coarse", C.c_int32)]
+
+
+class OrbmMapParams(C.Structure):
+    _fields_ = [("inertial", C.c_int32), ("far_points", C.c_int32), ("th_far", C.c_float), ("scale_factor_1", C.c_float)]
+
+
+class OrbmNewPoints(C.Structure):
+    _fields_ = [("neighbour", C.c_void_p), ("idx2", C.c_void_p), ("x3d", C.c_void_p), ("point_stereo", C.c_void_p),
+                ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("n_matched", C.c_void_p), ("n_created", C.c_void_p),
+                ("match12", C.c_void_p)]
+
+
+def _fill_map_key_frame(s, k, keep, name):
+    """one OrbmMapKeyFrame from a dict; the C side copies n rows of every per-feature array, so unequal lengths are refused here"""
+    a = dict(desc=np.ascontiguousarray(k["desc"], np.uint8), has_mp=np.ascontiguousarray(k["has_mp"], np.uint8),
+             stereo=np.ascontiguousarray(k["stereo"], np.uint8), x=np.ascontiguousarray(k["x"], np.float32),
+             y=np.ascontiguousarray(k["y"], np.float32), octave=np.ascontiguousarray(k["octave"], np.int32),
+             u_right=np.ascontiguousarray(k["u_right"], np.float32), depth=np.ascontiguousarray(k["depth"], np.float32))
+    for f in ("key_x", "key_y"):
+        if k.get(f) is not None:
+            a[f] = np.ascontiguousarray(k[f], np.float32)
+    n = len(a["x"])
+    for f, v in a.items():
+        if v.shape != ((n, 32) if f == "desc" else (n,)):
+            raise ValueError("%s: %s does not hold %d features" % (name, f, n))
+    sig, sc = np.ascontiguousarray(k["level_sigma2"], np.float32), np.ascontiguousarray(k["scale_factors"], np.float32)
+    if sig.shape != sc.shape or sig.ndim != 1:
+        raise ValueError("%s: level_sigma2 and scale_factors differ in length" % name)
+    fv = _fv(k["fv"])
+    keep.append((a, sig, sc, fv))
+    s.side = Matcher._TriSide(n, a["desc"].ctypes.data, a["has_mp"].ctypes.data, a["stereo"].ctypes.data, a["x"].ctypes.data,
+                              a["y"].ctypes.data, a["octave"].ctypes.data, None, fv)
+    s.u_right, s.depth = a["u_right"].ctypes.data, a["depth"].ctypes.data
+    s.key_x = a["key_x"].ctypes.data if "key_x" in a else None
+    s.key_y = a["key_y"].ctypes.data if "key_y" in a else None
+    for f, m in (("Rcw", 9), ("tcw", 3), ("Ow", 3)):
+        v = np.asarray(k[f], np.float32).reshape(-1)
+        if v.shape != (m,):
+            raise ValueError("%s: %s does not hold %d values" % (name, f, m))
+        getattr(s, f)[:] = [float(t) for t in v]
+    for f in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf"):
+        setattr(s, f, float(k[f]))
+    s.level_sigma2, s.scale_factors, s.n_levels = sig.ctypes.data, sc.ctypes.data, len(sc)
+
+
 class _BowSideDevice(C.Structure):
     _fields_ = [("desc", C.c_void_p), ("kps", C.c_void_p), ("n", C.c_void_p), ("cap", C.c_int32), ("valid", C.c_void_p),
                 ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p), ("n_fv_nodes", C.c_void_p)]

@@ -1,0 +1,300 @@
+// orbm_new_points.hip -- LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:392-716) as one launch:
+// SearchForTriangulation against every neighbour plus the per-match geometry (orbm_new_points_geometry.h).
+//
+// The reference's call site builds ORBmatcher(0.6, false) (no rotation histogram), never writes vbMatched2 and visits every
+// neighbour once, so a key-frame-1 feature interacts with nothing but its own chain: it walks the neighbours in order until
+// the first one where it matches and passes every gate.  The kernel gives each entry of key frame 1's feature vector a
+// group of 16 lanes: the lanes spread over the neighbour's features of the same vocabulary node, a (distance, position)
+// key reduction picks what k_triangulation's sequential `dist > bestDist -> continue` rule picks (the LAST of the equally
+// good candidates that pass the epipolar test), and lane 0 of the group runs the geometry.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "../../include/orbslam3_hip.h"
+#include "hip_check.h"
+#include "orbm_host.h"
+#include "orbm_new_points_geometry.h"
+
+namespace orbm {
+
+constexpr int kNmpGroup = 16;           // lanes per key-frame-1 feature: a vocabulary node holds 10-20 features of a 1000-2000 feature key frame
+constexpr int kNmpThreads = 256;
+
+struct NmpKeyFrameDev {
+    const uint8_t* desc; const uint8_t* has_mp; const uint8_t* stereo;
+    const float* x; const float* y; const int32_t* octave;
+    const float* u_right; const float* depth; const float* key_x; const float* key_y;
+    const int32_t* off; const uint32_t* feat;       // mFeatVec, flattened
+    const float* sigma2; const float* scale;
+    const int32_t* node_of;                         // [nodes of key frame 1] -> the same vocabulary node in this key frame's mFeatVec or -1 (neighbours only)
+    nmp::Camera cam;
+    float F12[9]; float ep_x, ep_y;                 // of the pair (key frame 1, this neighbour)
+    int32_t coarse;
+};
+
+struct NmpArgs {
+    const NmpKeyFrameDev* kf;                       // [1 + n_nb], key frame 1 first
+    const int32_t* entry_node;                      // [total1]: node (index into key frame 1's mFeatVec) of each flattened entry
+    int32_t total1, n_nb, n1;
+    nmp::Rule rule;
+    float last_scale;                               // kf1->mvScaleFactors[nLevels - 1]
+    int32_t* neighbour; int32_t* idx2; float* x3d; uint8_t* point_stereo;       // [n1], neighbour pre-set to -1
+    float* normal; float* max_dist; float* min_dist;
+    int32_t* n_matched; int32_t* n_created;         // [n_nb], pre-set to 0
+    int32_t* match12;                               // [n_nb][n1] pre-set to -1, or NULL
+};
+
+__device__ __forceinline__ nmp::Obs nmp_obs(const NmpKeyFrameDev& K, int i)
+{
+    nmp::Obs o;
+    o.x = K.x[i]; o.y = K.y[i]; o.ur = K.u_right[i]; o.depth = K.depth[i];
+    o.kx = K.key_x[i]; o.ky = K.key_y[i];
+    const int oct = K.octave[i];
+    o.sigma2 = K.sigma2[oct]; o.scale = K.scale[oct];
+    return o;
+}
+
+__global__ __launch_bounds__(kNmpThreads) void k_new_map_points(NmpArgs A)
+{
+    const int e1 = (blockIdx.x * kNmpThreads + threadIdx.x) / kNmpGroup;        // the 16 lanes of a group share e1 and every branch below
+    const int sub = threadIdx.x & (kNmpGroup - 1);
+    if (e1 >= A.total1) return;
+    const NmpKeyFrameDev& K1 = A.kf[0];
+    const int idx1 = (int)K1.feat[e1];
+    if (K1.has_mp[idx1]) return;                                // already a MapPoint (src/ORBmatcher.cc:968)
+    const int node1 = A.entry_node[e1];
+    const bool bStereo1 = K1.stereo[idx1] != 0;
+    const uint8_t* dd1 = K1.desc + (size_t)idx1 * 32;
+    const float x1 = K1.x[idx1], y1 = K1.y[idx1];
+
+    for (int j = 0; j < A.n_nb; j++) {
+        const NmpKeyFrameDev& K2 = A.kf[1 + j];
+        const int l2 = K2.node_of[node1];
+        if (l2 < 0) continue;
+        const float la = x1 * K2.F12[0] + y1 * K2.F12[3] + K2.F12[6];           // Pinhole::epipolarConstrain, as k_triangulation
+        const float lb = x1 * K2.F12[1] + y1 * K2.F12[4] + K2.F12[7];
+        const float lc = x1 * K2.F12[2] + y1 * K2.F12[5] + K2.F12[8];
+        const float den = la * la + lb * lb;
+        const int b2 = K2.off[l2], n2 = K2.off[l2 + 1] - b2;
+        // min over (dist, ~position): the smallest distance among the candidates that pass every test, the last of them on ties
+        unsigned long long key = ~0ull;
+        for (int p = sub; p < n2; p += kNmpGroup) {
+            const int idx2 = (int)K2.feat[b2 + p];
+            if (K2.has_mp[idx2]) continue;
+            const int dist = hamming256(dd1, K2.desc + (size_t)idx2 * 32);
+            if (dist > TH_LOW) continue;
+            const float kx = K2.x[idx2], ky = K2.y[idx2];
+            const int o2 = K2.octave[idx2];
+            if (!bStereo1 && !K2.stereo[idx2]) {
+                const float distex = K2.ep_x - kx, distey = K2.ep_y - ky;
+                if (distex * distex + distey * distey < 100 * K2.scale[o2]) continue;       // too close to the epipole (:1011)
+            }
+            bool ok = K2.coarse != 0;
+            if (!ok && den != 0) {
+                const float num = la * kx + lb * ky + lc;
+                const float dsqr = num * num / den;
+                ok = (double)dsqr < 3.84 * (double)K2.sigma2[o2];
+            }
+            if (ok) {
+                const unsigned long long k = ((unsigned long long)dist << 32) | (unsigned)(0x7FFFFFFF - p);
+                key = k < key ? k : key;
+            }
+        }
+        for (int o = kNmpGroup / 2; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(key, o, kNmpGroup);
+            key = other < key ? other : key;
+        }
+        if (key == ~0ull) continue;
+        const int idx2 = (int)K2.feat[b2 + (0x7FFFFFFF - (int)(key & 0xFFFFFFFFu))];
+        int created = 0;
+        if (sub == 0) {
+            atomicAdd(&A.n_matched[j], 1);
+            if (A.match12) A.match12[(size_t)j * A.n1 + idx1] = idx2;
+            float x3D[3];
+            int pstereo = 0;
+            created = nmp::new_point(K1.cam, nmp_obs(K1, idx1), K2.cam, nmp_obs(K2, idx2), A.rule, x3D, &pstereo) ? 1 : 0;
+            if (created) {
+                A.neighbour[idx1] = j; A.idx2[idx1] = idx2; A.point_stereo[idx1] = (uint8_t)pstereo;
+                A.x3d[3 * idx1] = x3D[0]; A.x3d[3 * idx1 + 1] = x3D[1]; A.x3d[3 * idx1 + 2] = x3D[2];
+                nmp::normal_and_depth(x3D, K1.cam.Ow, K2.cam.Ow, K1.scale[K1.octave[idx1]], A.last_scale,
+                                      A.normal + 3 * idx1, A.max_dist + idx1, A.min_dist + idx1);
+                atomicAdd(&A.n_created[j], 1);
+            }
+        }
+        if (__shfl(created, 0, kNmpGroup)) break;               // the feature holds a map point from here on
+    }
+}
+
+}  // namespace orbm
+
+namespace {
+
+int check_key_frame(const OrbmMapKeyFrame* k, const char* name)
+{
+    const OrbmTriSide& s = k->side;
+    if (s.n < 0) return fail(ORBX_ERR_ARG, "%s: negative feature count", name);
+    if (s.n > 0 && (!s.desc || !s.has_mp || !s.stereo || !s.x || !s.y || !s.octave || !k->u_right || !k->depth))
+        return fail(ORBX_ERR_ARG, "%s: NULL key-frame arrays", name);
+    if ((k->key_x == nullptr) != (k->key_y == nullptr)) return fail(ORBX_ERR_ARG, "%s: key_x and key_y go together", name);
+    if (k->n_levels < 1 || !k->level_sigma2 || !k->scale_factors) return fail(ORBX_ERR_ARG, "%s: NULL scale tables", name);
+    const int r = check_fv(&s.fv, s.n, name);
+    if (r) return r;
+    if (s.fv.n_nodes > 0 && s.fv.offset[0] != 0) return fail(ORBX_ERR_ARG, "%s: feature-vector offsets must start at 0", name);
+    if (!features_unique(&s.fv, s.n)) return fail(ORBX_ERR_ARG, "%s: a feature appears in two vocabulary nodes", name);
+    for (int i = 0; i < s.n; i++)
+        if (s.octave[i] < 0 || s.octave[i] >= k->n_levels) return fail(ORBX_ERR_ARG, "%s: octave out of range", name);
+    return ORBX_OK;
+}
+
+struct KeyFrameOffsets { size_t desc, has_mp, stereo, x, y, octave, u_right, depth, key_x, key_y, off, feat, sigma2, scale, node_of; };
+
+}  // namespace
+
+extern "C" {
+
+int orbm_create_new_map_points(orbm_matcher* m, const OrbmMapKeyFrame* kf1, const OrbmMapKeyFrame* neighbours, int n_neighbours,
+                               const OrbmMapPair* pairs, const OrbmMapParams* params, OrbmNewPoints* out)
+{
+    if (!kf1 || !params || !out) return fail(ORBX_ERR_ARG, "NULL argument");
+    if (n_neighbours < 0 || n_neighbours > ORBM_MAX_NEIGHBOURS) return fail(ORBX_ERR_ARG, "n_neighbours %d outside [0, %d]", n_neighbours, ORBM_MAX_NEIGHBOURS);
+    if (n_neighbours > 0 && (!neighbours || !pairs || !out->n_matched || !out->n_created)) return fail(ORBX_ERR_ARG, "NULL neighbour arrays");
+    int r = check_key_frame(kf1, "kf1");
+    if (r) return r;
+    for (int j = 0; j < n_neighbours; j++)
+        if ((r = check_key_frame(&neighbours[j], "neighbour")) != ORBX_OK) return r;
+    const int n1 = kf1->side.n;
+    if (n1 > 0 && (!out->neighbour || !out->idx2 || !out->x3d || !out->point_stereo)) return fail(ORBX_ERR_ARG, "NULL output arrays");
+    const bool want_normal = out->normal || out->max_dist || out->min_dist;
+    if (want_normal && n1 > 0 && (!out->normal || !out->max_dist || !out->min_dist)) return fail(ORBX_ERR_ARG, "normal, max_dist and min_dist go together");
+    if (!m) {                                                   // no handle exists without a device: there is no CPU fallback
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
+        return fail(ORBX_ERR_ARG, "NULL matcher");
+    }
+    for (int i = 0; i < n1; i++) {
+        out->neighbour[i] = -1; out->idx2[i] = -1; out->point_stereo[i] = 0;
+        out->x3d[3 * i] = out->x3d[3 * i + 1] = out->x3d[3 * i + 2] = 0.f;
+        if (want_normal) { out->normal[3 * i] = out->normal[3 * i + 1] = out->normal[3 * i + 2] = 0.f; out->max_dist[i] = out->min_dist[i] = 0.f; }
+    }
+    for (int j = 0; j < n_neighbours; j++) out->n_matched[j] = out->n_created[j] = 0;
+    if (out->match12)
+        for (size_t i = 0; i < (size_t)n1 * n_neighbours; i++) out->match12[i] = -1;
+    const OrbmFeatVec& fv1 = kf1->side.fv;
+    const int nn1 = fv1.n_nodes, total1 = nn1 > 0 ? fv1.offset[nn1] : 0;
+    if (n1 == 0 || n_neighbours == 0 || total1 == 0) return 0;
+
+    ORBX_HIP(hipSetDevice(m->device));
+    Blob blob(m->h_blob);
+    const int nkf = 1 + n_neighbours;
+    std::vector<KeyFrameOffsets> o(nkf);
+    std::vector<int32_t> node_of(nn1);
+    for (int q = 0; q < nkf; q++) {
+        const OrbmMapKeyFrame* k = q ? &neighbours[q - 1] : kf1;
+        const OrbmTriSide& s = k->side;
+        const int n = s.n, nn = s.fv.n_nodes, tot = nn > 0 ? s.fv.offset[nn] : 0;
+        KeyFrameOffsets& f = o[q];
+        f.desc = blob.put(s.desc, (size_t)n * 32); f.has_mp = blob.put(s.has_mp, n); f.stereo = blob.put(s.stereo, n);
+        f.x = blob.put(s.x, sizeof(float) * n); f.y = blob.put(s.y, sizeof(float) * n); f.octave = blob.put(s.octave, sizeof(int32_t) * n);
+        f.u_right = blob.put(k->u_right, sizeof(float) * n); f.depth = blob.put(k->depth, sizeof(float) * n);
+        f.key_x = k->key_x ? blob.put(k->key_x, sizeof(float) * n) : f.x;
+        f.key_y = k->key_y ? blob.put(k->key_y, sizeof(float) * n) : f.y;
+        f.off = blob.put(s.fv.offset, sizeof(int32_t) * (nn > 0 ? nn + 1 : 0)); f.feat = blob.put(s.fv.feat, sizeof(uint32_t) * tot);
+        f.sigma2 = blob.put(k->level_sigma2, sizeof(float) * k->n_levels); f.scale = blob.put(k->scale_factors, sizeof(float) * k->n_levels);
+        f.node_of = 0;
+        if (q) {                                                // both node lists ascend (check_fv): one merge pass per neighbour
+            int b = 0;
+            for (int a = 0; a < nn1; a++) {
+                while (b < nn && s.fv.node_id[b] < fv1.node_id[a]) b++;
+                node_of[a] = (b < nn && s.fv.node_id[b] == fv1.node_id[a]) ? b : -1;
+            }
+            f.node_of = blob.put(node_of.data(), sizeof(int32_t) * nn1);
+        }
+    }
+    std::vector<int32_t> entry_node(total1);
+    for (int a = 0; a < nn1; a++)
+        for (int e = fv1.offset[a]; e < fv1.offset[a + 1]; e++) entry_node[e] = a;
+    const size_t o_entry = blob.put(entry_node.data(), sizeof(int32_t) * total1);
+    const size_t o_kf = blob.reserve(sizeof(orbm::NmpKeyFrameDev) * nkf);
+    // outputs: `neighbour` (-1) and the two counters (0) travel with the inputs, the rest is written where neighbour >= 0
+    const size_t o_out = blob.reserve(0);
+    const size_t o_nb = blob.reserve(sizeof(int32_t) * n1);
+    const size_t o_nm = blob.reserve(sizeof(int32_t) * n_neighbours), o_nc = blob.reserve(sizeof(int32_t) * n_neighbours);
+    const size_t in_bytes = m->h_blob.size();
+    const size_t o_idx2 = blob.reserve(sizeof(int32_t) * n1), o_x3d = blob.reserve(sizeof(float) * 3 * n1), o_ps = blob.reserve(n1);
+    const size_t o_nrm = blob.reserve(sizeof(float) * 3 * n1), o_mx = blob.reserve(sizeof(float) * n1), o_mn = blob.reserve(sizeof(float) * n1);
+    const size_t o_m12 = out->match12 ? blob.reserve(sizeof(int32_t) * n1 * n_neighbours) : 0;
+    const size_t all_bytes = m->h_blob.size();
+    r = m->ensure(all_bytes);
+    if (r) return r;
+    uint8_t* b = m->d_blob;
+    uint8_t* h = m->h_blob.data();
+    std::memset(h + o_nb, 0xFF, sizeof(int32_t) * n1);
+    for (int q = 0; q < nkf; q++) {
+        const OrbmMapKeyFrame* k = q ? &neighbours[q - 1] : kf1;
+        const KeyFrameOffsets& f = o[q];
+        orbm::NmpKeyFrameDev d;
+        std::memset(&d, 0, sizeof(d));
+        d.desc = b + f.desc; d.has_mp = b + f.has_mp; d.stereo = b + f.stereo;
+        d.x = (const float*)(b + f.x); d.y = (const float*)(b + f.y); d.octave = (const int32_t*)(b + f.octave);
+        d.u_right = (const float*)(b + f.u_right); d.depth = (const float*)(b + f.depth);
+        d.key_x = (const float*)(b + f.key_x); d.key_y = (const float*)(b + f.key_y);
+        d.off = (const int32_t*)(b + f.off); d.feat = (const uint32_t*)(b + f.feat);
+        d.sigma2 = (const float*)(b + f.sigma2); d.scale = (const float*)(b + f.scale);
+        d.node_of = (const int32_t*)(b + f.node_of);
+        std::memcpy(d.cam.Rcw, k->Rcw, sizeof(d.cam.Rcw)); std::memcpy(d.cam.tcw, k->tcw, sizeof(d.cam.tcw)); std::memcpy(d.cam.Ow, k->Ow, sizeof(d.cam.Ow));
+        d.cam.fx = k->fx; d.cam.fy = k->fy; d.cam.cx = k->cx; d.cam.cy = k->cy; d.cam.invfx = k->invfx; d.cam.invfy = k->invfy;
+        d.cam.mb = k->mb; d.cam.mbf = k->mbf;
+        if (q) {
+            const OrbmMapPair& p = pairs[q - 1];
+            std::memcpy(d.F12, p.F12, sizeof(d.F12)); d.ep_x = p.ep_x; d.ep_y = p.ep_y; d.coarse = p.coarse;
+        }
+        std::memcpy(h + o_kf + sizeof(d) * q, &d, sizeof(d));
+    }
+    orbm::NmpArgs A;
+    A.kf = (const orbm::NmpKeyFrameDev*)(b + o_kf); A.entry_node = (const int32_t*)(b + o_entry);
+    A.total1 = total1; A.n_nb = n_neighbours; A.n1 = n1;
+    A.match12 = out->match12 ? (int32_t*)(b + o_m12) : nullptr;
+    A.rule.inertial = params->inertial; A.rule.far_points = params->far_points; A.rule.th_far = params->th_far;
+    A.rule.ratio_factor = 1.5f * params->scale_factor_1;
+    A.last_scale = kf1->scale_factors[kf1->n_levels - 1];
+    A.neighbour = (int32_t*)(b + o_nb); A.idx2 = (int32_t*)(b + o_idx2); A.x3d = (float*)(b + o_x3d); A.point_stereo = b + o_ps;
+    A.normal = (float*)(b + o_nrm); A.max_dist = (float*)(b + o_mx); A.min_dist = (float*)(b + o_mn);
+    A.n_matched = (int32_t*)(b + o_nm); A.n_created = (int32_t*)(b + o_nc);
+    for (hipEvent_t& e : m->nmp_ev)
+        if (!e) ORBX_HIP(hipEventCreate(&e));
+    ORBX_HIP(hipMemcpyAsync(b, h, in_bytes, hipMemcpyHostToDevice, m->stream));
+    if (out->match12) ORBX_HIP(hipMemsetAsync(b + o_m12, 0xFF, sizeof(int32_t) * n1 * n_neighbours, m->stream));
+    const int groups_per_block = orbm::kNmpThreads / orbm::kNmpGroup;
+    ORBX_HIP(hipEventRecord(m->nmp_ev[0], m->stream));
+    hipLaunchKernelGGL(orbm::k_new_map_points, dim3((total1 + groups_per_block - 1) / groups_per_block), dim3(orbm::kNmpThreads), 0, m->stream, A);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(m->nmp_ev[1], m->stream));
+    ORBX_HIP(hipMemcpyAsync(h + o_out, b + o_out, all_bytes - o_out, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipEventElapsedTime(&m->nmp_kernel_ms, m->nmp_ev[0], m->nmp_ev[1]));
+
+    const int32_t* h_nb = (const int32_t*)(h + o_nb); const int32_t* h_idx2 = (const int32_t*)(h + o_idx2);
+    const float* h_x3d = (const float*)(h + o_x3d); const float* h_nrm = (const float*)(h + o_nrm);
+    const float* h_mx = (const float*)(h + o_mx); const float* h_mn = (const float*)(h + o_mn);
+    int created = 0;
+    for (int i = 0; i < n1; i++) {
+        if (h_nb[i] < 0) continue;
+        created++;
+        out->neighbour[i] = h_nb[i]; out->idx2[i] = h_idx2[i]; out->point_stereo[i] = h[o_ps + i];
+        for (int c = 0; c < 3; c++) out->x3d[3 * i + c] = h_x3d[3 * i + c];
+        if (want_normal) {
+            for (int c = 0; c < 3; c++) out->normal[3 * i + c] = h_nrm[3 * i + c];
+            out->max_dist[i] = h_mx[i]; out->min_dist[i] = h_mn[i];
+        }
+    }
+    if (out->match12) std::memcpy(out->match12, h + o_m12, sizeof(int32_t) * n1 * n_neighbours);
+    std::memcpy(out->n_matched, h + o_nm, sizeof(int32_t) * n_neighbours);
+    std::memcpy(out->n_created, h + o_nc, sizeof(int32_t) * n_neighbours);
+    return created;
+}
+
+float orbm_create_new_map_points_last_kernel_ms(const orbm_matcher* m) { return m ? m->nmp_kernel_ms : 0.0f; }
+
+}  // extern "C"

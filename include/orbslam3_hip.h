@@ -902,6 +902,66 @@ typedef struct Sim3OptResult {
  * return (0: nulled at :2323 or :2369).  mAcumHessian is only zeroed by the reference (:2356); the caller does the same. */
 int  sim3_optimize_batch(sim3_solver* s, const Sim3OptProblem* problems, int n_problems, Sim3OptResult* results, uint8_t* const* keep_out);
 
+/* ---- pose graph: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1501-1783, and the merge overload :1785-2113) ----
+ * essg_optimize is what both overloads do between building the graph and writing the map back: VertexSim3Expmap vertices,
+ * EdgeSim3 edges with identity information and no robust kernel, g2o's numeric Jacobians (central differences, delta = 1e-9,
+ * through oplusImpl), Levenberg with setUserLambdaInit(lambda_init) and optimize(max_iters), all in double; then the SE3
+ * recovery [R | t / s] and the map-point correction of :1735-1777.  Every vertex is a pose, so there is no Schur complement:
+ * the 7 x 7-block system over the free vertices is assembled densely and factored by the Cholesky kernels of the global BA.
+ * The caller flattens the graph (include/orbslam3_shim_loop.hpp does it for the reference's types):
+ *   - vertex k: sim3[8k..] = Scw as q x y z w (used as given), t, s; fixed[k] != 0 for setFixed(true);
+ *   - edge e: edge_vertices[2e] = vertex 0 (nIDi), [2e + 1] = vertex 1 (nIDj), edge_measurement[8e..] = Sji.  An edge between
+ *     two fixed vertices stays in the graph (it counts in chi2), and the same pair may appear more than once;
+ *   - fix_scale: VertexSim3Expmap::_fix_scale of every vertex.  The system keeps 7 unknowns per vertex; the seventh entry of an
+ *     update is zeroed before exp, so the scale of a vertex comes back bit-identical;
+ *   - point p (optional): points[3p..] = GetWorldPos() (float), point_ref[p] = vertex of its reference key frame; the result is
+ *     correctedSwr.map(Srw.map(P)) with Srw the INPUT sim3 of that vertex, computed in double and cast to float.
+ * pose_q / pose_t (may be NULL): rotation().cast<float>() normalised in float (Sophus::SO3f's constructor) and
+ * translation().cast<float>() / (float)s, as :1747 evaluates it.  The merge overload divides in double (:2071): take sim3_out.
+ * Capacity: ESSG_MAX_FREE_VERTICES free vertices (any number of fixed ones); above it ORBX_ERR_CAPACITY, and the adapter falls
+ * back to the reference.  The dense factorisation grows with the cube of the number of free vertices.
+ * Argument checks (ORBX_ERR_ARG) are made before anything touches a device: NULL pointers, negative sizes, an index out of
+ * range, an edge from a vertex to itself, no free vertex, a scale that is not positive, a value that is not finite,
+ * lambda_init <= 0 (the reference always sets 1e-16).
+ * stop_flag (may be NULL): polled, never written, before every iteration and after every Levenberg trial (stop reason 3).
+ * A handle serves ONE call at a time, on its own stream: calls on the same handle from several threads must be serialised by
+ * the caller; use one handle per thread otherwise. */
+#define ESSG_MAX_FREE_VERTICES 1024
+
+typedef struct EssgProblem {
+    int32_t n_vertices;
+    const double* sim3;             /* [n_vertices][8] */
+    const uint8_t* fixed;           /* [n_vertices] */
+    int32_t n_edges;
+    const int32_t* edge_vertices;   /* [n_edges][2] */
+    const double* edge_measurement; /* [n_edges][8] */
+    int32_t fix_scale;
+    int32_t max_iters;              /* optimize(20) */
+    double lambda_init;             /* setUserLambdaInit(1e-16) */
+    int32_t n_points;
+    const float* points;            /* [n_points][3] or NULL */
+    const int32_t* point_ref;       /* [n_points] or NULL */
+} EssgProblem;
+
+typedef struct EssgResult {
+    double* sim3_out;               /* [n_vertices][8]: the optimised Scw; fixed vertices bit-identical to the input */
+    float* pose_q;                  /* [n_vertices][4] or NULL */
+    float* pose_t;                  /* [n_vertices][3] or NULL */
+    float* points_out;              /* [n_points][3] */
+    LbaStats stats;
+} EssgResult;
+
+typedef struct essg_solver essg_solver;
+int  essg_create(int device, essg_solver** out);
+void essg_destroy(essg_solver* s);
+int  essg_optimize(essg_solver* s, const EssgProblem* problem, EssgResult* result, const volatile uint8_t* stop_flag);
+/* the argument checks of essg_optimize alone (host only, no device needed): ORBX_OK, ORBX_ERR_ARG or ORBX_ERR_CAPACITY */
+int  essg_check(const EssgProblem* problem, const EssgResult* result);
+/* device time of the LAST call (HIP events on the solver's stream around all of its launches), milliseconds; stage_ms (may be
+ * NULL) receives the host-side wall time of that call split into [0] graph structure + upload, [1] Levenberg rounds,
+ * [2] epilogue + download */
+double essg_last_device_ms(const essg_solver* s, double* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

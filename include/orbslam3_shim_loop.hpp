@@ -15,7 +15,11 @@
 
 #ifdef ORBSLAM3_HIP_WITH_REFERENCE
 
+#include <map>
 #include <memory>
+#include <mutex>
+#include <set>
+#include <type_traits>
 
 namespace ORB_SLAM3 {
 
@@ -335,6 +339,345 @@ int OptimizeSim3HIP(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMa
         for (int c = 0; c < 7; c++) mAcumHessian(r, c) = 0.0;                           // :2356 (the reference only zeroes it)
     g2oS12 = Sim3T(Eigen::Quaterniond(res.q[3], res.q[0], res.q[1], res.q[2]), Eigen::Vector3d(res.t[0], res.t[1], res.t[2]), res.s);   // :2377-2378
     return res.n_in;
+}
+
+
+// ---- Optimizer::OptimizeEssentialGraph, both overloads (src/Optimizer.cc:1501-1783, :1785-2113), on essg_optimize ----
+// The adapters walk the graph as the reference does and hand it over as arrays (EssentialGraphFlat); the walk is separate from
+// the call so that it can be checked without a device (tests/stubs/shim_essential_toy.cpp).  KF / MP / MapT are the reference's
+// KeyFrame / MapPoint / Map (template parameters, so that the stand-ins of the tests can add the members they lack by
+// derivation); Sim3T = g2o::Sim3; PoseMap = LoopClosing::KeyFrameAndPose; Opt = the class whose OptimizeEssentialGraph serves what
+// the device does not: invalid input (ORBX_ERR_ARG), more than ESSG_MAX_FREE_VERTICES free key frames (ORBX_ERR_CAPACITY).
+// OptimizeEssentialGraph4DoF (the inertial case, :2115 ff. of LoopClosing's dispatch) is a different function and stays the reference's.
+struct EssentialGraphFlat {
+    std::vector<long unsigned int> id;      // mnId per vertex, in the order the reference adds them
+    std::vector<double> sim3;               // [8] per vertex: q x y z w, t, s
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> edges;             // [2] per edge: vertex 0 (nIDi), vertex 1 (nIDj), as indices into id
+    std::vector<double> meas;               // [8] per edge: Sji
+    std::vector<float> points;              // loop overload: GetWorldPos() of every map point that is not bad
+    std::vector<int32_t> point_ref;
+    std::vector<size_t> point_index;        // its index in GetAllMapPoints()
+    int dropped_edges = 0;                  // edges g2o's addEdge refuses because a vertex is missing (a bad key frame)
+    int fix_scale = 0;
+};
+
+namespace essential_detail {
+
+struct S8 { double v[8]; };     // q x y z w, t, s
+
+inline S8 identity() { S8 a; for (int i = 0; i < 8; i++) a.v[i] = (i == 3 || i == 7) ? 1.0 : 0.0; return a; }
+inline void rotate(const double* q, const double* p, double* o)         // Eigen's quaternion * vector
+{
+    const double ux = 2 * (q[1] * p[2] - q[2] * p[1]), uy = 2 * (q[2] * p[0] - q[0] * p[2]), uz = 2 * (q[0] * p[1] - q[1] * p[0]);
+    o[0] = p[0] + q[3] * ux + (q[1] * uz - q[2] * uy);
+    o[1] = p[1] + q[3] * uy + (q[2] * ux - q[0] * uz);
+    o[2] = p[2] + q[3] * uz + (q[0] * uy - q[1] * ux);
+}
+inline S8 mul(const S8& a, const S8& b)                                  // g2o::Sim3::operator* (sim3.h:266-272)
+{
+    S8 o;
+    double rt[3];
+    rotate(a.v, b.v + 4, rt);
+    o.v[3] = a.v[3] * b.v[3] - a.v[0] * b.v[0] - a.v[1] * b.v[1] - a.v[2] * b.v[2];
+    o.v[0] = a.v[3] * b.v[0] + a.v[0] * b.v[3] + a.v[1] * b.v[2] - a.v[2] * b.v[1];
+    o.v[1] = a.v[3] * b.v[1] + a.v[1] * b.v[3] + a.v[2] * b.v[0] - a.v[0] * b.v[2];
+    o.v[2] = a.v[3] * b.v[2] + a.v[2] * b.v[3] + a.v[0] * b.v[1] - a.v[1] * b.v[0];
+    for (int i = 0; i < 3; i++) o.v[4 + i] = a.v[7] * rt[i] + a.v[4 + i];
+    o.v[7] = a.v[7] * b.v[7];
+    return o;
+}
+inline S8 inverse(const S8& a)                                           // g2o::Sim3::inverse (sim3.h:233-236)
+{
+    S8 o;
+    const double m = -1. / a.v[7];
+    const double t[3] = {m * a.v[4], m * a.v[5], m * a.v[6]};
+    o.v[0] = -a.v[0]; o.v[1] = -a.v[1]; o.v[2] = -a.v[2]; o.v[3] = a.v[3];
+    rotate(o.v, t, o.v + 4);
+    o.v[7] = 1. / a.v[7];
+    return o;
+}
+template <class Sim3T>
+inline S8 from_sim3(const Sim3T& g)
+{
+    S8 a;
+    const Eigen::Quaterniond q = g.rotation();
+    const Eigen::Vector3d t = g.translation();
+    a.v[0] = q.x(); a.v[1] = q.y(); a.v[2] = q.z(); a.v[3] = q.w();
+    a.v[4] = t[0]; a.v[5] = t[1]; a.v[6] = t[2]; a.v[7] = g.scale();
+    return a;
+}
+template <class KF>
+inline S8 from_pose(KF* pKF)      // g2o::Sim3(Tcw.unit_quaternion(), Tcw.translation(), 1.0) of GetPose().cast<double>() (:1551-1552)
+{
+    const Sophus::SE3d Tcw = pKF->GetPose().template cast<double>();
+    S8 a;
+    const Eigen::Quaterniond q = Tcw.unit_quaternion();
+    const Eigen::Vector3d t = Tcw.translation();
+    a.v[0] = q.x(); a.v[1] = q.y(); a.v[2] = q.z(); a.v[3] = q.w();
+    a.v[4] = t[0]; a.v[5] = t[1]; a.v[6] = t[2]; a.v[7] = 1.0;
+    return a;
+}
+
+struct Builder {
+    EssentialGraphFlat& g;
+    std::map<long unsigned int, int> index;
+    void vertex(long unsigned int id, const S8& s, bool fixed)
+    {
+        index[id] = (int)g.id.size();
+        g.id.push_back(id);
+        g.sim3.insert(g.sim3.end(), s.v, s.v + 8);
+        g.fixed.push_back(fixed ? 1 : 0);
+    }
+    // optimizer.addEdge refuses an edge with a vertex the optimizer does not hold (hyper_graph.cpp: a NULL vertex)
+    void edge(long unsigned int idi, long unsigned int idj, const S8& Sji)
+    {
+        const auto a = index.find(idi), b = index.find(idj);
+        if (a == index.end() || b == index.end()) { g.dropped_edges++; return; }
+        g.edges.push_back(a->second); g.edges.push_back(b->second);
+        g.meas.insert(g.meas.end(), Sji.v, Sji.v + 8);
+    }
+};
+
+inline essg_solver* solver()        // one handle per calling thread (orbslam3_hip.h)
+{
+    static thread_local essg_solver* s = nullptr;
+    if (!s) orbslam3_hip::check(essg_create(0, &s));
+    return s;
+}
+
+}  // namespace essential_detail
+
+// the graph of the loop overload (:1517-1726).  Vertices: the key frames of the map that are not bad.  Edges: loop connections
+// first, then per key frame the spanning-tree edge, its loop edges, its covisibility edges, the inertial edge.
+template <class KF, class MP, class MapT, class PoseMap, class ConnMap>
+void FlattenEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                           const ConnMap& LoopConnections, const bool bFixScale, EssentialGraphFlat& g)
+{
+    namespace ed = essential_detail;
+    ed::Builder b{g, {}};
+    g.fix_scale = bFixScale ? 1 : 0;
+    const std::vector<KF*> vpKFs = pMap->GetAllKeyFrames();
+    const std::vector<MP*> vpMPs = pMap->GetAllMapPoints();
+    std::map<long unsigned int, ed::S8> vScw;
+    const int minFeat = 100;
+    for (KF* pKF : vpKFs) {                                                                 // :1533-1568
+        if (pKF->isBad()) continue;
+        const auto it = CorrectedSim3.find(pKF);
+        const ed::S8 Siw = it != CorrectedSim3.end() ? ed::from_sim3(it->second) : ed::from_pose(pKF);
+        vScw[pKF->mnId] = Siw;
+        b.vertex(pKF->mnId, Siw, pKF->mnId == pMap->GetInitKFid());
+    }
+    auto scw = [&](long unsigned int id) { const auto it = vScw.find(id); return it != vScw.end() ? it->second : ed::identity(); };   // vScw is value-initialised (:1522)
+    auto non_corrected = [&](KF* pKF) { const auto it = NonCorrectedSim3.find(pKF); return it != NonCorrectedSim3.end() ? ed::from_sim3(it->second) : scw(pKF->mnId); };
+    std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+    for (auto mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {         // :1577-1605
+        KF* pKF = mit->first;
+        const long unsigned int nIDi = pKF->mnId;
+        const ed::S8 Swi = ed::inverse(scw(nIDi));
+        for (KF* pKFj : mit->second) {
+            const long unsigned int nIDj = pKFj->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+            b.edge(nIDi, nIDj, ed::mul(scw(nIDj), Swi));
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (KF* pKF : vpKFs) {                                                                 // :1608-1726
+        const long unsigned int nIDi = pKF->mnId;
+        const ed::S8 Swi = ed::inverse(non_corrected(pKF));
+        KF* pParentKF = pKF->GetParent();
+        if (pParentKF) b.edge(nIDi, pParentKF->mnId, ed::mul(non_corrected(pParentKF), Swi));
+        const std::set<KF*> sLoopEdges = pKF->GetLoopEdges();
+        for (KF* pLKF : sLoopEdges)
+            if (pLKF->mnId < pKF->mnId) b.edge(nIDi, pLKF->mnId, ed::mul(non_corrected(pLKF), Swi));
+        const std::vector<KF*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+        for (KF* pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    b.edge(nIDi, pKFn->mnId, ed::mul(non_corrected(pKFn), Swi));
+                }
+            }
+        }
+        if (pKF->bImu && pKF->mPrevKF) b.edge(nIDi, pKF->mPrevKF->mnId, ed::mul(non_corrected(static_cast<KF*>(pKF->mPrevKF)), Swi));
+    }
+    for (size_t i = 0; i < vpMPs.size(); i++) {                                             // :1752-1769
+        MP* pMP = vpMPs[i];
+        if (pMP->isBad()) continue;
+        const long unsigned int nIDr = pMP->mnCorrectedByKF == pCurKF->mnId ? pMP->mnCorrectedReference : pMP->GetReferenceKeyFrame()->mnId;
+        const auto it = b.index.find(nIDr);
+        g.point_ref.push_back(it != b.index.end() ? it->second : -1);                       // -1: refused by essg_optimize, the reference decides
+        const Eigen::Vector3f P = pMP->GetWorldPos();
+        for (int k = 0; k < 3; k++) g.points.push_back(P[k]);
+        g.point_index.push_back(i);
+    }
+}
+
+// the graph of the merge overload (:1806-2051): three groups of vertices, _fix_scale on the first group only in the reference
+// (the members of the other two are left at the constructor's value, false: types_seven_dof_expmap.cpp), relations between two
+// "good" (corrected) or two "bad" (not yet corrected) poses only.
+template <class KF>
+void FlattenEssentialGraphMerge(KF* /*pCurKF*/, const std::vector<KF*>& vpFixedKFs, const std::vector<KF*>& vpFixedCorrectedKFs,
+                                const std::vector<KF*>& vpNonFixedKFs, EssentialGraphFlat& g)
+{
+    namespace ed = essential_detail;
+    ed::Builder b{g, {}};
+    g.fix_scale = 0;
+    std::map<long unsigned int, ed::S8> vScw, vCorrectedSwc;
+    std::map<long unsigned int, bool> good, bad;
+    const int minFeat = 100;
+    for (KF* pKFi : vpFixedKFs) {                                                           // :1815-1842
+        if (pKFi->isBad()) continue;
+        const ed::S8 Siw = ed::from_pose(pKFi);
+        vCorrectedSwc[pKFi->mnId] = ed::inverse(Siw);
+        b.vertex(pKFi->mnId, Siw, true);
+        good[pKFi->mnId] = true; bad[pKFi->mnId] = false;
+    }
+    std::set<unsigned long> sIdKF;
+    for (KF* pKFi : vpFixedCorrectedKFs) {                                                  // :1846-1877
+        if (pKFi->isBad()) continue;
+        const ed::S8 Siw = ed::from_pose(pKFi);
+        vCorrectedSwc[pKFi->mnId] = ed::inverse(Siw);
+        const Sophus::SE3d Tb = pKFi->mTcwBefMerge.template cast<double>();
+        ed::S8 Sb;
+        const Eigen::Quaterniond q = Tb.unit_quaternion();
+        const Eigen::Vector3d t = Tb.translation();
+        Sb.v[0] = q.x(); Sb.v[1] = q.y(); Sb.v[2] = q.z(); Sb.v[3] = q.w(); Sb.v[4] = t[0]; Sb.v[5] = t[1]; Sb.v[6] = t[2]; Sb.v[7] = 1.0;
+        vScw[pKFi->mnId] = Sb;
+        b.vertex(pKFi->mnId, Siw, true);
+        sIdKF.insert(pKFi->mnId);
+        good[pKFi->mnId] = true; bad[pKFi->mnId] = true;
+    }
+    for (KF* pKFi : vpNonFixedKFs) {                                                        // :1879-1910
+        if (pKFi->isBad()) continue;
+        if (sIdKF.count(pKFi->mnId)) continue;
+        const ed::S8 Siw = ed::from_pose(pKFi);
+        vScw[pKFi->mnId] = Siw;
+        b.vertex(pKFi->mnId, Siw, false);
+        sIdKF.insert(pKFi->mnId);
+        good[pKFi->mnId] = false; bad[pKFi->mnId] = true;
+    }
+    std::vector<KF*> vpKFs;
+    vpKFs.insert(vpKFs.end(), vpFixedKFs.begin(), vpFixedKFs.end());
+    vpKFs.insert(vpKFs.end(), vpFixedCorrectedKFs.begin(), vpFixedCorrectedKFs.end());
+    vpKFs.insert(vpKFs.end(), vpNonFixedKFs.begin(), vpNonFixedKFs.end());
+    const std::set<KF*> spKFs(vpKFs.begin(), vpKFs.end());
+    auto get = [](const std::map<long unsigned int, ed::S8>& m, long unsigned int id) { const auto it = m.find(id); return it != m.end() ? it->second : ed::identity(); };
+    auto flag = [](const std::map<long unsigned int, bool>& m, long unsigned int id) { const auto it = m.find(id); return it != m.end() && it->second; };
+    // Sjw of a relation between i and j, or false (:1944-1953 and its two repetitions)
+    auto relation = [&](long unsigned int i, long unsigned int j, ed::S8& Sjw) {
+        if (flag(good, i) && flag(good, j)) { Sjw = ed::inverse(get(vCorrectedSwc, j)); return true; }
+        if (flag(bad, i) && flag(bad, j)) { Sjw = get(vScw, j); return true; }
+        return false;
+    };
+    for (KF* pKFi : vpKFs) {                                                                // :1921-2051
+        const long unsigned int nIDi = pKFi->mnId;
+        const ed::S8 Swi = flag(bad, nIDi) ? ed::inverse(get(vScw, nIDi)) : ed::identity();     // Swi stays default-constructed for a pose that is only "good" (:1927-1932)
+        ed::S8 Sjw;
+        KF* pParentKFi = pKFi->GetParent();
+        if (pParentKFi && spKFs.count(pParentKFi) && relation(nIDi, pParentKFi->mnId, Sjw)) b.edge(nIDi, pParentKFi->mnId, ed::mul(Sjw, Swi));
+        const std::set<KF*> sLoopEdges = pKFi->GetLoopEdges();
+        for (KF* pLKF : sLoopEdges)
+            if (spKFs.count(pLKF) && pLKF->mnId < pKFi->mnId && relation(nIDi, pLKF->mnId, Sjw)) b.edge(nIDi, pLKF->mnId, ed::mul(Sjw, Swi));
+        const std::vector<KF*> vpConnectedKFs = pKFi->GetCovisiblesByWeight(minFeat);
+        for (KF* pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != pParentKFi && !pKFi->hasChild(pKFn) && !sLoopEdges.count(pKFn) && spKFs.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKFi->mnId && relation(nIDi, pKFn->mnId, Sjw)) b.edge(nIDi, pKFn->mnId, ed::mul(Sjw, Swi));
+            }
+        }
+    }
+}
+
+namespace essential_detail {
+// essg_optimize on a flattened graph; false when the device refuses it (invalid input, over capacity): the caller falls back
+inline bool run(const EssentialGraphFlat& g, std::vector<double>& sim3_out, std::vector<float>& q, std::vector<float>& t, std::vector<float>& pts)
+{
+    EssgProblem p;
+    p.n_vertices = (int32_t)g.id.size(); p.sim3 = g.sim3.data(); p.fixed = g.fixed.data();
+    p.n_edges = (int32_t)(g.edges.size() / 2); p.edge_vertices = g.edges.data(); p.edge_measurement = g.meas.data();
+    p.fix_scale = g.fix_scale; p.max_iters = 20; p.lambda_init = 1e-16;
+    p.n_points = (int32_t)g.point_ref.size(); p.points = g.points.data(); p.point_ref = g.point_ref.data();
+    sim3_out.assign(g.sim3.size(), 0.0); q.assign(4 * g.id.size(), 0.f); t.assign(3 * g.id.size(), 0.f); pts.assign(g.points.size() + 3, 0.f);
+    EssgResult r;
+    r.sim3_out = sim3_out.data(); r.pose_q = q.data(); r.pose_t = t.data(); r.points_out = pts.data();
+    const int ok = essg_check(&p, &r);                  // before a handle (and with it a device) is asked for
+    if (ok == ORBX_ERR_ARG || ok == ORBX_ERR_CAPACITY) return false;
+    orbslam3_hip::check(essg_optimize(solver(), &p, &r, nullptr));
+    return true;
+}
+}  // namespace essential_detail
+
+// void Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+//                                        const KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>&, const bool&)
+template <class Opt = Optimizer, class KF, class MapT, class PoseMap, class ConnMap>
+void OptimizeEssentialGraphHIP(MapT* pMap, KF* pLoopKF, KF* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                               const ConnMap& LoopConnections, const bool& bFixScale)
+{
+    typedef typename std::remove_pointer<typename decltype(pMap->GetAllMapPoints())::value_type>::type MP;
+    EssentialGraphFlat g;
+    FlattenEssentialGraph<KF, MP>(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale, g);
+    std::vector<double> sim3_out;
+    std::vector<float> q, t, pts;
+    if (g.dropped_edges > 0 || !essential_detail::run(g, sim3_out, q, t, pts)) {
+        Opt::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
+        return;
+    }
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                               // :1733
+    const std::vector<KF*> vpKFs = pMap->GetAllKeyFrames();
+    std::map<long unsigned int, int> index;
+    for (size_t k = 0; k < g.id.size(); k++) index[g.id[k]] = (int)k;
+    for (KF* pKFi : vpKFs) {                                                                // :1736-1749
+        const auto it = index.find(pKFi->mnId);
+        if (it == index.end()) continue;
+        const int k = it->second;
+        pKFi->SetPose(Sophus::SE3f(Eigen::Quaternionf(q[4 * k + 3], q[4 * k], q[4 * k + 1], q[4 * k + 2]), Eigen::Vector3f(t[3 * k], t[3 * k + 1], t[3 * k + 2])));
+    }
+    const std::vector<MP*> vpMPs = pMap->GetAllMapPoints();
+    for (size_t k = 0; k < g.point_index.size(); k++) {                                     // :1752-1779
+        MP* pMP = vpMPs[g.point_index[k]];
+        pMP->SetWorldPos(Eigen::Vector3f(pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();                                                            // :1782
+}
+
+// void Optimizer::OptimizeEssentialGraph(KeyFrame* pCurKF, vector<KeyFrame*>& vpFixedKFs, vector<KeyFrame*>& vpFixedCorrectedKFs,
+//                                        vector<KeyFrame*>& vpNonFixedKFs, vector<MapPoint*>& vpNonCorrectedMPs)
+template <class Opt = Optimizer, class KF, class MP>
+void OptimizeEssentialGraphHIP(KF* pCurKF, std::vector<KF*>& vpFixedKFs, std::vector<KF*>& vpFixedCorrectedKFs, std::vector<KF*>& vpNonFixedKFs,
+                               std::vector<MP*>& vpNonCorrectedMPs)
+{
+    EssentialGraphFlat g;
+    FlattenEssentialGraphMerge(pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs, g);
+    std::vector<double> s;
+    std::vector<float> q, t, pts;
+    if (g.dropped_edges > 0 || !essential_detail::run(g, s, q, t, pts)) {
+        Opt::OptimizeEssentialGraph(pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs, vpNonCorrectedMPs);
+        return;
+    }
+    std::unique_lock<std::mutex> lock(pCurKF->GetMap()->mMutexMapUpdate);                   // :2057
+    std::map<long unsigned int, int> index;
+    std::map<long unsigned int, bool> bad;
+    for (size_t k = 0; k < g.id.size(); k++) index[g.id[k]] = (int)k;
+    for (KF* pKFi : vpFixedCorrectedKFs) if (!pKFi->isBad()) bad[pKFi->mnId] = true;
+    for (KF* pKFi : vpNonFixedKFs) {                                                        // :2060-2076: [R | t / s] in double, then to float
+        if (pKFi->isBad()) continue;
+        bad[pKFi->mnId] = true;
+        const double* e = s.data() + 8 * (size_t)index[pKFi->mnId];
+        const Sophus::SE3d Tiw(Eigen::Quaterniond(e[3], e[0], e[1], e[2]), Eigen::Vector3d(e[4], e[5], e[6]) / e[7]);
+        pKFi->mTcwBefMerge = pKFi->GetPose();
+        pKFi->mTwcBefMerge = pKFi->GetPoseInverse();
+        pKFi->SetPose(Tiw.template cast<float>());
+    }
+    for (MP* pMPi : vpNonCorrectedMPs) {                                                    // :2079-2112, in float on the host as there
+        if (pMPi->isBad()) continue;
+        KF* pRefKF = static_cast<KF*>(pMPi->GetReferenceKeyFrame());
+        while (pRefKF && pRefKF->isBad()) { pMPi->EraseObservation(pRefKF); pRefKF = static_cast<KF*>(pMPi->GetReferenceKeyFrame()); }
+        if (!pRefKF || !bad.count(pRefKF->mnId)) continue;
+        const Sophus::SE3f TNonCorrectedwr = pRefKF->mTwcBefMerge, Twr = pRefKF->GetPoseInverse();
+        pMPi->SetWorldPos(Twr * (TNonCorrectedwr.inverse() * pMPi->GetWorldPos()));
+        pMPi->UpdateNormalAndDepth();
+    }
 }
 
 }  // namespace ORB_SLAM3

@@ -1552,3 +1552,79 @@ class Sim3Solver:
 
     def optimize(self, w):
         return self.optimize_batch([w])[0]
+
+
+ESSG_MAX_FREE_VERTICES = 1024
+
+
+class EssgProblem(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("sim3", C.c_void_p), ("fixed", C.c_void_p),
+                ("n_edges", C.c_int32), ("edge_vertices", C.c_void_p), ("edge_measurement", C.c_void_p),
+                ("fix_scale", C.c_int32), ("max_iters", C.c_int32), ("lambda_init", C.c_double),
+                ("n_points", C.c_int32), ("points", C.c_void_p), ("point_ref", C.c_void_p)]
+
+
+class EssgResult(C.Structure):
+    _fields_ = [("sim3_out", C.c_void_p), ("pose_q", C.c_void_p), ("pose_t", C.c_void_p), ("points_out", C.c_void_p),
+                ("stats", LbaStats)]
+
+
+def essg_prepare(w):
+    """EssgProblem / EssgResult of a graph dictionary (synth_posegraph.make_posegraph) with the arrays they point to"""
+    k = dict(sim3=np.ascontiguousarray(w["sim3"], np.float64).reshape(-1, 8), fixed=np.ascontiguousarray(w["fixed"], np.uint8),
+             ev=np.ascontiguousarray(w["edge_vertices"], np.int32).reshape(-1, 2),
+             meas=np.ascontiguousarray(w["edge_measurement"], np.float64).reshape(-1, 8),
+             points=np.ascontiguousarray(w.get("points", np.zeros((0, 3))), np.float32).reshape(-1, 3),
+             ref=np.ascontiguousarray(w.get("point_ref", np.zeros(0)), np.int32))
+    nv, ne, npt = len(k["sim3"]), len(k["ev"]), len(k["points"])
+    if len(k["fixed"]) != nv or len(k["meas"]) != ne or len(k["ref"]) != npt:
+        raise ValueError("essential graph arrays of unequal length")
+    k.update(sim3_out=np.zeros((nv, 8)), pose_q=np.zeros((nv, 4), np.float32), pose_t=np.zeros((nv, 3), np.float32),
+             points_out=np.zeros((npt, 3), np.float32))
+    pr = EssgProblem(nv, k["sim3"].ctypes.data, k["fixed"].ctypes.data, ne, k["ev"].ctypes.data if ne else None,
+                     k["meas"].ctypes.data if ne else None, int(w.get("fix_scale", 0)), int(w.get("max_iters", 20)),
+                     float(w.get("lambda_init", 1e-16)), npt, k["points"].ctypes.data if npt else None, k["ref"].ctypes.data if npt else None)
+    res = EssgResult(k["sim3_out"].ctypes.data, k["pose_q"].ctypes.data, k["pose_t"].ctypes.data,
+                     k["points_out"].ctypes.data if npt else None)
+    return dict(problem=pr, result=res, arrays=k)
+
+
+lib.essg_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+lib.essg_destroy.argtypes = [C.c_void_p]
+lib.essg_optimize.argtypes = [C.c_void_p, C.POINTER(EssgProblem), C.POINTER(EssgResult), C.c_void_p]
+lib.essg_last_device_ms.argtypes = [C.c_void_p, C.c_void_p]
+lib.essg_check.argtypes = [C.POINTER(EssgProblem), C.POINTER(EssgResult)]
+lib.essg_last_device_ms.restype = C.c_double
+
+
+class EssentialGraph:
+    """Optimizer::OptimizeEssentialGraph between building the graph and writing the map back (reference src/Optimizer.cc:1729-1779):
+    essg_optimize of include/orbslam3_hip.h.  One handle serves one call at a time."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        _check(lib.essg_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.essg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optimize(self, w, stop_flag=None):
+        prep = essg_prepare(w)
+        _check(lib.essg_optimize(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
+        k = prep["arrays"]
+        return dict(sim3_out=k["sim3_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
+                    stats=_stats_dict(prep["result"].stats))
+
+    def last_device_ms(self):
+        st = (C.c_double * 3)()
+        ms = lib.essg_last_device_ms(self._h, st)
+        return ms, dict(structure_upload=st[0], rounds=st[1], epilogue_download=st[2])

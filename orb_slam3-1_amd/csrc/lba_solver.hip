@@ -2606,3 +2606,4 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
 }  // extern "C"
 
 #include "inertial_solver.inc"
+#include "essential_graph.inc"

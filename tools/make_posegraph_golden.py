@@ -1,0 +1,34 @@
+"""Writes tests/golden/posegraph_60.npz: one seeded essential graph (orb_slam3-1_amd/synth_posegraph.py, the case loop60 of
+tests/posegraph_cases.py) plus the outputs of the numpy reference (tests/posegraph_reference.py, float64) on it, so that the
+tests do not depend on the generator's RNG stream.  Needs the built library only because the package loads it; no GPU."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import posegraph_reference as ref  # noqa: E402
+from posegraph_cases import CASES  # noqa: E402
+
+KEYS = ("sim3", "fixed", "edge_vertices", "edge_measurement", "fix_scale", "max_iters", "lambda_init", "points", "point_ref")
+
+
+def main():
+    sp = importlib.import_module("orb_slam3-1_amd.synth_posegraph")
+    p = sp.make_posegraph(**CASES["loop60"])
+    a, b = ref.optimize(p, np.float64), ref.optimize(p, np.longdouble)
+    flow = lambda r: (r["stats"]["iterations"], r["stats"]["trials"], r["stats"]["stop_reason"])
+    assert flow(a) == flow(b)
+    st = a["stats"]
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "posegraph_60.npz"), **{k: p[k] for k in KEYS},
+                        ref_sim3=a["sim3_out"], ref_pose_q=a["pose_q"], ref_pose_t=a["pose_t"], ref_points=a["points_out"],
+                        ref_flow=np.array(flow(a)), ref_chi2_initial=float(st["chi2_initial"]), ref_chi2_final=float(st["chi2_final"]),
+                        ref_flow_margin=a["flow_margin"], ref_branch_margin=a["branch_margin"])
+    print("posegraph_60: %d edges, flow %s, chi2 %.6g -> %.6g, margins %.1e %s" % (len(p["edge_vertices"]), flow(a), st["chi2_initial"],
+                                                                                    st["chi2_final"], a["flow_margin"], a["branch_margin"]))
+
+
+if __name__ == "__main__":
+    main()

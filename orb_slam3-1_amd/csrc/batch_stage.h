@@ -1,16 +1,25 @@
-// Host side of the one-workgroup-per-problem solvers (pose_solver.hip, sim3_solver.hip): a batch is laid out in ONE pinned
-// buffer with a device image, [descriptors | inputs] go up, one launch runs, [outputs] come down.  Host only.
+// The host kit of the solver handles.  For all of them: handle creation and destruction (open / close; the device check,
+// stage::check_device, is in hip_check.h, where the handles that use nothing else of this header find it).  For
+// the one-workgroup-per-problem solvers (pose_solver.hip, sim3_solver.hip): a batch laid out in ONE pinned buffer with a device
+// image, [descriptors | inputs] go up, one launch runs, [outputs] come down (reserve / Cursor / run).  For the host-driven
+// Levenberg solvers (lba_solver.hip and its .inc files): the host-mapped scalars a trial's result arrives in (HostScalars), the
+// window-setup thread pool (for_each_window) and the pinned result buffer of a batch (PinnedOut).  Host only.
 #pragma once
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
+#include <cstring>
 #include <exception>
 #include <new>
+#include <thread>
+#include <vector>
 
 #include "hip_check.h"
 
 namespace stage {
 
-struct Batch {
+struct Batch {                      // (the Levenberg handles built on open / close use the stream and the events only, not the blobs)
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -40,9 +49,7 @@ int open(int device, S** out)
 {
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     S* s = new (std::nothrow) S();
     if (!s) return fail(ORBX_ERR_INTERNAL, "out of host memory");
@@ -114,5 +121,127 @@ int guarded(const char* what, Body&& body)
         return fail(ORBX_ERR_INTERNAL, "%s: unknown exception", what);
     }
 }
+
+// ---- the host-driven Levenberg solvers ----
+// The reduction kernel that ends a linearisation or a trial writes its scalars into a host-mapped, coherent buffer, h[0..7], and
+// then publishes the sequence number of the launch in h[8] (system-scope release): the host polls that word instead of paying
+// a device-to-host copy and a stream synchronisation per trial.  A batched handle makes ONE allocation of 16 doubles per window
+// and hands out views.
+struct HostScalars {
+    double* h = nullptr;            // pinned, host-mapped, coherent [16] (the owner: [slots][16])
+    double* d = nullptr;            // the same words as the device sees them
+    unsigned long long seq = 0;     // sequence number of the last launch that publishes here
+    bool owner = false;
+
+    int alloc(int slots = 1)
+    {
+        if (hipHostMalloc((void**)&h, (size_t)slots * 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { h = nullptr; return fail(ORBX_ERR_HIP, "hipHostMalloc failed"); }
+        owner = true;
+        if (hipHostGetDevicePointer((void**)&d, h, 0) != hipSuccess) return fail(ORBX_ERR_HIP, "hipHostGetDevicePointer failed");
+        std::memset(h, 0, (size_t)slots * 16 * sizeof(double));
+        return ORBX_OK;
+    }
+    // window `slot` of the allocation; the numbering goes on from what was last published there
+    HostScalars view(int slot = 0) const
+    {
+        HostScalars v;
+        v.h = h + 16 * (size_t)slot; v.d = d + 16 * (size_t)slot;
+        v.seq = *(const unsigned long long*)(v.h + 8);
+        return v;
+    }
+    void release()
+    {
+        if (owner && h) (void)hipHostFree(h);
+        h = d = nullptr; owner = false;
+    }
+    // until launch `seq` has published: polling (a trial is a few hundred microseconds of kernels); after 20 ms a stream
+    // synchronisation instead, which also surfaces faults
+    int wait(hipStream_t stream) const
+    {
+        const volatile unsigned long long* flag = (const volatile unsigned long long*)(h + 8);
+        const auto t0 = std::chrono::steady_clock::now();
+        int spins = 0;
+        while (*flag != seq) {
+            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
+                ORBX_HIP(hipStreamSynchronize(stream));
+                if (*flag != seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
+                break;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        return ORBX_OK;
+    }
+};
+
+// setup(i) for the W windows of a batch (structure build + upload: host work, ~0.3 ms a window) on up to 16 threads, each with
+// `device` current.  The first window that failed is reported by number.
+template <class Setup>
+int for_each_window(int W, int device, Setup&& setup)
+{
+    const int n_thr = std::max(1, std::min({W, (int)std::thread::hardware_concurrency(), 16}));
+    std::vector<int> rcs((size_t)W, ORBX_OK);
+    std::atomic<int> next(0);
+    auto worker = [&]() {
+        (void)hipSetDevice(device);
+        for (int i = next.fetch_add(1); i < W; i = next.fetch_add(1)) rcs[i] = setup(i);
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < n_thr; t++) th.emplace_back(worker);
+    worker();
+    for (auto& t : th) t.join();
+    for (int i = 0; i < W; i++)
+        if (rcs[i]) return fail(rcs[i], "window %d could not be set up (code %d; the worker thread holds the detailed message)", i, rcs[i]);
+    return ORBX_OK;
+}
+
+// The results of the W windows of a batch back to back in one pinned buffer (with_device: and a device image of it), so that a
+// call ends with one synchronisation: window i's slice starts at off[i], every array inside it on a 64-byte boundary.
+struct PinnedOut {
+    uint8_t *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    std::vector<size_t> off;
+    static size_t al(size_t v) { return (v + 63) & ~(size_t)63; }
+    // a window's slice: its states (state_bytes), 3 doubles per point, a double (chi2) and a byte (depth sign) per edge
+    static size_t slice_bytes(size_t state_bytes, int n_points, int n_edges) { return al(state_bytes) + al(3 * (size_t)n_points * 8) + al((size_t)n_edges * 8) + al((size_t)n_edges); }
+    struct Slice { uint8_t *state, *points, *chi2, *depth; };
+    static Slice slice(uint8_t* base, size_t state_bytes, int n_points, int n_edges)
+    {
+        uint8_t* const points = base + al(state_bytes);
+        uint8_t* const chi2 = points + al(3 * (size_t)n_points * 8);
+        return Slice{base, points, chi2, chi2 + al((size_t)n_edges * 8)};
+    }
+    void clear() { off.assign(1, 0); }
+    void add(size_t state_bytes, int n_points, int n_edges) { off.push_back(off.back() + slice_bytes(state_bytes, n_points, n_edges)); }
+    size_t total() const { return off.back(); }
+    // room for total(); a buffer that is too small is replaced by one a quarter larger than the need
+    int reserve(bool with_device)
+    {
+        if (total() <= cap) return ORBX_OK;
+        release();
+        const size_t want = total() + total() / 4 + 4096;
+        if (hipHostMalloc((void**)&h, want) != hipSuccess || (with_device && hipMalloc((void**)&d, want) != hipSuccess))
+            return fail(ORBX_ERR_HIP, with_device ? "result buffer allocation failed" : "pinned result buffer allocation failed");
+        cap = want;
+        return ORBX_OK;
+    }
+    void release()
+    {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        h = d = nullptr; cap = 0;
+    }
+};
+
+// poses7 [n][7] (qx qy qz qw tx ty tz) -> pose_q [n][4], pose_t [n][3]; either may be NULL
+inline void split_poses7(const double* poses7, int n, double* pose_q, double* pose_t)
+{
+    for (int i = 0; i < n; i++) {
+        if (pose_q) for (int k = 0; k < 4; k++) pose_q[4 * i + k] = poses7[7 * (size_t)i + k];
+        if (pose_t) for (int k = 0; k < 3; k++) pose_t[3 * i + k] = poses7[7 * (size_t)i + 4 + k];
+    }
+}
+
+using Clock = std::chrono::steady_clock;
+inline double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
 }  // namespace stage

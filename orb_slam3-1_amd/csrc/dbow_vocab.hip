@@ -316,9 +316,7 @@ int orbv_create(int device, const OrbvVocabulary* voc, orbv_vocab** out)
     const int n_child = voc->child_off[nn];
     for (int c = 0; c < n_child; c++)
         if (voc->child_id[c] == 0 || voc->child_id[c] >= (uint32_t)nn) return fail(ORBX_ERR_ARG, "child id %u out of range", voc->child_id[c]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     orbv_vocab* v = new orbv_vocab();
     v->device = device;

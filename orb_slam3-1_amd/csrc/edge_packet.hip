@@ -197,9 +197,7 @@ int orbe_create(int device, orbe_codec** out)
 {
     if (!out) return fail(ORBX_ERR_ARG, "null out");
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(ORBX_ERR_NO_DEVICE, "no HIP device: the packet codec runs on the GPU only");
-    if (device < 0 || device >= count) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     orbe_codec* c = new orbe_codec;
     c->device = device;

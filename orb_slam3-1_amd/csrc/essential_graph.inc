@@ -1,7 +1,7 @@
 // essential_graph.inc -- the pose-graph solver of loop closing and map merging: Optimizer::OptimizeEssentialGraph (reference
-// src/Optimizer.cc:1501-1783, :1785-2113) between "the graph is built" and "the map is written back".  Included at the end of
-// lba_solver.hip (like inertial_solver.inc) for the dense Cholesky kernels (k_chol_flow, k_chol_diag / panel / update,
-// k_chol_solve) and wait_scalars, which it uses unchanged.
+// src/Optimizer.cc:1501-1783, :1785-2113) between "the graph is built" and "the map is written back".  It stands on
+// dense_chol.h (chol::enqueue_factor / enqueue_solve) and the host kit of batch_stage.h (stage::open / close, HostScalars), and is
+// compiled as part of lba_solver.hip, the one translation unit that holds the k_chol_* kernels (dense_chol.h says why).
 //
 // Every vertex is a Sim3 pose (VertexSim3Expmap), every edge an EdgeSim3 with identity information and no robust kernel, so
 // there is no Schur complement: H is a symmetric matrix of 7 x 7 blocks over the free vertices, assembled densely, (n + 1) x n
@@ -13,6 +13,9 @@
 // One linearisation: k_essg_linearize writes a record per edge (no atomics); the assembly sums a block's records in the order of
 // a CSR the host builds once per call, so results do not depend on scheduling.
 
+#include "batch_stage.h"
+#include "dense_chol.h"
+#include "lm_control.h"
 #include "sim3_group.h"
 
 namespace essg {
@@ -198,13 +201,8 @@ __global__ __launch_bounds__(256) void k_essg_epilogue(Dev d, const double* __re
 
 }  // namespace essg
 
-struct essg_solver {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double* h_scal = nullptr;       // pinned, host-mapped, coherent [16]
-    double* d_hmap = nullptr;
-    unsigned long long seq = 0;
+struct essg_solver : stage::Batch {      // its stream, the two events around the device work of a call
+    stage::HostScalars hs;
     unsigned* flow = nullptr;
     unsigned flow_epoch = 0;
     double* scal = nullptr;
@@ -212,9 +210,15 @@ struct essg_solver {
     enum { kEst0, kEstA, kEstB, kMeas, kEv, kCol, kRecs, kChi, kPart, kBlkI, kBlkJ, kBlkOff, kBlkEnt, kX, kBfull, kS, kLp, kLinv,
            kPts, kRef, kPtsOut, kPoseQ, kPoseT, kNumBufs };
     Buf buf[kNumBufs];
-    size_t solve_lds_set = 0;       // dynamic LDS k_chol_solve<false> has been allowed so far
     double last_device_ms = 0.0;
     double stage_ms[3] = {0, 0, 0};
+    ~essg_solver()
+    {
+        for (auto& b : buf) if (b.p) (void)hipFree(b.p);
+        if (flow) (void)hipFree(flow);
+        if (scal) (void)hipFree(scal);
+        hs.release();
+    }
 };
 
 static int essg_reserve(essg_solver* s, int which, size_t bytes, void** out)
@@ -273,47 +277,25 @@ extern "C" {
 
 int essg_create(int device, essg_solver** out)
 {
-    if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBX_HIP(hipSetDevice(device));
-    essg_solver* s = new essg_solver();
-    s->device = device;
-    bool ok = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreate(&s->ev0) == hipSuccess && hipEventCreate(&s->ev1) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer((void**)&s->d_hmap, s->h_scal, 0) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s->flow, lba::kFlowFlags * sizeof(unsigned)) == hipSuccess;
+    int r = stage::open(device, out);
+    if (r) return r;
+    essg_solver* s = *out;
+    bool ok = s->hs.alloc() == ORBX_OK;
+    ok = ok && hipMalloc((void**)&s->flow, chol::kFlowFlags * sizeof(unsigned)) == hipSuccess;
     ok = ok && hipMalloc((void**)&s->scal, 16 * sizeof(double)) == hipSuccess;
-    ok = ok && hipMemsetAsync(s->flow, 0, lba::kFlowFlags * sizeof(unsigned), s->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(s->flow, 0, chol::kFlowFlags * sizeof(unsigned), s->stream) == hipSuccess;
     ok = ok && hipMemsetAsync(s->scal, 0, 16 * sizeof(double), s->stream) == hipSuccess;
-    ok = ok && hipFuncSetAttribute((const void*)lba::k_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds) == hipSuccess;
+    ok = ok && chol::raise_lds_limits(chol::kMaxUnknowns) == ORBX_OK;       // (the value shard_create_impl sets: one limit, whoever sets it)
     ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
-        essg_destroy(s);
+        stage::close(s);
+        *out = nullptr;
         return fail(ORBX_ERR_HIP, "essg_create: stream / buffer creation failed");
     }
-    std::memset(s->h_scal, 0, 16 * sizeof(double));
-    *out = s;
     return ORBX_OK;
 }
 
-void essg_destroy(essg_solver* s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (auto& b : s->buf) if (b.p) (void)hipFree(b.p);
-    if (s->flow) (void)hipFree(s->flow);
-    if (s->scal) (void)hipFree(s->scal);
-    if (s->h_scal) (void)hipHostFree(s->h_scal);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
+void essg_destroy(essg_solver* s) { stage::close(s); }
 
 int essg_check(const EssgProblem* p, const EssgResult* res)
 {
@@ -333,12 +315,8 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     int nF = 0;
     int r = essg_validate(p, res, &nF);
     if (r) return r;
-    if (!s) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-        return fail(ORBX_ERR_ARG, "essg_optimize: NULL solver");
-    }
-    const auto t_start = std::chrono::steady_clock::now();
+    if (!s) return (r = stage::check_device(0)) ? r : fail(ORBX_ERR_ARG, "essg_optimize: NULL solver");       // no device is an error of its own
+    const auto t_start = stage::Clock::now();
     ORBX_HIP(hipSetDevice(s->device));
     const int nV = p->n_vertices, nE = p->n_edges, nP = p->n_points;
     // ---- structure: free-vertex columns and the block CSR (diagonal blocks first, then the off-diagonal ones in (row, column)
@@ -366,8 +344,8 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     blk_off.push_back((int)blk_ent.size());
     const int nBlk = (int)blk_i.size();
     const int n = 7 * nF + ((7 * nF) & 1);
-    const int nblk = (n + lba::NB - 1) / lba::NB;
-    const bool fused = nblk <= lba::kFusedMaxBlocks;
+    const int nblk = (n + chol::NB - 1) / chol::NB;
+    const bool fused = nblk <= chol::kFusedMaxBlocks;
     const size_t sys = ((size_t)n + 1) * (size_t)n;
 
     essg::Dev d{};
@@ -384,7 +362,7 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     ESSG_BUF(kX, 8 * (size_t)n, d.x); ESSG_BUF(kBfull, 8 * (size_t)n, d.bfull);
     ESSG_BUF(kS, 8 * sys, S);
     if (fused) ESSG_BUF(kLp, 8 * sys, Lp);
-    ESSG_BUF(kLinv, 8 * (size_t)nblk * lba::NB * lba::NB, Linv);
+    ESSG_BUF(kLinv, 8 * (size_t)nblk * chol::NB * chol::NB, Linv);
     ESSG_BUF(kPoseQ, 16 * (size_t)nV, pose_q); ESSG_BUF(kPoseT, 12 * (size_t)nV, pose_t);
     if (nP > 0) { ESSG_BUF(kPts, 12 * (size_t)nP, pts); ESSG_BUF(kRef, 4 * (size_t)nP, ref); ESSG_BUF(kPtsOut, 12 * (size_t)nP, pts_out); }
 #undef ESSG_BUF
@@ -406,7 +384,7 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
         ORBX_HIP(hipMemcpyAsync(ref, p->point_ref, 4 * (size_t)nP, hipMemcpyHostToDevice, st));
     }
     ORBX_HIP(hipStreamSynchronize(st));         // the host vectors above go out of use here
-    const auto t_uploaded = std::chrono::steady_clock::now();
+    const auto t_uploaded = stage::Clock::now();
     ORBX_HIP(hipEventRecord(s->ev0, st));
 
     double* est[2] = {estA, estB};
@@ -414,20 +392,15 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     double chi_cur = 0;
     bool have_chi = false;
     const dim3 items((std::max(nV, nE) + 255) / 256);
-    const size_t solve_lds = ((size_t)n + 64 + 16 * 64 + lba::NB * (lba::NB + 1)) * sizeof(double);
-    if (!fused && solve_lds > 64 * 1024 && solve_lds > s->solve_lds_set) {      // from about 490 free vertices on
-        ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds));
-        s->solve_lds_set = solve_lds;
-    }
     lm::Levenberg ctl(p->max_iters);
     while (!ctl.capped()) {
         if (!ctl.begin_iteration(stop_flag && *stop_flag)) break;
         if (nE > 0) hipLaunchKernelGGL(essg::k_essg_linearize, dim3((nE + essg::kLinGroups - 1) / essg::kLinGroups), dim3(256), 0, st, d, (const double*)est[cur]);
         if (!have_chi) {        // later iterations start from an accepted trial, whose chi2 is the same sum of the same terms
-            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 0, s->d_hmap, ++s->seq);
+            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 0, s->hs.d, ++s->hs.seq);
             ORBX_HIP(hipGetLastError());
-            if ((r = wait_scalars(s->h_scal, s->seq, st))) return r;
-            chi_cur = s->h_scal[0];
+            if ((r = s->hs.wait(st))) return r;
+            chi_cur = s->hs.h[0];
             have_chi = true;
         }
         ctl.linearized(chi_cur, p->lambda_init);
@@ -436,37 +409,21 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
             const double lambda = ctl.lambda();
             ORBX_HIP(hipMemsetAsync(S, 0, 8 * sys, st));
             hipLaunchKernelGGL(essg::k_essg_assemble, dim3(nBlk + 1), dim3(64), 0, st, d, S, lambda);
-            if (fused) {
-                hipLaunchKernelGGL(lba::k_chol_flow, dim3(nblk * (nblk + 1) / 2), dim3(256), lba::kStepLds, st, S, Lp, n, nblk, Linv, d.scal, s->flow, ++s->flow_epoch);
-                hipLaunchKernelGGL(lba::k_chol_solve<true>, dim3(1), dim3(1024), solve_lds, st, (const double*)Lp, n, (const double*)Linv,
-                                   (const double*)(Lp + (size_t)n * n), (const double*)(S + (size_t)n * n), d.x, (const double*)d.scal, 1);
-            } else {
-                for (int K = 0; K < nblk; K++) {
-                    const int k0 = K * lba::NB, nb = std::min(lba::NB, n - k0);
-                    const int rows_below = (n + 1) - k0 - nb;       // includes the right-hand-side row n
-                    hipLaunchKernelGGL(lba::k_chol_diag, dim3(1), dim3(256), 0, st, (const double*)S, n, k0, nb, Linv, d.scal);
-                    hipLaunchKernelGGL(lba::k_chol_panel, dim3((rows_below + lba::kPanelRows - 1) / lba::kPanelRows), dim3(1024), 0, st,
-                                       S, n, n + 1, k0, nb, (const double*)Linv, (const double*)d.scal);
-                    if (k0 + nb < n) {
-                        const int t = (rows_below + 31) / 32;
-                        hipLaunchKernelGGL(lba::k_chol_update, dim3(t, t), dim3(256), 0, st, S, n, n + 1, k0, nb, (const double*)d.scal);
-                    }
-                }
-                hipLaunchKernelGGL(lba::k_chol_solve<false>, dim3(1), dim3(1024), solve_lds, st, (const double*)S, n, (const double*)Linv,
-                                   (const double*)(S + (size_t)n * n), (const double*)(S + (size_t)n * n), d.x, (const double*)d.scal, 0);
-            }
+            chol::enqueue_factor(st, S, Lp, n, nblk, Linv, d.scal, s->flow, &s->flow_epoch);
+            chol::enqueue_solve(st, S, Lp, n, nblk, Linv, d.x, d.scal);
             hipLaunchKernelGGL(essg::k_essg_update_errors, items, dim3(256), 0, st, d, lambda, (const double*)est[cur], est[1 - cur]);
-            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 1, s->d_hmap, ++s->seq);
+            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 1, s->hs.d, ++s->hs.seq);
             ORBX_HIP(hipGetLastError());
-            if ((r = wait_scalars(s->h_scal, s->seq, st))) return r;
-            const lm::TrialStatus status = lm::trial_status(s->h_scal[5]);
+            if ((r = s->hs.wait(st))) return r;
+            const double* h = s->hs.h;
+            const lm::TrialStatus status = lm::trial_status(h[5]);
             if (status == lm::TrialStatus::kStalled) return fail(ORBX_ERR_INTERNAL, "essg_optimize: the factorisation stalled (a spin wait between workgroups expired)");
-            if (ctl.trial(status == lm::TrialStatus::kSolved, s->h_scal[0], s->h_scal[3])) { cur = 1 - cur; chi_cur = s->h_scal[0]; }
+            if (ctl.trial(status == lm::TrialStatus::kSolved, h[0], h[3])) { cur = 1 - cur; chi_cur = h[0]; }
             stopped = stop_flag && *stop_flag;
         } while (ctl.more_trials(stopped));
         if (!ctl.end_iteration()) break;
     }
-    const auto t_solved = std::chrono::steady_clock::now();
+    const auto t_solved = stage::Clock::now();
     hipLaunchKernelGGL(essg::k_essg_epilogue, dim3((std::max(nV, nP) + 255) / 256), dim3(256), 0, st, d, (const double*)est0, (const double*)est[cur],
                        pose_q, pose_t, (const float*)pts, (const int*)ref, pts_out);
     ORBX_HIP(hipGetLastError());
@@ -479,9 +436,7 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     float ms = 0;
     ORBX_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_device_ms = ms;
-    const auto t_end = std::chrono::steady_clock::now();
-    auto wall = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    s->stage_ms[0] = wall(t_start, t_uploaded); s->stage_ms[1] = wall(t_uploaded, t_solved); s->stage_ms[2] = wall(t_solved, t_end);
+    s->stage_ms[0] = stage::ms(t_start, t_uploaded); s->stage_ms[1] = stage::ms(t_uploaded, t_solved); s->stage_ms[2] = stage::ms(t_solved, stage::Clock::now());
     res->stats = ctl.stats();
     return ORBX_OK;
 }

@@ -1,6 +1,7 @@
 // inertial_solver.inc -- gfx950 kernels + C ABI for the numerical core of Optimizer::LocalInertialBA (reference
-// src/Optimizer.cc:2383-2958; vertices / edges of src/G2oTypes.cc, include/G2oTypes.h).  Included at the end of
-// lba_solver.hip: the reduced-system factorisation (k_chol_diag / k_chol_step / k_chol_solve) is shared with LocalBA.
+// src/Optimizer.cc:2383-2958; vertices / edges of src/G2oTypes.cc, include/G2oTypes.h).  It stands on dense_chol.h (its kernels
+// wrap chol::chol_flow_body / chol_solve_body), device_scope.h and the host kit of batch_stage.h (HostScalars, for_each_window,
+// PinnedOut), and is compiled as part of lba_solver.hip, the one translation unit that holds the Cholesky kernels.
 //
 // Unknowns per key frame: body pose (6, ImuCamPose::Update: twb += Rwb ut, Rwb <- Rwb Exp(ur)), velocity, gyro bias,
 // accelerometer bias (3 each); landmarks are marginalised.  The reduced system has 15 unknowns per temporal key frame (<= 25
@@ -8,9 +9,15 @@
 // accumulated in link order by one thread (deterministic), the visual edges by ordered gathers exactly as in LocalBA
 // (per landmark, per key frame, per pair list of a Schur block).  First version: correctness and the shared factorisation;
 // no tuning yet.
+#include "batch_stage.h"
+#include "dense_chol.h"
+#include "device_scope.h"
+#include "lm_control.h"
+#include "se3_device.h"
+
 namespace liba {
 
-using lba::NB;
+using chol::NB;
 
 struct KFState { double Rwb[9], twb[3], v[3], bg[3], ba[3], Rcw[9], tcw[3]; int its, pad; };
 
@@ -208,7 +215,7 @@ __device__ inline void link_error(const LibaLink& L, const KFState& k1, const KF
 // ---------------------------------------------------------------------------------------------------------------------------
 // Launch structure (round 3): every kernel takes the windows of a batch (grid.y = window; liba_solve is a batch of one) and the
 // per-round state of each window by value.  A linearisation is ONE launch (ki_lin: a workgroup per inertial link beside the
-// visual edges), a Levenberg trial FIVE (ki_system, ki_schur_blocks, the factorisation lba::chol_flow_body, ki_solve_update,
+// visual edges), a Levenberg trial FIVE (ki_system, ki_schur_blocks, the factorisation chol::chol_flow_body, ki_solve_update,
 // ki_points_errors); the first version needed twelve plus a memset, and its link kernel (one workgroup for all links, then
 // colour-ordered read-modify-write accumulation into a dense matrix) alone took 45 us.  No stage accumulates into memory any more:
 // every entry of the reduced system has ONE writer that gathers its terms in a fixed order.
@@ -225,15 +232,6 @@ constexpr int kMaxIBatch = 64;
 struct IDynAll { IDyn w[kMaxIBatch]; };
 enum { kIwErrors = 1, kIwLin = 2, kIwTrial = 4 };
 constexpr int kPtThreads = 256, kPtLandmarks = kPtThreads / 8;
-
-__device__ __forceinline__ void st_agent(double* p, double v)       // agent-scope store (see lba::update_errors_body)
-{
-    __hip_atomic_store((unsigned long long*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_agent(const double* p)
-{
-    return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 // robust chi2 of link l (EdgeInertial + the two random walks) at the state `st`
 __device__ inline double link_chi2(const Dev& d, const LibaLink& L, const KFState* __restrict__ st)
@@ -736,7 +734,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (!(y.flags & kIwTrial)) return;
     const IWin& w = wins[w0 + blockIdx.y];
     if ((int)blockIdx.x >= w.nblk * (w.nblk + 1) / 2) return;
-    lba::chol_flow_body(w.S, w.Lp, w.d.npad, w.nblk, w.Linv, w.d.scal, w.flow, (unsigned)y.seq, (int)blockIdx.x, sm_step);
+    chol::chol_flow_body(w.S, w.Lp, w.d.npad, w.nblk, w.Linv, w.d.scal, w.flow, (unsigned)y.seq, (int)blockIdx.x, sm_step);
 }
 
 // substitution (LocalBA's single-workgroup kernel) and, by the same workgroup, the trial state of every key frame (oplus into the
@@ -749,7 +747,7 @@ __global__ __launch_bounds__(1024) void ki_solve_update(const IWin* __restrict__
     const IWin& w = wins[blockIdx.y];
     const Dev& d = w.d;
     const int np = d.npad;
-    lba::chol_solve_body<true>(w.Lp, np, w.Linv, w.Lp + (size_t)np * np, w.S + (size_t)np * np, d.x, d.scal, 1, 0, sm);
+    chol::chol_solve_body<true>(w.Lp, np, w.Linv, w.Lp + (size_t)np * np, w.S + (size_t)np * np, d.x, d.scal, 1, 0, sm);
     __syncthreads();                // x is complete (global memory, same workgroup)
     const double lambda = y.lambda;
     const KFState* __restrict__ st = w.st[y.cur];
@@ -939,6 +937,7 @@ __device__ __forceinline__ double dpp_mov_f64(double v)
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
 }
+// (NOT a duplicate of chol::row16_sum, a __shfl_xor butterfly: the two add in different orders and differ in the last bits.)
 __device__ __forceinline__ double row16_allsum(double v)       // every lane gets the sum over its row of 16 lanes
 {
     v += dpp_mov_f64<0x121>(v);         // row_ror:1
@@ -969,7 +968,7 @@ struct CholRowStep {
         if constexpr (J < N) {
             const double dj = readlane_f64<J>(A[J]);
             if (!(dj > 0.0) || !isfinite(dj)) ok = false;
-            const double inv = lba::rsqrt_newton(dj);
+            const double inv = chol::rsqrt_newton(dj);
             invd[J] = inv;
             const double lij = A[J] * inv;
             A[J] = lij;
@@ -1445,25 +1444,22 @@ __global__ __launch_bounds__(384) void k_pose_inertial(PIDev d)
 
 }  // namespace liba
 
-struct liba_io { uint8_t* h_out = nullptr; uint8_t* d_out = nullptr; size_t cap = 0; };       // result buffer of a handle: device + pinned host
-struct liba_solver {
+struct liba_solver {                // also a window slot of a liba_batch, with the batch's stream and a view of its scalars
     int device = 0;
     hipStream_t stream = nullptr;
     liba::IWin* d_wins = nullptr;   // the window table of liba_solve (one entry)
-    liba_io io;
+    stage::PinnedOut io;            // result buffer of the handle: device + pinned host
     std::vector<void*> allocs;
     // bump arena reused across calls (a window needs ~45 device buffers; without it the hipMalloc / hipFree pairs cost more
     // than the optimisation); buffers that do not fit fall back to hipMalloc and the arena grows for the next call
     uint8_t* arena = nullptr;
     size_t arena_cap = 0, arena_off = 0, wanted = 0;
-    double* h_scal = nullptr;       // pinned, host-mapped, coherent [16]: scalars + sequence number at [8]
+    stage::HostScalars hs;          // scalars + sequence number at [8]
     uint8_t* h_mirror = nullptr;    // pinned mirror of the arena (stage / flush)
     size_t h_mirror_cap = 0;
     std::vector<std::pair<size_t, size_t> > pending;     // (arena offset, bytes) waiting for flush()
     uint8_t* h_stage = nullptr;     // pinned staging buffer of the per-frame optimisation (grown on demand)
     size_t h_stage_cap = 0;
-    double* d_hmap = nullptr;
-    unsigned long long seq = 0;
     template <typename T>
     int dalloc(T** p, size_t count)
     {
@@ -1486,6 +1482,8 @@ struct liba_solver {
     }
     // Host-to-device data goes through a pinned mirror of the arena: a window's two dozen small arrays become one or two copies
     // (adjacent allocations merge) issued by flush() before the first kernel, instead of a pageable-memory copy each.
+    // (lba_shard::put / flush_stage is NOT the same thing: a shard allocates everything it uploads first and sends the arena's
+    // prefix in ONE copy; here uploads and scratch interleave, so segments are merged.  One for both would change the copies.)
     int stage(void* dev, const void* src, size_t bytes)
     {
         if (!bytes) return ORBX_OK;
@@ -1522,13 +1520,22 @@ struct liba_solver {
         }
         arena_off = 0; wanted = 0;
     }
+    ~liba_solver()
+    {
+        release();
+        if (arena) (void)hipFree(arena);
+        if (h_stage) (void)hipHostFree(h_stage);
+        if (h_mirror) (void)hipHostFree(h_mirror);
+        if (d_wins) (void)hipFree(d_wins);
+        hs.release();
+        io.release();
+    }
 };
 
 static int liba_kernel_attributes()
 {
-    ORBX_HIP(hipFuncSetAttribute((const void*)liba::ki_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
-    ORBX_HIP(hipFuncSetAttribute((const void*)liba::ki_solve_update, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    return ORBX_OK;
+    int r = chol::allow_lds(liba::ki_chol_flow, chol::kStepLds);
+    return r ? r : chol::allow_lds(liba::ki_solve_update, chol::kFusedSolveLds);
 }
 
 extern "C" {
@@ -1537,23 +1544,15 @@ int liba_create(int device, liba_solver** out)
 {
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     liba_solver* s = new liba_solver();
     s->device = device;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return fail(ORBX_ERR_HIP, "stream creation failed"); }
-    if (hipHostMalloc((void**)&s->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&s->d_hmap, s->h_scal, 0) != hipSuccess ||
-        hipMalloc((void**)&s->d_wins, sizeof(liba::IWin)) != hipSuccess || liba_kernel_attributes() != ORBX_OK) {
-        (void)hipStreamDestroy(s->stream);
-        if (s->h_scal) (void)hipHostFree(s->h_scal);
-        if (s->d_wins) (void)hipFree(s->d_wins);
-        delete s;
+    if (s->hs.alloc() != ORBX_OK || hipMalloc((void**)&s->d_wins, sizeof(liba::IWin)) != hipSuccess || liba_kernel_attributes() != ORBX_OK) {
+        liba_destroy(s);
         return fail(ORBX_ERR_HIP, "solver buffer creation failed");
     }
-    std::memset(s->h_scal, 0, 16 * sizeof(double));
     *out = s;
     return ORBX_OK;
 }
@@ -1563,14 +1562,6 @@ void liba_destroy(liba_solver* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    s->release();
-    if (s->arena) (void)hipFree(s->arena);
-    if (s->h_scal) (void)hipHostFree(s->h_scal);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->h_mirror) (void)hipHostFree(s->h_mirror);
-    if (s->d_wins) (void)hipFree(s->d_wins);
-    if (s->io.h_out) (void)hipHostFree(s->io.h_out);
-    if (s->io.d_out) (void)hipFree(s->io.d_out);
     delete s;
 }
 
@@ -1615,8 +1606,8 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
     if (np == 0) return fail(ORBX_ERR_ARG, "nothing to optimise");
     const int npad = (np + 1) & ~1;             // the factorisation kernels use 16-byte loads: an even leading dimension
     d.np = np; d.npad = npad;
-    const int nblk = (npad + lba::NB - 1) / lba::NB;
-    if (nblk > lba::kFusedMaxBlocks) return fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the inertial solver's limit", np);
+    const int nblk = (npad + chol::NB - 1) / chol::NB;
+    if (nblk > chol::kFusedMaxBlocks) return fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the inertial solver's limit", np);
     // row -> (key frame, local index: pose 0-5, velocity 6-8, gyro bias 9-11, accelerometer bias 12-14); padding rows: -1
     std::vector<int> row_kf(npad, -1), row_loc(npad, 0);
     for (int i = 0; i < nKF; i++) {
@@ -1702,12 +1693,12 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
     LIBA_TRY(sv->dalloc(&d.x, (size_t)npad)); LIBA_TRY(sv->dalloc(&d.part, (size_t)nL + nKF)); LIBA_TRY(sv->dalloc(&d.chi_part, (size_t)nL));
     {   // zeroed per call in one memset: the device scalars (failure flag in [5]), the ticket of ki_points_errors, the tile flags of the factorisation
         uint8_t* zb;
-        const size_t zbytes = 16 * sizeof(double) + 64 + lba::kFlowFlags * sizeof(unsigned);
+        const size_t zbytes = 16 * sizeof(double) + 64 + chol::kFlowFlags * sizeof(unsigned);
         LIBA_TRY(sv->dalloc(&zb, zbytes));
         d.scal = (double*)zb; d.ticket = (unsigned*)(zb + 16 * sizeof(double)); w.flow = (unsigned*)(zb + 16 * sizeof(double) + 64);
         out->zero_block = zb; out->zero_bytes = zbytes;
     }
-    LIBA_TRY(sv->dalloc(&w.S, ((size_t)npad + 1) * npad)); LIBA_TRY(sv->dalloc(&w.Linv, (size_t)nblk * lba::NB * lba::NB));
+    LIBA_TRY(sv->dalloc(&w.S, ((size_t)npad + 1) * npad)); LIBA_TRY(sv->dalloc(&w.Linv, (size_t)nblk * chol::NB * chol::NB));
     LIBA_TRY(sv->dalloc(&w.Lp, ((size_t)npad + 1) * npad));
 #undef LIBA_TRY
     for (int k = 0; k < 9; k++) { d.Rcb[k] = p->Rcb[k]; d.Rbc[k] = p->Rcb[3 * (k % 3) + k / 3]; }
@@ -1715,7 +1706,7 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
     d.fx = p->fx; d.fy = p->fy; d.cx = p->cx; d.cy = p->cy; d.bf = p->bf;
     d.huber_mono = p->huber_mono; d.huber_stereo = p->huber_stereo; d.huber_inertial = p->huber_inertial;
     w.d = d;
-    w.hmap = sv->d_hmap;
+    w.hmap = sv->hs.d;
     w.nblk = nblk;
     w.edge_blocks = (nE + liba::kLinThreads - 1) / liba::kLinThreads;
     w.lm_blocks = (nL + liba::kPtLandmarks - 1) / liba::kPtLandmarks;
@@ -1727,61 +1718,31 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
 // (levenberg.cpp:61-169) with the user lambda, one Levenberg controller (lm_control.h) per window, cut where the host waits for the device; a round =
 // [errors of the accepted state where they are stale] [linearisation where an iteration starts] [one trial], every stage ONE launch
 // for all windows.
-static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, liba::IWin* d_wins, liba_io* io, const LibaProblem* problems,
+static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, liba::IWin* d_wins, stage::PinnedOut* io, const LibaProblem* problems,
                     const LibaOutputs* outputs, int W, LbaStats* stats_out, float* device_ms, hipEvent_t ev0, hipEvent_t ev1)
 {
     static const bool timing = std::getenv("ORBX_LBA_TIMING") != nullptr;
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = stage::Clock::now();
     int r = ORBX_OK;
     for (int i = 0; i < W; i++) if ((r = liba_validate(&problems[i]))) return r;
     ORBX_HIP(hipSetDevice(device));
     for (int i = 0; i < W; i++) slots[i]->release();
     auto cleanup = [&]() { for (int i = 0; i < W; i++) slots[i]->release(); };
     std::vector<LibaWindow> win((size_t)W);
-    {
-        const int n_thr = std::max(1, std::min({W, (int)std::thread::hardware_concurrency(), 16}));
-        std::vector<int> rcs((size_t)W, ORBX_OK);
-        if (n_thr == 1) {
-            for (int i = 0; i < W; i++) rcs[i] = liba_window_setup(slots[i], &problems[i], &win[i]);
-        } else {
-            std::atomic<int> next(0);
-            auto worker = [&]() {
-                (void)hipSetDevice(device);
-                for (int i = next.fetch_add(1); i < W; i = next.fetch_add(1)) rcs[i] = liba_window_setup(slots[i], &problems[i], &win[i]);
-            };
-            std::vector<std::thread> th;
-            for (int t = 1; t < n_thr; t++) th.emplace_back(worker);
-            worker();
-            for (auto& t : th) t.join();
-        }
-        for (int i = 0; i < W; i++) if (rcs[i] && !r) r = W == 1 ? rcs[i] : fail(rcs[i], "window %d could not be set up (code %d; the worker thread holds the detailed message)", i, rcs[i]);
-        if (r) { (void)hipStreamSynchronize(stream); cleanup(); return r; }
-    }
+    if (W == 1) r = liba_window_setup(slots[0], &problems[0], &win[0]);        // (liba_solve: the window's own message stands)
+    else r = stage::for_each_window(W, device, [&](int i) { return liba_window_setup(slots[i], &problems[i], &win[i]); });
+    if (r) { (void)hipStreamSynchronize(stream); cleanup(); return r; }
     std::vector<liba::IWin> hw((size_t)W);
     int max_lin = 1, max_pt = 1, max_sys = 1, max_sb = 1, max_nblk = 1, max_kf = 1, max_epi = 1;
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    std::vector<size_t> off((size_t)W + 1, 0);
-    for (int i = 0; i < W; i++) {
-        const liba::Dev& d = win[i].w.d;
-        off[i + 1] = off[i] + al((size_t)d.nKF * sizeof(liba::KFState)) + al(3 * (size_t)d.nL * 8) + al((size_t)d.nE * 8) + al((size_t)d.nE);
-    }
-    if (off[W] > io->cap) {
-        if (io->h_out) (void)hipHostFree(io->h_out);
-        if (io->d_out) (void)hipFree(io->d_out);
-        io->h_out = io->d_out = nullptr; io->cap = 0;
-        const size_t cap = off[W] + off[W] / 4 + 4096;
-        if (hipHostMalloc((void**)&io->h_out, cap) == hipSuccess && hipMalloc((void**)&io->d_out, cap) == hipSuccess) io->cap = cap;
-        else r = fail(ORBX_ERR_HIP, "result buffer allocation failed");
-    }
+    io->clear();
+    for (int i = 0; i < W; i++) io->add((size_t)win[i].w.d.nKF * sizeof(liba::KFState), win[i].w.d.nL, win[i].w.d.nE);
+    r = io->reserve(true);
     for (int i = 0; i < W && !r; i++) {
         hw[i] = win[i].w;
         liba::IWin& w = hw[i];
         {
-            uint8_t* o = io->d_out + off[i];
-            w.o_st = (liba::KFState*)o; o += al((size_t)w.d.nKF * sizeof(liba::KFState));
-            w.o_pts = (double*)o; o += al(3 * (size_t)w.d.nL * 8);
-            w.o_chi2 = (double*)o; o += al((size_t)w.d.nE * 8);
-            w.o_depth = o;
+            const stage::PinnedOut::Slice o = io->slice(io->d + io->off[i], (size_t)w.d.nKF * sizeof(liba::KFState), w.d.nL, w.d.nE);
+            w.o_st = (liba::KFState*)o.state; w.o_pts = (double*)o.points; w.o_chi2 = (double*)o.chi2; w.o_depth = o.depth;
         }
         max_lin = std::max(max_lin, w.d.nLinks + w.edge_blocks); max_pt = std::max(max_pt, w.lm_blocks + 1);
         max_sys = std::max(max_sys, w.lm_blocks + w.d.nKF + w.entry_blocks); max_sb = std::max(max_sb, w.d.nBlocks);
@@ -1791,10 +1752,9 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     }
     if (!r && hipMemcpyAsync(d_wins, hw.data(), (size_t)W * sizeof(liba::IWin), hipMemcpyHostToDevice, stream) != hipSuccess) r = fail(ORBX_ERR_HIP, "window table upload failed");
     if (r) { cleanup(); return r; }
-    const size_t solve_lds = 65536;
     hipLaunchKernelGGL(liba::ki_init_states, dim3((max_kf + 63) / 64, W), dim3(64), 0, stream, (const liba::IWin*)d_wins);
     if (ev0) (void)hipEventRecord(ev0, stream);
-    const auto t_setup = std::chrono::steady_clock::now();
+    const auto t_setup = stage::Clock::now();
 
     std::vector<lm::Levenberg> ctl;                 // one Levenberg controller per window (lm_control.h), started at the user lambda
     for (int i = 0; i < W; i++) ctl.emplace_back(problems[i].max_iters, problems[i].lambda_init);
@@ -1803,7 +1763,7 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
     liba::IDynAll dyn;
     std::memset(&dyn, 0, sizeof(dyn));
     const int tiles = max_nblk * (max_nblk + 1) / 2;
-    const int flow_windows = std::max(1, lba::kMaxFlowGroups / tiles);
+    const int flow_windows = std::max(1, chol::kMaxFlowGroups / tiles);
     for (bool final_round = false;;) {
         bool any_lin = false, any_err = false, any_trial = false;
         for (int i = 0; i < W; i++) {
@@ -1820,7 +1780,7 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
                 if (c.step() == lm::Levenberg::kLinearize || c.step() == lm::Levenberg::kTrial) y.flags |= liba::kIwTrial;
             }
             y.lambda = c.lambda(); y.cur = cur[i];
-            if (y.flags) y.seq = ++slots[i]->seq;
+            if (y.flags) y.seq = ++slots[i]->hs.seq;
             any_lin |= (y.flags & liba::kIwLin) != 0; any_err |= (y.flags & liba::kIwErrors) != 0; any_trial |= (y.flags & liba::kIwTrial) != 0;
         }
         if (!any_lin && !any_trial && !any_err) { if (final_round) break; final_round = true; continue; }
@@ -1831,19 +1791,19 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
             hipLaunchKernelGGL(liba::ki_system, dim3(max_sys, W), dim3(liba::kSysThreads), 0, stream, dw, dyn);
             hipLaunchKernelGGL(liba::ki_schur_blocks, dim3(max_sb, W), dim3(1024), 0, stream, dw, dyn);
             for (int w0 = 0; w0 < W; w0 += flow_windows)
-                hipLaunchKernelGGL(liba::ki_chol_flow, dim3(tiles, std::min(flow_windows, W - w0)), dim3(256), lba::kStepLds, stream, dw, dyn, w0);
-            hipLaunchKernelGGL(liba::ki_solve_update, dim3(1, W), dim3(1024), solve_lds, stream, dw, dyn);
+                hipLaunchKernelGGL(liba::ki_chol_flow, dim3(tiles, std::min(flow_windows, W - w0)), dim3(256), chol::kStepLds, stream, dw, dyn, w0);
+            hipLaunchKernelGGL(liba::ki_solve_update, dim3(1, W), dim3(1024), chol::kFusedSolveLds, stream, dw, dyn);
             hipLaunchKernelGGL(liba::ki_points_errors, dim3(max_pt, W), dim3(liba::kPtThreads), 0, stream, dw, dyn, 1);
         }
         if (hipGetLastError() != hipSuccess) { r = fail(ORBX_ERR_HIP, "launch failed"); break; }
         if (final_round) break;
         for (int i = 0; i < W && !r; i++)
-            if (dyn.w[i].flags) r = wait_scalars(slots[i]->h_scal, slots[i]->seq, stream);
+            if (dyn.w[i].flags) r = slots[i]->hs.wait(stream);
         if (r) break;
         for (int i = 0; i < W; i++) {
             lm::Levenberg& c = ctl[i];
             const int f = dyn.w[i].flags;
-            const double* h = slots[i]->h_scal;
+            const double* h = slots[i]->hs.h;
             if (f & liba::kIwErrors) err_current[i] = 1;
             if (f & liba::kIwLin) c.linearized(c.iteration() == 0 ? h[6] : c.chi2(), problems[i].lambda_init);     // (chi2 of the initial state)
             if (!(f & liba::kIwTrial)) continue;
@@ -1860,8 +1820,7 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
         if (r) break;
     }
     if (ev1) (void)hipEventRecord(ev1, stream);
-    const auto t_solved = std::chrono::steady_clock::now();
-#define BTRY(expr) do { if (!r && (expr) != hipSuccess) r = fail(ORBX_ERR_HIP, "%s failed", #expr); } while (0)
+    const auto t_solved = stage::Clock::now();
     if (!r) {
         // results of all windows: one epilogue launch into the handle's device buffer, ONE copy, one synchronisation, then the scatter
         for (int i = 0; i < W; i++) {
@@ -1870,16 +1829,16 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
         }
         if (outputs) {
             hipLaunchKernelGGL(liba::ki_epilogue, dim3(max_epi, W), dim3(256), 0, stream, (const liba::IWin*)d_wins, dyn);
-            BTRY(hipGetLastError());
-            BTRY(hipMemcpyAsync(io->h_out, io->d_out, off[W], hipMemcpyDeviceToHost, stream));
+            ORBX_HIP_FIRST(r, hipGetLastError());
+            ORBX_HIP_FIRST(r, hipMemcpyAsync(io->h, io->d, io->total(), hipMemcpyDeviceToHost, stream));
         }
-        BTRY(hipStreamSynchronize(stream));
+        ORBX_HIP_FIRST(r, hipStreamSynchronize(stream));
         if (!r && device_ms && ev0 && ev1) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *device_ms = ms; }
         for (int i = 0; i < W && !r && outputs; i++) {
             const liba::Dev& d = hw[i].d;
             const LibaOutputs& o = outputs[i];
-            const uint8_t* h = io->h_out + off[i];
-            const liba::KFState* st = (const liba::KFState*)h;
+            const stage::PinnedOut::Slice h = io->slice(io->h + io->off[i], (size_t)d.nKF * sizeof(liba::KFState), d.nL, d.nE);
+            const liba::KFState* st = (const liba::KFState*)h.state;
             for (int k = 0; k < d.nKF; k++) {
                 if (o.Rwb) std::memcpy(o.Rwb + 9 * k, st[k].Rwb, 72);
                 if (o.twb) std::memcpy(o.twb + 3 * k, st[k].twb, 24);
@@ -1887,23 +1846,19 @@ static int liba_run(int device, hipStream_t stream, liba_solver* const* slots, l
                 if (o.bg) std::memcpy(o.bg + 3 * k, st[k].bg, 24);
                 if (o.ba) std::memcpy(o.ba + 3 * k, st[k].ba, 24);
             }
-            h += al((size_t)d.nKF * sizeof(liba::KFState));
-            if (o.points && d.nL > 0) std::memcpy(o.points, h, 3 * (size_t)d.nL * 8);
-            h += al(3 * (size_t)d.nL * 8);
-            if (o.chi2_per_edge && d.nE > 0) std::memcpy(o.chi2_per_edge, h, (size_t)d.nE * 8);
-            h += al((size_t)d.nE * 8);
-            if (o.depth_positive && d.nE > 0) std::memcpy(o.depth_positive, h, (size_t)d.nE);
+            if (o.points && d.nL > 0) std::memcpy(o.points, h.points, 3 * (size_t)d.nL * 8);
+            if (o.chi2_per_edge && d.nE > 0) std::memcpy(o.chi2_per_edge, h.chi2, (size_t)d.nE * 8);
+            if (o.depth_positive && d.nE > 0) std::memcpy(o.depth_positive, h.depth, (size_t)d.nE);
         }
     } else {
         (void)hipStreamSynchronize(stream);
     }
-#undef BTRY
     if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        using stage::ms;
         int its = 0, trials = 0;
         for (int i = 0; i < W; i++) { its += ctl[i].stats().iterations; trials += ctl[i].stats().trials; }
         std::fprintf(stderr, "[liba_solve] %d window(s): structure + upload %.3f ms, %d iterations / %d trials %.3f ms, download %.3f ms\n", W, ms(t_start, t_setup),
-                     its, trials, ms(t_setup, t_solved), ms(t_solved, std::chrono::steady_clock::now()));
+                     its, trials, ms(t_setup, t_solved), ms(t_solved, stage::Clock::now()));
     }
     cleanup();
     return r;
@@ -1920,56 +1875,36 @@ int liba_solve(liba_solver* sv, const LibaProblem* p, double* Rwb_out, double* t
     return liba_run(sv->device, sv->stream, &slot, sv->d_wins, &sv->io, p, &o, 1, stats_out, nullptr, nullptr, nullptr);
 }
 
-struct liba_batch {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct liba_batch : stage::Batch {          // its stream, the two events around the Levenberg rounds
     std::vector<liba_solver*> slots;        // one arena per window
-    double* h_scal = nullptr;               // pinned, host-mapped [kMaxIBatch][16]
-    double* d_hmap = nullptr;
+    stage::HostScalars hs;                  // [kMaxIBatch][16]
     liba::IWin* d_wins = nullptr;
-    liba_io io;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    stage::PinnedOut io;
     float last_device_ms = 0.f;
+    ~liba_batch()
+    {
+        for (liba_solver* s : slots) delete s;
+        hs.release();
+        if (d_wins) (void)hipFree(d_wins);
+        io.release();
+    }
 };
 
 int liba_batch_create(int device, liba_batch** out)
 {
-    if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBX_HIP(hipSetDevice(device));
-    liba_batch* b = new liba_batch();
-    b->device = device;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&b->h_scal, (size_t)liba::kMaxIBatch * 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&b->d_hmap, b->h_scal, 0) != hipSuccess ||
-        hipMalloc((void**)&b->d_wins, (size_t)liba::kMaxIBatch * sizeof(liba::IWin)) != hipSuccess ||
-        hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess || liba_kernel_attributes() != ORBX_OK) {
-        liba_batch_destroy(b);
+    int r = stage::open(device, out);
+    if (r) return r;
+    liba_batch* b = *out;
+    if (b->hs.alloc(liba::kMaxIBatch) != ORBX_OK || hipMalloc((void**)&b->d_wins, (size_t)liba::kMaxIBatch * sizeof(liba::IWin)) != hipSuccess ||
+        liba_kernel_attributes() != ORBX_OK) {
+        stage::close(b);
+        *out = nullptr;
         return fail(ORBX_ERR_HIP, "batch creation failed");
     }
-    std::memset(b->h_scal, 0, (size_t)liba::kMaxIBatch * 16 * sizeof(double));
-    *out = b;
     return ORBX_OK;
 }
 
-void liba_batch_destroy(liba_batch* b)
-{
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (liba_solver* s : b->slots) { s->release(); if (s->arena) (void)hipFree(s->arena); if (s->h_mirror) (void)hipHostFree(s->h_mirror); delete s; }
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    if (b->h_scal) (void)hipHostFree(b->h_scal);
-    if (b->d_wins) (void)hipFree(b->d_wins);
-    if (b->io.h_out) (void)hipHostFree(b->io.h_out);
-    if (b->io.d_out) (void)hipFree(b->io.d_out);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    delete b;
-}
+void liba_batch_destroy(liba_batch* b) { stage::close(b); }
 
 int liba_solve_batch(liba_batch* b, const LibaProblem* problems, const LibaOutputs* outputs, int n_windows, LbaStats* stats_out)
 {
@@ -1979,7 +1914,7 @@ int liba_solve_batch(liba_batch* b, const LibaProblem* problems, const LibaOutpu
     while ((int)b->slots.size() < n_windows) {
         liba_solver* sv = new liba_solver();
         sv->device = b->device; sv->stream = b->stream;
-        sv->h_scal = b->h_scal + 16 * b->slots.size(); sv->d_hmap = b->d_hmap + 16 * b->slots.size();
+        sv->hs = b->hs.view((int)b->slots.size());
         b->slots.push_back(sv);
     }
     return liba_run(b->device, b->stream, b->slots.data(), b->d_wins, &b->io, problems, outputs, n_windows, stats_out, &b->last_device_ms, b->ev0, b->ev1);

@@ -11,17 +11,15 @@
 //   k_schur_landmarks  D^-1 = (Hll + lambda I)^-1, db = D^-1 b_l, Z_e = W_e D^-1          (1 thread / landmark)
 //   k_schur_blocks     S_ij = [Hpp_ii] - sum_pairs Z_a W_b^T ,  b_s = b_p - sum W_e db        (1 wave / block)
 //   (multi-GPU: the caller all-reduces [S | b_s | b_p | diag Hpp] here -- RCCL over xGMI)
-//   k_add_lambda, blocked Cholesky (k_chol_panel / k_chol_update per 60-column step), k_chol_solve
+//   k_add_lambda, then the dense Cholesky of dense_chol.h (k_chol_flow, or k_chol_diag / panel / update per 60-column step)
 //   k_chol_solve_update  substitution, then trial poses = oplus(poses, x_p) and the pose part of the scale sum
 //   k_update_errors    x_l = D^-1 (b_l - W^T x_p), trial points, residuals + Huber rho of the trial state per landmark; the last
 //                      workgroup sums chi2 / scale in a fixed order
 // Every reduction is ordered (CSR gather or fixed tree), so results are reproducible run to run.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <chrono>
-
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -29,17 +27,16 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
-#include "hip_check.h"
+#include "batch_stage.h"
+#include "dense_chol.h"
+#include "device_scope.h"
 #include "lm_control.h"
 #include "se3_device.h"
 
 namespace lba {
-
-constexpr int NB = 60;      // Cholesky block size (10 poses)
 
 struct Cam { double fx, fy, cx, cy, bf, huber_mono, huber_stereo, dsqr_mono, dsqr_stereo; };
 
@@ -497,718 +494,6 @@ __global__ void k_add_lambda(double* S, int n, double lambda)
     if (i < n) S[(size_t)i * n + i] += lambda;
 }
 
-// ---- blocked right-looking Cholesky of the (dense, small) reduced camera system, lower triangle ----
-// Per 60-column step: k_chol_diag factors the diagonal block AND inverts it (Gauss-Jordan on [L | I]) in LDS with
-// O(1)-depth steps; k_chol_panel then gets the rows below as a dense product X = A * Linv^T (no substitution chains);
-// k_chol_update applies the trailing update.  The substitutions in k_chol_solve also only need Linv.
-// Factor AND invert one diagonal block held in registers.  Thread (ty, tx) of a 16 x 16 grid owns the elements
-// (ty + 16a, tx + 16b), a, b < 4, of the 64 x 64-padded block L (identity beyond nb) and of X = L^-1.
-// (History: one column per barrier 33.7 us per 60-column block, two columns 27.5 us, four columns 19.1 us.)
-// FOUR columns per barrier.  The owners publish the raw columns j0..j0+3 of L and rows j0..j0+3 of X; every thread factors the
-// 4 x 4 pivot block P = Lp Lp^T itself and forms M = Lp^-1 (replicated: no broadcast), then
-//   U = A[:, j0..j0+3] M^T  (its rows / its columns),   Xn = M X[j0..j0+3][:],
-//   rows below the pivot block:  L -= U U^T,  X -= U Xn;   rows of the pivot block: X <- Xn.
-// L itself is not an output (only X = L^-1 is), so finished columns are never written back, and garbage above the diagonal of
-// the diagonal 16 x 16 tiles is never read (columns are consumed from their diagonal element downwards).
-typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-struct CholVec4 { double col[2][4][64], row[2][4][64]; };
-__device__ __forceinline__ double rsqrt_newton(double d)
-{
-    double inv = __builtin_amdgcn_rsq(d);
-    inv = inv * fma(-0.5 * d * inv, inv, 1.5);
-    return inv * fma(-0.5 * d * inv, inv, 1.5);
-}
-// The rank-4 updates of the step run on the f64 matrix pipe.  A 256-thread workgroup is one wave per SIMD,
-// where a v_fma_f64 issues every ~8.5 clocks and v_mfma_f64_16x16x4 (2048 FLOP) every 64 (tools/probes/f64_rates.hip): the
-// 128 FMAs per thread of the register-tile update become at most 5 MFMAs, and a lane only prepares the operands the MFMA takes
-// from it (one value of U, one of V or Xn per column block: 4 FMAs each on M's row k = lane >> 4) instead of the 48 values
-// its 4 x 4 tile would need.  Thread (ty, tx) = lane (ty & 3) * 16 + tx of wave ty >> 2 owns rows ty + 16 a: exactly the rows
-// of accumulator component a when the wave feeds the MFMA rows m -> 4 w + (m & 3) + 16 (m >> 2) (as k_chol_step does), so
-// Lacc[b][a] / Xacc[b][a] ARE the thread's elements (ty + 16 a, tx + 16 b).
-#ifdef LBA_STEP_TIMING       // cycle split of the 4-column groups of chol_tile_mfma (thread 0 of the factoring workgroup)
-__device__ unsigned long long d_tile_prof[8];
-#define LBA_TTICK(k) if (threadIdx.x == 0) { const long long t_now = clock64(); d_tile_prof[k] += (unsigned long long)(t_now - t_tile); t_tile = t_now; }
-#else
-#define LBA_TTICK(k)
-#endif
-__device__ __forceinline__ bool chol_tile_mfma(double (&Lr)[4][4], int nb, double* __restrict__ Li, CholVec4& sv)
-{
-#ifdef LBA_STEP_TIMING
-    long long t_tile = clock64();
-#endif
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    const int lk = ty & 3, wv4 = ty & ~3;                   // MFMA k index of this lane; first row of the wave's row group
-    const int r_u = wv4 + (tx & 3) + 16 * (tx >> 2);        // the row whose U value this lane feeds (MFMA row m = tx)
-    mfma_d4 Lacc[4], Xacc[4];
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-#pragma unroll
-        for (int a = 0; a < 4; a++) { Lacc[b][a] = Lr[a][b]; Xacc[b][a] = (ty + 16 * a == tx + 16 * b) ? 1.0 : 0.0; }
-    bool failed = false;
-#pragma unroll
-    for (int ja = 0; ja < 4; ja++) {
-        for (int jy = 0; jy < 16; jy += 4) {
-            const int j0 = 16 * ja + jy;
-            if (j0 >= nb || failed) break;                  // a partial last group pairs with the identity padding
-            const int p = (jy >> 2) & 1;
-            const int ko = tx - jy;                         // 0..3: this thread owns a pivot column
-            const bool own_rows = wv4 == jy;                // wave-uniform: this wave owns the pivot rows j0 + (ty & 3)
-            LBA_TTICK(0)
-            if (ko >= 0 && ko < 4) {
-#pragma unroll
-                for (int a = 0; a < 4; a++) sv.col[p][ko][ty + 16 * a] = Lacc[ja][a];
-            }
-            if (own_rows) {
-#pragma unroll
-                for (int b = 0; b < 4; b++) sv.row[p][lk][tx + 16 * b] = Xacc[b][ja];
-            }
-            LBA_TTICK(1)
-            __syncthreads();
-            LBA_TTICK(2)
-            // the operand reads go out first: they land while the pivot chain below runs
-            // A operand: -U[r_u][lk], zero for the rows of the pivot block and above (they take no update)
-            const double c0u = sv.col[p][0][r_u], c1u = sv.col[p][1][r_u], c2u = sv.col[p][2][r_u], c3u = sv.col[p][3][r_u];
-            double cv[4][4], rv[4][4];
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int c = tx + 16 * b;
-                if (b >= ja) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) cv[b][k] = sv.col[p][k][c];
-                }
-                if (b <= ja) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) rv[b][k] = sv.row[p][k][c];
-                }
-            }
-            // pivot block (lower triangle): P[k][m] = column m, row j0 + k
-            const double P00 = sv.col[p][0][j0], P10 = sv.col[p][0][j0 + 1], P20 = sv.col[p][0][j0 + 2], P30 = sv.col[p][0][j0 + 3];
-            const double P11 = sv.col[p][1][j0 + 1], P21 = sv.col[p][1][j0 + 2], P31 = sv.col[p][1][j0 + 3];
-            const double P22 = sv.col[p][2][j0 + 2], P32 = sv.col[p][2][j0 + 3], P33 = sv.col[p][3][j0 + 3];
-            bool ok = (P00 > 0.0) && isfinite(P00);                                 // (checked once per group: one uniform branch, not four)
-            const double i0 = rsqrt_newton(P00);
-            const double l10 = P10 * i0, l20 = P20 * i0, l30 = P30 * i0;
-            const double d1 = fma(-l10, l10, P11);
-            ok = ok && (d1 > 0.0) && isfinite(d1);
-            const double i1 = rsqrt_newton(d1);
-            const double l21 = fma(-l20, l10, P21) * i1, l31 = fma(-l30, l10, P31) * i1;
-            const double d2 = fma(-l21, l21, fma(-l20, l20, P22));
-            ok = ok && (d2 > 0.0) && isfinite(d2);
-            const double i2 = rsqrt_newton(d2);
-            const double l32 = fma(-l31, l21, fma(-l30, l20, P32)) * i2;
-            const double d3 = fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, P33)));
-            ok = ok && (d3 > 0.0) && isfinite(d3);
-            const double i3 = rsqrt_newton(d3);
-            if (!ok) { failed = true; break; }          // uniform: same values in every thread
-            // M = Lp^-1 (lower triangular); this lane needs row lk of it
-            const double M10 = -(l10 * i0) * i1;
-            const double M20 = -fma(l21, M10, l20 * i0) * i2, M21 = -(l21 * i1) * i2;
-            const double M30 = -fma(l32, M20, fma(l31, M10, l30 * i0)) * i3, M31 = -fma(l32, M21, l31 * i1) * i3, M32 = -(l32 * i2) * i3;
-            const double m0 = lk == 0 ? i0 : lk == 1 ? M10 : lk == 2 ? M20 : M30;
-            const double m1 = lk == 0 ? 0.0 : lk == 1 ? i1 : lk == 2 ? M21 : M31;
-            const double m2 = lk < 2 ? 0.0 : lk == 2 ? i2 : M32;
-            const double m3 = lk < 3 ? 0.0 : i3;
-#ifdef LBA_STEP_TIMING
-            if (threadIdx.x == 0 && m3 == 12345.678) d_tile_prof[7] += 1;      // (keeps the pivot chain ahead of the tick)
-#endif
-            LBA_TTICK(3)
-            // independent FMA trees the scheduler can interleave, the MFMAs back to back after them
-            double au = fma(m1, c1u, m0 * c0u) + fma(m3, c3u, m2 * c2u);
-            au = (r_u > j0 + 3) ? -au : 0.0;
-            double vb[4], xb[4];
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int c = tx + 16 * b;
-                if (b >= ja) {      // columns right of the pivot group belong to L:  L -= U V^T
-                    vb[b] = fma(m1, cv[b][1], m0 * cv[b][0]) + fma(m3, cv[b][3], m2 * cv[b][2]);
-                    if (b == ja && c <= j0 + 3) vb[b] = 0.0;
-                }
-                if (b <= ja)        // the others to X:  X -= U Xn, and the pivot rows of X become Xn
-                    xb[b] = fma(m1, rv[b][1], m0 * rv[b][0]) + fma(m3, rv[b][3], m2 * rv[b][2]);
-            }
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int c = tx + 16 * b;
-                if (b >= ja) Lacc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, vb[b], Lacc[b], 0, 0, 0);
-                if (b <= ja) {
-                    const double xop = (b == ja && c > j0 + 3) ? 0.0 : xb[b];
-                    Xacc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, xop, Xacc[b], 0, 0, 0);
-                    if (own_rows) Xacc[b][ja] = xb[b];      // X[j0 + lk][c] = Xn[lk][c]
-                }
-            }
-        }
-    }
-    LBA_TTICK(0)
-    if (failed) return false;
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int r = ty + 16 * a, c = tx + 16 * b;
-            if (r < nb && c < nb) Li[r * NB + c] = (c <= r) ? Xacc[b][a] : 0.0;
-        }
-    return true;
-}
-
-// (Measured, round 2, per 60-column block: register-tile VALU updates with 16 x 16 threads 19.4 us; the same with 32 x 32 threads
-// and 2 x 2 tiles 26.1 us; this MFMA form 18.7 us.  The step is bound by its dependent chain -- barrier, pivot loads, four pivots
-// of rsqrt + two Newton steps at ~15 clocks per dependent v_fma_f64 (tools/probes/f64_rates.hip) -- not by f64 issue.
-// EIGHT columns per barrier (8 x 8 pivot block and its inverse replicated in every thread, two MFMA k-steps per update) was built
-// and is bit-compatible, but slower: 29 us per block against 22 -- the replicated pivot algebra grows with the cube of the group
-// width and outweighs the publish / barrier / operand rounds it saves.  Per 4-column group (tools/lba_step_timing.py): operands +
-// MFMA 1400-1700 cycles, pivot block + M 1000-1300, publish 475, barrier 290.)
-__device__ __forceinline__ void chol_diag_body(const double* __restrict__ S, int n, int k0, int nb,
-                                                   double* __restrict__ Linv, double* __restrict__ scal, const int bx)
-{
-    __shared__ CholVec4 sv;
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    double Lr[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int r = ty + 16 * a, c = tx + 16 * b;
-            Lr[a][b] = (r < nb && c < nb) ? S[(size_t)(k0 + r) * n + k0 + c] : ((r == c) ? 1.0 : 0.0);
-        }
-    if (!chol_tile_mfma(Lr, nb, Linv + (size_t)(k0 / NB) * NB * NB, sv) && tid == 0) scal[5] = 1.0;
-}
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_chol_diag(const double* __restrict__ S, int n, int k0, int nb,
-                                                   double* __restrict__ Linv, double* __restrict__ scal)
-{
-    chol_diag_body(S, n, k0, nb, Linv, scal, (int)blockIdx.x);
-}
-
-// One launch per block column K (instead of panel + update + the next diagonal factorisation): the workgroup of trailing
-// tile (bi, bj), K < bj <= bi, recomputes the two panel blocks it needs, X_i = A_iK Linv_K^T and X_j (a 60^3 product each --
-// cheaper than a launch), applies T_ij -= X_i X_j^T to its register tile, and the workgroup of tile (K+1, K+1) goes straight
-// on to factor and invert it, while the other tiles are still being updated.  The tiles of block column K+1 also store their
-// X_i (= L_iK) into a second (n+1) x n buffer Lp, which the substitution kernel then reads.  The right-hand side (row n of the (n+1) x n buffer) rides along as a 61st row of the last block row.
-#ifdef LBA_STEP_TIMING       // phase times (wall clock ticks, 100 MHz) of the factoring workgroup of k_chol_step, summed (tools/lba_step_timing.py)
-__device__ unsigned long long d_step_prof[8];
-#define LBA_STICK(k) if (bi == K + 1 && bj == K + 1 && threadIdx.x == 0) { const unsigned long long t_now = wall_clock64(); d_step_prof[k] += t_now - t_prev; t_prev = t_now; }
-#else
-#define LBA_STICK(k)
-#endif
-constexpr int kFusedMaxBlocks = 8;       // up to 480 reduced unknowns (80 key frames); larger systems keep panel / update launches
-static_assert(NB + 16 * 28 >= kFusedMaxBlocks * NB, "k_chol_solve<true> prefetches at most 28 rows per row group");
-constexpr int kStepLds = (NB * (NB + 1) + 2 * 64 * (NB + 1)) * 8 + (int)sizeof(CholVec4);
-// workgroups of one flow-factorisation launch (k_chol_flow_b, ki_chol_flow) that are resident at once: kStepLds (100 KB of LDS)
-// allows one per CU, and every workgroup of such a launch may wait on others, so all of them must be resident
-constexpr int kMaxFlowGroups = 240;
-__device__ __forceinline__ void chol_step_body(double* __restrict__ S, double* __restrict__ Lp, int n, int K, int nblk,
-                                                   double* __restrict__ Linv, double* __restrict__ scal, const int bx, double* __restrict__ sm_step)
-{
-    constexpr int P = NB + 1;
-    double* sI = sm_step;
-    double* sXi = sI + NB * P;
-    double* sXj = sXi + 64 * P;
-    CholVec4& sv = *(CholVec4*)(sXj + 64 * P);
-    if (scal[5] != 0.0) return;         // an earlier diagonal block was not positive definite
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    int li = 0, t = bx;
-    while (t > li) { t -= li + 1; li++; }
-    const int bi = K + 1 + li, bj = K + 1 + t;
-    const bool diag_tile = bi == bj;
-    const int k0 = K * NB;                                              // block K is a full one (it is not the last)
-    const int r0 = bi * NB, nri = min(NB, n - r0) + (bi == nblk - 1 ? 1 : 0);       // + the right-hand-side row
-    const int c0 = bj * NB, ncj = min(NB, n - c0);
-    const double* Lk = Linv + (size_t)K * NB * NB;
-#ifdef LBA_STEP_TIMING
-    unsigned long long t_prev = wall_clock64();
-#endif
-    {
-        // staging: all loads of a thread are issued before the first LDS store (16-byte loads; n = 6 * poses is even and
-        // every row segment starts at an even column, so the double2 accesses are aligned)
-        constexpr int H = NB / 2, kIt = (64 * H + 255) / 256;          // 30 double2 per row, 8 rounds
-        double2 vI[kIt], vA[kIt], vB[kIt];
-#pragma unroll
-        for (int it = 0; it < kIt; it++) {
-            const int i = tid + 256 * it, r = i / H, q2 = i - r * H;
-            vI[it] = make_double2(0.0, 0.0); vA[it] = vI[it]; vB[it] = vI[it];
-            if (r < NB) vI[it] = *(const double2*)(Lk + r * NB + 2 * q2);
-            if (r < nri) vA[it] = *(const double2*)(S + (size_t)(r0 + r) * n + k0 + 2 * q2);
-            if (!diag_tile && r < ncj) vB[it] = *(const double2*)(S + (size_t)(c0 + r) * n + k0 + 2 * q2);
-        }
-#pragma unroll
-        for (int it = 0; it < kIt; it++) {
-            const int i = tid + 256 * it, r = i / H, q2 = i - r * H;
-            if (r < NB) { sI[r * P + 2 * q2] = vI[it].x; sI[r * P + 2 * q2 + 1] = vI[it].y; }
-            if (r < 64) {
-                sXi[r * P + 2 * q2] = vA[it].x; sXi[r * P + 2 * q2 + 1] = vA[it].y;
-                sXj[r * P + 2 * q2] = vB[it].x; sXj[r * P + 2 * q2 + 1] = vB[it].y;
-            }
-        }
-    }
-    __syncthreads();
-    LBA_STICK(0)
-    // X = A Linv^T, X[r][c] = sum_{q <= c} A[r][q] Linv[c][q], on the f64 matrix pipe (v_mfma_f64_16x16x4: lane l feeds
-    // A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15], 1/8 of the LDS bytes of a register-blocked VALU product).  Wave w owns
-    // rows 16w .. 16w+15 (it reads and overwrites only those, so the product is done in place); column block C needs the
-    // k-steps up to its last column only (Linv is lower triangular).
-    {
-        const int wv = tid >> 6, ln = tid & 63, lr = ln & 15, lk = ln >> 4;
-        mfma_d4 xa[4], xb[4];
-#pragma unroll
-        for (int C = 0; C < 4; C++) { xa[C] = mfma_d4{0.0, 0.0, 0.0, 0.0}; xb[C] = xa[C]; }
-        const double* pa = sXi + (16 * wv + lr) * P + lk;
-        const double* pb = sXj + (16 * wv + lr) * P + lk;
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ks++) {
-            const double av = pa[4 * ks];
-            const double bv = diag_tile ? 0.0 : pb[4 * ks];
-#pragma unroll
-            for (int C = 0; C < 4; C++) {
-                if (ks >= 4 * C + 4) continue;              // compile-time: above the diagonal of Linv
-                const int c = 16 * C + lr;
-                const double lv = (c < NB) ? sI[c * P + 4 * ks + lk] : 0.0;
-                xa[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, lv, xa[C], 0, 0, 0);
-                if (!diag_tile) xb[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv, lv, xb[C], 0, 0, 0);
-            }
-        }
-        // results: lane l, component i = row (l >> 4) + 4 i, column l & 15 of the 16 x 16 block
-#pragma unroll
-        for (int C = 0; C < 4; C++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int c = 16 * C + lr;
-                if (c < NB) {
-                    sXi[(16 * wv + lk + 4 * i) * P + c] = xa[C][i];
-                    if (!diag_tile) sXj[(16 * wv + lk + 4 * i) * P + c] = xb[C][i];
-                }
-            }
-    }
-    __syncthreads();
-    LBA_STICK(1)
-    if (bj == K + 1) {      // this tile's X_i is L_iK: keep it -- in Lp, because the other tiles of this block row still read A_iK from S
-        for (int i = tid; i < nri * NB; i += 256) { const int r = i / NB, q = i - r * NB; Lp[(size_t)(r0 + r) * n + k0 + q] = sXi[r * P + q]; }
-    }
-    LBA_STICK(2)
-    const double* sB = diag_tile ? sXi : sXj;
-    double Lr[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int r = ty + 16 * a, c = tx + 16 * b;
-            Lr[a][b] = (r < nri && c < ncj) ? S[(size_t)(r0 + r) * n + c0 + c] : 0.0;
-        }
-    LBA_STICK(3)
-    {
-        // T -= X_i X_j^T on the matrix pipe.  Wave w feeds the 16 rows its threads own (local row m = global row
-        // 4w + (m & 3) + 16 (m >> 2)), so component i of column block C of the result IS this thread's element (ty + 16 i, tx + 16 C).
-        const int wv = tid >> 6, ln = tid & 63, lr = ln & 15, lk = ln >> 4;
-        const double* pa = sXi + (4 * wv + (lr & 3) + 16 * (lr >> 2)) * P + lk;
-        const double* pb = sB + lr * P + lk;
-        mfma_d4 acc[4];
-#pragma unroll
-        for (int C = 0; C < 4; C++) acc[C] = mfma_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ks++) {
-            const double av = pa[4 * ks];
-#pragma unroll
-            for (int C = 0; C < 4; C++) acc[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[16 * C * P + 4 * ks], acc[C], 0, 0, 0);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) Lr[a][b] -= acc[b][a];
-    }
-    LBA_STICK(4)
-    const bool factor_here = diag_tile && bi == K + 1;
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int r = ty + 16 * a, c = tx + 16 * b;
-            const bool live = r < nri && c < ncj && (!diag_tile || c <= r);
-            // the tile that is factored next stays in registers, except a right-hand-side row riding along with it
-            if (live && (!factor_here || r >= ncj)) S[(size_t)(r0 + r) * n + c0 + c] = Lr[a][b];
-            if (factor_here && (r >= ncj || c >= ncj)) Lr[a][b] = (r == c) ? 1.0 : 0.0;
-        }
-    LBA_STICK(5)
-    if (factor_here) {
-        if (!chol_tile_mfma(Lr, ncj, Linv + (size_t)bi * NB * NB, sv) && tid == 0) scal[5] = 1.0;
-    }
-    LBA_STICK(6)
-#ifdef LBA_STEP_TIMING
-    if (bi == K + 1 && bj == K + 1 && threadIdx.x == 0) d_step_prof[7] += 1;
-#endif
-}
-
-// ---- the whole factorisation in ONE launch (round 3): a workgroup per lower-triangle tile (r, c) of the block matrix ----
-// k_chol_diag + k_chol_step x (nblk - 1) is a chain of launches whose critical path is the factoring workgroup of every block
-// column; between two of them lie a launch boundary, a tile write-back and a tile load.  Here tile (r, c) is ONE workgroup
-// for its whole life: it loads its tile into registers once, and for K = 0 .. c-1 waits until block column K is factored
-// (flag fac[K]) and the tiles (r, K), (c, K) are final (flags done[.][K]), recomputes the two panel blocks X_r = A_rK Linv_K^T,
-// X_c (as k_chol_step does), applies T -= X_r X_c^T in registers, and at the end either factors and inverts its tile (r == c,
-// publishes fac[c]) or writes it back (publishes done[r][c]).  The panel inputs of a step are final long before the pivot block
-// they wait for, so everything except [load Linv_K, panel product, update] is off the critical path.
-// Synchronisation between workgroups (other CUs, other XCDs): producer stores, workgroup barrier, thread 0: agent-scope
-// release fence + flag store; consumer thread 0: agent-scope spin on the flag, acquire fence, workgroup barrier, plain loads
-// (MI355X_MICROARCH.md, correctness boundaries).  Flags carry the EPOCH of the trial (no reset between trials).  A workgroup
-// only waits for workgroups of smaller linear index (column-major tile order), so the grid cannot deadlock as long as every XCD
-// starts its workgroups in index order; the launch sites keep the grid within what is resident at once anyway.  Every spin is
-// bounded and also watches the failure flag (a pivot block that is not positive definite ends the factorisation for everybody).
-constexpr int kFlowFlags = kFusedMaxBlocks + kFusedMaxBlocks * kFusedMaxBlocks;
-__device__ __forceinline__ bool flow_wait(const unsigned* flag, unsigned epoch, double* scal)
-{
-    __shared__ int s_ok;
-    if (threadIdx.x == 0) {
-        int ok = 0;
-        for (int spin = 0; spin < (1 << 21); spin++) {
-            if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) { ok = 1; break; }
-            if (__longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(scal + 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0.0) break;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (!ok && __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(scal + 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0.0)
-            __hip_atomic_store((unsigned long long*)(scal + 5), (unsigned long long)__double_as_longlong(2.0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // timed out
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        s_ok = ok;
-    }
-    __syncthreads();
-    const bool r = s_ok != 0;
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ void flow_publish(unsigned* flag, unsigned epoch)
-{
-    __syncthreads();                // every thread's stores of the tile / the inverted block are issued and counted
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__device__ __forceinline__ void chol_flow_body(double* __restrict__ S, double* __restrict__ Lp, int n, int nblk, double* __restrict__ Linv,
-                                               double* __restrict__ scal, unsigned* __restrict__ flow, unsigned epoch, const int bx, double* __restrict__ sm_step)
-{
-    constexpr int P = NB + 1;
-    double* sI = sm_step;
-    double* sXi = sI + NB * P;
-    double* sXj = sXi + 64 * P;
-    CholVec4& sv = *(CholVec4*)(sXj + 64 * P);
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    // column-major tile order: (0,0) (1,0) .. (nblk-1,0) (1,1) (2,1) ..
-    int c = 0, t = bx;
-    while (t >= nblk - c) { t -= nblk - c; c++; }
-    const int r = c + t;
-    unsigned* fac = flow;
-    unsigned* done = flow + kFusedMaxBlocks;
-    const bool diag_tile = r == c;
-    const int r0 = r * NB, nri = min(NB, n - r0) + (r == nblk - 1 ? 1 : 0);         // + the right-hand-side row
-    const int c0 = c * NB, ncj = min(NB, n - c0);
-    if (!diag_tile && c == 0) return;        // the tiles of block column 0 are final as they are: nothing to do, nothing to publish
-    // the tile, in registers for the workgroup's whole life
-    double Lr[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int rr = ty + 16 * a, cc = tx + 16 * b;
-            Lr[a][b] = (rr < nri && cc < ncj) ? S[(size_t)(r0 + rr) * n + c0 + cc] : 0.0;
-        }
-    for (int K = 0; K < c; K++) {
-        const int k0 = K * NB;
-        // the panel inputs A_rK, A_cK: final once the workgroups (r, K), (c, K) are done (block column 0: from the start)
-        if (K > 0) {
-            if (!flow_wait(done + r * kFusedMaxBlocks + K, epoch, scal)) return;
-            if (!diag_tile && !flow_wait(done + c * kFusedMaxBlocks + K, epoch, scal)) return;
-        }
-        {
-            constexpr int H = NB / 2, kIt = (64 * H + 255) / 256;
-            double2 vA[kIt], vB[kIt];
-#pragma unroll
-            for (int it = 0; it < kIt; it++) {
-                const int i = tid + 256 * it, rr = i / H, q2 = i - rr * H;
-                vA[it] = make_double2(0.0, 0.0); vB[it] = vA[it];
-                if (rr < nri) vA[it] = *(const double2*)(S + (size_t)(r0 + rr) * n + k0 + 2 * q2);
-                if (!diag_tile && rr < ncj) vB[it] = *(const double2*)(S + (size_t)(c0 + rr) * n + k0 + 2 * q2);
-            }
-#pragma unroll
-            for (int it = 0; it < kIt; it++) {
-                const int i = tid + 256 * it, rr = i / H, q2 = i - rr * H;
-                if (rr < 64) {
-                    sXi[rr * P + 2 * q2] = vA[it].x; sXi[rr * P + 2 * q2 + 1] = vA[it].y;
-                    sXj[rr * P + 2 * q2] = vB[it].x; sXj[rr * P + 2 * q2 + 1] = vB[it].y;
-                }
-            }
-        }
-        // the inverted pivot block of column K: the critical wait
-        if (!flow_wait(fac + K, epoch, scal)) return;
-        {
-            constexpr int H = NB / 2, kIt = (NB * H + 255) / 256;
-            const double* Lk = Linv + (size_t)K * NB * NB;
-            double2 vI[kIt];
-#pragma unroll
-            for (int it = 0; it < kIt; it++) {
-                const int i = tid + 256 * it, rr = i / H, q2 = i - rr * H;
-                vI[it] = make_double2(0.0, 0.0);
-                if (rr < NB) vI[it] = *(const double2*)(Lk + rr * NB + 2 * q2);
-            }
-#pragma unroll
-            for (int it = 0; it < kIt; it++) {
-                const int i = tid + 256 * it, rr = i / H, q2 = i - rr * H;
-                if (rr < NB) { sI[rr * P + 2 * q2] = vI[it].x; sI[rr * P + 2 * q2 + 1] = vI[it].y; }
-            }
-        }
-        __syncthreads();
-        // X = A Linv^T on the f64 matrix pipe, in place (as k_chol_step)
-        {
-            const int wv = tid >> 6, ln = tid & 63, lr = ln & 15, lk = ln >> 4;
-            mfma_d4 xa[4], xb[4];
-#pragma unroll
-            for (int C = 0; C < 4; C++) { xa[C] = mfma_d4{0.0, 0.0, 0.0, 0.0}; xb[C] = xa[C]; }
-            const double* pa = sXi + (16 * wv + lr) * P + lk;
-            const double* pb = sXj + (16 * wv + lr) * P + lk;
-#pragma unroll
-            for (int ks = 0; ks < NB / 4; ks++) {
-                const double av = pa[4 * ks];
-                const double bv = diag_tile ? 0.0 : pb[4 * ks];
-#pragma unroll
-                for (int C = 0; C < 4; C++) {
-                    if (ks >= 4 * C + 4) continue;
-                    const int cc = 16 * C + lr;
-                    const double lv = (cc < NB) ? sI[cc * P + 4 * ks + lk] : 0.0;
-                    xa[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, lv, xa[C], 0, 0, 0);
-                    if (!diag_tile) xb[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv, lv, xb[C], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int C = 0; C < 4; C++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int cc = 16 * C + lr;
-                    if (cc < NB) {
-                        sXi[(16 * wv + lk + 4 * i) * P + cc] = xa[C][i];
-                        if (!diag_tile) sXj[(16 * wv + lk + 4 * i) * P + cc] = xb[C][i];
-                    }
-                }
-        }
-        __syncthreads();
-        if (c == K + 1) {       // this tile's X_r is L_rK: the substitution kernel reads it from Lp
-            for (int i = tid; i < nri * NB; i += 256) { const int rr = i / NB, q = i - rr * NB; Lp[(size_t)(r0 + rr) * n + k0 + q] = sXi[rr * P + q]; }
-        }
-        const double* sB = diag_tile ? sXi : sXj;
-        {
-            const int wv = tid >> 6, ln = tid & 63, lr = ln & 15, lk = ln >> 4;
-            const double* pa = sXi + (4 * wv + (lr & 3) + 16 * (lr >> 2)) * P + lk;
-            const double* pb = sB + lr * P + lk;
-            mfma_d4 acc[4];
-#pragma unroll
-            for (int C = 0; C < 4; C++) acc[C] = mfma_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int ks = 0; ks < NB / 4; ks++) {
-                const double av = pa[4 * ks];
-#pragma unroll
-                for (int C = 0; C < 4; C++) acc[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[16 * C * P + 4 * ks], acc[C], 0, 0, 0);
-            }
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) Lr[a][b] -= acc[b][a];
-        }
-        __syncthreads();                // sXi / sXj are free for the next block column
-    }
-    if (!diag_tile) {
-        // final A_rc (the panel input of block column c for the tiles to its right)
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int rr = ty + 16 * a, cc = tx + 16 * b;
-                if (rr < nri && cc < ncj) S[(size_t)(r0 + rr) * n + c0 + cc] = Lr[a][b];
-            }
-        flow_publish(done + r * kFusedMaxBlocks + c, epoch);
-        return;
-    }
-    // diagonal tile: a right-hand-side row riding along goes back to S (the substitution reads it there), then factor + invert
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int rr = ty + 16 * a, cc = tx + 16 * b;
-            if (rr < nri && cc < ncj && rr >= ncj) S[(size_t)(r0 + rr) * n + c0 + cc] = Lr[a][b];
-            if (rr >= ncj || cc >= ncj) Lr[a][b] = (rr == cc) ? 1.0 : 0.0;
-        }
-    if (!chol_tile_mfma(Lr, ncj, Linv + (size_t)c * NB * NB, sv)) {
-        if (tid == 0) __hip_atomic_store((unsigned long long*)(scal + 5), (unsigned long long)__double_as_longlong(1.0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;                         // (the waiters watch the failure flag)
-    }
-    flow_publish(fac + c, epoch);
-}
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_chol_flow(double* __restrict__ S, double* __restrict__ Lp, int n, int nblk,
-                                                   double* __restrict__ Linv, double* __restrict__ scal, unsigned* __restrict__ flow, unsigned epoch)
-{
-    extern __shared__ __align__(16) double sm_step[];
-    chol_flow_body(S, Lp, n, nblk, Linv, scal, flow, epoch, (int)blockIdx.x, sm_step);
-}
-
-constexpr int kPanelRows = 64;
-// nr = n + 1: the right-hand side b_schur is stored right behind S in the reduce buffer, i.e. it IS row n of an
-// (n+1) x n row-major matrix; carrying it through panel/update as an extra row performs the forward substitution
-// y = L^-1 b for free.
-__global__ __launch_bounds__(1024) void k_chol_panel(double* __restrict__ S, int n, int nr, int k0, int nb, const double* __restrict__ Linv,
-                                                     const double* __restrict__ scal)
-{
-    constexpr int P = NB + 1;
-    __shared__ double sI[NB * P];
-    __shared__ double sA[kPanelRows * P];
-    if (scal[5] != 0.0) return;         // diagonal block was not positive definite
-    const int tid = threadIdx.x;
-    const int row0 = k0 + nb + blockIdx.x * kPanelRows;
-    const int nrows = min(kPanelRows, nr - row0);
-    const double* Li = Linv + (size_t)(k0 / NB) * NB * NB;
-    for (int i = tid; i < NB * NB; i += 1024) { const int r = i / NB, c = i - r * NB; sI[r * P + c] = (r < nb && c < nb) ? Li[r * NB + c] : 0.0; }
-    for (int i = tid; i < nrows * nb; i += 1024) { const int r = i / nb, c = i - r * nb; sA[r * P + c] = S[(size_t)(row0 + r) * n + k0 + c]; }
-    __syncthreads();
-    // X = A * Linv^T :  X[r][c] = sum_{q <= c} A[r][q] * Linv[c][q]   (Linv is stored with explicit zeros above the diagonal)
-    // thread = (row, group of 4 adjacent columns): 4 independent accumulators share every a[q] load
-    const int r = tid >> 4, cg = tid & 15;
-    if (r < nrows && cg < NB / 4) {
-        const double* a = sA + r * P;
-        const double* l0 = sI + (4 * cg) * P;
-        double acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-        const int qmax = min(nb, 4 * cg + 4);
-#pragma unroll 4
-        for (int q = 0; q < qmax; q++) {
-            const double aq = a[q];
-            acc0 += aq * l0[q]; acc1 += aq * l0[P + q]; acc2 += aq * l0[2 * P + q]; acc3 += aq * l0[3 * P + q];
-        }
-        double* out = S + (size_t)(row0 + r) * n + k0 + 4 * cg;
-        if (4 * cg < nb) out[0] = acc0;
-        if (4 * cg + 1 < nb) out[1] = acc1;
-        if (4 * cg + 2 < nb) out[2] = acc2;
-        if (4 * cg + 3 < nb) out[3] = acc3;
-    }
-}
-
-// trailing update S22 -= L21 L21^T (lower triangle), 32x32 tiles, panel rows staged in LDS
-__global__ __launch_bounds__(256) void k_chol_update(double* __restrict__ S, int n, int nr, int k0, int nb, const double* __restrict__ scal)
-{
-    __shared__ double sA[32 * (NB + 1)], sB[32 * (NB + 1)];
-    const int base = k0 + nb;
-    const int ti = blockIdx.y, tj = blockIdx.x;
-    if (tj > ti || scal[5] != 0.0) return;
-    const int r0 = base + ti * 32, c0 = base + tj * 32;
-    const int tid = threadIdx.x, P = NB + 1;
-    for (int i = tid; i < 32 * nb; i += 256) {
-        const int r = i / nb, q = i % nb;
-        sA[r * P + q] = (r0 + r < nr) ? S[(size_t)(r0 + r) * n + k0 + q] : 0.0;
-        sB[r * P + q] = (c0 + r < n) ? S[(size_t)(c0 + r) * n + k0 + q] : 0.0;
-    }
-    __syncthreads();
-    const int tr = tid / 32, tc = tid % 32;
-    for (int rr = tr; rr < 32; rr += 8) {
-        const int r = r0 + rr, c = c0 + tc;
-        if (r < nr && c < n && c <= r) {
-            double sv = 0;
-#pragma unroll 4
-            for (int q = 0; q < nb; q++) sv += sA[rr * P + q] * sB[tc * P + q];
-            S[(size_t)r * n + c] -= sv;
-        }
-    }
-}
-
-// x = L^-T y by block back-substitution with the inverted diagonal blocks (y = L^-1 b was produced by the factorisation
-// itself, see k_chol_panel); one 1024-thread workgroup, 16 row groups x 64 columns, coalesced along the columns.
-__device__ __forceinline__ double row16_sum(double v)          // sum over the 16 lanes of a DPP row (every lane gets it)
-{
-    v += __shfl_xor(v, 1, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 8, 16);
-    return v;
-}
-// PRE (the fused path, n <= 480): the L_JK rows of block K-1 are fetched into registers while block K is being processed, so the
-// serial sweep never waits for global memory.
-constexpr int kSolvePre = 28;       // rows below the first block of a 480-unknown system / 16 row groups, rounded up
-template <bool PRE>
-__device__ __forceinline__ void chol_solve_body(const double* __restrict__ S, int n, const double* __restrict__ Linv,
-                                                     const double* __restrict__ yin, const double* __restrict__ yin_last,
-                                                     double* __restrict__ x, const double* __restrict__ scal, int last_forward, const int bx, double* __restrict__ sm)
-{
-    constexpr int P = NB + 1;
-    double* y = sm;
-    double* t = sm + n;
-    double* part = t + 64;
-    double* sL = part + 16 * 64;
-    const int tid = threadIdx.x;
-    if (scal[5] != 0.0) { for (int i = tid; i < n; i += 1024) x[i] = 0.0; return; }
-    const int nblk = (n + NB - 1) / NB;
-    // fused factorisation: S = the L panels, yin = their right-hand-side row, yin_last = the updated b of the last block
-    for (int i = tid; i < n; i += 1024) y[i] = (last_forward && i >= (nblk - 1) * NB) ? yin_last[i] : yin[i];
-    const int g64 = tid >> 6, r64 = tid & 63;       // 16 groups x 64 rows
-    // backward sweep: x_K = Linv_KK^T (y_K - sum_{J>K} L_JK^T x_J); the inverted diagonal block is staged in LDS (its loads
-    // are in flight together with those of the L_JK rows)
-    double pre[PRE ? kSolvePre : 1];
-    double li[4];                       // the inverted diagonal block on its way to LDS (PRE: fetched one block ahead)
-    for (int K = nblk - 1; K >= 0; K--) {
-        const int k0 = K * NB, nb = min(NB, n - k0);
-        {
-            if (K == nblk - 1 || !PRE) {
-                const double* Li = Linv + (size_t)K * NB * NB;
-#pragma unroll
-                for (int it = 0; it < 4; it++) { const int i = tid + 1024 * it; li[it] = (i < NB * NB) ? Li[i] : 0.0; }
-            }
-            __syncthreads();            // y complete (first round) / previous block done with sL, t, part
-#pragma unroll
-            for (int it = 0; it < 4; it++) { const int i = tid + 1024 * it; if (i < NB * NB) { const int r = i / NB; sL[r * P + i - r * NB] = li[it]; } }
-        }
-        const int col = tid >> 4, sub = tid & 15;       // 16 lanes per column for the small matrix-vector products (row-wide reductions)
-        if (K == nblk - 1 && last_forward) {    // the fused factorisation stops at the last diagonal block: y = L^-1 b for that block
-            __syncthreads();
-            double sv = 0;
-            if (col < nb)
-                for (int q = sub; q <= col; q += 16) sv += y[k0 + q] * sL[col * P + q];
-            sv = row16_sum(sv);
-            __syncthreads();
-            if (col < nb && sub == 0) y[k0 + col] = sv;
-            __syncthreads();
-        }
-        {
-            double sv = 0;
-            if (PRE) {
-#pragma unroll
-                for (int j = 0; j < kSolvePre; j++) { const int q = k0 + nb + g64 + 16 * j; if (q < n) sv += pre[j] * y[q]; }
-            } else if (r64 < nb) {
-#pragma unroll 8
-                for (int q = k0 + nb + g64; q < n; q += 16) sv += S[(size_t)q * n + k0 + r64] * y[q];
-            }
-            part[g64 * 64 + r64] = sv;
-            if (PRE && K > 0) {         // rows k0 + g64 + 16 j of block column K-1 (a full block): in flight during the rest of this block
-                const double* Li = Linv + (size_t)(K - 1) * NB * NB;
-#pragma unroll
-                for (int it = 0; it < 4; it++) { const int i = tid + 1024 * it; li[it] = (i < NB * NB) ? Li[i] : 0.0; }
-#pragma unroll
-                for (int j = 0; j < kSolvePre; j++) {
-                    const int q = k0 + g64 + 16 * j;
-                    pre[j] = 0.0;
-                    if (q < n && r64 < NB) pre[j] = S[(size_t)q * n + (k0 - NB) + r64];
-                }
-            }
-        }
-        __syncthreads();
-        {
-            const double tot = row16_sum(part[sub * 64 + col]);
-            if (sub == 0 && col < nb) t[col] = y[k0 + col] - tot;
-        }
-        __syncthreads();
-        {
-            double sv = 0;
-            if (col < nb)
-                for (int q = col + sub; q < nb; q += 16) sv += sL[q * P + col] * t[q];
-            sv = row16_sum(sv);
-            if (sub == 0 && col < nb) y[k0 + col] = sv;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) x[i] = y[i];
-}
-template <bool PRE>
-__global__ __launch_bounds__(1024) void k_chol_solve(const double* __restrict__ S, int n, const double* __restrict__ Linv,
-                                                     const double* __restrict__ yin, const double* __restrict__ yin_last,
-                                                     double* __restrict__ x, const double* __restrict__ scal, int last_forward)
-{
-    extern __shared__ double sm[];      // y[n], t[64], part[16][64], Linv block [NB][NB + 1]
-    chol_solve_body<PRE>(S, n, Linv, yin, yin_last, x, scal, last_forward, (int)blockIdx.x, sm);
-}
-
 // ---- the trial's tail in two launches (round 3; it was four: substitution, k_backsub_update, k_errors, k_reduce) ----
 // (a) the substitution workgroup goes straight on to the trial poses: oplus of every pose and the pose part of the scale sum
 __device__ __forceinline__ void pose_update_tail(const Dev& d, double lambda, const double* __restrict__ bp_full,
@@ -1235,8 +520,7 @@ __global__ __launch_bounds__(1024) void k_chol_solve_update(const double* __rest
                                                             Dev d, double lambda, const double* __restrict__ bp_full,
                                                             const double* __restrict__ poses, double* __restrict__ poses_new)
 {
-    extern __shared__ double sm[];
-    if (n > 0) chol_solve_body<PRE>(S, n, Linv, yin, yin_last, d.x, scal, last_forward, 0, sm);
+    if (n > 0) chol::chol_solve_body<PRE>(S, n, Linv, yin, yin_last, d.x, scal, last_forward, 0, chol::sm_solve);
     pose_update_tail(d, lambda, bp_full, poses, poses_new);
 }
 
@@ -1246,10 +530,6 @@ __global__ __launch_bounds__(1024) void k_chol_solve_update(const double* __rest
 // the workgroup that finishes last sums the per-landmark partials in a fixed order and publishes the scalars to the host
 // (as k_reduce mode 1 did).
 constexpr int kUpdThreads = 256, kUpdLandmarks = kUpdThreads / 8;
-__device__ __forceinline__ void st_agent(double* p, double v)       // agent-scope store (reaches memory every XCD sees)
-{
-    __hip_atomic_store((unsigned long long*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ void update_errors_body(const Dev& d, double lambda, const double* __restrict__ pts,
                                                    const double* __restrict__ poses_new, double* __restrict__ pts_new,
                                                    double* __restrict__ hmap, unsigned long long seq, const int bx, const int n_blocks)
@@ -1325,12 +605,9 @@ __device__ __forceinline__ void update_errors_body(const Dev& d, double lambda, 
     if (tid == 0) s_ticket = __hip_atomic_fetch_add(d.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (s_ticket != (unsigned)(n_blocks - 1)) return;
-    auto ld = [](const double* p) {     // agent-scope load: never served from a cache that another XCD's store has not reached
-        return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    };
-    double a = 0, b = 0, c = 0;
-    for (int i = tid; i < d.nL; i += kUpdThreads) { a += ld(d.chi_part + i); c += ld(d.part + i); }
-    for (int i = tid; i < d.nP; i += kUpdThreads) b += ld(d.part + d.nL + i);
+    double a = 0, b = 0, c = 0;     // (agent-scope loads: never served from a cache that another XCD's store has not reached)
+    for (int i = tid; i < d.nL; i += kUpdThreads) { a += ld_agent(d.chi_part + i); c += ld_agent(d.part + i); }
+    for (int i = tid; i < d.nP; i += kUpdThreads) b += ld_agent(d.part + d.nL + i);
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); c += __shfl_xor(c, o); }
     if ((tid & 63) == 0) { s_a[tid >> 6] = a; s_b[tid >> 6] = b; s_c[tid >> 6] = c; }
     __syncthreads();
@@ -1418,7 +695,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (!(y.flags & kBwTrial)) return;
     const BWin& w = wins[blockIdx.y];
     if (w.d.n <= 0) return;
-    chol_diag_body(w.S, w.d.n, 0, min(NB, w.d.n), w.Linv, w.d.scal, 0);
+    chol::chol_diag_body(w.S, w.d.n, 0, min(chol::NB, w.d.n), w.Linv, w.d.scal, 0);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_chol_step_b(const BWin* __restrict__ wins, BDynAll dyn, int K)
 {
@@ -1428,7 +705,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const BWin& w = wins[blockIdx.y];
     const int T = w.nblk - 1 - K;
     if (T <= 0 || (int)blockIdx.x >= T * (T + 1) / 2) return;
-    chol_step_body(w.S, w.Lp, w.d.n, K, w.nblk, w.Linv, w.d.scal, (int)blockIdx.x, sm_step);
+    chol::chol_step_body(w.S, w.Lp, w.d.n, K, w.nblk, w.Linv, w.d.scal, (int)blockIdx.x, sm_step);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_chol_flow_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
@@ -1437,26 +714,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (!(y.flags & kBwTrial)) return;
     const BWin& w = wins[blockIdx.y];
     if (w.d.n <= 0 || (int)blockIdx.x >= w.nblk * (w.nblk + 1) / 2) return;
-    chol_flow_body(w.S, w.Lp, w.d.n, w.nblk, w.Linv, w.d.scal, w.flow, (unsigned)y.seq, (int)blockIdx.x, sm_step);
+    chol::chol_flow_body(w.S, w.Lp, w.d.n, w.nblk, w.Linv, w.d.scal, w.flow, (unsigned)y.seq, (int)blockIdx.x, sm_step);
 }
 __global__ __launch_bounds__(1024) void k_chol_solve_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
-    extern __shared__ double sm[];
     const BDyn y = dyn.w[blockIdx.y];
     if (!(y.flags & kBwTrial)) return;
     const BWin& w = wins[blockIdx.y];
     const int n = w.d.n;
     if (n <= 0) return;
-    chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, sm);
+    chol::chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, chol::sm_solve);
 }
 __global__ __launch_bounds__(1024) void k_chol_solve_update_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
-    extern __shared__ double sm[];
     const BDyn y = dyn.w[blockIdx.y];
     if (!(y.flags & kBwTrial)) return;
     const BWin& w = wins[blockIdx.y];
     const int n = w.d.n;
-    if (n > 0) chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, sm);
+    if (n > 0) chol::chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, chol::sm_solve);
     pose_update_tail(w.d, y.lambda, w.bpf, w.poses[y.cur], w.poses[1 - y.cur]);
 }
 __global__ __launch_bounds__(kUpdThreads) void k_update_errors_b(const BWin* __restrict__ wins, BDynAll dyn)
@@ -1520,9 +795,7 @@ struct lba_shard {
     bool lambda_added = false;
     double* d_chi2 = nullptr;
     uint8_t* d_depth = nullptr;
-    double* h_scal = nullptr;   // pinned, host-mapped and coherent [16]: [0..5] scalars, [8] sequence number of the last k_reduce
-    double* d_hmap = nullptr;   // the same buffer as the device sees it
-    unsigned long long seq = 0;
+    stage::HostScalars hs;      // [0..5] scalars, [8] sequence number of the last k_reduce / k_update_errors; a solver handle's shards take a view of its buffer
     int64_t reduce_len = 0;
     bool err_valid = false;
     bool err_current = false;           // d.err / d.rho0 belong to the accepted state poses[cur]
@@ -1550,7 +823,7 @@ struct lba_shard {
     // optional bump arena owned by an lba_solver (avoids ~40 hipMalloc/hipFree per LocalBundleAdjustment call)
     uint8_t* arena = nullptr;
     size_t arena_cap = 0, arena_off = 0, bytes_wanted = 0, upload_bytes = 0;
-    bool owns_stream = true, owns_hscal = true;
+    bool owns_stream = true;
     // optional pinned mirror of the arena's prefix (also the solver's): the problem arrays are packed there and go up in ONE
     // asynchronous copy instead of ~20 synchronous ones from pageable memory
     uint8_t* stage = nullptr;
@@ -1571,28 +844,21 @@ struct lba_shard {
         allocs.push_back(*p);
         return ORBX_OK;
     }
-#define LBA_TRY_RET(x) do { const int r_ = (x); if (r_) return r_; } while (0)
-    template <typename T>
-    int upload(const T** p, const std::vector<T>& v)
-    {
-        T* q;
-        int r = dalloc(&q, v.size());
-        if (r) return r;
-        if (!v.empty()) LBA_TRY_RET(put(q, v.data(), v.size() * sizeof(T)));
-        *p = q;
-        return ORBX_OK;
-    }
     template <typename T>
     int upload_raw(const T** p, const T* src, size_t count)
     {
         T* q;
         int r = dalloc(&q, count);
-        if (r) return r;
-        if (count) LBA_TRY_RET(put(q, src, count * sizeof(T)));
+        if (r || (count && (r = put(q, src, count * sizeof(T))))) return r;
         *p = q;
         return ORBX_OK;
     }
-    // host -> device: through the pinned mirror when the destination lies in the mirrored arena prefix (flushed by flush_stage)
+    template <typename T>
+    int upload(const T** p, const std::vector<T>& v) { return upload_raw(p, v.data(), v.size()); }
+    // host -> device: through the pinned mirror when the destination lies in the mirrored arena prefix (flushed by flush_stage).
+    // (liba_solver::stage / flush is NOT the same thing: everything a shard uploads is allocated first, so ONE copy of the arena's
+    // prefix carries it; an inertial window interleaves uploads with scratch, so it copies merged segments.  Sharing one of
+    // the two would change what goes over the bus.)
     int put(void* dst, const void* src, size_t bytes)
     {
         const uint8_t* d8 = (const uint8_t*)dst;
@@ -1631,14 +897,20 @@ static int shard_validate(const LbaProblem* p)
     return ORBX_OK;
 }
 
-struct lba_solver {
+struct lba_solver {                 // also a window slot of an lba_batch, with the batch's stream and a view of its scalars
     int device = 0;
     uint8_t* arena = nullptr;
     size_t arena_cap = 0;
     hipStream_t stream = nullptr;
-    double* h_scal = nullptr;
+    stage::HostScalars hs;
     uint8_t* stage = nullptr;       // pinned mirror of the arena prefix that holds the uploaded arrays
     size_t stage_cap = 0;
+    ~lba_solver()
+    {
+        if (arena) (void)hipFree(arena);
+        if (stage) (void)hipHostFree(stage);
+        hs.release();
+    }
 };
 
 extern "C" void lba_shard_destroy(lba_shard* s);
@@ -1665,23 +937,20 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
     int r = shard_validate(p);
-    if (r) return r;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (r || (r = stage::check_device(device))) return r;
     ORBX_HIP(hipSetDevice(device));
     lba_shard* s = new lba_shard();
     s->device = device;
     if (owner) {
         s->arena = owner->arena; s->arena_cap = owner->arena_cap;
         s->stream = owner->stream; s->owns_stream = false;
-        s->h_scal = owner->h_scal; s->owns_hscal = false;
+        s->hs = owner->hs.view();
         s->stage = owner->stage; s->stage_cap = owner->stage_cap;
     }
     std::memset(&s->d, 0, sizeof(s->d));
     lba::Dev& d = s->d;
     static const bool build_timing = std::getenv("ORBX_LBA_TIMING") != nullptr;
-    const auto tb0 = std::chrono::steady_clock::now();
+    const auto tb0 = stage::Clock::now();
     d.nPoses = p->n_poses; d.nL = p->n_points; d.nE = p->n_edges;
     std::vector<int> pose_col(p->n_poses, -1), col_pose;
     for (int i = 0; i < p->n_poses; i++) if (!p->pose_fixed[i]) { pose_col[i] = (int)col_pose.size(); col_pose.push_back(i); }
@@ -1694,7 +963,7 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     for (int c = 0; c < d.nP; c++) p_off[c + 1] += p_off[c];
     std::vector<int> l_edge(std::max(d.nE, 1)), p_edge(std::max(p_off[d.nP], 1)), lc(l_off.begin(), l_off.end() - 1), pc(p_off.begin(), p_off.end() - 1);
     for (int e = 0; e < d.nE; e++) { l_edge[lc[p->edge_point[e]]++] = e; const int c = pose_col[p->edge_pose[e]]; if (c >= 0) p_edge[pc[c]++] = e; }
-    const auto tb1 = std::chrono::steady_clock::now();
+    const auto tb1 = stage::Clock::now();
     // pair list per block (i <= j).  A landmark is seen at most once by a pose (one observation per key frame), so a block gets at most ONE
     // pair per landmark and its pairs stand in landmark order whatever the order inside a landmark: each landmark's (column, edge) list
     // is sorted by column once and only the a <= b half is walked (110 k steps for the bench window instead of two passes of 200 k with
@@ -1774,7 +1043,7 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
                 }
             }
     }
-    const auto tb2 = std::chrono::steady_clock::now();
+    const auto tb2 = stage::Clock::now();
     std::vector<double> poses(7 * (size_t)p->n_poses);
     for (int i = 0; i < p->n_poses; i++) {
         for (int k = 0; k < 4; k++) poses[7 * i + k] = p->pose_q[4 * i + k];
@@ -1800,35 +1069,23 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     LBA_TRY(s->dalloc(&s->poses[1], 7 * (size_t)p->n_poses)); LBA_TRY(s->dalloc(&s->pts[1], 3 * (size_t)d.nL));
     s->reduce_len = (int64_t)d.n * d.n + 3 * (int64_t)d.n;
     LBA_TRY(s->dalloc(&s->reduce, (size_t)s->reduce_len));
-    s->nblk = (d.n + lba::NB - 1) / lba::NB;
-    LBA_TRY(s->dalloc(&s->Linv, (size_t)std::max(s->nblk, 1) * lba::NB * lba::NB));
-    if (s->nblk <= lba::kFusedMaxBlocks) LBA_TRY(s->dalloc(&s->Lp, ((size_t)d.n + 1) * (size_t)std::max(d.n, 1)));
-    // (the dynamic-LDS limits of the factorisation / substitution kernels: once per device and process, not per window)
+    s->nblk = (d.n + chol::NB - 1) / chol::NB;
+    LBA_TRY(s->dalloc(&s->Linv, (size_t)std::max(s->nblk, 1) * chol::NB * chol::NB));
+    if (s->nblk <= chol::kFusedMaxBlocks) LBA_TRY(s->dalloc(&s->Lp, ((size_t)d.n + 1) * (size_t)std::max(d.n, 1)));
+    LBA_TRY(s->dalloc(&s->flow, (size_t)chol::kFlowFlags));
+    ORBX_HIP(hipMemsetAsync(s->flow, 0, chol::kFlowFlags * sizeof(unsigned), s->stream));
+    if (d.n > chol::kMaxUnknowns) LBA_TRY(fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the substitution kernel's LDS", d.n));
+    // (the dynamic-LDS limits for the largest system the check above lets through: once per device and process, not per window)
     static std::atomic<unsigned long long> attr_done{0};
-    const bool set_attr = !((attr_done.load() >> device) & 1ull);
-    if (set_attr) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_flow, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds));
+    if (!((attr_done.load() >> device) & 1ull)) {
+        LBA_TRY(chol::raise_lds_limits(chol::kMaxUnknowns));
+        LBA_TRY(chol::allow_lds(lba::k_chol_solve_update<true>, chol::solve_lds_bytes(chol::kMaxUnknowns)));
+        LBA_TRY(chol::allow_lds(lba::k_chol_solve_update<false>, chol::solve_lds_bytes(chol::kMaxUnknowns)));
+        attr_done.fetch_or(1ull << device);
     }
-    LBA_TRY(s->dalloc(&s->flow, (size_t)lba::kFlowFlags));
-    ORBX_HIP(hipMemsetAsync(s->flow, 0, lba::kFlowFlags * sizeof(unsigned), s->stream));
-    {
-        const size_t solve_lds = ((size_t)d.n + 64 + 16 * 64 + lba::NB * (lba::NB + 1)) * sizeof(double);
-        if (solve_lds > 160 * 1024) LBA_TRY(fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the substitution kernel's LDS", d.n));
-        if (set_attr) {     // (a limit, not an allocation: the largest system the check above lets through)
-            const int lim = 160 * 1024;
-            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            ORBX_HIP(hipFuncSetAttribute((const void*)lba::k_chol_solve_update<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            attr_done.fetch_or(1ull << device);
-        }
-    }
-    LBA_TRY(s->dalloc(&s->Ldiag, (size_t)lba::NB * lba::NB));
+    LBA_TRY(s->dalloc(&s->Ldiag, (size_t)chol::NB * chol::NB));
     LBA_TRY(s->dalloc(&s->d_chi2, (size_t)d.nE)); LBA_TRY(s->dalloc(&s->d_depth, (size_t)d.nE));
-    if (s->owns_hscal && hipHostMalloc((void**)&s->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { lba_shard_destroy(s); return fail(ORBX_ERR_HIP, "hipHostMalloc failed"); }
-    if (hipHostGetDevicePointer((void**)&s->d_hmap, s->h_scal, 0) != hipSuccess) { lba_shard_destroy(s); return fail(ORBX_ERR_HIP, "hipHostGetDevicePointer failed"); }
-    s->seq = *(const unsigned long long*)(s->h_scal + 8);      // a solver handle reuses the buffer across shards: continue its numbering
-    if (s->owns_hscal) { std::memset(s->h_scal, 0, 16 * sizeof(double)); s->seq = 0; }
+    if (!owner) LBA_TRY(s->hs.alloc());
     if (s->owns_stream && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { lba_shard_destroy(s); return fail(ORBX_ERR_HIP, "stream create failed"); }
 #undef LBA_TRY
     if ((r = s->put(s->poses[0], poses.data(), poses.size() * sizeof(double))) || (d.nL > 0 && (r = s->put(s->pts[0], p->points, 3 * (size_t)d.nL * sizeof(double)))) ||
@@ -1847,8 +1104,8 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
         ORBX_HIP(hipStreamSynchronize(s->stream));
     }
     if (build_timing) {
-        auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        std::fprintf(stderr, "[lba structure] CSR %.0f us, pair lists %.0f us, staging + enqueue %.0f us\n", us(tb0, tb1), us(tb1, tb2), us(tb2, std::chrono::steady_clock::now()));
+        std::fprintf(stderr, "[lba structure] CSR %.0f us, pair lists %.0f us, staging + enqueue %.0f us\n", 1e3 * stage::ms(tb0, tb1), 1e3 * stage::ms(tb1, tb2),
+                     1e3 * stage::ms(tb2, stage::Clock::now()));
     }
     *out = s;
     return ORBX_OK;
@@ -1858,15 +1115,15 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
 extern "C" int lba_debug_step_prof(unsigned long long* out8)
 {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(lba::d_step_prof), sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(lba::d_step_prof), z, sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
+    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(chol::d_step_prof), sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(chol::d_step_prof), z, sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
     return ORBX_OK;
 }
 extern "C" int lba_debug_tile_prof(unsigned long long* out8)
 {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(lba::d_tile_prof), sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(lba::d_tile_prof), z, sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
+    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(chol::d_tile_prof), sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(chol::d_tile_prof), z, sizeof(z)) != hipSuccess) return ORBX_ERR_HIP;
     return ORBX_OK;
 }
 #endif
@@ -1895,7 +1152,7 @@ void lba_shard_destroy(lba_shard* s)
     (void)hipSetDevice(s->device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); if (s->owns_stream) (void)hipStreamDestroy(s->stream); }
     for (void* p : s->allocs) (void)hipFree(p);
-    if (s->h_scal && s->owns_hscal) (void)hipHostFree(s->h_scal);
+    s->hs.release();
     for (hipEvent_t e : s->prof_ev) (void)hipEventDestroy(e);
     if (s->ev_fence) (void)hipEventDestroy(s->ev_fence);
     if (s->h_coll) (void)hipHostFree(s->h_coll);
@@ -1986,25 +1243,6 @@ int lba_shard_set_reduce_buffer(lba_shard* s, double* device_buffer)
     return ORBX_OK;
 }
 
-// The reduction kernels write their scalars into the host-mapped buffer h_scal[0..7] and then publish sequence number `seq` in
-// h_scal[8]: poll for it (a trial is a few hundred microseconds of kernels); after 20 ms fall back to a stream synchronisation,
-// which also surfaces faults.  Shared by the LocalBA drivers and liba_run (inertial_solver.inc).
-static int wait_scalars(const double* h_scal, unsigned long long seq, hipStream_t stream)
-{
-    const volatile unsigned long long* flag = (const volatile unsigned long long*)(h_scal + 8);
-    const auto t0 = std::chrono::steady_clock::now();
-    int spins = 0;
-    while (*flag != seq) {
-        if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-            ORBX_HIP(hipStreamSynchronize(stream));
-            if (*flag != seq) return fail(ORBX_ERR_INTERNAL, "reduction results did not arrive");
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return ORBX_OK;
-}
-
 // Optional: the lambda the first trial after the NEXT lba_shard_linearize will use (known from the second iteration on, or with a
 // user lambda).  The linearisation then also performs the landmark side of the Schur complement, saving a dependent launch.
 int lba_shard_hint_lambda(lba_shard* s, double lambda)
@@ -2037,14 +1275,14 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
     s->mark(lba::kStageIdle);
     if (!reuse) {
         s->mark(lba::kStageReduce);
-        hipLaunchKernelGGL(lba::k_reduce, dim3(1), dim3(1024), 0, s->stream, d, 0, s->d_hmap, ++s->seq);
+        hipLaunchKernelGGL(lba::k_reduce, dim3(1), dim3(1024), 0, s->stream, d, 0, s->hs.d, ++s->hs.seq);
         s->mark(lba::kStageIdle);
         ORBX_HIP(hipGetLastError());
-        int r = wait_scalars(s->h_scal, s->seq, s->stream);
+        int r = s->hs.wait(s->stream);
         if (r) return r;
-        s->chi_current = s->h_scal[0];
-        s->mdp_cached = s->h_scal[1];
-        s->mdl_cached = s->h_scal[2];
+        s->chi_current = s->hs.h[0];
+        s->mdp_cached = s->hs.h[1];
+        s->mdl_cached = s->hs.h[2];
     } else {
         ORBX_HIP(hipGetLastError());
     }
@@ -2091,28 +1329,12 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     s->mark(lba::kStageFactor);
     if (n > 0) {
         if (!s->lambda_added) hipLaunchKernelGGL(lba::k_add_lambda, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->S(), n, lambda);
-        const bool fused = s->nblk <= lba::kFusedMaxBlocks;
-        if (fused) {
-            // the whole factorisation as one launch: a workgroup per lower-triangle tile, flags between them (k_chol_flow)
-            hipLaunchKernelGGL(lba::k_chol_flow, dim3(s->nblk * (s->nblk + 1) / 2), dim3(256), lba::kStepLds, s->stream, s->S(), s->Lp, n, s->nblk, s->Linv, d.scal,
-                               s->flow, ++s->flow_epoch);
-        }
-        for (int K = 0; K < s->nblk && !fused; K++) {
-            const int k0 = K * lba::NB, nb = std::min(lba::NB, n - k0);
-            const int rows_below = (n + 1) - k0 - nb;       // includes the right-hand-side row n (always >= 1)
-            hipLaunchKernelGGL(lba::k_chol_diag, dim3(1), dim3(256), 0, s->stream, (const double*)s->S(), n, k0, nb, s->Linv, d.scal);
-            hipLaunchKernelGGL(lba::k_chol_panel, dim3((rows_below + lba::kPanelRows - 1) / lba::kPanelRows), dim3(1024), 0, s->stream,
-                               s->S(), n, n + 1, k0, nb, (const double*)s->Linv, (const double*)d.scal);
-            if (k0 + nb < n) {
-                const int t = (rows_below + 31) / 32;
-                hipLaunchKernelGGL(lba::k_chol_update, dim3(t, t), dim3(256), 0, s->stream, s->S(), n, n + 1, k0, nb, (const double*)d.scal);
-            }
-        }
+        chol::enqueue_factor(s->stream, s->S(), s->Lp, n, s->nblk, s->Linv, d.scal, s->flow, &s->flow_epoch);
     }
     s->mark(lba::kStageSolve);
     {
-        const bool fused = n > 0 && s->nblk <= lba::kFusedMaxBlocks;
-        const size_t solve_lds = ((size_t)n + 64 + 16 * 64 + lba::NB * (lba::NB + 1)) * sizeof(double);
+        const bool fused = n > 0 && s->nblk <= chol::kFusedMaxBlocks;
+        const size_t solve_lds = chol::solve_lds_bytes(n);
         if (fused || n == 0)
             hipLaunchKernelGGL(lba::k_chol_solve_update<true>, dim3(1), dim3(1024), solve_lds, s->stream, (const double*)s->Lp, n, (const double*)s->Linv,
                                (const double*)(s->Lp ? s->Lp + (size_t)n * n : nullptr), (const double*)s->bs(), (const double*)d.scal, 1, d, lambda, (const double*)s->bpf(), P, Pn);
@@ -2121,17 +1343,18 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
                                (const double*)s->bs(), (const double*)s->bs(), (const double*)d.scal, 0, d, lambda, (const double*)s->bpf(), P, Pn);
     }
     s->mark(lba::kStageUpdate);
-    hipLaunchKernelGGL(lba::k_update_errors, dim3(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1)), dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->d_hmap, ++s->seq);
+    hipLaunchKernelGGL(lba::k_update_errors, dim3(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1)), dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
     s->mark(lba::kStageIdle);
     ORBX_HIP(hipGetLastError());
-    int r = wait_scalars(s->h_scal, s->seq, s->stream);
+    int r = s->hs.wait(s->stream);
     if (r) return r;
-    s->chi_trial = s->h_scal[0];
+    const double* h = s->hs.h;
+    s->chi_trial = h[0];
     s->err_current = false;         // the error buffer now belongs to the trial state
-    if (chi2_local_new) *chi2_local_new = s->h_scal[0];
-    if (scale_poses) *scale_poses = s->h_scal[3];
-    if (scale_landmarks_local) *scale_landmarks_local = s->h_scal[4];
-    switch (lm::trial_status(s->h_scal[5])) {
+    if (chi2_local_new) *chi2_local_new = h[0];
+    if (scale_poses) *scale_poses = h[3];
+    if (scale_landmarks_local) *scale_landmarks_local = h[4];
+    switch (lm::trial_status(h[5])) {
     case lm::TrialStatus::kSolved: return 1;
     case lm::TrialStatus::kNotPositiveDefinite: return 0;
     default: return fail(ORBX_ERR_INTERNAL, "lba_shard_finish: the factorisation stalled (a spin wait between workgroups expired)");
@@ -2163,10 +1386,7 @@ int lba_shard_download(lba_shard* s, double* pose_q, double* pose_t, double* poi
     if (chi2_per_edge && d.nE > 0) ORBX_HIP(hipMemcpyAsync(chi2_per_edge, s->d_chi2, (size_t)d.nE * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (depth_positive && d.nE > 0) ORBX_HIP(hipMemcpyAsync(depth_positive, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, s->stream));
     ORBX_HIP(hipStreamSynchronize(s->stream));
-    for (int i = 0; i < d.nPoses; i++) {
-        if (pose_q) for (int k = 0; k < 4; k++) pose_q[4 * i + k] = poses[7 * (size_t)i + k];
-        if (pose_t) for (int k = 0; k < 3; k++) pose_t[3 * i + k] = poses[7 * (size_t)i + 4 + k];
-    }
+    stage::split_poses7(poses.data(), d.nPoses, pose_q, pose_t);
     return ORBX_OK;
 }
 
@@ -2263,17 +1483,14 @@ int lba_create(int device, lba_solver** out)
 {
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     lba_solver* s = new lba_solver();
     s->device = device;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipHostMalloc((void**)&s->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        delete s;
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || s->hs.alloc() != ORBX_OK) {
+        lba_destroy(s);
         return fail(ORBX_ERR_HIP, "stream / pinned buffer creation failed");
     }
-    std::memset(s->h_scal, 0, 16 * sizeof(double));
     *out = s;
     return ORBX_OK;
 }
@@ -2283,9 +1500,6 @@ void lba_destroy(lba_solver* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->arena) (void)hipFree(s->arena);
-    if (s->stage) (void)hipHostFree(s->stage);
-    if (s->h_scal) (void)hipHostFree(s->h_scal);
     delete s;
 }
 
@@ -2296,23 +1510,23 @@ int lba_solve(lba_solver* sv, const LbaProblem* problem, const volatile uint8_t*
     if (!sv) return fail(ORBX_ERR_ARG, "NULL solver");
     lba_shard* s = nullptr;
     static const bool timing = std::getenv("ORBX_LBA_TIMING") != nullptr;      // phase times of the call on stderr (tools/lba_prof.py)
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = stage::Clock::now();
     int r = shard_create_impl(sv->device, problem, &s, sv);
     if (r) return r;
-    const auto t_created = std::chrono::steady_clock::now();
+    const auto t_created = stage::Clock::now();
     s->sync_after_reduce = false;
     s->lambda_in_reduce = true;
     const size_t wanted = s->bytes_wanted, wanted_stage = s->upload_bytes;
     LbaStats st;
     r = lba_shard_optimize(s, nullptr, nullptr, 1, max_iters, lambda_init, stop_flag, &st);
-    const auto t_solved = std::chrono::steady_clock::now();
+    const auto t_solved = stage::Clock::now();
     if (!r) r = lba_shard_download(s, pose_q_out, pose_t_out, points_out, chi2_per_edge, depth_positive);
-    const auto t_down = std::chrono::steady_clock::now();
+    const auto t_down = stage::Clock::now();
     lba_shard_destroy(s);
     if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        using stage::ms;
         std::fprintf(stderr, "[lba_solve] structure + upload %.3f ms, %d iterations / %d trials %.3f ms, epilogue + download %.3f ms, destroy %.3f ms\n",
-                     ms(t_start, t_created), st.iterations, st.trials, ms(t_created, t_solved), ms(t_solved, t_down), ms(t_down, std::chrono::steady_clock::now()));
+                     ms(t_start, t_created), st.iterations, st.trials, ms(t_created, t_solved), ms(t_solved, t_down), ms(t_down, stage::Clock::now()));
     }
     solver_grow(sv, wanted, wanted_stage);
     if (stats_out) *stats_out = st;
@@ -2327,60 +1541,37 @@ int lba_solve(lba_solver* sv, const LbaProblem* problem, const volatile uint8_t*
 // (same kernel bodies, same order of operations -> bit-identical results); the host keeps one Levenberg controller
 // (lm_control.h) per window and a round is: [linearise the windows that start an iteration] + [one trial of every window that is not finished].
 // ---------------------------------------------------------------------------------------------------------------
-struct lba_batch {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct lba_batch : stage::Batch {       // its stream, the two events around the Levenberg rounds
     std::vector<lba_solver*> slots;     // arena + pinned staging per window slot (they grow to the windows they have seen)
     lba::BWin* d_wins = nullptr;
-    double* h_scal = nullptr;           // host-mapped, coherent: 16 doubles per slot
+    stage::HostScalars hs;              // 16 doubles per slot
     double last_device_ms = 0.0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t* h_out = nullptr;           // pinned staging of the results of all windows (one synchronisation per call)
-    size_t h_out_cap = 0;
+    stage::PinnedOut out;               // the results of all windows (one synchronisation per call)
+    ~lba_batch()
+    {
+        for (lba_solver* sv : slots) delete sv;
+        if (d_wins) (void)hipFree(d_wins);
+        hs.release();
+        out.release();
+    }
 };
 
 extern "C" {
 
 int lba_batch_create(int device, lba_batch** out)
 {
-    if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
-    ORBX_HIP(hipSetDevice(device));
-    lba_batch* b = new lba_batch();
-    b->device = device;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&b->h_scal, lba::kMaxBatch * 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipMalloc((void**)&b->d_wins, lba::kMaxBatch * sizeof(lba::BWin)) != hipSuccess ||
-        hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) {
-        lba_batch_destroy(b);
+    int r = stage::open(device, out);
+    if (r) return r;
+    lba_batch* b = *out;
+    if (b->hs.alloc(lba::kMaxBatch) != ORBX_OK || hipMalloc((void**)&b->d_wins, lba::kMaxBatch * sizeof(lba::BWin)) != hipSuccess) {
+        stage::close(b);
+        *out = nullptr;
         return fail(ORBX_ERR_HIP, "batch handle creation failed");
     }
-    std::memset(b->h_scal, 0, lba::kMaxBatch * 16 * sizeof(double));
-    *out = b;
     return ORBX_OK;
 }
 
-void lba_batch_destroy(lba_batch* b)
-{
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (lba_solver* sv : b->slots) {
-        if (sv->arena) (void)hipFree(sv->arena);
-        if (sv->stage) (void)hipHostFree(sv->stage);
-        delete sv;
-    }
-    if (b->d_wins) (void)hipFree(b->d_wins);
-    if (b->h_scal) (void)hipHostFree(b->h_scal);
-    if (b->h_out) (void)hipHostFree(b->h_out);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-}
+void lba_batch_destroy(lba_batch* b) { stage::close(b); }
 
 double lba_batch_last_device_ms(const lba_batch* b) { return b ? b->last_device_ms : 0.0; }
 
@@ -2394,7 +1585,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     const int W = n_windows;
     while ((int)b->slots.size() < W) {
         lba_solver* sv = new lba_solver();
-        sv->device = b->device; sv->stream = b->stream; sv->h_scal = b->h_scal + 16 * b->slots.size();
+        sv->device = b->device; sv->stream = b->stream; sv->hs = b->hs.view((int)b->slots.size());
         b->slots.push_back(sv);
     }
     std::vector<lba_shard*> sh((size_t)W, nullptr);
@@ -2409,40 +1600,26 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     std::vector<lba::BWin> hw((size_t)W);
     int max_lin = 1, max_e = 1, max_lm = 1, max_sb = 1, max_nblk = 1, max_upd = 1, max_n = 0;
     static const bool timing = std::getenv("ORBX_LBA_TIMING") != nullptr;
-    const auto t_start = std::chrono::steady_clock::now();
-    {
-        // structure build (CSR lists, pair lists) + upload of every window: host work, spread over threads (a window is ~0.3 ms)
-        const int n_thr = std::max(1, std::min({W, (int)std::thread::hardware_concurrency(), 16}));
-        std::vector<int> rcs((size_t)W, ORBX_OK);
-        std::atomic<int> next(0);
-        auto worker = [&]() {
-            (void)hipSetDevice(b->device);
-            for (int i = next.fetch_add(1); i < W; i = next.fetch_add(1)) rcs[i] = shard_create_impl(b->device, &problems[i], &sh[i], b->slots[i]);
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < n_thr; t++) th.emplace_back(worker);
-        worker();
-        for (auto& t : th) t.join();
-        for (int i = 0; i < W; i++) if (rcs[i] && !r) r = fail(rcs[i], "window %d could not be set up (code %d; the worker thread holds the detailed message)", i, rcs[i]);
-    }
-    const auto t_created = std::chrono::steady_clock::now();
+    const auto t_start = stage::Clock::now();
+    // structure build (CSR lists, pair lists) + upload of every window
+    r = stage::for_each_window(W, b->device, [&](int i) { return shard_create_impl(b->device, &problems[i], &sh[i], b->slots[i]); });
+    const auto t_created = stage::Clock::now();
     for (int i = 0; i < W && !r; i++) {
         lba_shard* s = sh[i];
         wanted[i] = s->bytes_wanted; wanted_stage[i] = s->upload_bytes;
-        if (s->nblk > lba::kFusedMaxBlocks) { r = fail(ORBX_ERR_CAPACITY, "window %d has %d reduced unknowns: the batched path takes at most %d (use lba_solve)", i, s->d.n, lba::kFusedMaxBlocks * lba::NB); break; }
+        if (s->nblk > chol::kFusedMaxBlocks) { r = fail(ORBX_ERR_CAPACITY, "window %d has %d reduced unknowns: the batched path takes at most %d (use lba_solve)", i, s->d.n, chol::kFusedMaxBlocks * chol::NB); break; }
         lba::BWin& w = hw[i];
         w.d = s->d; w.poses[0] = s->poses[0]; w.poses[1] = s->poses[1]; w.pts[0] = s->pts[0]; w.pts[1] = s->pts[1];
-        w.S = s->S(); w.bs = s->bs(); w.bpf = s->bpf(); w.diag = s->diag(); w.Lp = s->Lp; w.Linv = s->Linv; w.hmap = s->d_hmap; w.flow = s->flow; w.nblk = s->nblk;
+        w.S = s->S(); w.bs = s->bs(); w.bpf = s->bpf(); w.diag = s->diag(); w.Lp = s->Lp; w.Linv = s->Linv; w.hmap = s->hs.d; w.flow = s->flow; w.nblk = s->nblk;
         const lba::Dev& d = s->d;
         max_lin = std::max(max_lin, d.nP + (d.nL + 31) / 32); max_e = std::max(max_e, (d.nE + 255) / 256); max_lm = std::max(max_lm, (d.nL + 7) / 8);
         max_sb = std::max(max_sb, d.nBlocks + d.nP); max_nblk = std::max(max_nblk, s->nblk); max_upd = std::max(max_upd, (d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks);
         max_n = std::max(max_n, d.n);
     }
     if (r) { cleanup(); return r; }
-    const size_t solve_lds = ((size_t)max_n + 64 + 16 * 64 + lba::NB * (lba::NB + 1)) * sizeof(double);
-    if (hipFuncSetAttribute((const void*)lba::k_chol_step_b, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)lba::k_chol_flow_b, hipFuncAttributeMaxDynamicSharedMemorySize, lba::kStepLds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)lba::k_chol_solve_update_b, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(solve_lds, (size_t)65536)) != hipSuccess ||
+    const size_t solve_lds = chol::solve_lds_bytes(max_n);      // (<= kFusedSolveLds: the windows are on the fused path)
+    if (chol::allow_lds(lba::k_chol_step_b, chol::kStepLds) || chol::allow_lds(lba::k_chol_flow_b, chol::kStepLds) ||
+        chol::allow_lds(lba::k_chol_solve_update_b, chol::kFusedSolveLds) ||
         hipMemcpyAsync(b->d_wins, hw.data(), (size_t)W * sizeof(lba::BWin), hipMemcpyHostToDevice, b->stream) != hipSuccess) {
         cleanup();
         return fail(ORBX_ERR_HIP, "batch setup failed");
@@ -2455,8 +1632,6 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     std::vector<double> hint((size_t)W, -1.0);         // the lambda the linearisation of the current iteration prepared the Schur side for
     std::vector<char> first_trial((size_t)W, 0);
     auto stopped = [&](int i) { return stop_flags && stop_flags[i] && *stop_flags[i]; };
-    std::vector<unsigned long long> seq((size_t)W);
-    for (int i = 0; i < W; i++) seq[i] = sh[i]->seq;
     lba::BDynAll dyn;
     std::memset(&dyn, 0, sizeof(dyn));
     for (;;) {
@@ -2477,7 +1652,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
                 if (!(first_trial[i] && hint[i] >= 0.0 && hint[i] == c.lambda())) y.flags |= lba::kBwSchurLm;
             }
             y.lambda = c.lambda(); y.hint = hint[i]; y.cur = s->cur;
-            if (y.flags & (lba::kBwReduce0 | lba::kBwTrial)) y.seq = ++seq[i];
+            if (y.flags & (lba::kBwReduce0 | lba::kBwTrial)) y.seq = ++s->hs.seq;
             any_lin |= (y.flags & lba::kBwLin) != 0; any_err |= (y.flags & lba::kBwErrors) != 0;
             any_trial |= (y.flags & lba::kBwTrial) != 0; any_lm |= (y.flags & lba::kBwSchurLm) != 0;
         }
@@ -2492,13 +1667,13 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             // the factorisation: one launch (a workgroup per tile and window, flags between them) while every workgroup of the launch
             // can be resident at once (it waits on others), else a launch per block column
             const int tiles = max_nblk * (max_nblk + 1) / 2;
-            if (tiles * W <= lba::kMaxFlowGroups) {
-                hipLaunchKernelGGL(lba::k_chol_flow_b, dim3(tiles, W), dim3(256), lba::kStepLds, st, (const lba::BWin*)b->d_wins, dyn);
+            if (tiles * W <= chol::kMaxFlowGroups) {
+                hipLaunchKernelGGL(lba::k_chol_flow_b, dim3(tiles, W), dim3(256), chol::kStepLds, st, (const lba::BWin*)b->d_wins, dyn);
             } else {
                 hipLaunchKernelGGL(lba::k_chol_diag_b, dim3(1, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
                 for (int K = 0; K + 1 < max_nblk; K++) {
                     const int T = max_nblk - 1 - K;
-                    hipLaunchKernelGGL(lba::k_chol_step_b, dim3(T * (T + 1) / 2, W), dim3(256), lba::kStepLds, st, (const lba::BWin*)b->d_wins, dyn, K);
+                    hipLaunchKernelGGL(lba::k_chol_step_b, dim3(T * (T + 1) / 2, W), dim3(256), chol::kStepLds, st, (const lba::BWin*)b->d_wins, dyn, K);
                 }
             }
             hipLaunchKernelGGL(lba::k_chol_solve_update_b, dim3(1, W), dim3(1024), solve_lds, st, (const lba::BWin*)b->d_wins, dyn);
@@ -2509,15 +1684,14 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         for (int i = 0; i < W && !r; i++) {
             const int f = dyn.w[i].flags;
             if (!(f & (lba::kBwReduce0 | lba::kBwTrial))) continue;
-            sh[i]->seq = seq[i];
-            r = wait_scalars(sh[i]->h_scal, seq[i], b->stream);
+            r = sh[i]->hs.wait(b->stream);
         }
         if (r) break;
         for (int i = 0; i < W; i++) {
             lm::Levenberg& c = ctl[i];
             lba_shard* s = sh[i];
             const int f = dyn.w[i].flags;
-            const double* h = s->h_scal;
+            const double* h = s->hs.h;
             if (f & lba::kBwReduce0) {      // linearised without a trial: chi2 and the diagonal maxima are in
                 s->err_current = true;
                 c.linearized(h[0], lm::initial_lambda(lambda_init, h[1], h[2]));
@@ -2538,67 +1712,48 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         if (r) break;
     }
     (void)hipEventRecord(b->ev1, b->stream);
-    const auto t_solved = std::chrono::steady_clock::now();
-#define BTRY(expr) do { if (!r && (expr) != hipSuccess) r = fail(ORBX_ERR_HIP, "%s failed", #expr); } while (0)
+    const auto t_solved = stage::Clock::now();
     // results of all windows: epilogue kernels and copies into ONE pinned buffer, one synchronisation, then the scatter
     {
-        auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-        std::vector<size_t> off((size_t)W + 1, 0);
-        for (int i = 0; i < W; i++) {
-            const lba::Dev& d = sh[i]->d;
-            off[i + 1] = off[i] + al(7 * (size_t)d.nPoses * 8) + al(3 * (size_t)d.nL * 8) + al((size_t)d.nE * 8) + al((size_t)d.nE);
-        }
-        if (outputs && off[W] > b->h_out_cap) {
-            if (b->h_out) (void)hipHostFree(b->h_out);
-            b->h_out = nullptr; b->h_out_cap = 0;
-            const size_t cap = off[W] + off[W] / 4 + 4096;
-            if (hipHostMalloc((void**)&b->h_out, cap) == hipSuccess) b->h_out_cap = cap;
-            else r = fail(ORBX_ERR_HIP, "pinned result buffer allocation failed");
-        }
+        stage::PinnedOut& po = b->out;
+        po.clear();
+        for (int i = 0; i < W; i++) po.add(7 * (size_t)sh[i]->d.nPoses * 8, sh[i]->d.nL, sh[i]->d.nE);
+        if (outputs && !r) r = po.reserve(false);
         for (int i = 0; i < W && !r; i++) {
             lba_shard* s = sh[i];
             if (stats_out) stats_out[i] = ctl[i].stats();
             if (!outputs) continue;
             const lba::Dev& d = s->d;
-            uint8_t* o = b->h_out + off[i];
-            if (d.nE > 0 && (outputs[i].chi2_per_edge || outputs[i].depth_positive))
+            const LbaOutputs& o = outputs[i];
+            const stage::PinnedOut::Slice h = po.slice(po.h + po.off[i], 7 * (size_t)d.nPoses * 8, d.nL, d.nE);
+            if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive))
                 hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, b->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-            BTRY(hipMemcpyAsync(o, s->poses[s->cur], 7 * (size_t)d.nPoses * 8, hipMemcpyDeviceToHost, b->stream));
-            o += al(7 * (size_t)d.nPoses * 8);
-            if (outputs[i].points && d.nL > 0) BTRY(hipMemcpyAsync(o, s->pts[s->cur], 3 * (size_t)d.nL * 8, hipMemcpyDeviceToHost, b->stream));
-            o += al(3 * (size_t)d.nL * 8);
-            if (outputs[i].chi2_per_edge && d.nE > 0) BTRY(hipMemcpyAsync(o, s->d_chi2, (size_t)d.nE * 8, hipMemcpyDeviceToHost, b->stream));
-            o += al((size_t)d.nE * 8);
-            if (outputs[i].depth_positive && d.nE > 0) BTRY(hipMemcpyAsync(o, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, b->stream));
+            ORBX_HIP_FIRST(r, hipMemcpyAsync(h.state, s->poses[s->cur], 7 * (size_t)d.nPoses * 8, hipMemcpyDeviceToHost, b->stream));
+            if (o.points && d.nL > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.points, s->pts[s->cur], 3 * (size_t)d.nL * 8, hipMemcpyDeviceToHost, b->stream));
+            if (o.chi2_per_edge && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.chi2, s->d_chi2, (size_t)d.nE * 8, hipMemcpyDeviceToHost, b->stream));
+            if (o.depth_positive && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.depth, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, b->stream));
         }
         if (!r) {
-            BTRY(hipStreamSynchronize(b->stream));
+            ORBX_HIP_FIRST(r, hipStreamSynchronize(b->stream));
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->last_device_ms = ms;
         }
         for (int i = 0; i < W && !r && outputs; i++) {
             const lba::Dev& d = sh[i]->d;
-            const uint8_t* o = b->h_out + off[i];
-            const double* poses = (const double*)o;
-            for (int k = 0; k < d.nPoses; k++) {
-                if (outputs[i].pose_q) for (int c = 0; c < 4; c++) outputs[i].pose_q[4 * k + c] = poses[7 * (size_t)k + c];
-                if (outputs[i].pose_t) for (int c = 0; c < 3; c++) outputs[i].pose_t[3 * k + c] = poses[7 * (size_t)k + 4 + c];
-            }
-            o += al(7 * (size_t)d.nPoses * 8);
-            if (outputs[i].points && d.nL > 0) std::memcpy(outputs[i].points, o, 3 * (size_t)d.nL * 8);
-            o += al(3 * (size_t)d.nL * 8);
-            if (outputs[i].chi2_per_edge && d.nE > 0) std::memcpy(outputs[i].chi2_per_edge, o, (size_t)d.nE * 8);
-            o += al((size_t)d.nE * 8);
-            if (outputs[i].depth_positive && d.nE > 0) std::memcpy(outputs[i].depth_positive, o, (size_t)d.nE);
+            const LbaOutputs& o = outputs[i];
+            const stage::PinnedOut::Slice h = po.slice(po.h + po.off[i], 7 * (size_t)d.nPoses * 8, d.nL, d.nE);
+            stage::split_poses7((const double*)h.state, d.nPoses, o.pose_q, o.pose_t);
+            if (o.points && d.nL > 0) std::memcpy(o.points, h.points, 3 * (size_t)d.nL * 8);
+            if (o.chi2_per_edge && d.nE > 0) std::memcpy(o.chi2_per_edge, h.chi2, (size_t)d.nE * 8);
+            if (o.depth_positive && d.nE > 0) std::memcpy(o.depth_positive, h.depth, (size_t)d.nE);
         }
     }
-#undef BTRY
-    const auto t_down = std::chrono::steady_clock::now();
+    const auto t_down = stage::Clock::now();
     cleanup();
     if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
+        using stage::ms;
         std::fprintf(stderr, "[lba_solve_batch] %d windows: structure + upload %.3f ms, Levenberg rounds %.3f ms, epilogue + download %.3f ms, destroy %.3f ms\n",
-                     W, ms(t_start, t_created), ms(t_created, t_solved), ms(t_solved, t_down), ms(t_down, std::chrono::steady_clock::now()));
+                     W, ms(t_start, t_created), ms(t_created, t_solved), ms(t_solved, t_down), ms(t_down, stage::Clock::now()));
     }
     return r;
 }

@@ -1910,9 +1910,7 @@ int orbm_create(int device, orbm_matcher** out)
 {
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range", device);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     orbm_matcher* m = new orbm_matcher();
     m->device = device;

@@ -169,9 +169,8 @@ int orbm_create_new_map_points(orbm_matcher* m, const OrbmMapKeyFrame* kf1, cons
     const bool want_normal = out->normal || out->max_dist || out->min_dist;
     if (want_normal && n1 > 0 && (!out->normal || !out->max_dist || !out->min_dist)) return fail(ORBX_ERR_ARG, "normal, max_dist and min_dist go together");
     if (!m) {                                                   // no handle exists without a device: there is no CPU fallback
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-        return fail(ORBX_ERR_ARG, "NULL matcher");
+        const int r = stage::check_device(0);
+        return r ? r : fail(ORBX_ERR_ARG, "NULL matcher");
     }
     for (int i = 0; i < n1; i++) {
         out->neighbour[i] = -1; out->idx2[i] = -1; out->point_stereo[i] = 0;

@@ -753,9 +753,7 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
     *out = nullptr;
     if (nlevels < 1 || nlevels > kMaxLevels || nfeatures < 1 || !(scale_factor > 1.0f))
         return fail(ORBX_ERR_ARG, "bad extractor parameters (nfeatures=%d scale=%f nlevels=%d)", nfeatures, scale_factor, nlevels);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ORBX_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(ORBX_ERR_ARG, "device %d out of range (%d devices)", device, ndev);
+    if (int r = stage::check_device(device)) return r;
     ORBX_HIP(hipSetDevice(device));
     orbx_extractor* e = new orbx_extractor();
     e->device = device;

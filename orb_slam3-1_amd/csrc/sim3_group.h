@@ -1,4 +1,4 @@
-// Sim(3) group arithmetic of the pose-graph solver (essential_graph.inc), restating g2o::Sim3 (reference
+// Sim(3) group arithmetic of the pose-graph solver (essential_graph.inc, which includes this header itself), restating g2o::Sim3 (reference
 // Thirdparty/g2o/g2o/types/sim3.h) and the Eigen formulas it relies on: exp (:70-142), log (:148-230), inverse (:233-236), the
 // product (:266-272), map (:144-146); VertexSim3Expmap::oplusImpl and EdgeSim3::computeError (types_seven_dof_expmap.h:60-69,
 // :106-114) and the numeric Jacobian of a binary edge (core/base_binary_edge.hpp:147-196).  A Sim3 is 8 doubles: the rotation

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Phase split of the factoring workgroup of k_chol_step_b, the per-block-column factorisation that lba_solve_batch takes when
-the tiles of all windows exceed one resident launch (here 32 windows of 15 tiles; GPU box).  Needs lba_solver.hip compiled with -DLBA_STEP_TIMING:
+the tiles of all windows exceed one resident launch (here 32 windows of 15 tiles; GPU box).  The counters are in dense_chol.h, which
+lba_solver.hip includes: that unit needs -DLBA_STEP_TIMING:
   cd orb_slam3-1_amd/csrc && hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -DLBA_STEP_TIMING -c -o lba_solver.o lba_solver.hip \\
      && hipcc --offload-arch=gfx950 -shared -fPIC -o ../liborbslam3_hip.so *.o        (then `make -B` restores the product build)"""
 import ctypes as C

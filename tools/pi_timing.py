@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Cycle split of the Gauss-Newton iterations of k_pose_inertial (one frame).  Needs lba_solver.hip compiled with
--DLIBA_PI_TIMING (hipcc ... -DLIBA_PI_TIMING -c lba_solver.hip, then make; rebuild with `make -B` afterwards)."""
+"""Cycle split of the Gauss-Newton iterations of k_pose_inertial (one frame).  The kernel is in inertial_solver.inc, which is compiled
+as part of lba_solver.hip: that unit needs -DLIBA_PI_TIMING (hipcc ... -DLIBA_PI_TIMING -c lba_solver.hip, then make; rebuild with
+`make -B` afterwards)."""
 import ctypes as C
 import importlib
 import os

@@ -18,7 +18,7 @@ for r in csv.DictReader(open(f)):
     if r["Counter_Name"] == "SQ_WAVE_CYCLES": cnt[k] += 1
 lines = []
 for k, v in sorted(acc.items()):
-    if not k.startswith("lba::"): continue
+    if not k.startswith(("lba::", "chol::")): continue      # the Cholesky kernels are chol:: (csrc/dense_chol.h)
     n = max(cnt[k], 1)
     # SQ_VALU_MFMA_BUSY_CYCLES counts cycles, SQ_BUSY_CYCLES quad-cycles per SE-aggregated SQ (MI355X_MICROARCH.md): report the raw ratio too
     lines.append("%-34s n=%4d  mfma_mops_f64/launch %10.0f  insts_mfma/launch %8.0f  insts_valu/launch %10.0f  mfma_busy_cycles/launch %10.0f  sq_busy_cycles/launch %10.0f  wave_cycles/launch %10.0f" % (

@@ -962,6 +962,10 @@ int  essg_check(const EssgProblem* problem, const EssgResult* result);
  * [2] epilogue + download */
 double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 
+/* ---- pose graph of an inertial map: Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5292-5588) on the same handle:
+ * Essg4DofProblem, Essg4DofResult and the two entry points that take them, documented where they are declared ---- */
+#include "orbslam3_hip_4dof.h"
+
 #ifdef __cplusplus
 }
 #endif

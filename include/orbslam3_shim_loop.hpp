@@ -348,7 +348,8 @@ int OptimizeSim3HIP(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMa
 // KeyFrame / MapPoint / Map (template parameters, so that the stand-ins of the tests can add the members they lack by
 // derivation); Sim3T = g2o::Sim3; PoseMap = LoopClosing::KeyFrameAndPose; Opt = the class whose OptimizeEssentialGraph serves what
 // the device does not: invalid input (ORBX_ERR_ARG), more than ESSG_MAX_FREE_VERTICES free key frames (ORBX_ERR_CAPACITY).
-// OptimizeEssentialGraph4DoF (the inertial case, :2115 ff. of LoopClosing's dispatch) is a different function and stays the reference's.
+// OptimizeEssentialGraph4DoF, which LoopClosing::CorrectLoop calls instead once the map's IMU is initialised (src/LoopClosing.cc:1182),
+// is a different graph (yaw + translation vertices, Edge4DoF): OptimizeEssentialGraph4DoFHIP at the end of this file, on essg_optimize_4dof.
 struct EssentialGraphFlat {
     std::vector<long unsigned int> id;      // mnId per vertex, in the order the reference adds them
     std::vector<double> sim3;               // [8] per vertex: q x y z w, t, s
@@ -678,6 +679,225 @@ void OptimizeEssentialGraphHIP(KF* pCurKF, std::vector<KF*>& vpFixedKFs, std::ve
         pMPi->SetWorldPos(Twr * (TNonCorrectedwr.inverse() * pMPi->GetWorldPos()));
         pMPi->UpdateNormalAndDepth();
     }
+}
+
+// ---- Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5292-5588), the pose graph of an inertial map, on essg_optimize_4dof ----
+// Same split as above: FlattenEssentialGraph4DoF walks the graph as the reference does (host only, checked without a device by
+// tests/stubs/shim_essential4dof_toy.cpp), OptimizeEssentialGraph4DoFHIP calls the device and writes the map back.  KF needs, besides
+// what the Sim3 walk uses, mPrevKF, mNextKF, mImuCalib, GetImuRotation and GetImuPosition.  Opt = the class whose
+// OptimizeEssentialGraph4DoF serves what the device does not: an edge g2o would have refused (a bad key frame has no vertex), input
+// essg_check_4dof refuses (ORBX_ERR_ARG), more than ESSG_MAX_FREE_VERTICES free key frames (ORBX_ERR_CAPACITY).
+struct EssentialGraph4DoFFlat {
+    std::vector<long unsigned int> id;      // mnId per vertex, in the order the reference adds them
+    std::vector<double> rcw, tcw, rwb, twb, rcb, tcb;   // [9] row-major / [3] per vertex: the ImuCamPose as its constructor leaves it
+    std::vector<double> scw;                // [8] per vertex: vScw as q x y z w, t, s (a CorrectedSim3 entry keeps its scale here)
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> edges;             // [2] per edge: vertex 0 (nIDi), vertex 1 (nIDj), as indices into id
+    std::vector<double> edge_rot, edge_trans;   // [9], [3] per edge: rotation and translation of Sij = Siw * Sjw^-1
+    std::vector<float> points;              // GetWorldPos() of every map point that is not bad
+    std::vector<int32_t> point_ref;
+    std::vector<size_t> point_index;        // its index in GetAllMapPoints()
+    int dropped_edges = 0;                  // edges g2o's addEdge refuses because a vertex is missing (a bad key frame)
+};
+
+namespace essential_detail {
+
+inline void to_matrix(const double* q, double* R)                       // Eigen's QuaternionBase::toRotationMatrix, row-major
+{
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+template <class M> inline void put9(const M& m, std::vector<double>& out) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) out.push_back((double)m(r, c)); }
+template <class V> inline void put3(const V& v, std::vector<double>& out) { for (int k = 0; k < 3; k++) out.push_back((double)v[k]); }
+
+struct Builder4DoF {
+    EssentialGraph4DoFFlat& g;
+    std::map<long unsigned int, int> index;
+    // VertexPose4DoF(pKF): ImuCamPose(KeyFrame*) (src/G2oTypes.cc:25-71), every member read from the key frame's float members
+    // (GetRotation / GetTranslation return the rotation and translation of the pose GetPose returns)
+    template <class KF>
+    void vertex_from_key_frame(KF* pKF, bool fixed)
+    {
+        const Sophus::SE3f Tcw = pKF->GetPose();
+        put9(Tcw.rotationMatrix(), g.rcw); put3(Tcw.translation(), g.tcw);
+        put9(pKF->GetImuRotation(), g.rwb); put3(pKF->GetImuPosition(), g.twb);
+        finish(pKF, fixed, from_pose(pKF));
+    }
+    // VertexPose4DoF(Rwc, twc, pKF) with Rwc, twc of Scw.inverse(), the scale dropped: ImuCamPose(Rwc, twc, pKF) (:121-146) in double
+    template <class KF>
+    void vertex_from_sim3(KF* pKF, bool fixed, const S8& Scw)
+    {
+        const S8 Swc = inverse(Scw);
+        double Rwc[9], Rcb[9], tcb[3];
+        to_matrix(Swc.v, Rwc);
+        const double* twc = Swc.v + 4;
+        const Eigen::Matrix3f Rcbf = pKF->mImuCalib.mTcb.rotationMatrix();
+        const Eigen::Vector3f tcbf = pKF->mImuCalib.mTcb.translation();
+        for (int r = 0; r < 3; r++) { tcb[r] = (double)tcbf[r]; for (int c = 0; c < 3; c++) Rcb[3 * r + c] = (double)Rcbf(r, c); }
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) {
+                g.rcw.push_back(Rwc[3 * c + r]);                                                                            // Rcw = Rwc^T
+                g.rwb.push_back(Rwc[3 * r] * Rcb[c] + Rwc[3 * r + 1] * Rcb[3 + c] + Rwc[3 * r + 2] * Rcb[6 + c]);           // Rwb = Rwc Rcb
+            }
+        for (int r = 0; r < 3; r++) {
+            g.tcw.push_back(-(Rwc[r] * twc[0] + Rwc[3 + r] * twc[1] + Rwc[6 + r] * twc[2]));                                // tcw = -Rcw twc
+            g.twb.push_back((Rwc[3 * r] * tcb[0] + Rwc[3 * r + 1] * tcb[1] + Rwc[3 * r + 2] * tcb[2]) + twc[r]);            // twb = Rwc tcb + twc
+        }
+        finish(pKF, fixed, Scw);
+    }
+    template <class KF>
+    void finish(KF* pKF, bool fixed, const S8& Scw)
+    {
+        put9(pKF->mImuCalib.mTcb.rotationMatrix(), g.rcb); put3(pKF->mImuCalib.mTcb.translation(), g.tcb);
+        index[pKF->mnId] = (int)g.id.size();
+        g.id.push_back(pKF->mnId);
+        g.scw.insert(g.scw.end(), Scw.v, Scw.v + 8);
+        g.fixed.push_back(fixed ? 1 : 0);
+    }
+    // Edge4DoF(Tij) with Tij the rotation and the translation of Sij (the scale of the product stays inside its translation, as
+    // g2o::Sim3::operator* leaves it); optimizer.addEdge refuses an edge with a vertex the optimizer does not hold
+    void edge(long unsigned int idi, long unsigned int idj, const S8& Sij)
+    {
+        const auto a = index.find(idi), b = index.find(idj);
+        if (a == index.end() || b == index.end()) { g.dropped_edges++; return; }
+        g.edges.push_back(a->second); g.edges.push_back(b->second);
+        double R[9];
+        to_matrix(Sij.v, R);
+        g.edge_rot.insert(g.edge_rot.end(), R, R + 9);
+        g.edge_trans.insert(g.edge_trans.end(), Sij.v + 4, Sij.v + 7);
+    }
+};
+
+}  // namespace essential_detail
+
+// the graph (:5322-5539).  Vertices: the key frames of the map that are not bad, pLoopKF alone fixed.  Edges: loop connections
+// first, then per key frame the inertial edge to mPrevKF, its loop edges, its covisibility edges.  pParentKF is NULL in the
+// reference (:5420): there is no spanning-tree edge, and no covisible key frame is excluded for being the parent.
+template <class KF, class MP, class MapT, class PoseMap, class ConnMap>
+void FlattenEssentialGraph4DoF(MapT* pMap, KF* pLoopKF, KF* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                               const ConnMap& LoopConnections, EssentialGraph4DoFFlat& g)
+{
+    namespace ed = essential_detail;
+    ed::Builder4DoF b{g, {}};
+    const std::vector<KF*> vpKFs = pMap->GetAllKeyFrames();
+    const std::vector<MP*> vpMPs = pMap->GetAllMapPoints();
+    std::map<long unsigned int, ed::S8> vScw;
+    const int minFeat = 100;
+    for (KF* pKF : vpKFs) {                                                                 // :5322-5359
+        if (pKF->isBad()) continue;
+        const auto it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) {
+            vScw[pKF->mnId] = ed::from_sim3(it->second);
+            b.vertex_from_sim3(pKF, pKF == pLoopKF, vScw[pKF->mnId]);
+        } else {
+            vScw[pKF->mnId] = ed::from_pose(pKF);
+            b.vertex_from_key_frame(pKF, pKF == pLoopKF);
+        }
+    }
+    auto scw = [&](long unsigned int id) { const auto it = vScw.find(id); return it != vScw.end() ? it->second : ed::identity(); };   // vScw is value-initialised (:5315)
+    auto non_corrected = [&](KF* pKF) { const auto it = NonCorrectedSim3.find(pKF); return it != NonCorrectedSim3.end() ? ed::from_sim3(it->second) : scw(pKF->mnId); };
+    std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+    for (auto mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {         // :5370-5400
+        KF* pKF = mit->first;
+        const long unsigned int nIDi = pKF->mnId;
+        const ed::S8 Siw = scw(nIDi);
+        for (KF* pKFj : mit->second) {
+            const long unsigned int nIDj = pKFj->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat) continue;
+            b.edge(nIDi, nIDj, ed::mul(Siw, ed::inverse(scw(nIDj))));
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (KF* pKF : vpKFs) {                                                                 // :5403-5539
+        const long unsigned int nIDi = pKF->mnId;
+        const ed::S8 Siw = non_corrected(pKF);
+        KF* prevKF = static_cast<KF*>(pKF->mPrevKF);
+        if (prevKF) b.edge(nIDi, prevKF->mnId, ed::mul(Siw, ed::inverse(non_corrected(prevKF))));
+        const std::set<KF*> sLoopEdges = pKF->GetLoopEdges();
+        for (KF* pLKF : sLoopEdges)
+            if (pLKF->mnId < pKF->mnId) b.edge(nIDi, pLKF->mnId, ed::mul(Siw, ed::inverse(non_corrected(pLKF))));
+        const std::vector<KF*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+        for (KF* pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != prevKF && pKFn != static_cast<KF*>(pKF->mNextKF) && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    b.edge(nIDi, pKFn->mnId, ed::mul(Siw, ed::inverse(non_corrected(pKFn))));
+                }
+            }
+        }
+    }
+    for (size_t i = 0; i < vpMPs.size(); i++) {                                             // :5566-5583: GetReferenceKeyFrame() alone, no mnCorrectedByKF
+        MP* pMP = vpMPs[i];
+        if (pMP->isBad()) continue;
+        const auto it = b.index.find(pMP->GetReferenceKeyFrame()->mnId);
+        g.point_ref.push_back(it != b.index.end() ? it->second : -1);                       // -1: refused by essg_check_4dof, the reference decides
+        const Eigen::Vector3f P = pMP->GetWorldPos();
+        for (int k = 0; k < 3; k++) g.points.push_back(P[k]);
+        g.point_index.push_back(i);
+    }
+}
+
+namespace essential_detail {
+// essg_optimize_4dof on a flattened graph; false when the device refuses it (invalid input, over capacity): the caller falls back
+inline bool run(const EssentialGraph4DoFFlat& g, std::vector<float>& q, std::vector<float>& t, std::vector<float>& pts)
+{
+    Essg4DofProblem p;
+    p.n_vertices = (int32_t)g.id.size();
+    p.rcw = g.rcw.data(); p.tcw = g.tcw.data(); p.rwb = g.rwb.data(); p.twb = g.twb.data(); p.rcb = g.rcb.data(); p.tcb = g.tcb.data();
+    p.fixed = g.fixed.data();
+    p.n_edges = (int32_t)(g.edges.size() / 2); p.edge_vertices = g.edges.data(); p.edge_rot = g.edge_rot.data(); p.edge_trans = g.edge_trans.data();
+    for (int k = 0; k < 36; k++) p.information[k] = 0.0;
+    for (int k = 0; k < 6; k++) p.information[7 * k] = k < 2 ? 1e3 : 1.0;                  // matLambda (:5363-5366): entry (2, 2) stays 1
+    p.max_iters = 20; p.lambda_init = 0.0;                                                  // no setUserLambdaInit: computeLambdaInit
+    p.n_points = (int32_t)g.point_ref.size(); p.points = g.points.data(); p.point_ref = g.point_ref.data();
+    p.scw = p.n_points > 0 ? g.scw.data() : nullptr;
+    std::vector<double> rcw_out(g.rcw.size()), tcw_out(g.tcw.size());
+    q.assign(4 * g.id.size(), 0.f); t.assign(3 * g.id.size(), 0.f); pts.assign(g.points.size() + 3, 0.f);
+    Essg4DofResult r;
+    r.rcw_out = rcw_out.data(); r.tcw_out = tcw_out.data(); r.pose_q = q.data(); r.pose_t = t.data(); r.points_out = pts.data();
+    const int ok = essg_check_4dof(&p, &r);             // before a handle (and with it a device) is asked for
+    if (ok == ORBX_ERR_ARG || ok == ORBX_ERR_CAPACITY) return false;
+    orbslam3_hip::check(essg_optimize_4dof(solver(), &p, &r, nullptr));
+    return true;
+}
+}  // namespace essential_detail
+
+// void Optimizer::OptimizeEssentialGraph4DoF(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+//                                            const KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>&)
+template <class Opt = Optimizer, class KF, class MapT, class PoseMap, class ConnMap>
+void OptimizeEssentialGraph4DoFHIP(MapT* pMap, KF* pLoopKF, KF* pCurKF, const PoseMap& NonCorrectedSim3, const PoseMap& CorrectedSim3,
+                                   const ConnMap& LoopConnections)
+{
+    typedef typename std::remove_pointer<typename decltype(pMap->GetAllMapPoints())::value_type>::type MP;
+    EssentialGraph4DoFFlat g;
+    FlattenEssentialGraph4DoF<KF, MP>(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, g);
+    std::vector<float> q, t, pts;
+    if (g.dropped_edges > 0 || !essential_detail::run(g, q, t, pts)) {
+        Opt::OptimizeEssentialGraph4DoF(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections);
+        return;
+    }
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                               // :5545
+    const std::vector<KF*> vpKFs = pMap->GetAllKeyFrames();
+    std::map<long unsigned int, int> index;
+    for (size_t k = 0; k < g.id.size(); k++) index[g.id[k]] = (int)k;
+    for (KF* pKFi : vpKFs) {                                                                // :5548-5563
+        const auto it = index.find(pKFi->mnId);
+        if (it == index.end()) continue;
+        const int k = it->second;
+        pKFi->SetPose(Sophus::SE3f(Eigen::Quaternionf(q[4 * k + 3], q[4 * k], q[4 * k + 1], q[4 * k + 2]), Eigen::Vector3f(t[3 * k], t[3 * k + 1], t[3 * k + 2])));
+    }
+    const std::vector<MP*> vpMPs = pMap->GetAllMapPoints();
+    for (size_t k = 0; k < g.point_index.size(); k++) {                                     // :5566-5586
+        MP* pMP = vpMPs[g.point_index[k]];
+        pMP->SetWorldPos(Eigen::Vector3f(pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();                                                            // :5587
 }
 
 }  // namespace ORB_SLAM3

@@ -1628,3 +1628,61 @@ class EssentialGraph:
         st = (C.c_double * 3)()
         ms = lib.essg_last_device_ms(self._h, st)
         return ms, dict(structure_upload=st[0], rounds=st[1], epilogue_download=st[2])
+
+
+class Essg4DofProblem(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("rcw", C.c_void_p), ("tcw", C.c_void_p), ("rwb", C.c_void_p), ("twb", C.c_void_p),
+                ("rcb", C.c_void_p), ("tcb", C.c_void_p), ("fixed", C.c_void_p),
+                ("n_edges", C.c_int32), ("edge_vertices", C.c_void_p), ("edge_rot", C.c_void_p), ("edge_trans", C.c_void_p),
+                ("information", C.c_double * 36), ("max_iters", C.c_int32), ("lambda_init", C.c_double),
+                ("n_points", C.c_int32), ("points", C.c_void_p), ("point_ref", C.c_void_p), ("scw", C.c_void_p)]
+
+
+class Essg4DofResult(C.Structure):
+    _fields_ = [("rcw_out", C.c_void_p), ("tcw_out", C.c_void_p), ("pose_q", C.c_void_p), ("pose_t", C.c_void_p),
+                ("points_out", C.c_void_p), ("stats", LbaStats)]
+
+
+ESSG4DOF_INFORMATION = np.diag([1e3, 1e3, 1.0, 1.0, 1.0, 1.0])      # matLambda of Optimizer::OptimizeEssentialGraph4DoF
+
+
+def essg4dof_prepare(w):
+    """Essg4DofProblem / Essg4DofResult of a graph dictionary (synth_posegraph.make_posegraph4dof) with the arrays they point to"""
+    f8 = lambda key, shape: np.ascontiguousarray(w[key], np.float64).reshape(shape)
+    k = dict(rcw=f8("rcw", (-1, 9)), tcw=f8("tcw", (-1, 3)), rwb=f8("rwb", (-1, 9)), twb=f8("twb", (-1, 3)), rcb=f8("rcb", (-1, 9)),
+             tcb=f8("tcb", (-1, 3)), fixed=np.ascontiguousarray(w["fixed"], np.uint8),
+             ev=np.ascontiguousarray(w["edge_vertices"], np.int32).reshape(-1, 2), edge_rot=f8("edge_rot", (-1, 9)),
+             edge_trans=f8("edge_trans", (-1, 3)),
+             points=np.ascontiguousarray(w.get("points", np.zeros((0, 3))), np.float32).reshape(-1, 3),
+             ref=np.ascontiguousarray(w.get("point_ref", np.zeros(0)), np.int32),
+             information=np.ascontiguousarray(w.get("information", ESSG4DOF_INFORMATION), np.float64).reshape(36))
+    nv, ne, npt = len(k["rcw"]), len(k["ev"]), len(k["points"])
+    k["scw"] = np.ascontiguousarray(w["scw"], np.float64).reshape(-1, 8) if npt else np.zeros((0, 8))
+    if any(len(k[key]) != nv for key in ("tcw", "rwb", "twb", "rcb", "tcb", "fixed")) or len(k["edge_rot"]) != ne or len(k["edge_trans"]) != ne \
+            or len(k["ref"]) != npt or (npt and len(k["scw"]) != nv):
+        raise ValueError("4-DoF essential graph arrays of unequal length")
+    k.update(rcw_out=np.zeros((nv, 3, 3)), tcw_out=np.zeros((nv, 3)), pose_q=np.zeros((nv, 4), np.float32), pose_t=np.zeros((nv, 3), np.float32),
+             points_out=np.zeros((npt, 3), np.float32))
+    ptr = lambda key, present=True: k[key].ctypes.data if present else None
+    pr = Essg4DofProblem(nv, ptr("rcw"), ptr("tcw"), ptr("rwb"), ptr("twb"), ptr("rcb"), ptr("tcb"), ptr("fixed"),
+                         ne, ptr("ev", ne), ptr("edge_rot", ne), ptr("edge_trans", ne), (C.c_double * 36)(*k["information"]),
+                         int(w.get("max_iters", 20)), float(w.get("lambda_init", 0.0)), npt, ptr("points", npt), ptr("ref", npt), ptr("scw", npt))
+    res = Essg4DofResult(ptr("rcw_out"), ptr("tcw_out"), ptr("pose_q"), ptr("pose_t"), ptr("points_out", npt))
+    return dict(problem=pr, result=res, arrays=k)
+
+
+lib.essg_optimize_4dof.argtypes = [C.c_void_p, C.POINTER(Essg4DofProblem), C.POINTER(Essg4DofResult), C.c_void_p]
+lib.essg_check_4dof.argtypes = [C.POINTER(Essg4DofProblem), C.POINTER(Essg4DofResult)]
+
+
+def _essg_optimize_4dof(self, pr, stop_flag=None):
+    """Optimizer::OptimizeEssentialGraph4DoF between building the graph and writing the map back (reference
+    src/Optimizer.cc:5541-5586): essg_optimize_4dof of include/orbslam3_hip.h on this handle"""
+    prep = essg4dof_prepare(pr)
+    _check(lib.essg_optimize_4dof(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
+    k = prep["arrays"]
+    return dict(rcw_out=k["rcw_out"], tcw_out=k["tcw_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
+                stats=_stats_dict(prep["result"].stats))
+
+
+EssentialGraph.optimize_4dof = _essg_optimize_4dof

@@ -208,7 +208,9 @@ struct essg_solver : stage::Batch {      // its stream, the two events around th
     double* scal = nullptr;
     struct Buf { void* p = nullptr; size_t cap = 0; };
     enum { kEst0, kEstA, kEstB, kMeas, kEv, kCol, kRecs, kChi, kPart, kBlkI, kBlkJ, kBlkOff, kBlkEnt, kX, kBfull, kS, kLp, kLinv,
-           kPts, kRef, kPtsOut, kPoseQ, kPoseT, kNumBufs };
+           kPts, kRef, kPtsOut, kPoseQ, kPoseT,
+           kConst4, kScw4, kRcwOut4, kTcwOut4,      // essential_graph_4dof.inc; it takes the others as they are sized per call
+           kNumBufs };
     Buf buf[kNumBufs];
     double last_device_ms = 0.0;
     double stage_ms[3] = {0, 0, 0};

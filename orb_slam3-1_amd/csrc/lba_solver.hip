@@ -1762,3 +1762,4 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
 
 #include "inertial_solver.inc"
 #include "essential_graph.inc"
+#include "essential_graph_4dof.inc"

@@ -1589,47 +1589,6 @@ def essg_prepare(w):
     return dict(problem=pr, result=res, arrays=k)
 
 
-lib.essg_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-lib.essg_destroy.argtypes = [C.c_void_p]
-lib.essg_optimize.argtypes = [C.c_void_p, C.POINTER(EssgProblem), C.POINTER(EssgResult), C.c_void_p]
-lib.essg_last_device_ms.argtypes = [C.c_void_p, C.c_void_p]
-lib.essg_check.argtypes = [C.POINTER(EssgProblem), C.POINTER(EssgResult)]
-lib.essg_last_device_ms.restype = C.c_double
-
-
-class EssentialGraph:
-    """Optimizer::OptimizeEssentialGraph between building the graph and writing the map back (reference src/Optimizer.cc:1729-1779):
-    essg_optimize of include/orbslam3_hip.h.  One handle serves one call at a time."""
-
-    def __init__(self, device=0):
-        h = C.c_void_p()
-        _check(lib.essg_create(device, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.essg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def optimize(self, w, stop_flag=None):
-        prep = essg_prepare(w)
-        _check(lib.essg_optimize(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
-        k = prep["arrays"]
-        return dict(sim3_out=k["sim3_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
-                    stats=_stats_dict(prep["result"].stats))
-
-    def last_device_ms(self):
-        st = (C.c_double * 3)()
-        ms = lib.essg_last_device_ms(self._h, st)
-        return ms, dict(structure_upload=st[0], rounds=st[1], epilogue_download=st[2])
-
-
 class Essg4DofProblem(C.Structure):
     _fields_ = [("n_vertices", C.c_int32), ("rcw", C.c_void_p), ("tcw", C.c_void_p), ("rwb", C.c_void_p), ("twb", C.c_void_p),
                 ("rcb", C.c_void_p), ("tcb", C.c_void_p), ("fixed", C.c_void_p),
@@ -1671,18 +1630,53 @@ def essg4dof_prepare(w):
     return dict(problem=pr, result=res, arrays=k)
 
 
+lib.essg_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+lib.essg_destroy.argtypes = [C.c_void_p]
+lib.essg_optimize.argtypes = [C.c_void_p, C.POINTER(EssgProblem), C.POINTER(EssgResult), C.c_void_p]
+lib.essg_last_device_ms.argtypes = [C.c_void_p, C.c_void_p]
+lib.essg_check.argtypes = [C.POINTER(EssgProblem), C.POINTER(EssgResult)]
+lib.essg_last_device_ms.restype = C.c_double
 lib.essg_optimize_4dof.argtypes = [C.c_void_p, C.POINTER(Essg4DofProblem), C.POINTER(Essg4DofResult), C.c_void_p]
 lib.essg_check_4dof.argtypes = [C.POINTER(Essg4DofProblem), C.POINTER(Essg4DofResult)]
 
 
-def _essg_optimize_4dof(self, pr, stop_flag=None):
-    """Optimizer::OptimizeEssentialGraph4DoF between building the graph and writing the map back (reference
-    src/Optimizer.cc:5541-5586): essg_optimize_4dof of include/orbslam3_hip.h on this handle"""
-    prep = essg4dof_prepare(pr)
-    _check(lib.essg_optimize_4dof(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
-    k = prep["arrays"]
-    return dict(rcw_out=k["rcw_out"], tcw_out=k["tcw_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
-                stats=_stats_dict(prep["result"].stats))
+class EssentialGraph:
+    """Optimizer::OptimizeEssentialGraph between building the graph and writing the map back (reference src/Optimizer.cc:1729-1779):
+    essg_optimize of include/orbslam3_hip.h.  One handle serves one call at a time."""
 
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        _check(lib.essg_create(device, C.byref(h)))
+        self._h = h
 
-EssentialGraph.optimize_4dof = _essg_optimize_4dof
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.essg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optimize(self, w, stop_flag=None):
+        prep = essg_prepare(w)
+        _check(lib.essg_optimize(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
+        k = prep["arrays"]
+        return dict(sim3_out=k["sim3_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
+                    stats=_stats_dict(prep["result"].stats))
+
+    def optimize_4dof(self, pr, stop_flag=None):
+        """Optimizer::OptimizeEssentialGraph4DoF between building the graph and writing the map back (reference
+        src/Optimizer.cc:5541-5586): essg_optimize_4dof of include/orbslam3_hip.h on this handle"""
+        prep = essg4dof_prepare(pr)
+        _check(lib.essg_optimize_4dof(self._h, C.byref(prep["problem"]), C.byref(prep["result"]), _p(stop_flag)))
+        k = prep["arrays"]
+        return dict(rcw_out=k["rcw_out"], tcw_out=k["tcw_out"], pose_q=k["pose_q"], pose_t=k["pose_t"], points_out=k["points_out"],
+                    stats=_stats_dict(prep["result"].stats))
+
+    def last_device_ms(self):
+        st = (C.c_double * 3)()
+        ms = lib.essg_last_device_ms(self._h, st)
+        return ms, dict(structure_upload=st[0], rounds=st[1], epilogue_download=st[2])

@@ -11,11 +11,17 @@
 // One Levenberg trial:  memset S -> k_essg_assemble(lambda) -> factorisation -> k_chol_solve -> k_essg_update_errors ->
 // k_essg_reduce -> the host reads chi2, dx^T (lambda dx + b) and the failure flag and lm::Levenberg decides.
 // One linearisation: k_essg_linearize writes a record per edge (no atomics); the assembly sums a block's records in the order of
-// a CSR the host builds once per call, so results do not depend on scheduling.
+// a CSR the host builds once per call (pose_graph_structure.h), so results do not depend on scheduling.
+//
+// The host half of this file is the driver of BOTH pose graphs (essential_graph_4dof.inc is included after it and brings only its
+// kernels, its Dev, its input packing and its own argument checks): essg_reserve, essg_validate_graph, essg_stage, essg_levenberg
+// and essg_finish are templates over the Dev / problem / result types, which name what they share alike; essg_optimize below is
+// their first user.
 
 #include "batch_stage.h"
 #include "dense_chol.h"
 #include "lm_control.h"
+#include "pose_graph_structure.h"
 #include "sim3_group.h"
 
 namespace essg {
@@ -223,7 +229,8 @@ struct essg_solver : stage::Batch {      // its stream, the two events around th
     }
 };
 
-static int essg_reserve(essg_solver* s, int which, size_t bytes, void** out)
+template <class T>
+static int essg_reserve(essg_solver* s, int which, size_t bytes, T** out)
 {
     essg_solver::Buf& b = s->buf[which];
     bytes = std::max<size_t>(bytes, 16);
@@ -232,47 +239,198 @@ static int essg_reserve(essg_solver* s, int which, size_t bytes, void** out)
         ORBX_HIP(hipMalloc(&b.p, bytes));
         b.cap = bytes;
     }
-    *out = b.p;
+    *out = (T*)b.p;
     return ORBX_OK;
 }
 
-// every check of the header, before anything touches a device; *n_free = number of free vertices
-static int essg_validate(const EssgProblem* p, const EssgResult* r, int* n_free)
+// ---- the host driver of a pose-graph call: P / R are the problem and result structs of an entry point, Dev its kernels' argument ----
+
+template <class T>
+static bool essg_finite(const T* a, int n)
 {
-    if (!p) return fail(ORBX_ERR_ARG, "essg_optimize: NULL problem");
-    if (!r) return fail(ORBX_ERR_ARG, "essg_optimize: NULL result");
-    if (p->n_vertices < 1 || p->n_edges < 0 || p->n_points < 0) return fail(ORBX_ERR_ARG, "essg_optimize: bad problem sizes");
-    if (!p->sim3 || !p->fixed) return fail(ORBX_ERR_ARG, "essg_optimize: NULL vertex arrays");
-    if (p->n_edges > 0 && (!p->edge_vertices || !p->edge_measurement)) return fail(ORBX_ERR_ARG, "essg_optimize: NULL edge arrays");
-    if (p->n_points > 0 && (!p->points || !p->point_ref)) return fail(ORBX_ERR_ARG, "essg_optimize: NULL point arrays");
-    if (!r->sim3_out) return fail(ORBX_ERR_ARG, "essg_optimize: NULL sim3_out");
-    if (p->n_points > 0 && !r->points_out) return fail(ORBX_ERR_ARG, "essg_optimize: NULL points_out");
-    if (p->max_iters < 0) return fail(ORBX_ERR_ARG, "essg_optimize: max_iters %d is negative", p->max_iters);
-    if (!(p->lambda_init > 0) || !std::isfinite(p->lambda_init)) return fail(ORBX_ERR_ARG, "essg_optimize: lambda_init must be positive and finite");
-    int nf = 0;
+    for (int k = 0; k < n; k++) if (!std::isfinite(a[k])) return false;
+    return true;
+}
+
+// a Sim3 among the arguments (q, t, s): finite, with a positive scale; `what` and i name it in the message
+static int essg_check_sim3(const char* name, const double* S, const char* what, int i)
+{
+    if (!essg_finite(S, 8)) return fail(ORBX_ERR_ARG, "%s: %s %d is not finite", name, what, i);
+    return S[7] > 0 ? ORBX_OK : fail(ORBX_ERR_ARG, "%s: %s %d has a scale that is not positive", name, what, i);
+}
+
+// Every check of the header, before anything touches a device, in the order the tests pin; *n_free (may be NULL) = number of free vertices.
+// The model supplies arrays() = the group of its pointers that holds a NULL (or nullptr), constants() = its checks of scalars,
+// vertex(v) / edge(e) = its checks of one vertex / of one edge's measurement, last() = what it checks after the points.
+template <class P, class R, class Arrays, class Constants, class Vertex, class Edge, class Last>
+static int essg_validate_graph(const char* name, const P* p, const R* r, int* n_free, Arrays&& arrays, Constants&& constants, Vertex&& vertex, Edge&& edge, Last&& last)
+{
+    if (!p) return fail(ORBX_ERR_ARG, "%s: NULL problem", name);
+    if (!r) return fail(ORBX_ERR_ARG, "%s: NULL result", name);
+    if (p->n_vertices < 1 || p->n_edges < 0 || p->n_points < 0) return fail(ORBX_ERR_ARG, "%s: bad problem sizes", name);
+    if (const char* what = arrays()) return fail(ORBX_ERR_ARG, "%s: NULL %s", name, what);
+    if (p->n_points > 0 && !r->points_out) return fail(ORBX_ERR_ARG, "%s: NULL points_out", name);
+    if (p->max_iters < 0) return fail(ORBX_ERR_ARG, "%s: max_iters %d is negative", name, p->max_iters);
+    int rc = constants(), nf = 0;
+    if (rc) return rc;
     for (int v = 0; v < p->n_vertices; v++) {
-        for (int k = 0; k < 8; k++)
-            if (!std::isfinite(p->sim3[8 * (size_t)v + k])) return fail(ORBX_ERR_ARG, "essg_optimize: vertex %d is not finite", v);
-        if (!(p->sim3[8 * (size_t)v + 7] > 0)) return fail(ORBX_ERR_ARG, "essg_optimize: vertex %d has a scale that is not positive", v);
+        if ((rc = vertex(v))) return rc;
         nf += p->fixed[v] ? 0 : 1;
     }
-    if (nf == 0) return fail(ORBX_ERR_ARG, "essg_optimize: no free vertex");
+    if (nf == 0) return fail(ORBX_ERR_ARG, "%s: no free vertex", name);
     for (int e = 0; e < p->n_edges; e++) {
         const int a = p->edge_vertices[2 * (size_t)e], b = p->edge_vertices[2 * (size_t)e + 1];
-        if (a < 0 || a >= p->n_vertices || b < 0 || b >= p->n_vertices) return fail(ORBX_ERR_ARG, "essg_optimize: edge %d has a vertex index out of range", e);
-        if (a == b) return fail(ORBX_ERR_ARG, "essg_optimize: edge %d joins vertex %d to itself", e, a);
-        for (int k = 0; k < 8; k++)
-            if (!std::isfinite(p->edge_measurement[8 * (size_t)e + k])) return fail(ORBX_ERR_ARG, "essg_optimize: the measurement of edge %d is not finite", e);
-        if (!(p->edge_measurement[8 * (size_t)e + 7] > 0)) return fail(ORBX_ERR_ARG, "essg_optimize: the measurement of edge %d has a scale that is not positive", e);
+        if (a < 0 || a >= p->n_vertices || b < 0 || b >= p->n_vertices) return fail(ORBX_ERR_ARG, "%s: edge %d has a vertex index out of range", name, e);
+        if (a == b) return fail(ORBX_ERR_ARG, "%s: edge %d joins vertex %d to itself", name, e, a);
+        if ((rc = edge(e))) return rc;
     }
     for (int k = 0; k < p->n_points; k++) {
-        if (p->point_ref[k] < 0 || p->point_ref[k] >= p->n_vertices) return fail(ORBX_ERR_ARG, "essg_optimize: point %d has a reference index out of range", k);
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(p->points[3 * (size_t)k + a])) return fail(ORBX_ERR_ARG, "essg_optimize: point %d is not finite", k);
+        if (p->point_ref[k] < 0 || p->point_ref[k] >= p->n_vertices) return fail(ORBX_ERR_ARG, "%s: point %d has a reference index out of range", name, k);
+        if (!essg_finite(p->points + 3 * (size_t)k, 3)) return fail(ORBX_ERR_ARG, "%s: point %d is not finite", name, k);
     }
-    if (nf > ESSG_MAX_FREE_VERTICES) return fail(ORBX_ERR_CAPACITY, "essg_optimize: %d free vertices, capacity %d", nf, ESSG_MAX_FREE_VERTICES);
-    *n_free = nf;
+    if ((rc = last())) return rc;
+    if (nf > ESSG_MAX_FREE_VERTICES) return fail(ORBX_ERR_CAPACITY, "%s: %d free vertices, capacity %d", name, nf, ESSG_MAX_FREE_VERTICES);
+    if (n_free) *n_free = nf;
     return ORBX_OK;
+}
+
+// what a call holds besides its Dev: the system's size, the buffers both graphs use, the current estimate, the marks of its stages
+struct EssgCall {
+    const char* name;               // the entry point, for messages
+    int n = 0, nblk = 0;            // unknowns (even: the factorisation loads pairs of doubles), Cholesky blocks
+    size_t sys = 0;                 // doubles of S: (n + 1) x n
+    double *est[2] = {nullptr, nullptr}, *S = nullptr, *Lp = nullptr, *Linv = nullptr;
+    float *pts = nullptr, *pts_out = nullptr, *pose_q = nullptr, *pose_t = nullptr;
+    int* ref = nullptr;
+    int cur = 0;                    // est[cur] is the estimate
+    LbaStats stats{};
+    stage::Clock::time_point t_start = stage::Clock::now(), t_uploaded, t_solved;
+};
+
+// Structure + upload.  Sets the fields of d that do not depend on the model, reserves what they point to and the buffers of c
+// (the estimates `state` doubles a vertex, the records `rec` doubles an edge, the system n unknowns), uploads the structure
+// (pose_graph_structure.h), the edges' vertices and the points.  inputs(stream) reserves and enqueues the uploads of the model's
+// own arrays; the host arrays of either go out of use at the synchronisation that ends the stage.
+template <class Dev, class P, class Inputs>
+static int essg_stage(essg_solver* s, const P* p, int n, int state, int rec, Dev& d, EssgCall& c, Inputs&& inputs)
+{
+    using B = essg_solver;
+    int r = ORBX_OK;
+    if (!s) return (r = stage::check_device(0)) ? r : fail(ORBX_ERR_ARG, "%s: NULL solver", c.name);      // no device is an error of its own
+    ORBX_HIP(hipSetDevice(s->device));
+    const size_t nV = p->n_vertices, nE = p->n_edges, nP = p->n_points;
+    const pgraph::Structure g = pgraph::build_structure(p->n_vertices, p->fixed, p->n_edges, p->edge_vertices);
+    const size_t nF = g.n_free, nBlk = g.blk_i.size(), nEnt = g.blk_ent.size();
+    d.nV = (int)nV; d.nE = (int)nE; d.nF = (int)nF; d.n = n; d.nBlk = (int)nBlk; d.nP = (int)nP; d.scal = s->scal;
+    c.n = n; c.nblk = (n + chol::NB - 1) / chol::NB; c.sys = ((size_t)n + 1) * (size_t)n;
+    auto buf = [&](int which, size_t bytes, auto** out) { if (!r) r = essg_reserve(s, which, bytes, out); };
+    buf(B::kEstA, 8 * state * nV, &c.est[0]); buf(B::kEstB, 8 * state * nV, &c.est[1]); buf(B::kEv, 8 * nE, &d.ev); buf(B::kCol, 4 * nV, &d.col);
+    buf(B::kRecs, 8 * rec * nE, &d.rec); buf(B::kChi, 8 * nE, &d.chi_e); buf(B::kPart, 8 * nF, &d.part);
+    buf(B::kBlkI, 4 * nBlk, &d.blk_i); buf(B::kBlkJ, 4 * nBlk, &d.blk_j); buf(B::kBlkOff, 4 * (nBlk + 1), &d.blk_off); buf(B::kBlkEnt, 4 * nEnt, &d.blk_ent);
+    buf(B::kX, 8 * (size_t)n, &d.x); buf(B::kBfull, 8 * (size_t)n, &d.bfull); buf(B::kS, 8 * c.sys, &c.S);
+    if (c.nblk <= chol::kFusedMaxBlocks) buf(B::kLp, 8 * c.sys, &c.Lp);
+    buf(B::kLinv, 8 * (size_t)c.nblk * chol::NB * chol::NB, &c.Linv); buf(B::kPoseQ, 16 * nV, &c.pose_q); buf(B::kPoseT, 12 * nV, &c.pose_t);
+    if (nP > 0) { buf(B::kPts, 12 * nP, &c.pts); buf(B::kRef, 4 * nP, &c.ref); buf(B::kPtsOut, 12 * nP, &c.pts_out); }
+    if (r) return r;
+    hipStream_t st = s->stream;
+    if ((r = inputs(st))) return r;
+    if (nE > 0) ORBX_HIP(hipMemcpyAsync((void*)d.ev, p->edge_vertices, 8 * nE, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync((void*)d.col, g.col.data(), 4 * nV, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync((void*)d.blk_i, g.blk_i.data(), 4 * nBlk, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync((void*)d.blk_j, g.blk_j.data(), 4 * nBlk, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync((void*)d.blk_off, g.blk_off.data(), 4 * (nBlk + 1), hipMemcpyHostToDevice, st));
+    if (nEnt > 0) ORBX_HIP(hipMemcpyAsync((void*)d.blk_ent, g.blk_ent.data(), 4 * nEnt, hipMemcpyHostToDevice, st));
+    if (nP > 0) {
+        ORBX_HIP(hipMemcpyAsync(c.pts, p->points, 12 * nP, hipMemcpyHostToDevice, st));
+        ORBX_HIP(hipMemcpyAsync(c.ref, p->point_ref, 4 * nP, hipMemcpyHostToDevice, st));
+    }
+    ORBX_HIP(hipStreamSynchronize(st));         // the host vectors above go out of use here
+    c.t_uploaded = stage::Clock::now();
+    ORBX_HIP(hipEventRecord(s->ev0, st));
+    return ORBX_OK;
+}
+
+// The Levenberg rounds.  The model's launches on the solver's stream: linearize(est), reduce(what) (it publishes to s->hs under
+// the next sequence number), assemble(S, lambda), update_errors(lambda, est, est_new); first_what = what the reduction after the
+// first linearisation computes, lambda0(h) = the first lambda from its scalars.  Leaves c.cur, c.stats and c.t_solved.
+template <class Dev, class Linearize, class Reduce, class Assemble, class Update, class Lambda0>
+static int essg_levenberg(essg_solver* s, const Dev& d, EssgCall& c, int max_iters, const volatile uint8_t* stop_flag, int first_what,
+                          Linearize&& linearize, Reduce&& reduce, Assemble&& assemble, Update&& update_errors, Lambda0&& lambda0)
+{
+    hipStream_t st = s->stream;
+    int r;
+    double chi_cur = 0, lambda_first = 0;
+    bool have_chi = false;
+    lm::Levenberg ctl(max_iters);
+    while (!ctl.capped()) {
+        if (!ctl.begin_iteration(stop_flag && *stop_flag)) break;
+        if (d.nE > 0) linearize((const double*)c.est[c.cur]);
+        if (!have_chi) {        // later iterations start from an accepted trial, whose chi2 is the same sum of the same terms
+            reduce(first_what);
+            ORBX_HIP(hipGetLastError());
+            if ((r = s->hs.wait(st))) return r;
+            chi_cur = s->hs.h[0];
+            lambda_first = lambda0((const double*)s->hs.h);
+            have_chi = true;
+        }
+        ctl.linearized(chi_cur, lambda_first);
+        bool stopped = false;
+        do {
+            const double lambda = ctl.lambda();
+            ORBX_HIP(hipMemsetAsync(c.S, 0, 8 * c.sys, st));
+            assemble(c.S, lambda);
+            chol::enqueue_factor(st, c.S, c.Lp, c.n, c.nblk, c.Linv, d.scal, s->flow, &s->flow_epoch);
+            chol::enqueue_solve(st, c.S, c.Lp, c.n, c.nblk, c.Linv, d.x, d.scal);
+            update_errors(lambda, (const double*)c.est[c.cur], c.est[1 - c.cur]);
+            reduce(1);
+            ORBX_HIP(hipGetLastError());
+            if ((r = s->hs.wait(st))) return r;
+            const double* h = s->hs.h;
+            const lm::TrialStatus status = lm::trial_status(h[5]);
+            if (status == lm::TrialStatus::kStalled) return fail(ORBX_ERR_INTERNAL, "%s: the factorisation stalled (a spin wait between workgroups expired)", c.name);
+            if (ctl.trial(status == lm::TrialStatus::kSolved, h[0], h[3])) { c.cur = 1 - c.cur; chi_cur = h[0]; }
+            stopped = stop_flag && *stop_flag;
+        } while (ctl.more_trials(stopped));
+        if (!ctl.end_iteration()) break;
+    }
+    c.stats = ctl.stats();
+    c.t_solved = stage::Clock::now();
+    return ORBX_OK;
+}
+
+// after the epilogue launch: the end of the device work, the downloads (the model's own, then what both graphs return), the wait
+// for them, the times and the stats of the call
+struct EssgDownload { void* to; const void* from; size_t bytes; };
+template <class R>
+static int essg_finish(essg_solver* s, const EssgCall& c, size_t n_vertices, size_t n_points, R* res, std::initializer_list<EssgDownload> own)
+{
+    hipStream_t st = s->stream;
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(s->ev1, st));
+    for (const EssgDownload& x : own) ORBX_HIP(hipMemcpyAsync(x.to, x.from, x.bytes, hipMemcpyDeviceToHost, st));
+    if (res->pose_q) ORBX_HIP(hipMemcpyAsync(res->pose_q, c.pose_q, 16 * n_vertices, hipMemcpyDeviceToHost, st));
+    if (res->pose_t) ORBX_HIP(hipMemcpyAsync(res->pose_t, c.pose_t, 12 * n_vertices, hipMemcpyDeviceToHost, st));
+    if (n_points > 0) ORBX_HIP(hipMemcpyAsync(res->points_out, c.pts_out, 12 * n_points, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipStreamSynchronize(st));
+    float ms = 0;
+    ORBX_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->last_device_ms = ms;
+    s->stage_ms[0] = stage::ms(c.t_start, c.t_uploaded); s->stage_ms[1] = stage::ms(c.t_uploaded, c.t_solved); s->stage_ms[2] = stage::ms(c.t_solved, stage::Clock::now());
+    res->stats = c.stats;
+    return ORBX_OK;
+}
+
+static int essg_validate(const EssgProblem* p, const EssgResult* r, int* n_free)
+{
+    return essg_validate_graph("essg_optimize", p, r, n_free,
+        [&] { return !p->sim3 || !p->fixed ? "vertex arrays"
+                   : p->n_edges > 0 && (!p->edge_vertices || !p->edge_measurement) ? "edge arrays"
+                   : p->n_points > 0 && (!p->points || !p->point_ref) ? "point arrays"
+                   : !r->sim3_out ? "sim3_out" : (const char*)nullptr; },
+        [&] { return p->lambda_init > 0 && std::isfinite(p->lambda_init) ? ORBX_OK : fail(ORBX_ERR_ARG, "essg_optimize: lambda_init must be positive and finite"); },
+        [&](int v) { return essg_check_sim3("essg_optimize", p->sim3 + 8 * (size_t)v, "vertex", v); },
+        [&](int e) { return essg_check_sim3("essg_optimize", p->edge_measurement + 8 * (size_t)e, "the measurement of edge", e); },
+        [] { return (int)ORBX_OK; });
 }
 
 extern "C" {
@@ -299,11 +457,7 @@ int essg_create(int device, essg_solver** out)
 
 void essg_destroy(essg_solver* s) { stage::close(s); }
 
-int essg_check(const EssgProblem* p, const EssgResult* res)
-{
-    int nF = 0;
-    return essg_validate(p, res, &nF);
-}
+int essg_check(const EssgProblem* p, const EssgResult* res) { return essg_validate(p, res, nullptr); }
 
 double essg_last_device_ms(const essg_solver* s, double* stage_ms)
 {
@@ -317,130 +471,31 @@ int essg_optimize(essg_solver* s, const EssgProblem* p, EssgResult* res, const v
     int nF = 0;
     int r = essg_validate(p, res, &nF);
     if (r) return r;
-    if (!s) return (r = stage::check_device(0)) ? r : fail(ORBX_ERR_ARG, "essg_optimize: NULL solver");       // no device is an error of its own
-    const auto t_start = stage::Clock::now();
-    ORBX_HIP(hipSetDevice(s->device));
+    EssgCall c{"essg_optimize"};
     const int nV = p->n_vertices, nE = p->n_edges, nP = p->n_points;
-    // ---- structure: free-vertex columns and the block CSR (diagonal blocks first, then the off-diagonal ones in (row, column)
-    // order; inside a block the edges in their own order) ----
-    std::vector<int> col((size_t)nV);
-    for (int v = 0, c = 0; v < nV; v++) col[v] = p->fixed[v] ? -1 : c++;
-    std::vector<std::vector<int>> diag((size_t)nF);
-    std::vector<std::pair<std::pair<int, int>, int>> off;       // ((row, column), entry)
-    for (int e = 0; e < nE; e++) {
-        const int ci = col[p->edge_vertices[2 * (size_t)e]], cj = col[p->edge_vertices[2 * (size_t)e + 1]];
-        if (ci >= 0) diag[ci].push_back(4 * e);
-        if (cj >= 0) diag[cj].push_back(4 * e + 1);
-        if (ci >= 0 && cj >= 0) off.push_back(ci > cj ? std::make_pair(std::make_pair(ci, cj), 4 * e + 2) : std::make_pair(std::make_pair(cj, ci), 4 * e + 3));
-    }
-    std::stable_sort(off.begin(), off.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    std::vector<int> blk_i, blk_j, blk_off, blk_ent;
-    for (int c = 0; c < nF; c++) {
-        blk_i.push_back(c); blk_j.push_back(c); blk_off.push_back((int)blk_ent.size());
-        blk_ent.insert(blk_ent.end(), diag[c].begin(), diag[c].end());
-    }
-    for (size_t k = 0; k < off.size(); k++) {
-        if (k == 0 || off[k].first != off[k - 1].first) { blk_i.push_back(off[k].first.first); blk_j.push_back(off[k].first.second); blk_off.push_back((int)blk_ent.size()); }
-        blk_ent.push_back(off[k].second);
-    }
-    blk_off.push_back((int)blk_ent.size());
-    const int nBlk = (int)blk_i.size();
-    const int n = 7 * nF + ((7 * nF) & 1);
-    const int nblk = (n + chol::NB - 1) / chol::NB;
-    const bool fused = nblk <= chol::kFusedMaxBlocks;
-    const size_t sys = ((size_t)n + 1) * (size_t)n;
-
     essg::Dev d{};
-    d.nV = nV; d.nE = nE; d.nF = nF; d.n = n; d.nBlk = nBlk; d.nP = nP; d.fix_scale = p->fix_scale ? 1 : 0;
-    double *est0, *estA, *estB, *S, *Lp = nullptr, *Linv;
-    float *pts = nullptr, *pts_out = nullptr, *pose_q, *pose_t;
-    int* ref = nullptr;
-#define ESSG_BUF(which, bytes, ptr) do { void* q_ = nullptr; if ((r = essg_reserve(s, essg_solver::which, (bytes), &q_))) return r; ptr = (decltype(ptr))q_; } while (0)
-    ESSG_BUF(kEst0, 64 * (size_t)nV, est0); ESSG_BUF(kEstA, 64 * (size_t)nV, estA); ESSG_BUF(kEstB, 64 * (size_t)nV, estB);
-    ESSG_BUF(kMeas, 64 * (size_t)nE, d.meas); ESSG_BUF(kEv, 8 * (size_t)nE, d.ev); ESSG_BUF(kCol, 4 * (size_t)nV, d.col);
-    ESSG_BUF(kRecs, 8 * (size_t)essg::kRec * nE, d.rec); ESSG_BUF(kChi, 8 * (size_t)nE, d.chi_e); ESSG_BUF(kPart, 8 * (size_t)nF, d.part);
-    ESSG_BUF(kBlkI, 4 * (size_t)nBlk, d.blk_i); ESSG_BUF(kBlkJ, 4 * (size_t)nBlk, d.blk_j); ESSG_BUF(kBlkOff, 4 * ((size_t)nBlk + 1), d.blk_off);
-    ESSG_BUF(kBlkEnt, 4 * blk_ent.size(), d.blk_ent);
-    ESSG_BUF(kX, 8 * (size_t)n, d.x); ESSG_BUF(kBfull, 8 * (size_t)n, d.bfull);
-    ESSG_BUF(kS, 8 * sys, S);
-    if (fused) ESSG_BUF(kLp, 8 * sys, Lp);
-    ESSG_BUF(kLinv, 8 * (size_t)nblk * chol::NB * chol::NB, Linv);
-    ESSG_BUF(kPoseQ, 16 * (size_t)nV, pose_q); ESSG_BUF(kPoseT, 12 * (size_t)nV, pose_t);
-    if (nP > 0) { ESSG_BUF(kPts, 12 * (size_t)nP, pts); ESSG_BUF(kRef, 4 * (size_t)nP, ref); ESSG_BUF(kPtsOut, 12 * (size_t)nP, pts_out); }
-#undef ESSG_BUF
-    d.scal = s->scal;
+    d.fix_scale = p->fix_scale ? 1 : 0;
+    double* est0 = nullptr;
+    r = essg_stage(s, p, 7 * nF + ((7 * nF) & 1), 8, essg::kRec, d, c, [&](hipStream_t st) {
+        int q;
+        if ((q = essg_reserve(s, essg_solver::kEst0, 64 * (size_t)nV, &est0)) || (q = essg_reserve(s, essg_solver::kMeas, 64 * (size_t)nE, &d.meas))) return q;
+        ORBX_HIP(hipMemcpyAsync(est0, p->sim3, 64 * (size_t)nV, hipMemcpyHostToDevice, st));
+        ORBX_HIP(hipMemcpyAsync(c.est[0], est0, 64 * (size_t)nV, hipMemcpyDeviceToDevice, st));
+        if (nE > 0) ORBX_HIP(hipMemcpyAsync((void*)d.meas, p->edge_measurement, 64 * (size_t)nE, hipMemcpyHostToDevice, st));
+        return (int)ORBX_OK;
+    });
+    if (r) return r;
     hipStream_t st = s->stream;
-    ORBX_HIP(hipMemcpyAsync(est0, p->sim3, 64 * (size_t)nV, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync(estA, est0, 64 * (size_t)nV, hipMemcpyDeviceToDevice, st));
-    if (nE > 0) {
-        ORBX_HIP(hipMemcpyAsync((void*)d.meas, p->edge_measurement, 64 * (size_t)nE, hipMemcpyHostToDevice, st));
-        ORBX_HIP(hipMemcpyAsync((void*)d.ev, p->edge_vertices, 8 * (size_t)nE, hipMemcpyHostToDevice, st));
-    }
-    ORBX_HIP(hipMemcpyAsync((void*)d.col, col.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_i, blk_i.data(), 4 * (size_t)nBlk, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_j, blk_j.data(), 4 * (size_t)nBlk, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_off, blk_off.data(), 4 * ((size_t)nBlk + 1), hipMemcpyHostToDevice, st));
-    if (!blk_ent.empty()) ORBX_HIP(hipMemcpyAsync((void*)d.blk_ent, blk_ent.data(), 4 * blk_ent.size(), hipMemcpyHostToDevice, st));
-    if (nP > 0) {
-        ORBX_HIP(hipMemcpyAsync(pts, p->points, 12 * (size_t)nP, hipMemcpyHostToDevice, st));
-        ORBX_HIP(hipMemcpyAsync(ref, p->point_ref, 4 * (size_t)nP, hipMemcpyHostToDevice, st));
-    }
-    ORBX_HIP(hipStreamSynchronize(st));         // the host vectors above go out of use here
-    const auto t_uploaded = stage::Clock::now();
-    ORBX_HIP(hipEventRecord(s->ev0, st));
-
-    double* est[2] = {estA, estB};
-    int cur = 0;
-    double chi_cur = 0;
-    bool have_chi = false;
-    const dim3 items((std::max(nV, nE) + 255) / 256);
-    lm::Levenberg ctl(p->max_iters);
-    while (!ctl.capped()) {
-        if (!ctl.begin_iteration(stop_flag && *stop_flag)) break;
-        if (nE > 0) hipLaunchKernelGGL(essg::k_essg_linearize, dim3((nE + essg::kLinGroups - 1) / essg::kLinGroups), dim3(256), 0, st, d, (const double*)est[cur]);
-        if (!have_chi) {        // later iterations start from an accepted trial, whose chi2 is the same sum of the same terms
-            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 0, s->hs.d, ++s->hs.seq);
-            ORBX_HIP(hipGetLastError());
-            if ((r = s->hs.wait(st))) return r;
-            chi_cur = s->hs.h[0];
-            have_chi = true;
-        }
-        ctl.linearized(chi_cur, p->lambda_init);
-        bool stopped = false;
-        do {
-            const double lambda = ctl.lambda();
-            ORBX_HIP(hipMemsetAsync(S, 0, 8 * sys, st));
-            hipLaunchKernelGGL(essg::k_essg_assemble, dim3(nBlk + 1), dim3(64), 0, st, d, S, lambda);
-            chol::enqueue_factor(st, S, Lp, n, nblk, Linv, d.scal, s->flow, &s->flow_epoch);
-            chol::enqueue_solve(st, S, Lp, n, nblk, Linv, d.x, d.scal);
-            hipLaunchKernelGGL(essg::k_essg_update_errors, items, dim3(256), 0, st, d, lambda, (const double*)est[cur], est[1 - cur]);
-            hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, 1, s->hs.d, ++s->hs.seq);
-            ORBX_HIP(hipGetLastError());
-            if ((r = s->hs.wait(st))) return r;
-            const double* h = s->hs.h;
-            const lm::TrialStatus status = lm::trial_status(h[5]);
-            if (status == lm::TrialStatus::kStalled) return fail(ORBX_ERR_INTERNAL, "essg_optimize: the factorisation stalled (a spin wait between workgroups expired)");
-            if (ctl.trial(status == lm::TrialStatus::kSolved, h[0], h[3])) { cur = 1 - cur; chi_cur = h[0]; }
-            stopped = stop_flag && *stop_flag;
-        } while (ctl.more_trials(stopped));
-        if (!ctl.end_iteration()) break;
-    }
-    const auto t_solved = stage::Clock::now();
-    hipLaunchKernelGGL(essg::k_essg_epilogue, dim3((std::max(nV, nP) + 255) / 256), dim3(256), 0, st, d, (const double*)est0, (const double*)est[cur],
-                       pose_q, pose_t, (const float*)pts, (const int*)ref, pts_out);
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(s->ev1, st));
-    ORBX_HIP(hipMemcpyAsync(res->sim3_out, est[cur], 64 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (res->pose_q) ORBX_HIP(hipMemcpyAsync(res->pose_q, pose_q, 16 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (res->pose_t) ORBX_HIP(hipMemcpyAsync(res->pose_t, pose_t, 12 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (nP > 0) ORBX_HIP(hipMemcpyAsync(res->points_out, pts_out, 12 * (size_t)nP, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    float ms = 0;
-    ORBX_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    s->last_device_ms = ms;
-    s->stage_ms[0] = stage::ms(t_start, t_uploaded); s->stage_ms[1] = stage::ms(t_uploaded, t_solved); s->stage_ms[2] = stage::ms(t_solved, stage::Clock::now());
-    res->stats = ctl.stats();
-    return ORBX_OK;
+    r = essg_levenberg(s, d, c, p->max_iters, stop_flag, 0,
+        [&](const double* est) { hipLaunchKernelGGL(essg::k_essg_linearize, dim3((nE + essg::kLinGroups - 1) / essg::kLinGroups), dim3(256), 0, st, d, est); },
+        [&](int what) { hipLaunchKernelGGL(essg::k_essg_reduce, dim3(1), dim3(1024), 0, st, d, what, s->hs.d, ++s->hs.seq); },
+        [&](double* S, double lambda) { hipLaunchKernelGGL(essg::k_essg_assemble, dim3(d.nBlk + 1), dim3(64), 0, st, d, S, lambda); },
+        [&](double lambda, const double* est, double* est_new) { hipLaunchKernelGGL(essg::k_essg_update_errors, dim3((std::max(nV, nE) + 255) / 256), dim3(256), 0, st, d, lambda, est, est_new); },
+        [&](const double*) { return p->lambda_init; });
+    if (r) return r;
+    hipLaunchKernelGGL(essg::k_essg_epilogue, dim3((std::max(nV, nP) + 255) / 256), dim3(256), 0, st, d, (const double*)est0, (const double*)c.est[c.cur],
+                       c.pose_q, c.pose_t, (const float*)c.pts, (const int*)c.ref, c.pts_out);
+    return essg_finish(s, c, nV, nP, res, {{res->sim3_out, c.est[c.cur], 64 * (size_t)nV}});
 }
 
 }  // extern "C"

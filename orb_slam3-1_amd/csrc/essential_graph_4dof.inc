@@ -1,6 +1,8 @@
 // essential_graph_4dof.inc -- the pose graph of loop closing in an inertial map: Optimizer::OptimizeEssentialGraph4DoF (reference
 // src/Optimizer.cc:5292-5588) between "the graph is built" and "the map is written back".  Included by lba_solver.hip right
-// after essential_graph.inc, whose handle (essg_solver: stream, scratch buffers, host-mapped scalars, flow flags) it shares.
+// after essential_graph.inc, whose handle (essg_solver: stream, scratch buffers, host-mapped scalars, flow flags) and whose host
+// driver (essg_validate_graph, essg_stage, essg_levenberg, essg_finish) it shares: here are the kernels, their Dev, the packing
+// of the inputs and the checks of this model alone.
 //
 // Every vertex is a VertexPose4DoF (yaw about the world's z and a world-frame translation of the body: 4 unknowns), every edge
 // an Edge4DoF (6 error components, one information matrix for all, no robust kernel, g2o's numeric Jacobian).  H is a symmetric
@@ -10,8 +12,8 @@
 // One Levenberg trial:  memset S -> k_essg4_assemble(lambda) -> factorisation -> k_chol_solve -> k_essg4_update_errors ->
 // k_essg4_reduce -> the host reads chi2, dx^T (lambda dx + b) and the failure flag and lm::Levenberg decides.
 // One linearisation: k_essg4_linearize writes a record per edge (no atomics); the assembly sums a block's records in the order of
-// a CSR the host builds once per call.  The first linearisation's reduction also returns max diag H, from which lambda_0 comes
-// when the caller sets none (computeLambdaInit: the reference sets no user lambda here).
+// a CSR the host builds once per call (pose_graph_structure.h).  The first linearisation's reduction also returns max diag H,
+// from which lambda_0 comes when the caller sets none (computeLambdaInit: the reference sets no user lambda here).
 
 #include "pose4dof_group.h"
 
@@ -224,105 +226,53 @@ __global__ __launch_bounds__(256) void k_essg4_epilogue(Dev d, const double* __r
 
 }  // namespace essg4
 
-// every check of the header, before anything touches a device; *n_free = number of free vertices
 static int essg4_validate(const Essg4DofProblem* p, const Essg4DofResult* r, int* n_free)
 {
-    if (!p) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL problem");
-    if (!r) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL result");
-    if (p->n_vertices < 1 || p->n_edges < 0 || p->n_points < 0) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: bad problem sizes");
-    if (!p->rcw || !p->tcw || !p->rwb || !p->twb || !p->rcb || !p->tcb || !p->fixed) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL vertex arrays");
-    if (p->n_edges > 0 && (!p->edge_vertices || !p->edge_rot || !p->edge_trans)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL edge arrays");
-    if (p->n_points > 0 && (!p->points || !p->point_ref || !p->scw)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL point arrays");
-    if (!r->rcw_out || !r->tcw_out) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL rcw_out / tcw_out");
-    if (p->n_points > 0 && !r->points_out) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL points_out");
-    if (p->max_iters < 0) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: max_iters %d is negative", p->max_iters);
-    if (!std::isfinite(p->lambda_init)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: lambda_init is not finite");
-    for (int a = 0; a < 6; a++) {
-        for (int b = 0; b < 6; b++) {
-            if (!std::isfinite(p->information[6 * a + b])) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix is not finite");
-            if (p->information[6 * a + b] != p->information[6 * b + a]) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix is not symmetric");
-        }
-        if (!(p->information[7 * a] > 0)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix has a diagonal entry that is not positive");
-    }
-    int nf = 0;
-    for (int v = 0; v < p->n_vertices; v++) {
-        bool ok = true;
-        for (int k = 0; k < 9; k++) ok = ok && std::isfinite(p->rcw[9 * (size_t)v + k]) && std::isfinite(p->rwb[9 * (size_t)v + k]) && std::isfinite(p->rcb[9 * (size_t)v + k]);
-        for (int k = 0; k < 3; k++) ok = ok && std::isfinite(p->tcw[3 * (size_t)v + k]) && std::isfinite(p->twb[3 * (size_t)v + k]) && std::isfinite(p->tcb[3 * (size_t)v + k]);
-        if (!ok) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: vertex %d is not finite", v);
-        nf += p->fixed[v] ? 0 : 1;
-    }
-    if (nf == 0) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: no free vertex");
-    for (int e = 0; e < p->n_edges; e++) {
-        const int a = p->edge_vertices[2 * (size_t)e], b = p->edge_vertices[2 * (size_t)e + 1];
-        if (a < 0 || a >= p->n_vertices || b < 0 || b >= p->n_vertices) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: edge %d has a vertex index out of range", e);
-        if (a == b) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: edge %d joins vertex %d to itself", e, a);
-        bool ok = true;
-        for (int k = 0; k < 9; k++) ok = ok && std::isfinite(p->edge_rot[9 * (size_t)e + k]);
-        for (int k = 0; k < 3; k++) ok = ok && std::isfinite(p->edge_trans[3 * (size_t)e + k]);
-        if (!ok) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the measurement of edge %d is not finite", e);
-    }
-    for (int k = 0; k < p->n_points; k++) {
-        if (p->point_ref[k] < 0 || p->point_ref[k] >= p->n_vertices) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: point %d has a reference index out of range", k);
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(p->points[3 * (size_t)k + a])) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: point %d is not finite", k);
-    }
-    if (p->n_points > 0)
-        for (int v = 0; v < p->n_vertices; v++) {
-            for (int k = 0; k < 8; k++)
-                if (!std::isfinite(p->scw[8 * (size_t)v + k])) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: scw of vertex %d is not finite", v);
-            if (!(p->scw[8 * (size_t)v + 7] > 0)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: scw of vertex %d has a scale that is not positive", v);
-        }
-    if (nf > ESSG_MAX_FREE_VERTICES) return fail(ORBX_ERR_CAPACITY, "essg_optimize_4dof: %d free vertices, capacity %d", nf, ESSG_MAX_FREE_VERTICES);
-    *n_free = nf;
-    return ORBX_OK;
+    return essg_validate_graph("essg_optimize_4dof", p, r, n_free,
+        [&] { return !p->rcw || !p->tcw || !p->rwb || !p->twb || !p->rcb || !p->tcb || !p->fixed ? "vertex arrays"
+                   : p->n_edges > 0 && (!p->edge_vertices || !p->edge_rot || !p->edge_trans) ? "edge arrays"
+                   : p->n_points > 0 && (!p->points || !p->point_ref || !p->scw) ? "point arrays"
+                   : !r->rcw_out || !r->tcw_out ? "rcw_out / tcw_out" : (const char*)nullptr; },
+        [&] {
+            if (!std::isfinite(p->lambda_init)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: lambda_init is not finite");
+            for (int a = 0; a < 6; a++) {
+                for (int b = 0; b < 6; b++) {
+                    if (!std::isfinite(p->information[6 * a + b])) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix is not finite");
+                    if (p->information[6 * a + b] != p->information[6 * b + a]) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix is not symmetric");
+                }
+                if (!(p->information[7 * a] > 0)) return fail(ORBX_ERR_ARG, "essg_optimize_4dof: the information matrix has a diagonal entry that is not positive");
+            }
+            return (int)ORBX_OK;
+        },
+        [&](int v) {
+            const size_t v3 = 3 * (size_t)v, v9 = 9 * (size_t)v;
+            const bool ok = essg_finite(p->rcw + v9, 9) && essg_finite(p->rwb + v9, 9) && essg_finite(p->rcb + v9, 9) &&
+                            essg_finite(p->tcw + v3, 3) && essg_finite(p->twb + v3, 3) && essg_finite(p->tcb + v3, 3);
+            return ok ? ORBX_OK : fail(ORBX_ERR_ARG, "essg_optimize_4dof: vertex %d is not finite", v);
+        },
+        [&](int e) {
+            const bool ok = essg_finite(p->edge_rot + 9 * (size_t)e, 9) && essg_finite(p->edge_trans + 3 * (size_t)e, 3);
+            return ok ? ORBX_OK : fail(ORBX_ERR_ARG, "essg_optimize_4dof: the measurement of edge %d is not finite", e);
+        },
+        [&] {
+            int rc = ORBX_OK;
+            for (int v = 0; v < p->n_vertices && p->n_points > 0 && !rc; v++) rc = essg_check_sim3("essg_optimize_4dof", p->scw + 8 * (size_t)v, "scw of vertex", v);
+            return rc;
+        });
 }
 
 extern "C" {
 
-int essg_check_4dof(const Essg4DofProblem* p, const Essg4DofResult* res)
-{
-    int nF = 0;
-    return essg4_validate(p, res, &nF);
-}
+int essg_check_4dof(const Essg4DofProblem* p, const Essg4DofResult* res) { return essg4_validate(p, res, nullptr); }
 
 int essg_optimize_4dof(essg_solver* s, const Essg4DofProblem* p, Essg4DofResult* res, const volatile uint8_t* stop_flag)
 {
     int nF = 0;
     int r = essg4_validate(p, res, &nF);
     if (r) return r;
-    if (!s) return (r = stage::check_device(0)) ? r : fail(ORBX_ERR_ARG, "essg_optimize_4dof: NULL solver");
-    const auto t_start = stage::Clock::now();
-    ORBX_HIP(hipSetDevice(s->device));
+    EssgCall c{"essg_optimize_4dof"};
     const int nV = p->n_vertices, nE = p->n_edges, nP = p->n_points;
     constexpr int kState = essg4::kState, kConst = essg4::kConst;
-    // ---- structure: free-vertex columns and the block CSR, as essg_optimize builds them ----
-    std::vector<int> col((size_t)nV);
-    for (int v = 0, c = 0; v < nV; v++) col[v] = p->fixed[v] ? -1 : c++;
-    std::vector<std::vector<int>> diag((size_t)nF);
-    std::vector<std::pair<std::pair<int, int>, int>> off;       // ((row, column), entry)
-    for (int e = 0; e < nE; e++) {
-        const int ci = col[p->edge_vertices[2 * (size_t)e]], cj = col[p->edge_vertices[2 * (size_t)e + 1]];
-        if (ci >= 0) diag[ci].push_back(4 * e);
-        if (cj >= 0) diag[cj].push_back(4 * e + 1);
-        if (ci >= 0 && cj >= 0) off.push_back(ci > cj ? std::make_pair(std::make_pair(ci, cj), 4 * e + 2) : std::make_pair(std::make_pair(cj, ci), 4 * e + 3));
-    }
-    std::stable_sort(off.begin(), off.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    std::vector<int> blk_i, blk_j, blk_off, blk_ent;
-    for (int c = 0; c < nF; c++) {
-        blk_i.push_back(c); blk_j.push_back(c); blk_off.push_back((int)blk_ent.size());
-        blk_ent.insert(blk_ent.end(), diag[c].begin(), diag[c].end());
-    }
-    for (size_t k = 0; k < off.size(); k++) {
-        if (k == 0 || off[k].first != off[k - 1].first) { blk_i.push_back(off[k].first.first); blk_j.push_back(off[k].first.second); blk_off.push_back((int)blk_ent.size()); }
-        blk_ent.push_back(off[k].second);
-    }
-    blk_off.push_back((int)blk_ent.size());
-    const int nBlk = (int)blk_i.size();
-    const int n = 4 * nF;
-    const int nblk = (n + chol::NB - 1) / chol::NB;
-    const bool fused = nblk <= chol::kFusedMaxBlocks;
-    const size_t sys = ((size_t)n + 1) * (size_t)n;
     // ---- the vertices as the kernels take them: the estimate (DR = I, its = 0) and what stays constant; the edges' dRij | dtij ----
     std::vector<double> state((size_t)nV * kState), konst((size_t)nV * kConst), meas((size_t)nE * 12);
     for (int v = 0; v < nV; v++) {
@@ -336,103 +286,34 @@ int essg_optimize_4dof(essg_solver* s, const Essg4DofProblem* p, Essg4DofResult*
         for (int k = 0; k < 9; k++) meas[12 * (size_t)e + k] = p->edge_rot[9 * (size_t)e + k];
         for (int k = 0; k < 3; k++) meas[12 * (size_t)e + 9 + k] = p->edge_trans[3 * (size_t)e + k];
     }
-
     essg4::Dev d{};
-    d.nV = nV; d.nE = nE; d.nF = nF; d.n = n; d.nBlk = nBlk; d.nP = nP;
     for (int k = 0; k < 36; k++) d.W[k] = p->information[k];
-    double *estA, *estB, *S, *Lp = nullptr, *Linv, *scw = nullptr, *rcw_out, *tcw_out;
-    float *pts = nullptr, *pts_out = nullptr, *pose_q, *pose_t;
-    int* ref = nullptr;
-#define ESSG_BUF(which, bytes, ptr) do { void* q_ = nullptr; if ((r = essg_reserve(s, essg_solver::which, (bytes), &q_))) return r; ptr = (decltype(ptr))q_; } while (0)
-    ESSG_BUF(kEstA, 8 * state.size(), estA); ESSG_BUF(kEstB, 8 * state.size(), estB); ESSG_BUF(kConst4, 8 * konst.size(), d.konst);
-    ESSG_BUF(kMeas, 8 * meas.size(), d.meas); ESSG_BUF(kEv, 8 * (size_t)nE, d.ev); ESSG_BUF(kCol, 4 * (size_t)nV, d.col);
-    ESSG_BUF(kRecs, 8 * (size_t)essg4::kRec * nE, d.rec); ESSG_BUF(kChi, 8 * (size_t)nE, d.chi_e); ESSG_BUF(kPart, 8 * (size_t)nF, d.part);
-    ESSG_BUF(kBlkI, 4 * (size_t)nBlk, d.blk_i); ESSG_BUF(kBlkJ, 4 * (size_t)nBlk, d.blk_j); ESSG_BUF(kBlkOff, 4 * ((size_t)nBlk + 1), d.blk_off);
-    ESSG_BUF(kBlkEnt, 4 * blk_ent.size(), d.blk_ent);
-    ESSG_BUF(kX, 8 * (size_t)n, d.x); ESSG_BUF(kBfull, 8 * (size_t)n, d.bfull);
-    ESSG_BUF(kS, 8 * sys, S);
-    if (fused) ESSG_BUF(kLp, 8 * sys, Lp);
-    ESSG_BUF(kLinv, 8 * (size_t)nblk * chol::NB * chol::NB, Linv);
-    ESSG_BUF(kRcwOut4, 72 * (size_t)nV, rcw_out); ESSG_BUF(kTcwOut4, 24 * (size_t)nV, tcw_out);
-    ESSG_BUF(kPoseQ, 16 * (size_t)nV, pose_q); ESSG_BUF(kPoseT, 12 * (size_t)nV, pose_t);
-    if (nP > 0) { ESSG_BUF(kPts, 12 * (size_t)nP, pts); ESSG_BUF(kRef, 4 * (size_t)nP, ref); ESSG_BUF(kPtsOut, 12 * (size_t)nP, pts_out); ESSG_BUF(kScw4, 64 * (size_t)nV, scw); }
-#undef ESSG_BUF
-    d.scal = s->scal;
+    double *scw = nullptr, *rcw_out = nullptr, *tcw_out = nullptr;
+    r = essg_stage(s, p, 4 * nF, kState, essg4::kRec, d, c, [&](hipStream_t st) {
+        using B = essg_solver;
+        int q;
+        if ((q = essg_reserve(s, B::kConst4, 8 * konst.size(), &d.konst)) || (q = essg_reserve(s, B::kMeas, 8 * meas.size(), &d.meas)) ||
+            (q = essg_reserve(s, B::kRcwOut4, 72 * (size_t)nV, &rcw_out)) || (q = essg_reserve(s, B::kTcwOut4, 24 * (size_t)nV, &tcw_out)) ||
+            (nP > 0 && (q = essg_reserve(s, B::kScw4, 64 * (size_t)nV, &scw))))
+            return q;
+        ORBX_HIP(hipMemcpyAsync(c.est[0], state.data(), 8 * state.size(), hipMemcpyHostToDevice, st));
+        ORBX_HIP(hipMemcpyAsync((void*)d.konst, konst.data(), 8 * konst.size(), hipMemcpyHostToDevice, st));
+        if (nE > 0) ORBX_HIP(hipMemcpyAsync((void*)d.meas, meas.data(), 8 * meas.size(), hipMemcpyHostToDevice, st));
+        if (nP > 0) ORBX_HIP(hipMemcpyAsync(scw, p->scw, 64 * (size_t)nV, hipMemcpyHostToDevice, st));
+        return (int)ORBX_OK;
+    });
+    if (r) return r;
     hipStream_t st = s->stream;
-    ORBX_HIP(hipMemcpyAsync(estA, state.data(), 8 * state.size(), hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.konst, konst.data(), 8 * konst.size(), hipMemcpyHostToDevice, st));
-    if (nE > 0) {
-        ORBX_HIP(hipMemcpyAsync((void*)d.meas, meas.data(), 8 * meas.size(), hipMemcpyHostToDevice, st));
-        ORBX_HIP(hipMemcpyAsync((void*)d.ev, p->edge_vertices, 8 * (size_t)nE, hipMemcpyHostToDevice, st));
-    }
-    ORBX_HIP(hipMemcpyAsync((void*)d.col, col.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_i, blk_i.data(), 4 * (size_t)nBlk, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_j, blk_j.data(), 4 * (size_t)nBlk, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipMemcpyAsync((void*)d.blk_off, blk_off.data(), 4 * ((size_t)nBlk + 1), hipMemcpyHostToDevice, st));
-    if (!blk_ent.empty()) ORBX_HIP(hipMemcpyAsync((void*)d.blk_ent, blk_ent.data(), 4 * blk_ent.size(), hipMemcpyHostToDevice, st));
-    if (nP > 0) {
-        ORBX_HIP(hipMemcpyAsync(pts, p->points, 12 * (size_t)nP, hipMemcpyHostToDevice, st));
-        ORBX_HIP(hipMemcpyAsync(ref, p->point_ref, 4 * (size_t)nP, hipMemcpyHostToDevice, st));
-        ORBX_HIP(hipMemcpyAsync(scw, p->scw, 64 * (size_t)nV, hipMemcpyHostToDevice, st));
-    }
-    ORBX_HIP(hipStreamSynchronize(st));         // the host vectors above go out of use here
-    const auto t_uploaded = stage::Clock::now();
-    ORBX_HIP(hipEventRecord(s->ev0, st));
-
-    double* est[2] = {estA, estB};
-    int cur = 0;
-    double chi_cur = 0, lambda0 = p->lambda_init;
-    bool have_chi = false;
-    const dim3 items((std::max(nV, nE) + 255) / 256);
-    lm::Levenberg ctl(p->max_iters);
-    while (!ctl.capped()) {
-        if (!ctl.begin_iteration(stop_flag && *stop_flag)) break;
-        if (nE > 0) hipLaunchKernelGGL(essg4::k_essg4_linearize, dim3((nE + essg4::kLinGroups - 1) / essg4::kLinGroups), dim3(256), 0, st, d, (const double*)est[cur]);
-        if (!have_chi) {        // later iterations start from an accepted trial, whose chi2 is the same sum of the same terms
-            hipLaunchKernelGGL(essg4::k_essg4_reduce, dim3(1), dim3(1024), 0, st, d, 2, s->hs.d, ++s->hs.seq);
-            ORBX_HIP(hipGetLastError());
-            if ((r = s->hs.wait(st))) return r;
-            chi_cur = s->hs.h[0];
-            lambda0 = lm::initial_lambda(p->lambda_init, s->hs.h[4], 0.0);
-            have_chi = true;
-        }
-        ctl.linearized(chi_cur, lambda0);
-        bool stopped = false;
-        do {
-            const double lambda = ctl.lambda();
-            ORBX_HIP(hipMemsetAsync(S, 0, 8 * sys, st));
-            hipLaunchKernelGGL(essg4::k_essg4_assemble, dim3((nBlk + essg4::kAsmSlots - 1) / essg4::kAsmSlots), dim3(256), 0, st, d, S, lambda);
-            chol::enqueue_factor(st, S, Lp, n, nblk, Linv, d.scal, s->flow, &s->flow_epoch);
-            chol::enqueue_solve(st, S, Lp, n, nblk, Linv, d.x, d.scal);
-            hipLaunchKernelGGL(essg4::k_essg4_update_errors, items, dim3(256), 0, st, d, lambda, (const double*)est[cur], est[1 - cur]);
-            hipLaunchKernelGGL(essg4::k_essg4_reduce, dim3(1), dim3(1024), 0, st, d, 1, s->hs.d, ++s->hs.seq);
-            ORBX_HIP(hipGetLastError());
-            if ((r = s->hs.wait(st))) return r;
-            const double* h = s->hs.h;
-            const lm::TrialStatus status = lm::trial_status(h[5]);
-            if (status == lm::TrialStatus::kStalled) return fail(ORBX_ERR_INTERNAL, "essg_optimize_4dof: the factorisation stalled (a spin wait between workgroups expired)");
-            if (ctl.trial(status == lm::TrialStatus::kSolved, h[0], h[3])) { cur = 1 - cur; chi_cur = h[0]; }
-            stopped = stop_flag && *stop_flag;
-        } while (ctl.more_trials(stopped));
-        if (!ctl.end_iteration()) break;
-    }
-    const auto t_solved = stage::Clock::now();
-    hipLaunchKernelGGL(essg4::k_essg4_epilogue, dim3((std::max(nV, nP) + 255) / 256), dim3(256), 0, st, d, (const double*)est[cur], (const double*)scw,
-                       rcw_out, tcw_out, pose_q, pose_t, (const float*)pts, (const int*)ref, pts_out);
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(s->ev1, st));
-    ORBX_HIP(hipMemcpyAsync(res->rcw_out, rcw_out, 72 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipMemcpyAsync(res->tcw_out, tcw_out, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (res->pose_q) ORBX_HIP(hipMemcpyAsync(res->pose_q, pose_q, 16 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (res->pose_t) ORBX_HIP(hipMemcpyAsync(res->pose_t, pose_t, 12 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    if (nP > 0) ORBX_HIP(hipMemcpyAsync(res->points_out, pts_out, 12 * (size_t)nP, hipMemcpyDeviceToHost, st));
-    ORBX_HIP(hipStreamSynchronize(st));
-    float ms = 0;
-    ORBX_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    s->last_device_ms = ms;
-    s->stage_ms[0] = stage::ms(t_start, t_uploaded); s->stage_ms[1] = stage::ms(t_uploaded, t_solved); s->stage_ms[2] = stage::ms(t_solved, stage::Clock::now());
-    res->stats = ctl.stats();
-    return ORBX_OK;
+    r = essg_levenberg(s, d, c, p->max_iters, stop_flag, 2,
+        [&](const double* est) { hipLaunchKernelGGL(essg4::k_essg4_linearize, dim3((nE + essg4::kLinGroups - 1) / essg4::kLinGroups), dim3(256), 0, st, d, est); },
+        [&](int what) { hipLaunchKernelGGL(essg4::k_essg4_reduce, dim3(1), dim3(1024), 0, st, d, what, s->hs.d, ++s->hs.seq); },
+        [&](double* S, double lambda) { hipLaunchKernelGGL(essg4::k_essg4_assemble, dim3((d.nBlk + essg4::kAsmSlots - 1) / essg4::kAsmSlots), dim3(256), 0, st, d, S, lambda); },
+        [&](double lambda, const double* est, double* est_new) { hipLaunchKernelGGL(essg4::k_essg4_update_errors, dim3((std::max(nV, nE) + 255) / 256), dim3(256), 0, st, d, lambda, est, est_new); },
+        [&](const double* h) { return lm::initial_lambda(p->lambda_init, h[4], 0.0); });      // max diag H of the first linearisation
+    if (r) return r;
+    hipLaunchKernelGGL(essg4::k_essg4_epilogue, dim3((std::max(nV, nP) + 255) / 256), dim3(256), 0, st, d, (const double*)c.est[c.cur], (const double*)scw,
+                       rcw_out, tcw_out, c.pose_q, c.pose_t, (const float*)c.pts, (const int*)c.ref, c.pts_out);
+    return essg_finish(s, c, nV, nP, res, {{res->rcw_out, rcw_out, 72 * (size_t)nV}, {res->tcw_out, tcw_out, 24 * (size_t)nV}});
 }
 
 }  // extern "C"

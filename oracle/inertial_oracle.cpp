@@ -580,8 +580,8 @@ extern "C" double inertial_oracle_jacobian_check(const OracleInertialProblem* P,
  * an outlier edge is recomputed at the current state (:4723-4726).  GROUNDWORK: oracle only, no HIP path yet.  PARITY UNPINNED.
  * Deviation: if the dense solve fails the round stops without applying an update (g2o applies the stale solution vector).
  * --------------------------------------------------------------------------------------------------------------------------- */
-extern "C" int pose_inertial_oracle_optimize(const OraclePoseInertialProblem* P, double* Rwb_out, double* twb_out, double* vel_out,
-                                             double* bg_out, double* ba_out, uint8_t* outlier, double* H15_out, int* n_bad_out)
+static int pose_inertial_optimize(const OraclePoseInertialProblem* P, double* Rwb_out, double* twb_out, double* vel_out,
+                                  double* bg_out, double* ba_out, uint8_t* outlier, double* H15_out, int* n_bad_out, double* prev_out)
 {
     Problem pr;
     OracleInertialProblem dummy;
@@ -827,5 +827,23 @@ extern "C" int pose_inertial_oracle_optimize(const OraclePoseInertialProblem* P,
     std::memcpy(Rwb_out, F.Rwb, 72); std::memcpy(twb_out, F.twb, 24); std::memcpy(vel_out, F.v, 24); std::memcpy(bg_out, F.bg, 24); std::memcpy(ba_out, F.ba, 24);
     if (H15_out) std::memcpy(H15_out, Hout, sizeof(double) * N * N);     /* 15 x 15, or 30 x 30 (before Optimizer::Marginalize) for the last-frame variant */
     if (n_bad_out) *n_bad_out = nBad;
+    if (prev_out) {                                          /* the state at which the last-frame variant's H is linearised: Rwb twb v bg ba */
+        std::memcpy(prev_out, K0.Rwb, 72); std::memcpy(prev_out + 9, K0.twb, 24); std::memcpy(prev_out + 12, K0.v, 24);
+        std::memcpy(prev_out + 15, K0.bg, 24); std::memcpy(prev_out + 18, K0.ba, 24);
+    }
     return n - nBad;
+}
+
+extern "C" int pose_inertial_oracle_optimize(const OraclePoseInertialProblem* P, double* Rwb_out, double* twb_out, double* vel_out,
+                                             double* bg_out, double* ba_out, uint8_t* outlier, double* H15_out, int* n_bad_out)
+{
+    return pose_inertial_optimize(P, Rwb_out, twb_out, vel_out, bg_out, ba_out, outlier, H15_out, n_bad_out, nullptr);
+}
+
+/* the same, and the final state of frame [0] (21 doubles: Rwb, twb, vel, bg, ba): the product ABI does not return it, the tests of the
+ * last-frame variant's Hessian need it */
+extern "C" int pose_inertial_oracle_optimize_prev(const OraclePoseInertialProblem* P, double* Rwb_out, double* twb_out, double* vel_out,
+                                                  double* bg_out, double* ba_out, uint8_t* outlier, double* H15_out, int* n_bad_out, double* prev_out)
+{
+    return pose_inertial_optimize(P, Rwb_out, twb_out, vel_out, bg_out, ba_out, outlier, H15_out, n_bad_out, prev_out);
 }

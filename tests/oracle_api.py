@@ -564,8 +564,11 @@ def oracle_pose_inertial_optimize(orc, pr):
     Rwb = np.zeros((3, 3)); twb = np.zeros(3); vel = np.zeros(3); bg = np.zeros(3); ba = np.zeros(3)
     N = 30 if s.last_frame else 15
     out = np.zeros(max(n, 1), np.uint8); H = np.zeros((N, N)); nb = C.c_int()
-    r = orc.lib.pose_inertial_oracle_optimize(C.byref(s), _p(Rwb), _p(twb), _p(vel), _p(bg), _p(ba), _p(out), _p(H), C.byref(nb))
-    return dict(Rwb=Rwb, twb=twb, vel=vel, bg=bg, ba=ba, outlier=out[:n], H=H, n_bad=nb.value, inliers=r)
+    prev = np.zeros(21)
+    r = orc.lib.pose_inertial_oracle_optimize_prev(C.byref(s), _p(Rwb), _p(twb), _p(vel), _p(bg), _p(ba), _p(out), _p(H), C.byref(nb), _p(prev))
+    # prev: frame [0]'s final state (it moves only in the last-frame variant); the product ABI has no such output
+    return dict(Rwb=Rwb, twb=twb, vel=vel, bg=bg, ba=ba, outlier=out[:n], H=H, n_bad=nb.value, inliers=r,
+                prev=dict(Rwb=prev[:9].reshape(3, 3).copy(), twb=prev[9:12].copy(), vel=prev[12:15].copy(), bg=prev[15:18].copy(), ba=prev[18:21].copy()))
 
 
 def oracle_undistort(orc, kps, K, dist, Knew):

@@ -1,7 +1,8 @@
 """LocalInertialBA restatement (oracle/inertial_oracle.cpp; reference src/Optimizer.cc:2383-2958, src/G2oTypes.cc) -- GROUNDWORK:
 there is no HIP counterpart yet.  PARITY UNPINNED; what can be checked without the reference is checked here: the restated
 analytic Jacobians of EdgeInertial against central differences through the restated update rule, that consistent data is a
-fixed point, and that a perturbed window converges back to the ground truth."""
+fixed point, and that a perturbed window converges back to the ground truth.  The 5e-3 of the Jacobian check here is as tight as the
+float getters allow; the tight check (1e-10, long double, smooth getters) is tests/test_dense_inertial_reference.py."""
 import os
 
 import numpy as np

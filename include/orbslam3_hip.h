@@ -965,6 +965,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 /* ---- pose graph of an inertial map: Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5292-5588) on the same handle:
  * Essg4DofProblem, Essg4DofResult and the two entry points that take them, documented where they are declared ---- */
 #include "orbslam3_hip_4dof.h"
+#include "orbslam3_hip_imu_init.h"
 
 #ifdef __cplusplus
 }

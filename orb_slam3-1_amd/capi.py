@@ -1680,3 +1680,106 @@ class EssentialGraph:
         st = (C.c_double * 3)()
         ms = lib.essg_last_device_ms(self._h, st)
         return ms, dict(structure_upload=st[0], rounds=st[1], epilogue_download=st[2])
+
+
+# ---- IMU initialisation: the three Optimizer::InertialOptimization overloads (include/orbslam3_hip_imu_init.h) ----
+IMU_INIT_MAX_KF = 256
+IMU_INIT_MAX_BATCH = 64
+
+
+class ImuInitProblem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("Rwb", C.c_void_p), ("twb", C.c_void_p), ("vel", C.c_void_p),
+                ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("Rwg", C.c_double * 9), ("scale", C.c_double),
+                ("n_links", C.c_int32), ("links", C.c_void_p),
+                ("free_vel", C.c_uint8), ("free_bias", C.c_uint8), ("free_gdir", C.c_uint8), ("free_scale", C.c_uint8),
+                ("prior_g", C.c_double), ("prior_a", C.c_double), ("huber_delta", C.c_double), ("gauss_newton", C.c_int32),
+                ("lambda_init", C.c_double), ("max_iters", C.c_int32)]
+
+
+class ImuInitResult(C.Structure):
+    _fields_ = [("vel_out", C.c_void_p), ("bg_out", C.c_double * 3), ("ba_out", C.c_double * 3), ("Rwg_out", C.c_double * 9),
+                ("scale_out", C.c_double), ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("stats", LbaStats)]
+
+
+def imu_init_fill(pr, res, w):
+    """fills one ImuInitProblem / ImuInitResult from a problem dictionary (synth_imuinit.make_imu_init); returns the arrays they point to"""
+    f8 = lambda key, shape: np.ascontiguousarray(w[key], np.float64).reshape(shape)
+    k = dict(Rwb=f8("Rwb", (-1, 9)), twb=f8("twb", (-1, 3)), vel=f8("vel", (-1, 3)))
+    n = len(k["Rwb"])
+    if len(k["twb"]) != n or len(k["vel"]) != n:
+        raise ValueError("IMU initialisation arrays of unequal length")
+    links = (_LibaLink * max(len(w["links"]), 1))()
+    for L, d in zip(links, w["links"]):
+        L.kf1, L.kf2, L.dT, L.robust = int(d["kf1"]), int(d["kf2"]), float(d["dT"]), int(d["robust"])
+        for name in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "bias0"):
+            getattr(L, name)[:] = np.asarray(d[name], np.float32).ravel().tolist()
+        L.info9[:] = np.asarray(d["info9"], np.float64).ravel().tolist()
+    k.update(links=links, vel_out=np.zeros((n, 3)))
+    pr.n_kf = n
+    pr.Rwb, pr.twb, pr.vel = (k[key].ctypes.data if n else None for key in ("Rwb", "twb", "vel"))
+    pr.bg[:] = [float(v) for v in w["bg"]]; pr.ba[:] = [float(v) for v in w["ba"]]
+    pr.Rwg[:] = np.asarray(w["Rwg"], np.float64).ravel().tolist(); pr.scale = float(w["scale"])
+    pr.n_links = len(w["links"]); pr.links = C.addressof(links) if len(w["links"]) else None
+    pr.free_vel, pr.free_bias, pr.free_gdir, pr.free_scale = (int(bool(w[key])) for key in ("free_vel", "free_bias", "free_gdir", "free_scale"))
+    pr.prior_g, pr.prior_a, pr.huber_delta = float(w.get("prior_g", 0.0)), float(w.get("prior_a", 0.0)), float(w.get("huber_delta", 0.0))
+    pr.gauss_newton, pr.lambda_init, pr.max_iters = int(w.get("gauss_newton", 0)), float(w.get("lambda_init", 0.0)), int(w.get("max_iters", 200))
+    res.vel_out = k["vel_out"].ctypes.data if n else None
+    return k
+
+
+def imu_init_prepare(problems):
+    """arrays of ImuInitProblem / ImuInitResult for a list of problem dictionaries, with everything they point to"""
+    n = len(problems)
+    prs, ress = (ImuInitProblem * max(n, 1))(), (ImuInitResult * max(n, 1))()
+    keep = [imu_init_fill(prs[i], ress[i], w) for i, w in enumerate(problems)]
+    return dict(problems=prs, results=ress, arrays=keep, n=n)
+
+
+def imu_init_results(prep):
+    out = []
+    for i in range(prep["n"]):
+        r = prep["results"][i]
+        out.append(dict(vel=prep["arrays"][i]["vel_out"], bg=np.array(r.bg_out[:]), ba=np.array(r.ba_out[:]), Rwg=np.array(r.Rwg_out[:]).reshape(3, 3),
+                        scale=r.scale_out, chi2_initial=r.chi2_initial, chi2_final=r.chi2_final, stats=_stats_dict(r.stats)))
+    return out
+
+
+lib.imu_init_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+lib.imu_init_destroy.argtypes = [C.c_void_p]
+lib.imu_init_check.argtypes = [C.POINTER(ImuInitProblem), C.POINTER(ImuInitResult)]
+lib.imu_init_optimize_batch.argtypes = [C.c_void_p, C.POINTER(ImuInitProblem), C.c_int, C.POINTER(ImuInitResult)]
+lib.imu_init_last_device_ms.argtypes = [C.c_void_p]
+lib.imu_init_last_device_ms.restype = C.c_double
+
+
+class ImuInit:
+    """The three Optimizer::InertialOptimization overloads (reference src/Optimizer.cc:3042, :3227, :3389) between the walk over
+    the map and the write-back: imu_init_optimize_batch of include/orbslam3_hip_imu_init.h.  One handle serves one call at a time."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        _check(lib.imu_init_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.imu_init_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optimize_batch(self, problems):
+        """one launch for up to IMU_INIT_MAX_BATCH problem dictionaries; a list of result dictionaries"""
+        prep = imu_init_prepare(problems)
+        _check(lib.imu_init_optimize_batch(self._h, prep["problems"], prep["n"], prep["results"]))
+        return imu_init_results(prep)
+
+    def optimize(self, problem):
+        return self.optimize_batch([problem])[0]
+
+    def last_device_ms(self):
+        return lib.imu_init_last_device_ms(self._h)

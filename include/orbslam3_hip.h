@@ -966,6 +966,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
  * Essg4DofProblem, Essg4DofResult and the two entry points that take them, documented where they are declared ---- */
 #include "orbslam3_hip_4dof.h"
 #include "orbslam3_hip_imu_init.h"
+#include "orbslam3_hip_fullba.h"
 
 #ifdef __cplusplus
 }

@@ -1783,3 +1783,71 @@ class ImuInit:
 
     def last_device_ms(self):
         return lib.imu_init_last_device_ms(self._h)
+
+
+FIBA_MAX_UNKNOWNS = 15732
+FIBA_MAX_KF = 4096
+
+
+class FibaProblem(C.Structure):
+    _fields_ = list(_LibaProblem._fields_) + [("shared_bias", C.c_uint8), ("shared_bg", C.c_double * 3), ("shared_ba", C.c_double * 3),
+                                              ("prior_g", C.c_double), ("prior_a", C.c_double), ("stop_flag", C.c_void_p)]
+
+
+class FibaOutputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("Rwb", "twb", "vel", "bg", "ba", "points")]
+
+
+def fiba_problem(pr, stop_flag=None):
+    """a FibaProblem from a problem dictionary (synth_fullba.make_full_map): the keys of a LocalInertialBA window plus shared_bias,
+    shared_bg, shared_ba, prior_g, prior_a; stop_flag: a uint8 array of one element, or None"""
+    base = _liba_problem(pr)
+    s = FibaProblem()
+    C.memmove(C.addressof(s), C.addressof(base), C.sizeof(_LibaProblem))
+    s.shared_bias = int(bool(pr.get("shared_bias", 0)))
+    s.shared_bg[:] = [float(v) for v in pr.get("shared_bg", (0, 0, 0))]; s.shared_ba[:] = [float(v) for v in pr.get("shared_ba", (0, 0, 0))]
+    s.prior_g, s.prior_a = float(pr.get("prior_g", 0.0)), float(pr.get("prior_a", 0.0))
+    s.stop_flag = None if stop_flag is None else stop_flag.ctypes.data
+    s._keep = (base, stop_flag)
+    return s
+
+
+class FullInertialBA:
+    """The numerical core of Optimizer::FullInertialBA (reference src/Optimizer.cc:392-811) on the device: fiba_solve of
+    include/orbslam3_hip_fullba.h.  One handle serves one call at a time."""
+
+    def __init__(self, device=0):
+        lib.fiba_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.fiba_destroy.argtypes = [C.c_void_p]
+        lib.fiba_solve.argtypes = [C.c_void_p, C.POINTER(FibaProblem), C.POINTER(FibaOutputs), C.POINTER(LbaStats)]
+        lib.fiba_check.argtypes = [C.POINTER(FibaProblem)]
+        lib.fiba_last_device_ms.argtypes = [C.c_void_p]
+        lib.fiba_last_device_ms.restype = C.c_double
+        h = C.c_void_p()
+        _check(lib.fiba_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.fiba_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, pr, stop_flag=None):
+        s = fiba_problem(pr, stop_flag)
+        n, m = s.n_kf, s.n_points
+        out = dict(Rwb=np.zeros((n, 3, 3)), twb=np.zeros((n, 3)), vel=np.zeros((n, 3)), bg=np.zeros((n, 3)), ba=np.zeros((n, 3)), points=np.zeros((max(m, 1), 3)))
+        o = FibaOutputs(*[out[k].ctypes.data for k in ("Rwb", "twb", "vel", "bg", "ba", "points")])
+        st = LbaStats()
+        _check(lib.fiba_solve(self._h, C.byref(s), C.byref(o), C.byref(st)))
+        out["points"] = out["points"][:m]
+        out["stats"] = _stats_dict(st)
+        return out
+
+    def last_device_ms(self):
+        return lib.fiba_last_device_ms(self._h)

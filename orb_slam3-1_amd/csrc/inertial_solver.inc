@@ -109,7 +109,7 @@ enum { kIwErrors = 1, kIwLin = 2, kIwTrial = 4 };
 constexpr int kPtThreads = 256, kPtLandmarks = kPtThreads / 8;
 
 // robust chi2 of link l (EdgeInertial + the two random walks) at the state `st`
-__device__ inline double link_chi2(const Dev& d, const LibaLink& L, const KFState* __restrict__ st)
+__device__ __forceinline__ double link_chi2(const Dev& d, const LibaLink& L, const KFState* __restrict__ st)
 {
     const KFState &k1 = st[L.kf1], &k2 = st[L.kf2];
     double e[9], eR[9], Rbw1[9], dbg[3], c = 0;
@@ -427,6 +427,54 @@ __device__ __forceinline__ double link_terms(const Dev& d, const KFState* __rest
     return v;
 }
 constexpr int kSysThreads = 256;
+// the links' part of entry (row of key frame kr, local lr < 9; shared column sc in 9 .. 14) or of its transpose, over the key frame's
+// links in link order (full_inertial.inc: ONE bias pair for the map): as P1 / V1 of a link the key frame meets the shared bias in the
+// link's own G1 / A1 columns, as P2 / V2 too
+__device__ __forceinline__ double border_terms(const Dev& d, int kr, int lr, int sc, bool kf_is_row)
+{
+    double v = 0;
+    for (int k = d.kl_off[kr]; k < d.kl_off[kr + 1]; k++) {
+        const int l = d.kl_link[k];
+        const int li = link_index24(d.links[l], kr, lr);
+        if (li >= 0) v += d.lH[576 * (size_t)l + (kf_is_row ? li * 24 + sc : sc * 24 + li)];
+    }
+    return v;
+}
+// entry idx of S / the right-hand side row outside the pose blocks.  SHARED (full_inertial.inc): rows with row_kf = nKF are the shared
+// bias; the shared block and its gradient rows belong to another workgroup
+template <bool SHARED>
+__device__ __forceinline__ void entry_body(const IWin& w, const IDyn& y, const size_t idx)
+{
+    const Dev& d = w.d;
+    const int np = d.npad;
+    const double lambda = y.lambda;
+    double* __restrict__ S = w.S;
+    const KFState* __restrict__ st = w.st[y.cur];
+    if (idx >= (size_t)np * np + np) return;
+    const int r = (int)(idx / np), c = (int)(idx - (size_t)r * np);
+    if (r == np) {          // the right-hand side row
+        const int kc = d.row_kf[c];
+        if (kc < 0) { S[idx] = 0.0; return; }
+        const int lc = d.row_loc[c];
+        if (SHARED && kc == d.nKF) return;
+        if (lc < 6) return;                                     // a pose row: its key-frame workgroup writes it
+        const double v = link_terms(d, st, kc, lc, -1, 0);
+        S[idx] = v; d.bp[c] = v;
+        return;
+    }
+    const int kr = d.row_kf[r], kc = d.row_kf[c];
+    if (kr < 0 || kc < 0) { S[idx] = (r == c) ? 1.0 : 0.0; return; }
+    const int lr = d.row_loc[r], lc = d.row_loc[c];
+    if (SHARED) {
+        if (kr == d.nKF && kc == d.nKF) return;
+        if (kr == d.nKF) { S[idx] = border_terms(d, kc, lc, lr, false); return; }
+        if (kc == d.nKF) { S[idx] = border_terms(d, kr, lr, lc, true); return; }
+    }
+    if (kr == kc && lr < 6 && lc < 6) return;                   // a pose block: its key-frame workgroup writes it
+    double v = link_terms(d, st, kr, lr, kc, lc);
+    if (r == c) v += lambda;
+    S[idx] = v;
+}
 __device__ __forceinline__ void system_body(const IWin& w, const IDyn& y, const int bx)
 {
     const Dev& d = w.d;
@@ -493,27 +541,7 @@ __device__ __forceinline__ void system_body(const IWin& w, const IDyn& y, const 
         }
         return;
     }
-    {
-        const size_t idx = (size_t)(bx - w.lm_blocks - d.nKF) * kSysThreads + tid;
-        if (idx >= (size_t)np * np + np) return;
-        const int r = (int)(idx / np), c = (int)(idx - (size_t)r * np);
-        if (r == np) {          // the right-hand side row
-            const int kc = d.row_kf[c];
-            if (kc < 0) { S[idx] = 0.0; return; }
-            const int lc = d.row_loc[c];
-            if (lc < 6) return;                                     // a pose row: its key-frame workgroup writes it
-            const double v = link_terms(d, st, kc, lc, -1, 0);
-            S[idx] = v; d.bp[c] = v;
-            return;
-        }
-        const int kr = d.row_kf[r], kc = d.row_kf[c];
-        if (kr < 0 || kc < 0) { S[idx] = (r == c) ? 1.0 : 0.0; return; }
-        const int lr = d.row_loc[r], lc = d.row_loc[c];
-        if (kr == kc && lr < 6 && lc < 6) return;                   // a pose block: its key-frame workgroup writes it
-        double v = link_terms(d, st, kr, lr, kc, lc);
-        if (r == c) v += lambda;
-        S[idx] = v;
-    }
+    entry_body<false>(w, y, (size_t)(bx - w.lm_blocks - d.nKF) * kSysThreads + tid);
 }
 __global__ __launch_bounds__(kSysThreads) void ki_system(const IWin* __restrict__ wins, IDynAll dyn)
 {
@@ -1440,10 +1468,10 @@ void liba_destroy(liba_solver* s)
     delete s;
 }
 
-static int liba_validate(const LibaProblem* p)
+static int liba_validate(const LibaProblem* p, int max_links = 64)
 {
     if (!p) return fail(ORBX_ERR_ARG, "NULL problem");
-    if (p->n_kf < 1 || p->n_points < 0 || p->n_edges < 0 || p->n_links < 0 || p->n_links > 64) return fail(ORBX_ERR_ARG, "bad sizes");
+    if (p->n_kf < 1 || p->n_points < 0 || p->n_edges < 0 || p->n_links < 0 || p->n_links > max_links) return fail(ORBX_ERR_ARG, "bad sizes");
     if (!p->Rwb || !p->twb || !p->vel || !p->bg || !p->ba || !p->pose_fixed || !p->has_imu || !p->imu_fixed) return fail(ORBX_ERR_ARG, "NULL key-frame arrays");
     if (p->n_points > 0 && !p->points) return fail(ORBX_ERR_ARG, "NULL points");
     if (p->n_edges > 0 && (!p->edge_kf || !p->edge_point || !p->edge_obs || !p->edge_inv_sigma2 || !p->edge_stereo)) return fail(ORBX_ERR_ARG, "NULL edge arrays");
@@ -1465,7 +1493,11 @@ struct LibaWindow {
     void* zero_block = nullptr;
     size_t zero_bytes = 0;
 };
-static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* out)
+// What full_inertial.inc asks of the setup beyond a local window: systems of more than kFusedMaxBlocks tiles (no panel copy Lp
+// then: the launch-per-block-column factorisation works in place) and, with shared_bias, ONE gyro and ONE accelerometer bias for
+// all key frames: their 6 rows come last, row_kf = n_kf, and off_g / off_a of every key frame with IMU states point there.
+struct LibaLayout { bool large = false, shared_bias = false; int max_unknowns = 0; };
+static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* out, const LibaLayout& lay = LibaLayout())
 {
     int r = ORBX_OK;
     liba::Dev d;
@@ -1476,19 +1508,28 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
     int np = 0;
     for (int i = 0; i < nKF; i++) {
         if (!p->pose_fixed[i]) { off_pose[i] = np; np += 6; }
-        if (p->has_imu[i] && !p->imu_fixed[i]) { off_v[i] = np; off_g[i] = np + 3; off_a[i] = np + 6; np += 9; }
+        if (p->has_imu[i] && !p->imu_fixed[i]) {
+            if (lay.shared_bias) { off_v[i] = np; np += 3; }
+            else { off_v[i] = np; off_g[i] = np + 3; off_a[i] = np + 6; np += 9; }
+        }
+    }
+    const int off_shared = np;
+    if (lay.shared_bias) {
+        np += 6;
+        for (int i = 0; i < nKF; i++) if (p->has_imu[i]) { off_g[i] = off_shared; off_a[i] = off_shared + 3; }
     }
     if (np == 0) return fail(ORBX_ERR_ARG, "nothing to optimise");
     const int npad = (np + 1) & ~1;             // the factorisation kernels use 16-byte loads: an even leading dimension
     d.np = np; d.npad = npad;
     const int nblk = (npad + chol::NB - 1) / chol::NB;
-    if (nblk > chol::kFusedMaxBlocks) return fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the inertial solver's limit", np);
+    if (lay.large ? np > lay.max_unknowns : nblk > chol::kFusedMaxBlocks) return fail(ORBX_ERR_CAPACITY, "%d reduced unknowns exceed the inertial solver's limit", np);
     // row -> (key frame, local index: pose 0-5, velocity 6-8, gyro bias 9-11, accelerometer bias 12-14); padding rows: -1
     std::vector<int> row_kf(npad, -1), row_loc(npad, 0);
     for (int i = 0; i < nKF; i++) {
         if (off_pose[i] >= 0) for (int q = 0; q < 6; q++) { row_kf[off_pose[i] + q] = i; row_loc[off_pose[i] + q] = q; }
-        if (off_v[i] >= 0) for (int q = 0; q < 9; q++) { row_kf[off_v[i] + q] = i; row_loc[off_v[i] + q] = 6 + q; }
+        if (off_v[i] >= 0) for (int q = 0; q < (lay.shared_bias ? 3 : 9); q++) { row_kf[off_v[i] + q] = i; row_loc[off_v[i] + q] = 6 + q; }
     }
+    if (lay.shared_bias) for (int q = 0; q < 6; q++) { row_kf[off_shared + q] = nKF; row_loc[off_shared + q] = 9 + q; }
     // the links of a key frame, in link order
     std::vector<int> kl_off(nKF + 1, 0), kl_link(std::max(2 * p->n_links, 1));
     for (int l = 0; l < p->n_links; l++) { kl_off[p->links[l].kf1 + 1]++; kl_off[p->links[l].kf2 + 1]++; }
@@ -1574,7 +1615,7 @@ static int liba_window_setup(liba_solver* sv, const LibaProblem* p, LibaWindow* 
         out->zero_block = zb; out->zero_bytes = zbytes;
     }
     LIBA_TRY(sv->dalloc(&w.S, ((size_t)npad + 1) * npad)); LIBA_TRY(sv->dalloc(&w.Linv, (size_t)nblk * chol::NB * chol::NB));
-    LIBA_TRY(sv->dalloc(&w.Lp, ((size_t)npad + 1) * npad));
+    if (nblk <= chol::kFusedMaxBlocks) LIBA_TRY(sv->dalloc(&w.Lp, ((size_t)npad + 1) * npad));
 #undef LIBA_TRY
     for (int k = 0; k < 9; k++) { d.Rcb[k] = p->Rcb[k]; d.Rbc[k] = p->Rcb[3 * (k % 3) + k / 3]; }
     for (int k = 0; k < 3; k++) { d.tcb[k] = p->tcb[k]; d.tbc[k] = p->tbc[k]; }

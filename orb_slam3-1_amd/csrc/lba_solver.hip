@@ -1761,5 +1761,6 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
 }  // extern "C"
 
 #include "inertial_solver.inc"
+#include "full_inertial.inc"
 #include "essential_graph.inc"
 #include "essential_graph_4dof.inc"

@@ -967,6 +967,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 #include "orbslam3_hip_4dof.h"
 #include "orbslam3_hip_imu_init.h"
 #include "orbslam3_hip_fullba.h"
+#include "orbslam3_hip_kb8.h"
 
 #ifdef __cplusplus
 }

@@ -707,6 +707,33 @@ class BowPlan:
             pass
 
 
+class OrbxKB8(C.Structure):
+    """OrbxKB8 of include/orbslam3_hip_kb8.h: KannalaBrandt8::mvParameters[0..7], floats promoted to double"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 4)]
+
+
+def _kb8(cam):
+    """dict(fx, fy, cx, cy, k=[k0..k3]) -> OrbxKB8"""
+    c = OrbxKB8(float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]))
+    c.k[:] = [float(v) for v in cam["k"]]
+    return c
+
+
+def _set_camera_kb8(fn, handle, cam):
+    fn.argtypes = [C.c_void_p, C.POINTER(OrbxKB8)]
+    _check(fn(handle, C.byref(_kb8(cam)) if cam is not None else None))
+
+
+def kb8_project(cam, Xc, want_jac=True, device=0):
+    """orbx_kb8_project: KannalaBrandt8::project (and projectJac, 2 x 3 row-major) of camera-frame points on the device"""
+    lib.orbx_kb8_project.argtypes = [C.c_int, C.POINTER(OrbxKB8), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    X = np.ascontiguousarray(Xc, np.float64).reshape(-1, 3)
+    uv = np.zeros((len(X), 2))
+    jac = np.zeros((len(X), 6)) if want_jac else None
+    _check(lib.orbx_kb8_project(device, C.byref(_kb8(cam)), _p(X), len(X), _p(uv), _p(jac)))
+    return (uv, jac.reshape(-1, 2, 3)) if want_jac else uv
+
+
 def _lba_problem(w):
     keep = {k: np.ascontiguousarray(w[k]) for k in ("pose_q", "pose_t", "pose_fixed", "points", "edge_point",
                                                       "edge_pose", "edge_obs", "edge_inv_sigma2", "edge_stereo")}
@@ -746,6 +773,10 @@ class LbaSolver:
         except Exception:
             pass
 
+    def set_camera_kb8(self, cam):
+        """lba_set_camera_kb8: dict(fx, fy, cx, cy, k) or None (back to the pinhole camera of the windows)"""
+        _set_camera_kb8(lib.lba_set_camera_kb8, self._h, cam)
+
     def solve(self, w, max_iters=10, lambda_init=0.0, stop_flag=None):
         pr = _lba_problem(w)
         k = pr._keep
@@ -784,6 +815,10 @@ class LbaBatch:
             self.close()
         except Exception:
             pass
+
+    def set_camera_kb8(self, cam):
+        """lba_batch_set_camera_kb8: one fisheye camera for every window of a call, or None"""
+        _set_camera_kb8(lib.lba_batch_set_camera_kb8, self._h, cam)
 
     def prepare(self, windows, want_outputs=True):
         """marshal once (a benchmark re-solves the same windows): problem structs, output arrays, stats"""
@@ -997,6 +1032,21 @@ class PoseSolver:
             self.close()
         except Exception:
             pass
+
+    def set_camera_kb8(self, cam):
+        """pose_set_camera_kb8: dict(fx, fy, cx, cy, k) or None (back to the pinhole camera of the problems)"""
+        _set_camera_kb8(lib.pose_set_camera_kb8, self._h, cam)
+
+    def optimize_one(self, w):
+        """pose_optimize: the single-frame entry"""
+        lib.pose_optimize.argtypes = [C.c_void_p, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.c_void_p]
+        pr, r = PoseProblem(), PoseResult()
+        keep = _pose_problem(w, pr)
+        outl = np.zeros(max(pr.n, 1), np.uint8)
+        _check(lib.pose_optimize(self._h, C.byref(pr), C.byref(r), _p(outl)))
+        del keep
+        return dict(q=np.array(r.q[:]), t=np.array(r.t[:]), inliers=r.inliers, n_bad=r.n_bad, iterations=list(r.iterations),
+                    trials=list(r.trials), chi2=list(r.chi2), outlier=outl[:pr.n].copy())
 
     def prepare(self, problems):
         """flatten a list of frames once (benchmarks re-run the same batch)"""

@@ -31,6 +31,7 @@
 
 #include "../../include/orbslam3_hip.h"
 #include "batch_stage.h"
+#include "camera_kb8.h"
 #include "dense_chol.h"
 #include "device_scope.h"
 #include "lm_control.h"
@@ -74,6 +75,20 @@ __device__ __forceinline__ void edge_residual(const Cam& c, const double* Xc, co
         const double ur = u - (double)((float)c.bf * invz);
         r[0] = obs[0] - u; r[1] = obs[1] - v; r[2] = obs[2] - ur;
     }
+}
+
+// the same edge with pCamera = KannalaBrandt8 (lba_set_camera_kb8): obs - project(Xc); such a window has no stereo edge.
+// The edge bodies below take their camera as a template parameter: ProblemCam (the pinhole figures of the window's own Dev, read
+// exactly where they were read before the parameter existed -- handing the bodies a reference to d.cam instead made k_lin_all
+// spill its whole Dev to scratch) or a kb8::Cam, which the _kb8 kernels receive by value.
+struct ProblemCam {};
+__device__ __forceinline__ const Cam& camera(const Dev& d, const ProblemCam&) { return d.cam; }
+__device__ __forceinline__ const kb8::Cam& camera(const Dev&, const kb8::Cam& c) { return c; }
+__device__ __forceinline__ void edge_residual(const kb8::Cam& c, const double* Xc, const double* obs, int, double* r)
+{
+    double uv[2];
+    kb8::project(c, Xc, uv);
+    r[0] = obs[0] - uv[0]; r[1] = obs[1] - uv[1]; r[2] = 0;
 }
 
 __device__ __forceinline__ void huber(const Cam& c, int stereo, double chi, double& rho0, double& rho1)
@@ -145,15 +160,30 @@ __device__ inline void edge_jacobians(const Cam& c, const double* T, const doubl
     }
 }
 
+// EdgeSE3ProjectXYZ::linearizeOplus with pCamera = KannalaBrandt8: -projectJac(Xc) R and -projectJac(Xc) SE3deriv
+__device__ inline void edge_jacobians(const kb8::Cam& c, const double* T, const double* Xc, int, double* Ji, double* Jj)
+{
+    double R[9], N[6];
+    quat_to_R(T, R);
+    kb8::pose_rows(c, Xc, N, Jj);
+    for (int k = 0; k < 3; k++) {
+        Ji[k] = N[0] * R[k] + N[1] * R[3 + k] + N[2] * R[6 + k];
+        Ji[3 + k] = N[3] * R[k] + N[4] * R[3 + k] + N[5] * R[6 + k];
+        Ji[6 + k] = 0;
+    }
+    for (int k = 12; k < 18; k++) Jj[k] = 0;
+}
+
 // ---- errors of a state (SparseOptimizer::computeActiveErrors + per-edge robust chi2) ----
-__device__ __forceinline__ void errors_body(Dev d, const double* __restrict__ poses, const double* __restrict__ pts, const int bx)
+template <class CamT>
+__device__ __forceinline__ void errors_body(Dev d, const CamT& cam, const double* __restrict__ poses, const double* __restrict__ pts, const int bx)
 {
     const int e = bx * 256 + threadIdx.x;
     if (e >= d.nE) return;
     double Xc[3], r[3];
     pose_map(poses + 7 * (size_t)d.e_pose[e], pts + 3 * (size_t)d.e_point[e], Xc);
     const int st = d.e_stereo[e];
-    edge_residual(d.cam, Xc, d.e_obs + 3 * (size_t)e, st, r);
+    edge_residual(camera(d, cam), Xc, d.e_obs + 3 * (size_t)e, st, r);
     const double w = d.e_w[e];
     double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
     if (st) chi += r[2] * (w * r[2]);
@@ -164,7 +194,11 @@ __device__ __forceinline__ void errors_body(Dev d, const double* __restrict__ po
 }
 __global__ __launch_bounds__(256) void k_errors(Dev d, const double* __restrict__ poses, const double* __restrict__ pts)
 {
-    errors_body(d, poses, pts, (int)blockIdx.x);
+    errors_body(d, ProblemCam(), poses, pts, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_errors_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts)
+{
+    errors_body(d, cam, poses, pts, (int)blockIdx.x);
 }
 
 // ---- buildSystem, landmark side: Hll, bl and the Hpl blocks W_e = B^T (rho1 Omega) A (6x3) ----
@@ -198,7 +232,8 @@ __device__ __forceinline__ void schur_landmark(const Dev& d, int l, int sub, con
 
 // (device function: the merged launch k_lin_all runs it in the workgroups behind the pose ones; lambda >= 0 also performs the landmark side of
 // the Schur complement for that lambda -- the W_e of a landmark's edges are written and read back by the same lanes)
-__device__ __forceinline__ void lin_landmarks_body(const Dev& d, const double* __restrict__ poses, const double* __restrict__ pts, int l, double lambda)
+template <class CamT>
+__device__ __forceinline__ void lin_landmarks_body(const Dev& d, const CamT& cam, const double* __restrict__ poses, const double* __restrict__ pts, int l, double lambda)
 {
     const int sub = threadIdx.x & 7;
     const bool live = l < d.nL;
@@ -213,7 +248,7 @@ __device__ __forceinline__ void lin_landmarks_body(const Dev& d, const double* _
             const int st = d.e_stereo[e];
             double Xc[3], Ji[9], Jj[18];
             pose_map(T, X, Xc);
-            edge_jacobians(d.cam, T, Xc, st, Ji, Jj);
+            edge_jacobians(camera(d, cam), T, Xc, st, Ji, Jj);
             const double* r = d.err + 3 * (size_t)e;
             const double w = d.e_w[e];
             double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
@@ -269,11 +304,12 @@ __device__ __forceinline__ void lin_landmarks_body(const Dev& d, const double* _
 }
 
 // ---- buildSystem, pose side: Hpp (6x6) and bp; one 256-thread workgroup per non-fixed pose, fixed reduction tree ----
-__device__ __forceinline__ void lin_all_body(Dev d, const double* __restrict__ poses, const double* __restrict__ pts, double lambda, const int bx)
+template <class CamT>
+__device__ __forceinline__ void lin_all_body(Dev d, const CamT& cam, const double* __restrict__ poses, const double* __restrict__ pts, double lambda, const int bx)
 {
     __shared__ double s_part[4][27];
     if ((int)bx >= d.nP) {          // landmark workgroups: 32 landmarks x 8 lanes
-        lin_landmarks_body(d, poses, pts, ((int)bx - d.nP) * 32 + (threadIdx.x >> 3), lambda);
+        lin_landmarks_body(d, cam, poses, pts, ((int)bx - d.nP) * 32 + (threadIdx.x >> 3), lambda);
         return;
     }
     const int col = bx, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -286,7 +322,7 @@ __device__ __forceinline__ void lin_all_body(Dev d, const double* __restrict__ p
         const int st = d.e_stereo[e];
         double Xc[3], Ji[9], Jj[18];
         pose_map(T, pts + 3 * (size_t)d.e_point[e], Xc);
-        edge_jacobians(d.cam, T, Xc, st, Ji, Jj);
+        edge_jacobians(camera(d, cam), T, Xc, st, Ji, Jj);
         const double* r = d.err + 3 * (size_t)e;
         const double w = d.e_w[e];
         double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
@@ -329,7 +365,11 @@ __device__ __forceinline__ void lin_all_body(Dev d, const double* __restrict__ p
 }
 __global__ __launch_bounds__(256) void k_lin_all(Dev d, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
 {
-    lin_all_body(d, poses, pts, lambda, (int)blockIdx.x);
+    lin_all_body(d, ProblemCam(), poses, pts, lambda, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_lin_all_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
+{
+    lin_all_body(d, cam, poses, pts, lambda, (int)blockIdx.x);
 }
 
 // ---- deterministic scalar reductions (single workgroup) ----
@@ -530,7 +570,8 @@ __global__ __launch_bounds__(1024) void k_chol_solve_update(const double* __rest
 // the workgroup that finishes last sums the per-landmark partials in a fixed order and publishes the scalars to the host
 // (as k_reduce mode 1 did).
 constexpr int kUpdThreads = 256, kUpdLandmarks = kUpdThreads / 8;
-__device__ __forceinline__ void update_errors_body(const Dev& d, double lambda, const double* __restrict__ pts,
+template <class CamT>
+__device__ __forceinline__ void update_errors_body(const Dev& d, const CamT& cam, double lambda, const double* __restrict__ pts,
                                                    const double* __restrict__ poses_new, double* __restrict__ pts_new,
                                                    double* __restrict__ hmap, unsigned long long seq, const int bx, const int n_blocks)
 {
@@ -583,7 +624,7 @@ __device__ __forceinline__ void update_errors_body(const Dev& d, double lambda, 
             double Xc[3], r[3];
             pose_map(poses_new + 7 * (size_t)d.e_pose[e], Xn, Xc);
             const int st = d.e_stereo[e];
-            edge_residual(d.cam, Xc, d.e_obs + 3 * (size_t)e, st, r);
+            edge_residual(camera(d, cam), Xc, d.e_obs + 3 * (size_t)e, st, r);
             const double w = d.e_w[e];
             double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
             if (st) chi += r[2] * (w * r[2]);
@@ -625,7 +666,12 @@ __device__ __forceinline__ void update_errors_body(const Dev& d, double lambda, 
 __global__ __launch_bounds__(kUpdThreads) void k_update_errors(Dev d, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
                                                                double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
 {
-    update_errors_body(d, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
+    update_errors_body(d, ProblemCam(), lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
+}
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors_kb8(Dev d, kb8::Cam cam, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
+                                                                   double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
+{
+    update_errors_body(d, cam, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -655,7 +701,16 @@ __global__ __launch_bounds__(256) void k_errors_b(const BWin* __restrict__ wins,
     const BWin& w = wins[blockIdx.y];
     if ((int)blockIdx.x * 256 >= w.d.nE) return;
     const int st = trial_state ? 1 - y.cur : y.cur;
-    errors_body(w.d, w.poses[st], w.pts[st], (int)blockIdx.x);
+    errors_body(w.d, ProblemCam(), w.poses[st], w.pts[st], (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_errors_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, int trial_state, kb8::Cam cam)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & (trial_state ? kBwTrial : kBwErrors))) return;
+    const BWin& w = wins[blockIdx.y];
+    if ((int)blockIdx.x * 256 >= w.d.nE) return;
+    const int st = trial_state ? 1 - y.cur : y.cur;
+    errors_body(w.d, cam, w.poses[st], w.pts[st], (int)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_lin_all_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
@@ -663,7 +718,15 @@ __global__ __launch_bounds__(256) void k_lin_all_b(const BWin* __restrict__ wins
     if (!(y.flags & kBwLin)) return;
     const BWin& w = wins[blockIdx.y];
     if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
-    lin_all_body(w.d, w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
+    lin_all_body(w.d, ProblemCam(), w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_lin_all_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, kb8::Cam cam)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & kBwLin)) return;
+    const BWin& w = wins[blockIdx.y];
+    if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
+    lin_all_body(w.d, cam, w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(1024) void k_reduce_b(const BWin* __restrict__ wins, BDynAll dyn, int mode)
 {
@@ -741,7 +804,16 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_errors_b(const BWin* __r
     const BWin& w = wins[blockIdx.y];
     const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
     if ((int)blockIdx.x >= nb) return;
-    update_errors_body(w.d, y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
+    update_errors_body(w.d, ProblemCam(), y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
+}
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, kb8::Cam cam)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & kBwTrial)) return;
+    const BWin& w = wins[blockIdx.y];
+    const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
+    if ((int)blockIdx.x >= nb) return;
+    update_errors_body(w.d, cam, y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
 }
 
 __global__ __launch_bounds__(256) void k_epilogue(Dev d, const double* __restrict__ poses, const double* __restrict__ pts,
@@ -779,6 +851,8 @@ struct lba_shard {
     int device = 0;
     hipStream_t stream = nullptr;
     lba::Dev d;
+    bool kb8_on = false;        // the window's camera is the fisheye one of its solver handle (lba_set_camera_kb8): the _kb8 kernels run
+    kb8::Cam kb8;
     int nblk = 0;
     std::vector<void*> allocs;
     double *poses[2] = {nullptr, nullptr}, *pts[2] = {nullptr, nullptr};
@@ -897,6 +971,22 @@ static int shard_validate(const LbaProblem* p)
     return ORBX_OK;
 }
 
+// a window of a handle with a KannalaBrandt8 camera has monocular edges only (host check, before any device work)
+static int kb8_reject_stereo(const LbaProblem* p)
+{
+    for (int e = 0; e < p->n_edges; e++)
+        if (p->edge_stereo[e]) return fail(ORBX_ERR_ARG, "edge %d is stereo, the handle's camera is KannalaBrandt8", e);
+    return ORBX_OK;
+}
+
+static int kb8_from_abi(const OrbxKB8* cam, kb8::Cam* out)
+{
+    if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
+    out->fx = cam->fx; out->fy = cam->fy; out->cx = cam->cx; out->cy = cam->cy;
+    for (int k = 0; k < 4; k++) out->k[k] = cam->k[k];
+    return ORBX_OK;
+}
+
 struct lba_solver {                 // also a window slot of an lba_batch, with the batch's stream and a view of its scalars
     int device = 0;
     uint8_t* arena = nullptr;
@@ -905,6 +995,8 @@ struct lba_solver {                 // also a window slot of an lba_batch, with 
     stage::HostScalars hs;
     uint8_t* stage = nullptr;       // pinned mirror of the arena prefix that holds the uploaded arrays
     size_t stage_cap = 0;
+    bool kb8_on = false;            // lba_set_camera_kb8
+    kb8::Cam kb8;
     ~lba_solver()
     {
         if (arena) (void)hipFree(arena);
@@ -937,11 +1029,13 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
     int r = shard_validate(p);
+    if (!r && owner && owner->kb8_on) r = kb8_reject_stereo(p);
     if (r || (r = stage::check_device(device))) return r;
     ORBX_HIP(hipSetDevice(device));
     lba_shard* s = new lba_shard();
     s->device = device;
     if (owner) {
+        s->kb8_on = owner->kb8_on; s->kb8 = owner->kb8;
         s->arena = owner->arena; s->arena_cap = owner->arena_cap;
         s->stream = owner->stream; s->owns_stream = false;
         s->hs = owner->hs.view();
@@ -1266,11 +1360,17 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
     // synchronising path (they are needed for lambda initialisation at the first iteration only).
     const bool reuse = s->err_current;
     s->mark(lba::kStageLinearize);
-    if (!reuse && d.nE > 0) hipLaunchKernelGGL(lba::k_errors, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, P, X);
+    if (!reuse && d.nE > 0) {
+        if (s->kb8_on) hipLaunchKernelGGL(lba::k_errors_kb8, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->kb8, P, X);
+        else hipLaunchKernelGGL(lba::k_errors, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, P, X);
+    }
     // one launch for both sides; with a lambda hint (lba_shard_hint_lambda) the landmark workgroups also do their part of the Schur complement
     const double hint = s->hint_lambda;
     s->hint_lambda = -1.0;
-    if (d.nP + d.nL > 0) hipLaunchKernelGGL(lba::k_lin_all, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, P, X, hint);
+    if (d.nP + d.nL > 0) {
+        if (s->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_kb8, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->kb8, P, X, hint);
+        else hipLaunchKernelGGL(lba::k_lin_all, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, P, X, hint);
+    }
     s->schur_lambda = hint;
     s->mark(lba::kStageIdle);
     if (!reuse) {
@@ -1343,7 +1443,9 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
                                (const double*)s->bs(), (const double*)s->bs(), (const double*)d.scal, 0, d, lambda, (const double*)s->bpf(), P, Pn);
     }
     s->mark(lba::kStageUpdate);
-    hipLaunchKernelGGL(lba::k_update_errors, dim3(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1)), dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    const dim3 upd_grid(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1));
+    if (s->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_kb8, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->kb8, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    else hipLaunchKernelGGL(lba::k_update_errors, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
     s->mark(lba::kStageIdle);
     ORBX_HIP(hipGetLastError());
     int r = s->hs.wait(s->stream);
@@ -1503,6 +1605,16 @@ void lba_destroy(lba_solver* s)
     delete s;
 }
 
+int lba_set_camera_kb8(lba_solver* s, const OrbxKB8* cam)
+{
+    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
+    if (!cam) { s->kb8_on = false; return ORBX_OK; }
+    kb8::Cam c;
+    if (int r = kb8_from_abi(cam, &c)) return r;
+    s->kb8 = c; s->kb8_on = true;
+    return ORBX_OK;
+}
+
 int lba_solve(lba_solver* sv, const LbaProblem* problem, const volatile uint8_t* stop_flag, int max_iters, double lambda_init,
               double* pose_q_out, double* pose_t_out, double* points_out,
               double* chi2_per_edge, uint8_t* depth_positive, LbaStats* stats_out)
@@ -1546,6 +1658,8 @@ struct lba_batch : stage::Batch {       // its stream, the two events around the
     lba::BWin* d_wins = nullptr;
     stage::HostScalars hs;              // 16 doubles per slot
     double last_device_ms = 0.0;
+    bool kb8_on = false;                // lba_batch_set_camera_kb8: one fisheye camera for every window of a call
+    kb8::Cam kb8;
     stage::PinnedOut out;               // the results of all windows (one synchronisation per call)
     ~lba_batch()
     {
@@ -1575,12 +1689,27 @@ void lba_batch_destroy(lba_batch* b) { stage::close(b); }
 
 double lba_batch_last_device_ms(const lba_batch* b) { return b ? b->last_device_ms : 0.0; }
 
+int lba_batch_set_camera_kb8(lba_batch* b, const OrbxKB8* cam)
+{
+    if (!b) return fail(ORBX_ERR_ARG, "NULL batch");
+    if (!cam) { b->kb8_on = false; return ORBX_OK; }
+    kb8::Cam c;
+    if (int r = kb8_from_abi(cam, &c)) return r;
+    b->kb8 = c; b->kb8_on = true;
+    return ORBX_OK;
+}
+
 int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* outputs, int n_windows,
                     const volatile uint8_t* const* stop_flags, int max_iters, double lambda_init, LbaStats* stats_out)
 {
     if (!b || !problems || n_windows < 0) return fail(ORBX_ERR_ARG, "NULL argument");
     if (n_windows > lba::kMaxBatch) return fail(ORBX_ERR_CAPACITY, "at most %d windows per call", lba::kMaxBatch);
     if (n_windows == 0) return ORBX_OK;
+    if (b->kb8_on)          // every window's check before the first one touches the device
+        for (int i = 0; i < n_windows; i++) {
+            int rc = shard_validate(&problems[i]);
+            if (rc || (rc = kb8_reject_stereo(&problems[i]))) return rc;
+        }
     ORBX_HIP(hipSetDevice(b->device));
     const int W = n_windows;
     while ((int)b->slots.size() < W) {
@@ -1588,6 +1717,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         sv->device = b->device; sv->stream = b->stream; sv->hs = b->hs.view((int)b->slots.size());
         b->slots.push_back(sv);
     }
+    for (int i = 0; i < W; i++) { b->slots[i]->kb8_on = b->kb8_on; b->slots[i]->kb8 = b->kb8; }
     std::vector<lba_shard*> sh((size_t)W, nullptr);
     std::vector<size_t> wanted((size_t)W, 0), wanted_stage((size_t)W, 0);
     int r = ORBX_OK;
@@ -1658,8 +1788,14 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         }
         if (!any_lin && !any_trial) break;
         hipStream_t st = b->stream;
-        if (any_err) hipLaunchKernelGGL(lba::k_errors_b, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
-        if (any_lin) hipLaunchKernelGGL(lba::k_lin_all_b, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
+        if (any_err) {
+            if (b->kb8_on) hipLaunchKernelGGL(lba::k_errors_b_kb8, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, b->kb8);
+            else hipLaunchKernelGGL(lba::k_errors_b, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
+        }
+        if (any_lin) {
+            if (b->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_b_kb8, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
+            else hipLaunchKernelGGL(lba::k_lin_all_b, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
+        }
         if (any_err) hipLaunchKernelGGL(lba::k_reduce_b, dim3(1, W), dim3(1024), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
         if (any_trial) {
             if (any_lm) hipLaunchKernelGGL(lba::k_schur_landmarks_b, dim3(max_lm, W), dim3(64), 0, st, (const lba::BWin*)b->d_wins, dyn);
@@ -1677,7 +1813,8 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
                 }
             }
             hipLaunchKernelGGL(lba::k_chol_solve_update_b, dim3(1, W), dim3(1024), solve_lds, st, (const lba::BWin*)b->d_wins, dyn);
-            hipLaunchKernelGGL(lba::k_update_errors_b, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn);
+            if (b->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_b_kb8, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
+            else hipLaunchKernelGGL(lba::k_update_errors_b, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn);
         }
         if (hipGetLastError() != hipSuccess) { r = fail(ORBX_ERR_HIP, "batched launch failed"); break; }
         // results of the round: every window that ran a reduction publishes its sequence number last

@@ -16,6 +16,7 @@
 
 #include "../../include/orbslam3_hip.h"
 #include "batch_stage.h"
+#include "camera_kb8.h"
 #include "dense_lm_device.h"
 #include "se3_device.h"
 
@@ -33,6 +34,11 @@ struct ProblemDev {
     uint8_t* active;        // [n] scratch: level 0
     PoseResult* result;
 };
+
+// camera policies of the edge bodies: the pinhole one reads fx .. bf of the problem, the fisheye one carries its own eight parameters
+// (monocular edges only; pose_set_camera_kb8)
+struct Pinhole { static constexpr bool kFisheye = false; };
+struct Fisheye { static constexpr bool kFisheye = true; kb8::Cam c; };
 
 // one edge in registers
 struct Edge {
@@ -55,11 +61,15 @@ __device__ __forceinline__ Edge load_edge(const ProblemDev& P, int e)
 
 // EdgeSE3ProjectXYZOnlyPose::computeError (include/OptimizableTypes.h:46-50) and
 // EdgeStereoSE3ProjectXYZOnlyPose::computeError (types_six_dof_expmap.h:203-207, cam_project .cpp:339-346)
-template <bool STEREO>
-__device__ __forceinline__ void edge_eval(const ProblemDev& P, const double* T, const Edge& d, double* Xc, double* r)
+template <bool STEREO, class CamT>
+__device__ __forceinline__ void edge_eval(const CamT& cam, const ProblemDev& P, const double* T, const Edge& d, double* Xc, double* r)
 {
     pose_map(T, d.X, Xc);
-    if (!STEREO || !d.st) {
+    if constexpr (CamT::kFisheye) {                             // obs - pCamera->project(Xc) (OptimizableTypes.h:46-50)
+        double uv[2];
+        kb8::project(cam.c, Xc, uv);
+        r[0] = d.o[0] - uv[0]; r[1] = d.o[1] - uv[1]; r[2] = 0;
+    } else if (!STEREO || !d.st) {
         r[0] = d.o[0] - (P.fx * Xc[0] / Xc[2] + P.cx);
         r[1] = d.o[1] - (P.fy * Xc[1] / Xc[2] + P.cy);
         r[2] = 0;
@@ -85,19 +95,22 @@ struct Robust {
 };
 
 // computeError + robustify + linearizeOplus + constructQuadraticForm of one edge, accumulated into acc[28]
-template <bool STEREO>
-__device__ __forceinline__ void edge_build(const ProblemDev& P, const double* T, const Edge& d, const Robust& rb, double* r, double* acc)
+template <bool STEREO, class CamT>
+__device__ __forceinline__ void edge_build(const CamT& cam, const ProblemDev& P, const double* T, const Edge& d, const Robust& rb, double* r, double* acc)
 {
     constexpr int D = STEREO ? 3 : 2;
     double Xc[3], J[D * 6];
-    edge_eval<STEREO>(P, T, d, Xc, r);
+    edge_eval<STEREO>(cam, P, T, d, Xc, r);
     const double chi = edge_chi2<STEREO>(d, r);
     const double delta = (STEREO && d.st) ? rb.delta_s : rb.delta_m, dsq = (STEREO && d.st) ? rb.dsq_s : rb.dsq_m;
     double rho0, rho1;
     dlm::huber(rb.on, chi, delta, dsq, rho0, rho1);
     acc[27] += rho0;
     const double x = Xc[0], y = Xc[1], z = Xc[2];
-    if (!STEREO || !d.st) {
+    if constexpr (CamT::kFisheye) {                             // -projectJac(Xc) * SE3deriv (OptimizableTypes.cpp:24-38)
+        double N[6];
+        kb8::pose_rows(cam.c, Xc, N, J);
+    } else if (!STEREO || !d.st) {
         const double p00 = -(P.fx / z), p02 = P.fx * x / (z * z), p11 = -(P.fy / z), p12 = P.fy * y / (z * z);
         J[0] = p02 * y; J[1] = p00 * z + p02 * (-x); J[2] = p00 * (-y); J[3] = p00; J[4] = 0; J[5] = p02;
         J[6] = p11 * (-z) + p12 * y; J[7] = p12 * (-x); J[8] = p11 * x; J[9] = 0; J[10] = p11; J[11] = p12;
@@ -131,11 +144,11 @@ __device__ __forceinline__ void edge_build(const ProblemDev& P, const double* T,
 }
 
 // computeError + robust chi2 of one edge under the trial pose
-template <bool STEREO>
-__device__ __forceinline__ double edge_trial(const ProblemDev& P, const double* T, const Edge& d, const Robust& rb, double* r)
+template <bool STEREO, class CamT>
+__device__ __forceinline__ double edge_trial(const CamT& cam, const ProblemDev& P, const double* T, const Edge& d, const Robust& rb, double* r)
 {
     double Xc[3];
-    edge_eval<STEREO>(P, T, d, Xc, r);
+    edge_eval<STEREO>(cam, P, T, d, Xc, r);
     const double chi = edge_chi2<STEREO>(d, r);
     const double delta = (STEREO && d.st) ? rb.delta_s : rb.delta_m, dsq = (STEREO && d.st) ? rb.dsq_s : rb.dsq_m;
     double rho0, rho1;
@@ -162,180 +175,15 @@ constexpr int kAccRow = 264;        // 256 partials + one pad per 32 (bank sprea
 template <bool STEREO, int kRegEdges>
 __global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__ problems)
 {
-    __shared__ double s_acc[28][kAccRow];       // per-thread partials of H (21), b (6), chi2 (1), transposed
-    __shared__ double s_out[28];
-    __shared__ double s_red[4];
-    const ProblemDev P = problems[blockIdx.x];
-    const int tid = threadIdx.x;
-    const int n = P.n;
-    const int e_rest = tid + kRegEdges * 256;   // first edge of this thread that lives in global memory
-
-    double T0[7] = {P.q[0], P.q[1], P.q[2], P.q[3], P.t[0], P.t[1], P.t[2]};
-    quat_normalize(T0);                                 // SE3Quat(Quaterniond, Vector3d) (:829)
-    double T[7];
-    for (int k = 0; k < 7; k++) T[k] = T0[k];
-    __shared__ int s_iters[4], s_trials[4];             // statistics only (thread 0)
-    __shared__ double s_chi[4];
-    if (tid < 4) { s_iters[tid] = 0; s_trials[tid] = 0; s_chi[tid] = 0; }
-    // register-resident edges: data, level (active), outlier flag, last computed error
-    Edge ce[kRegEdges];
-    double cerr[kRegEdges][3];
-    bool cvalid[kRegEdges], cact[kRegEdges], cout_[kRegEdges];
-#pragma unroll
-    for (int j = 0; j < kRegEdges; j++) {
-        const int e = tid + j * 256;
-        cvalid[j] = e < n;
-        if (cvalid[j]) ce[j] = load_edge<STEREO>(P, e);
-        else { ce[j].X[0] = 0; ce[j].X[1] = 0; ce[j].X[2] = 1; ce[j].o[0] = 0; ce[j].o[1] = 0; ce[j].o[2] = 0; ce[j].w = 0; ce[j].st = 0; }
-        cact[j] = cvalid[j]; cout_[j] = false;
-        cerr[j][0] = 0; cerr[j][1] = 0; cerr[j][2] = 0;
-    }
-    for (int e = e_rest; e < n; e += 256) { P.active[e] = 1; P.outlier[e] = 0; P.err[3 * (size_t)e] = 0; P.err[3 * (size_t)e + 1] = 0; P.err[3 * (size_t)e + 2] = 0; }
-    Robust rb;
-    rb.on = true;
-    rb.delta_m = P.huber_mono; rb.delta_s = P.huber_stereo;
-    rb.dsq_m = P.huber_mono * P.huber_mono; rb.dsq_s = P.huber_stereo * P.huber_stereo;
-    int nBad = 0;
-#ifdef POSE_TIMING
-    long long tm[6] = {0, 0, 0, 0, 0, 0}, t_prev = clock64();
-#define POSE_TICK(k) { const long long t_now = clock64(); tm[k] += t_now - t_prev; t_prev = t_now; }
-#else
-#define POSE_TICK(k)
-#endif
-    const int rounds = (n >= 3) ? 4 : 0;                // nInitialCorrespondences < 3 -> return 0 (:998-999)
-#pragma unroll 1
-    for (int round = 0; round < rounds; round++) {
-        for (int k = 0; k < 7; k++) T[k] = T0[k];       // every round restarts from the frame pose (:1007-1008)
-        // ---- optimizer.initializeOptimization(0); optimizer.optimize(10) ----
-        double cnt = 0;
-#pragma unroll
-        for (int j = 0; j < kRegEdges; j++) cnt += cact[j] ? 1.0 : 0.0;
-        for (int e = e_rest; e < n; e += 256) cnt += P.active[e];
-        const int n_active = (int)dlm::block_sum(cnt, s_red);
-        if (n_active > 0) {
-            double lambda = 0, ni = 2;
-            int nbad_lm = 0;
-#pragma unroll 1
-            for (int it = 0; it < 10; it++) {
-                // computeActiveErrors + activeRobustChi2 + buildSystem on the current estimate
-                double acc[28];
-                for (int k = 0; k < 28; k++) acc[k] = 0;
-#pragma unroll
-                for (int j = 0; j < kRegEdges; j++)
-                    if (cact[j]) edge_build<STEREO>(P, T, ce[j], rb, cerr[j], acc);
-                for (int e = e_rest; e < n; e += 256) {
-                    if (!P.active[e]) continue;
-                    const Edge d = load_edge<STEREO>(P, e);
-                    double r[3];
-                    edge_build<STEREO>(P, T, d, rb, r, acc);
-                    P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
-                }
-                POSE_TICK(0)
-                // two-stage ordered reduction through LDS: 28 values x 256 partials -> 8 partials of 32 -> 1
-#pragma unroll
-                for (int k = 0; k < 28; k++) s_acc[k][tid + (tid >> 5)] = acc[k];
-                __syncthreads();
-                if (tid < 224) {
-                    const int k = tid >> 3, part = tid & 7;
-                    const double* src = &s_acc[k][part * 33];
-                    double v = 0;
-#pragma unroll 8
-                    for (int i = 0; i < 32; i++) v += src[i];
-                    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-                    if (part == 0) s_out[k] = v;
-                }
-                __syncthreads();
-                double Hu[21], b[6];
-#pragma unroll
-                for (int k = 0; k < 21; k++) Hu[k] = s_out[k];
-#pragma unroll
-                for (int k = 0; k < 6; k++) b[k] = s_out[21 + k];
-                double cur = s_out[27];
-                const double ini = cur;
-                if (it == 0) { lambda = dlm::lambda_init<6>(Hu); ni = 2; nbad_lm = 0; }
-                POSE_TICK(1)
-                // ---- LM trial loop (levenberg.cpp:102-149) ----
-                int qmax = 0;
-                double rho = 0;
-#pragma unroll 1
-                do {
-                    double x[6], Tt[7];
-                    const bool ok2 = dlm::ldlt_solve<6, true>(Hu, lambda, b, x);
-                    if (ok2) pose_oplus<true>(T, x, Tt);
-                    else {
-                        for (int k = 0; k < 7; k++) Tt[k] = T[k];
-                        for (int k = 0; k < 6; k++) x[k] = 0;
-                    }
-                    POSE_TICK(2)
-                    double tchi = 0;
-#pragma unroll
-                    for (int j = 0; j < kRegEdges; j++)
-                        if (cact[j]) tchi += edge_trial<STEREO>(P, Tt, ce[j], rb, cerr[j]);
-                    for (int e = e_rest; e < n; e += 256) {
-                        if (!P.active[e]) continue;
-                        const Edge d = load_edge<STEREO>(P, e);
-                        double r[3];
-                        tchi += edge_trial<STEREO>(P, Tt, d, rb, r);
-                        P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
-                    }
-                    POSE_TICK(3)
-                    const double tempChi = dlm::block_sum(tchi, s_red);
-                    double scale = 0;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    if (dlm::trial(ok2, tempChi, scale, lambda, ni, cur, rho))
-                        for (int k = 0; k < 7; k++) T[k] = Tt[k];     // discardTop(); after pop() the estimate stays
-                    qmax++;
-                    POSE_TICK(4)
-                } while (dlm::more_trials(rho, qmax));
-                if (tid == 0) { s_iters[round]++; s_trials[round] += qmax; s_chi[round] = cur; }
-                if (dlm::stop_reason(qmax, rho, ini, cur, nbad_lm)) break;      // stop rules (:151-166)
-            }
-        }
-        // ---- inlier / outlier classification with float chi2 (:1016-1100) ----
-        double bad = 0;
-#pragma unroll
-        for (int j = 0; j < kRegEdges; j++) {
-            if (!cvalid[j]) continue;
-            double Xc[3];
-            if (cout_[j]) edge_eval<STEREO>(P, T, ce[j], Xc, cerr[j]);      // inactive edges did not follow the estimate: e->computeError()
-            const bool o = edge_is_outlier<STEREO>(ce[j], cerr[j]);
-            cout_[j] = o; cact[j] = !o; bad += o ? 1.0 : 0.0;
-        }
-        for (int e = e_rest; e < n; e += 256) {
-            const Edge d = load_edge<STEREO>(P, e);
-            double r[3];
-            if (P.outlier[e]) {
-                double Xc[3];
-                edge_eval<STEREO>(P, T, d, Xc, r);
-                P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
-            } else {
-                r[0] = P.err[3 * (size_t)e]; r[1] = P.err[3 * (size_t)e + 1]; r[2] = P.err[3 * (size_t)e + 2];
-            }
-            const bool o = edge_is_outlier<STEREO>(d, r);
-            P.outlier[e] = o ? 1 : 0; P.active[e] = o ? 0 : 1; bad += o ? 1.0 : 0.0;
-        }
-        nBad = (int)dlm::block_sum(bad, s_red);
-        POSE_TICK(5)
-        if (round == 2) rb.on = false;      // setRobustKernel(0) after the third round
-        if (n < 10) break;                  // optimizer.edges().size() < 10
-    }
-#pragma unroll
-    for (int j = 0; j < kRegEdges; j++)
-        if (cvalid[j]) P.outlier[tid + j * 256] = cout_[j] ? 1 : 0;
-    if (tid == 0) {
-        PoseResult R;
-        for (int k = 0; k < 4; k++) R.q[k] = T[k];
-        for (int k = 0; k < 3; k++) R.t[k] = T[4 + k];
-        R.n_bad = nBad;
-        R.inliers = (n < 3) ? 0 : n - nBad;
-        for (int k = 0; k < 4; k++) { R.iterations[k] = s_iters[k]; R.trials[k] = s_trials[k]; R.chi2[k] = s_chi[k]; }
-#ifdef POSE_TIMING
-        for (int k = 0; k < 4; k++) R.chi2[k] = (double)tm[k];
-        R.t[0] = (double)tm[4]; R.t[1] = (double)tm[5];
-#endif
-        *P.result = R;
-    }
+    const Pinhole cam;
+#include "pose_opt_body.inc"
+}
+// the fisheye instantiation: monocular edges only, the camera of the handle by value
+template <int kRegEdges>
+__global__ __launch_bounds__(256) void k_pose_opt_kb8(const ProblemDev* __restrict__ problems, const Fisheye cam)
+{
+    constexpr bool STEREO = false;
+#include "pose_opt_body.inc"
 }
 
 
@@ -425,19 +273,40 @@ __global__ __launch_bounds__(256) void k_pose_scatter(const ProblemDev* __restri
     }
 }
 
+// orbx_kb8_project: kb8::project and kb8::project_jac of n points
+__global__ __launch_bounds__(256) void k_kb8_project(kb8::Cam c, const double* __restrict__ X, int n, double* __restrict__ uv, double* __restrict__ jac)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x[3] = {X[3 * (size_t)i], X[3 * (size_t)i + 1], X[3 * (size_t)i + 2]};
+    double o[2];
+    kb8::project(c, x, o);
+    uv[2 * (size_t)i] = o[0]; uv[2 * (size_t)i + 1] = o[1];
+    if (jac) {
+        double J[6];
+        kb8::project_jac(c, x, J);
+        for (int k = 0; k < 6; k++) jac[6 * (size_t)i + k] = J[k];
+    }
+}
+
 }  // namespace poseopt
 
 // staging: [descriptors | inputs] up, [results | outlier flags] down, scratch behind them on the device
 struct pose_solver : stage::Batch {
     uint8_t* d_dev = nullptr;       // arena of the device-resident entry (edge slots, problem descriptors, results)
     size_t dev_cap = 0;
+    bool kb8_on = false;            // pose_set_camera_kb8: the fisheye camera replaces fx .. bf of every problem
+    poseopt::Fisheye kb8;
     ~pose_solver() { if (d_dev) (void)hipFree(d_dev); }
 };
 
 namespace {
-inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p)
+inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p, const poseopt::Fisheye* kb8 = nullptr)
 {
-    if (stereo) {
+    if (kb8) {
+        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<4>), dim3(n), dim3(256), 0, st, p, *kb8);
+        else hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<2>), dim3(n), dim3(256), 0, st, p, *kb8);
+    } else if (stereo) {
         if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<true, 4>), dim3(n), dim3(256), 0, st, p);
         else hipLaunchKernelGGL((poseopt::k_pose_opt<true, 2>), dim3(n), dim3(256), 0, st, p);
     } else {
@@ -449,6 +318,10 @@ inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, con
 int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
 {
     if (!s || !problems || !results || n_problems < 1) return fail(ORBX_ERR_ARG, "bad arguments");
+    if (s->kb8_on)          // a fisheye frame is monocular (or a two-camera rig, which this library does not take): before any device work
+        for (int i = 0; i < n_problems; i++)
+            for (int k = 0; k < problems[i].n && problems[i].stereo; k++)
+                if (problems[i].stereo[k]) return fail(ORBX_ERR_ARG, "problem %d: edge %d is stereo, the handle's camera is KannalaBrandt8", i, k);
     ORBX_HIP(hipSetDevice(s->device));
     // layout: [ProblemDev x N][per problem: Xw obs w stereo]  ||  [PoseResult x N][per problem: outlier]  ||  scratch
     struct Off { size_t Xw, obs, w, st, outl, err, act; };
@@ -501,7 +374,7 @@ int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, 
         descs[i] = d;
     }
     const int rr = stage::run(*s, up_bytes, res_off, down_end,
-                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base); });
+                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base, s->kb8_on ? &s->kb8 : nullptr); });
     if (rr != ORBX_OK) return rr;
     std::memcpy(results, s->h_blob + res_off, sizeof(PoseResult) * (size_t)n_problems);
     if (outlier_out)
@@ -528,6 +401,7 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
                                uint8_t* d_outlier, PoseResult* d_results, void* stream)
 {
     if (!s || !f || batch < 1) return fail(ORBX_ERR_ARG, "bad arguments");
+    if (s->kb8_on) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 path: reset the camera (pose_set_camera_kb8(s, NULL)) or use pose_optimize_batch");
     if (!f->d_kps || !f->d_n || !f->d_assign || !f->d_mp_xyz || !f->d_pose || !f->inv_level_sigma2) return fail(ORBX_ERR_ARG, "NULL arrays");
     if (f->cap < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap / mp_cap / n_levels");
     ORBX_HIP(hipSetDevice(s->device));
@@ -568,6 +442,43 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
     hipLaunchKernelGGL(poseopt::k_pose_scatter, dim3(batch), dim3(256), 0, st, (const poseopt::ProblemDev*)A.problems, (const uint8_t*)s->d_dev, A.slot_bytes, A.o_idx,
                        f->cap, d_pose_out, d_inliers, d_outlier, d_results);
     ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+int pose_set_camera_kb8(pose_solver* s, const OrbxKB8* cam)
+{
+    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
+    if (!cam) { s->kb8_on = false; return ORBX_OK; }
+    if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
+    s->kb8.c.fx = cam->fx; s->kb8.c.fy = cam->fy; s->kb8.c.cx = cam->cx; s->kb8.c.cy = cam->cy;
+    for (int k = 0; k < 4; k++) s->kb8.c.k[k] = cam->k[k];
+    s->kb8_on = true;
+    return ORBX_OK;
+}
+
+// diagnostic: the two device functions of camera_kb8.h on n points
+int orbx_kb8_project(int device, const OrbxKB8* cam, const double* Xc, int n, double* uv, double* jac)
+{
+    if (!cam || n < 0 || (n > 0 && (!Xc || !uv))) return fail(ORBX_ERR_ARG, "bad arguments");
+    if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
+    if (int r = stage::check_device(device)) return r;
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(device));
+    kb8::Cam c;
+    c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
+    for (int k = 0; k < 4; k++) c.k[k] = cam->k[k];
+    double* d = nullptr;
+    const size_t N = (size_t)n;
+    ORBX_HIP(hipMalloc((void**)&d, 11 * N * sizeof(double)));          // [X 3n | uv 2n | jac 6n]
+    hipError_t e = hipMemcpy(d, Xc, 3 * N * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(poseopt::k_kb8_project, dim3((n + 255) / 256), dim3(256), 0, 0, c, (const double*)d, n, d + 3 * N, jac ? d + 5 * N : nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(uv, d + 3 * N, 2 * N * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && jac) e = hipMemcpy(jac, d + 5 * N, 6 * N * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(ORBX_ERR_HIP, "orbx_kb8_project: %s", hipGetErrorString(e));
     return ORBX_OK;
 }
 

@@ -177,6 +177,8 @@ private:
 #include "ORBmatcher.h"     // the reference entry points the adapters fall back to for rigs outside the accelerated path
 #include "Optimizer.h"
 
+#include "orbslam3_shim_marshal.hpp"     // the marshalling the adapters of this header and of orbslam3_shim_*.hpp share
+
 namespace ORB_SLAM3 {
 
 // Drop-in for ORB_SLAM3::ORBextractor (same public surface incl. mvImagePyramid, filled lazily on request).
@@ -647,11 +649,7 @@ inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g)
     g.fixed.resize(g.kfs.size());
     for (size_t i = 0; i < g.kfs.size(); i++) {
         g.kfIndex[g.kfs[i]] = (int)i;
-        const Sophus::SE3<float> Tcw = g.kfs[i]->GetPose();
-        const Eigen::Quaterniond qd = Tcw.unit_quaternion().cast<double>();
-        const Eigen::Vector3d td = Tcw.translation().cast<double>();
-        g.q[4 * i] = qd.x(); g.q[4 * i + 1] = qd.y(); g.q[4 * i + 2] = qd.z(); g.q[4 * i + 3] = qd.w();
-        g.t[3 * i] = td.x(); g.t[3 * i + 1] = td.y(); g.t[3 * i + 2] = td.z();
+        orbslam3_hip::pose_in(g.kfs[i]->GetPose(), &g.q[4 * i], &g.t[3 * i]);
         g.fixed[i] = g.kfs[i]->mnBALocalForKF != pKF->mnId || g.kfs[i]->mnId == pMap->GetInitKFid();     // :1220, :1237
     }
     g.num_OptKF = (int)g.lLocalKeyFrames.size();                                    // :1227
@@ -669,14 +667,64 @@ inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g)
             const cv::KeyPoint& kpUn = pKFi->mvKeysUn[leftIndex];
             const float ur = pKFi->mvuRight[leftIndex];
             g.ePoint.push_back(g.mpIndex.at(pMP)); g.ePose.push_back(g.kfIndex.at(pKFi));      // .at(): an observer outside the window is a bug, not vertex 0
-            g.eObs.push_back(kpUn.pt.x); g.eObs.push_back(kpUn.pt.y); g.eObs.push_back(ur >= 0 ? (double)ur : -1.0);
+            orbslam3_hip::push_edge_obs(kpUn, ur, g.eObs, g.eStereo);
             g.eW.push_back((double)pKFi->mvInvLevelSigma2[kpUn.octave]);
-            g.eStereo.push_back(ur >= 0);
             g.eKF.push_back(pKFi); g.eMP.push_back(pMP);
             g.fx = pKFi->fx; g.fy = pKFi->fy; g.cx = pKFi->cx; g.cy = pKFi->cy; g.bf = pKFi->mbf;
         }
     g.num_edges = (int)g.ePoint.size();                                             // :1404
     return true;
+}
+
+// The steps after the walk (:1406-1497), for a pinhole window (cam == nullptr) and for a window of one monocular KannalaBrandt8
+// camera (orbslam3_shim_kb8.hpp) alike: the problem and the solve with the camera set around it, the write-back, and
+// LocalBundleAdjustmentFinish, which sets the counters and runs the two.
+inline void LocalBundleAdjustmentSolve(const LbaGraph& g, bool* pbStopFlag, Map* pMap, const OrbxKB8* cam, std::vector<double>& qo, std::vector<double>& to,
+                                       std::vector<double>& Xo, std::vector<double>& chi2, std::vector<uint8_t>& depthPos)
+{
+    const double camera[5] = {cam ? cam->fx : g.fx, cam ? cam->fy : g.fy, cam ? cam->cx : g.cx, cam ? cam->cy : g.cy, cam ? 0.0 : g.bf};   // bf is not read while a KB8 camera is set
+    const LbaProblem pr = orbslam3_hip::lba_problem(g.q, g.t, g.fixed, g.X.data(), (int)g.mps.size(), g.ePoint, g.ePose, g.eObs, g.eW, g.eStereo, camera,
+                                                    orbslam3_hip::huber_mono(), orbslam3_hip::huber_stereo());                      // :1275-1276
+    lba_solver* solver = orbslam3_hip::thread_handle<lba_solver, lba_create>();
+    qo.resize(g.q.size()); to.resize(g.t.size()); Xo.resize(g.X.size()); chi2.resize(g.num_edges); depthPos.resize(g.num_edges);
+    LbaStats st;
+    orbslam3_hip::CameraScope<lba_solver, lba_set_camera_kb8> scope(solver, cam);
+    orbslam3_hip::check(lba_solve(solver, &pr, (const volatile uint8_t*)pbStopFlag, 10, pMap->IsInertial() ? 100.0 : 0.0,
+                                  qo.data(), to.data(), Xo.data(), chi2.data(), depthPos.data(), &st));
+}
+
+inline void LocalBundleAdjustmentWriteBack(const LbaGraph& g, Map* pMap, const std::vector<double>& qo, const std::vector<double>& to, const std::vector<double>& Xo,
+                                           const std::vector<double>& chi2, const std::vector<uint8_t>& depthPos)
+{
+    std::vector<std::pair<KeyFrame*, MapPoint*> > vToErase;                         // :1413-1460 (a KB8 window has no stereo edge)
+    for (int e = 0; e < g.num_edges; e++) {
+        if (g.eMP[e]->isBad()) continue;
+        if (chi2[e] > (g.eStereo[e] ? 7.815 : 5.991) || !depthPos[e]) vToErase.push_back(std::make_pair(g.eKF[e], g.eMP[e]));
+    }
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                       // :1464
+    for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
+    for (KeyFrame* pKFi : g.lLocalKeyFrames) {
+        const int i = g.kfIndex.at(pKFi);
+        pKFi->SetPose(orbslam3_hip::pose_out(&qo[4 * i], &to[3 * i]));
+    }
+    for (MapPoint* pMP : g.lLocalMapPoints) {
+        pMP->SetWorldPos(orbslam3_hip::point_out(&Xo[3 * g.mpIndex.at(pMP)]));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();
+}
+
+// ok = what LocalBundleAdjustmentGraph returned for g
+inline void LocalBundleAdjustmentFinish(const LbaGraph& g, bool ok, bool* pbStopFlag, Map* pMap, const OrbxKB8* cam, int& num_fixedKF, int& num_OptKF, int& num_edges)
+{
+    num_fixedKF = g.num_fixedKF;                                                    // num_MPs is never assigned by the reference overload either
+    if (!ok) return;                                                                // :1182-1186: the other counters keep the caller's values
+    num_OptKF = g.num_OptKF; num_edges = g.num_edges;
+    if (pbStopFlag && *pbStopFlag) return;                                          // :1406-1408
+    std::vector<double> qo, to, Xo, chi2;
+    std::vector<uint8_t> depthPos;
+    LocalBundleAdjustmentSolve(g, pbStopFlag, pMap, cam, qo, to, Xo, chi2, depthPos);
+    LocalBundleAdjustmentWriteBack(g, pMap, qo, to, Xo, chi2, depthPos);
 }
 
 inline void LocalBundleAdjustmentHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges)
@@ -692,46 +740,7 @@ inline void LocalBundleAdjustmentHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap,
             Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
             return;
         }
-    (void)num_MPs;      // never assigned by the reference overload either
-    num_fixedKF = g.num_fixedKF;
-    if (!ok) return;                                                                // :1182-1186: the other counters keep the caller's values
-    num_OptKF = g.num_OptKF; num_edges = g.num_edges;
-    if (pbStopFlag && *pbStopFlag) return;                                          // :1406-1408
-
-    LbaProblem pr;
-    pr.n_poses = (int)g.kfs.size(); pr.pose_q = g.q.data(); pr.pose_t = g.t.data(); pr.pose_fixed = g.fixed.data();
-    pr.n_points = (int)g.mps.size(); pr.points = g.X.data();
-    pr.n_edges = num_edges; pr.edge_point = g.ePoint.data(); pr.edge_pose = g.ePose.data(); pr.edge_obs = g.eObs.data();
-    pr.edge_inv_sigma2 = g.eW.data(); pr.edge_stereo = g.eStereo.data();
-    pr.fx = g.fx; pr.fy = g.fy; pr.cx = g.cx; pr.cy = g.cy; pr.bf = g.bf;
-    const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815);             // :1275-1276 (through float)
-    pr.huber_mono = thHuberMono; pr.huber_stereo = thHuberStereo;
-    static thread_local lba_solver* solver = nullptr;
-    if (!solver) orbslam3_hip::check(lba_create(0, &solver));
-    std::vector<double> qo(g.q.size()), to(g.t.size()), Xo(g.X.size()), chi2(num_edges);
-    std::vector<uint8_t> depthPos(num_edges);
-    LbaStats st;
-    orbslam3_hip::check(lba_solve(solver, &pr, (const volatile uint8_t*)pbStopFlag, 10, pMap->IsInertial() ? 100.0 : 0.0,
-                                  qo.data(), to.data(), Xo.data(), chi2.data(), depthPos.data(), &st));
-
-    std::vector<std::pair<KeyFrame*, MapPoint*> > vToErase;                         // :1413-1460
-    for (int e = 0; e < num_edges; e++) {
-        if (g.eMP[e]->isBad()) continue;
-        if (chi2[e] > (g.eStereo[e] ? 7.815 : 5.991) || !depthPos[e]) vToErase.push_back(std::make_pair(g.eKF[e], g.eMP[e]));
-    }
-    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                       // :1464
-    for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
-    for (KeyFrame* pKFi : g.lLocalKeyFrames) {
-        const int i = g.kfIndex.at(pKFi);
-        const Eigen::Quaterniond qd(qo[4 * i + 3], qo[4 * i], qo[4 * i + 1], qo[4 * i + 2]);
-        pKFi->SetPose(Sophus::SE3f(qd.cast<float>(), Eigen::Vector3d(to[3 * i], to[3 * i + 1], to[3 * i + 2]).cast<float>()));
-    }
-    for (MapPoint* pMP : g.lLocalMapPoints) {
-        const int i = g.mpIndex.at(pMP);
-        pMP->SetWorldPos(Eigen::Vector3d(Xo[3 * i], Xo[3 * i + 1], Xo[3 * i + 2]).cast<float>());
-        pMP->UpdateNormalAndDepth();
-    }
-    pMap->IncreaseChangeIndex();
+    LocalBundleAdjustmentFinish(g, ok, pbStopFlag, pMap, nullptr, num_fixedKF, num_OptKF, num_edges);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -783,11 +792,7 @@ inline void BundleAdjustmentGraph(const std::vector<KeyFrame*>& vpKFs, const std
     for (auto& kv : vertexOfId) { g.kfIndex[kv.second] = (int)g.kfs.size(); g.kfs.push_back(kv.second); }
     g.q.resize(g.kfs.size() * 4); g.t.resize(g.kfs.size() * 3); g.fixed.resize(g.kfs.size());
     for (size_t i = 0; i < g.kfs.size(); i++) {
-        const Sophus::SE3<float> Tcw = g.kfs[i]->GetPose();
-        const Eigen::Quaterniond qd = Tcw.unit_quaternion().cast<double>();
-        const Eigen::Vector3d td = Tcw.translation().cast<double>();
-        g.q[4 * i] = qd.x(); g.q[4 * i + 1] = qd.y(); g.q[4 * i + 2] = qd.z(); g.q[4 * i + 3] = qd.w();
-        g.t[3 * i] = td.x(); g.t[3 * i + 1] = td.y(); g.t[3 * i + 2] = td.z();
+        orbslam3_hip::pose_in(g.kfs[i]->GetPose(), &g.q[4 * i], &g.t[3 * i]);
         g.fixed[i] = g.kfs[i]->mnId == pMap->GetInitKFid();                         // :125
     }
     // first pass: which map points keep an edge (their vertex order is by id, their edges are in vpMP order)
@@ -823,9 +828,8 @@ inline void BundleAdjustmentGraph(const std::vector<KeyFrame*>& vpKFs, const std
             const cv::KeyPoint& kpUn = pKF->mvKeysUn[o.leftIndex];
             const float ur = pKF->mvuRight[o.leftIndex];
             g.ePoint.push_back(g.mpIndex.at(vpMP[i])); g.ePose.push_back(g.kfIndex.at(pKF));
-            g.eObs.push_back(kpUn.pt.x); g.eObs.push_back(kpUn.pt.y); g.eObs.push_back(ur >= 0 ? (double)ur : -1.0);
+            orbslam3_hip::push_edge_obs(kpUn, ur, g.eObs, g.eStereo);               // :160 mono iff mvuRight < 0, :196 stereo
             g.eW.push_back((double)pKF->mvInvLevelSigma2[kpUn.octave]);
-            g.eStereo.push_back(ur >= 0);                                           // :160 mono iff mvuRight < 0, :196 stereo
             g.fx = pKF->fx; g.fy = pKF->fy; g.cx = pKF->cx; g.cy = pKF->cy; g.bf = pKF->mbf;
         }
 }
@@ -852,14 +856,10 @@ inline void BundleAdjustmentHIP(const std::vector<KeyFrame*>& vpKFs, const std::
             eObs.insert(eObs.end(), g.eObs.begin() + 3 * e, g.eObs.begin() + 3 * e + 3);
             eW.push_back(g.eW[e]); eStereo.push_back(g.eStereo[e]);
         }
-    LbaProblem pr;
-    pr.n_poses = (int)g.kfs.size(); pr.pose_q = g.q.data(); pr.pose_t = g.t.data(); pr.pose_fixed = g.fixed.data();
-    pr.n_points = hi - lo; pr.points = g.X.data() + 3 * (size_t)lo;
-    pr.n_edges = (int)ePoint.size(); pr.edge_point = ePoint.data(); pr.edge_pose = ePose.data(); pr.edge_obs = eObs.data();
-    pr.edge_inv_sigma2 = eW.data(); pr.edge_stereo = eStereo.data();
-    pr.fx = g.fx; pr.fy = g.fy; pr.cx = g.cx; pr.cy = g.cy; pr.bf = g.bf;
     const float thHuber2D = sqrt(5.99), thHuber3D = sqrt(7.815);                    // :130-131 (through float; 5.99, not 5.991)
-    pr.huber_mono = bRobust ? (double)thHuber2D : 0.0; pr.huber_stereo = bRobust ? (double)thHuber3D : 0.0;
+    const double camera[5] = {g.fx, g.fy, g.cx, g.cy, g.bf};
+    const LbaProblem pr = orbslam3_hip::lba_problem(g.q, g.t, g.fixed, g.X.data() + 3 * (size_t)lo, hi - lo, ePoint, ePose, eObs, eW, eStereo, camera,
+                                                    bRobust ? (double)thHuber2D : 0.0, bRobust ? (double)thHuber3D : 0.0);
 
     lba_shard* sh = nullptr;
     orbslam3_hip::check(lba_shard_create(shard ? shard->device : 0, &pr, &sh));
@@ -876,11 +876,10 @@ inline void BundleAdjustmentHIP(const std::vector<KeyFrame*>& vpKFs, const std::
         for (KeyFrame* pKF : vpKFs) {
             if (pKF->isBad()) continue;
             const int i = g.kfIndex.at(pKF);
-            const Eigen::Quaterniond qd(qo[4 * i + 3], qo[4 * i], qo[4 * i + 1], qo[4 * i + 2]);
-            const Eigen::Vector3d td(to[3 * i], to[3 * i + 1], to[3 * i + 2]);
-            if (toMap) pKF->SetPose(Sophus::SE3f(qd.cast<float>(), td.cast<float>()));
+            if (toMap) pKF->SetPose(orbslam3_hip::pose_out(&qo[4 * i], &to[3 * i]));
             else {
-                pKF->mTcwGBA = Sophus::SE3d(qd, td).cast<float>();
+                const Eigen::Quaterniond qd(qo[4 * i + 3], qo[4 * i], qo[4 * i + 1], qo[4 * i + 2]);
+                pKF->mTcwGBA = Sophus::SE3d(qd, Eigen::Vector3d(to[3 * i], to[3 * i + 1], to[3 * i + 2])).cast<float>();
                 pKF->mnBAGlobalForKF = nLoopKF;
                 // (:304-369 count edges of key frames that moved by more than 1 m into local variables nothing reads: no effect)
             }
@@ -979,27 +978,8 @@ inline void LocalInertialBAHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& 
         if (!(pKFi->bImu && pKFi->mPrevKF->bImu && pKFi->mpImuPreintegrated)) continue;
         IMU::Preintegrated* pInt = pKFi->mpImuPreintegrated;
         pInt->SetNewBias(pKFi->mPrevKF->GetImuBias());
-        LibaLink L;
-        std::memset(&L, 0, sizeof(L));
-        L.kf1 = kfIndex.at(pKFi->mPrevKF); L.kf2 = kfIndex.at(pKFi);
-        auto put3x3 = [](float* dst, const Eigen::Matrix3f& M) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = M(r, c); };
-        put3x3(L.dR, pInt->dR); put3x3(L.JRg, pInt->JRg); put3x3(L.JVg, pInt->JVg); put3x3(L.JVa, pInt->JVa); put3x3(L.JPg, pInt->JPg); put3x3(L.JPa, pInt->JPa);
-        for (int r = 0; r < 3; r++) { L.dV[r] = pInt->dV(r); L.dP[r] = pInt->dP(r); }
-        L.dT = pInt->dT;
-        const IMU::Bias b = pInt->GetOriginalBias();
-        L.bias0[0] = b.bax; L.bias0[1] = b.bay; L.bias0[2] = b.baz; L.bias0[3] = b.bwx; L.bias0[4] = b.bwy; L.bias0[5] = b.bwz;
-        Eigen::Matrix<double, 9, 9> Info = pInt->C.block<9, 9>(0, 0).cast<double>().inverse();   // EdgeInertial ctor, G2oTypes.cc:510-518
-        Info = (Info + Info.transpose()) / 2;
-        Eigen::SelfAdjointEigenSolver<Eigen::Matrix<double, 9, 9> > es(Info);
-        Eigen::Matrix<double, 9, 1> eigs = es.eigenvalues();
-        for (int k = 0; k < 9; k++) if (eigs[k] < 1e-12) eigs[k] = 0;
-        Info = es.eigenvectors() * eigs.asDiagonal() * es.eigenvectors().transpose();
-        L.robust = (i == N - 1 || bRecInit);
-        if (i == N - 1) Info *= 1e-2;                                               // :2651
-        const Eigen::Matrix3d InfoG = pInt->C.block<3, 3>(9, 9).cast<double>().inverse(), InfoA = pInt->C.block<3, 3>(12, 12).cast<double>().inverse();
-        for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) L.info9[9 * r + c] = Info(r, c);
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { L.info_gyro[3 * r + c] = InfoG(r, c); L.info_acc[3 * r + c] = InfoA(r, c); }
-        links.push_back(L);
+        links.push_back(orbslam3_hip::imu_link(pInt, kfIndex.at(pKFi->mPrevKF), kfIndex.at(pKFi), i == N - 1 ? 1e-2 : 1.0, pInt,   // :2651
+                                               i == N - 1 || bRecInit));                                                        // :2643-2653
     }
     std::vector<MapPoint*> mps(lLocalMapPoints.begin(), lLocalMapPoints.end());     // :2714-2840
     std::map<MapPoint*, int> mpIndex;
@@ -1027,8 +1007,8 @@ inline void LocalInertialBAHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& 
             const float unc2 = pKFi->mpCamera->uncertainty2(o2);
             const float invSigma2 = pKFi->mvInvLevelSigma2[kpUn.octave] / unc2;
             eKFi.push_back(kfIndex.at(pKFi)); ePt.push_back(mpIndex.at(pMP));
-            eObs.push_back(kpUn.pt.x); eObs.push_back(kpUn.pt.y); eObs.push_back(ur >= 0 ? (double)ur : -1.0);
-            eW.push_back((double)invSigma2); eStereo.push_back(ur >= 0);
+            orbslam3_hip::push_edge_obs(kpUn, ur, eObs, eStereo);
+            eW.push_back((double)invSigma2);
             eKF.push_back(pKFi); eMP.push_back(pMP);
         }
     num_edges = (int)eKFi.size();
@@ -1037,18 +1017,14 @@ inline void LocalInertialBAHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& 
     std::memset(&pr, 0, sizeof(pr));
     pr.n_kf = nKF; pr.Rwb = Rwb.data(); pr.twb = twb.data(); pr.vel = vel.data(); pr.bg = bg.data(); pr.ba = ba.data();
     pr.pose_fixed = poseFixed.data(); pr.has_imu = hasImu.data(); pr.imu_fixed = imuFixed.data();
-    const Eigen::Matrix3d Rcb = pKF->mImuCalib.mTcb.rotationMatrix().cast<double>();
-    const Eigen::Vector3d tcb = pKF->mImuCalib.mTcb.translation().cast<double>(), tbc = pKF->mImuCalib.mTbc.translation().cast<double>();
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pr.Rcb[3 * r + c] = Rcb(r, c); pr.tcb[r] = tcb(r); pr.tbc[r] = tbc(r); }
+    orbslam3_hip::imu_calib(pKF->mImuCalib, pr.Rcb, pr.tcb, pr.tbc);
     pr.fx = pKF->fx; pr.fy = pKF->fy; pr.cx = pKF->cx; pr.cy = pKF->cy; pr.bf = pKF->mbf;
     pr.n_points = (int)mps.size(); pr.points = X.data();
     pr.n_edges = num_edges; pr.edge_kf = eKFi.data(); pr.edge_point = ePt.data(); pr.edge_obs = eObs.data(); pr.edge_inv_sigma2 = eW.data(); pr.edge_stereo = eStereo.data();
     pr.n_links = (int)links.size(); pr.links = links.data();
-    const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815);             // :2694-2697 (through float)
-    pr.huber_mono = thHuberMono; pr.huber_stereo = thHuberStereo; pr.huber_inertial = sqrt(16.92);
+    pr.huber_mono = orbslam3_hip::huber_mono(); pr.huber_stereo = orbslam3_hip::huber_stereo(); pr.huber_inertial = sqrt(16.92);    // :2694-2697
     pr.lambda_init = bLarge ? 1e-2 : 1e0; pr.max_iters = opt_it;
-    static thread_local liba_solver* solver = nullptr;
-    if (!solver) orbslam3_hip::check(liba_create(0, &solver));
+    liba_solver* solver = orbslam3_hip::thread_handle<liba_solver, liba_create>();
     std::vector<double> Ro(Rwb.size()), to(twb.size()), vo(vel.size()), go(bg.size()), ao(ba.size()), Xo(X.size()), chi2(num_edges);
     std::vector<uint8_t> depthPos(num_edges);
     LbaStats st;
@@ -1069,20 +1045,15 @@ inline void LocalInertialBAHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& 
     for (KeyFrame* k : lFixedKeyFrames) k->mnBAFixedForKF = 0;
     for (int i = 0; i < N; i++) {                                                   // :2913-2934
         KeyFrame* pKFi = vpOptimizableKFs[i];
-        Eigen::Matrix3d R; Eigen::Vector3d t;
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R(r, c) = Ro[9 * i + 3 * r + c]; t(r) = to[3 * i + r]; }
-        const Eigen::Matrix3d Rcw = Rcb * R.transpose();                            // ImuCamPose: Rcw = Rcb Rbw, tcw = Rcb tbw + tcb
-        const Eigen::Vector3d tcw = Rcb * (-R.transpose() * t) + tcb;
-        pKFi->SetPose(Sophus::SE3f(Rcw.cast<float>(), tcw.cast<float>()));
+        pKFi->SetPose(orbslam3_hip::camera_pose(pr.Rcb, pr.tcb, &Ro[9 * i], &to[3 * i]));
         pKFi->mnBALocalForKF = 0;
         if (pKFi->bImu) {
-            pKFi->SetVelocity(Eigen::Vector3d(vo[3 * i], vo[3 * i + 1], vo[3 * i + 2]).cast<float>());
+            pKFi->SetVelocity(orbslam3_hip::point_out(&vo[3 * i]));
             pKFi->SetNewBias(IMU::Bias(ao[3 * i], ao[3 * i + 1], ao[3 * i + 2], go[3 * i], go[3 * i + 1], go[3 * i + 2]));
         }
     }
     for (MapPoint* pMP : lLocalMapPoints) {                                         // :2947-2954
-        const int i = mpIndex[pMP];
-        pMP->SetWorldPos(Eigen::Vector3d(Xo[3 * i], Xo[3 * i + 1], Xo[3 * i + 2]).cast<float>());
+        pMP->SetWorldPos(orbslam3_hip::point_out(&Xo[3 * mpIndex[pMP]]));
         pMP->UpdateNormalAndDepth();
     }
     pMap->IncreaseChangeIndex();
@@ -1114,8 +1085,8 @@ inline int PoseInertialOptimizationHIP(Frame* pFrame, bool bRecInit, bool lastFr
             pFrame->mvbOutlier[i] = false;
             feat.push_back(i);
             Xw.push_back(X.x()); Xw.push_back(X.y()); Xw.push_back(X.z());
-            obs.push_back(kpUn.pt.x); obs.push_back(kpUn.pt.y); obs.push_back(ur >= 0 ? (double)ur : -1.0);
-            w.push_back((double)invSigma2); stereo.push_back(ur >= 0); closePt.push_back(pMP->mTrackDepth < 10.f);
+            orbslam3_hip::push_edge_obs(kpUn, ur, obs, stereo);
+            w.push_back((double)invSigma2); closePt.push_back(pMP->mTrackDepth < 10.f);
         }
     }
     KeyFrame* pKF = pFrame->mpLastKeyFrame;
@@ -1130,32 +1101,12 @@ inline int PoseInertialOptimizationHIP(Frame* pFrame, bool bRecInit, bool lastFr
     if (lastFrame) putState(0, pFp->GetImuRotation(), pFp->GetImuPosition(), pFp->GetVelocity(), pFp->mImuBias);
     else putState(0, pKF->GetImuRotation(), pKF->GetImuPosition(), pKF->GetVelocity(), pKF->GetImuBias());
     putState(1, pFrame->GetImuRotation(), pFrame->GetImuPosition(), pFrame->GetVelocity(), pFrame->mImuBias);
-    const Eigen::Matrix3d Rcb = pFrame->mImuCalib.mTcb.rotationMatrix().cast<double>();
-    const Eigen::Vector3d tcb = pFrame->mImuCalib.mTcb.translation().cast<double>(), tbc = pFrame->mImuCalib.mTbc.translation().cast<double>();
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pr.Rcb[3 * r + c] = Rcb(r, c); pr.tcb[r] = tcb(r); pr.tbc[r] = tbc(r); }
+    orbslam3_hip::imu_calib(pFrame->mImuCalib, pr.Rcb, pr.tcb, pr.tbc);
     pr.fx = pFrame->fx; pr.fy = pFrame->fy; pr.cx = pFrame->cx; pr.cy = pFrame->cy; pr.bf = pFrame->mbf;
     pr.n = (int)feat.size(); pr.Xw = Xw.data(); pr.obs = obs.data(); pr.inv_sigma2 = w.data(); pr.stereo = stereo.data(); pr.close_point = closePt.data();
-    LibaLink& L = pr.link;
-    L.kf1 = 0; L.kf2 = 1;
-    auto put3x3 = [](float* dst, const Eigen::Matrix3f& M) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = M(r, c); };
-    put3x3(L.dR, pInt->dR); put3x3(L.JRg, pInt->JRg); put3x3(L.JVg, pInt->JVg); put3x3(L.JVa, pInt->JVa); put3x3(L.JPg, pInt->JPg); put3x3(L.JPa, pInt->JPa);
-    for (int r = 0; r < 3; r++) { L.dV[r] = pInt->dV(r); L.dP[r] = pInt->dP(r); }
-    L.dT = pInt->dT;
-    const IMU::Bias b0 = pInt->GetOriginalBias();
-    L.bias0[0] = b0.bax; L.bias0[1] = b0.bay; L.bias0[2] = b0.baz; L.bias0[3] = b0.bwx; L.bias0[4] = b0.bwy; L.bias0[5] = b0.bwz;
-    Eigen::Matrix<double, 9, 9> Info = pInt->C.block<9, 9>(0, 0).cast<double>().inverse();       // EdgeInertial ctor, G2oTypes.cc:510-518
-    Info = (Info + Info.transpose()) / 2;
-    Eigen::SelfAdjointEigenSolver<Eigen::Matrix<double, 9, 9> > es(Info);
-    Eigen::Matrix<double, 9, 1> eigs = es.eigenvalues();
-    for (int k = 0; k < 9; k++) if (eigs[k] < 1e-12) eigs[k] = 0;
-    Info = es.eigenvectors() * eigs.asDiagonal() * es.eigenvectors().transpose();
-    // both variants take the random-walk informations from pFrame->mpImuPreintegrated (:4686, :5069)
-    const Eigen::Matrix3d InfoG = pFrame->mpImuPreintegrated->C.block<3, 3>(9, 9).cast<double>().inverse();
-    const Eigen::Matrix3d InfoA = pFrame->mpImuPreintegrated->C.block<3, 3>(12, 12).cast<double>().inverse();
-    for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) L.info9[9 * r + c] = Info(r, c);
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { L.info_gyro[3 * r + c] = InfoG(r, c); L.info_acc[3 * r + c] = InfoA(r, c); }
-    const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815);
-    pr.huber_mono = thHuberMono; pr.huber_stereo = thHuberStereo; pr.rec_init = bRecInit;
+    // both variants take the random-walk informations from pFrame->mpImuPreintegrated (:4686, :5069); the link's robust is not read
+    pr.link = orbslam3_hip::imu_link(pInt, 0, 1, 1.0, pFrame->mpImuPreintegrated, false);
+    pr.huber_mono = orbslam3_hip::huber_mono(); pr.huber_stereo = orbslam3_hip::huber_stereo(); pr.rec_init = bRecInit;
     if (lastFrame) {                                                                // EdgePriorPoseImu(pFp->mpcpi) (:5079-5090)
         const ConstraintPoseImu* c = pFp->mpcpi;
         pr.last_frame = 1;
@@ -1165,8 +1116,7 @@ inline int PoseInertialOptimizationHIP(Frame* pFrame, bool bRecInit, bool lastFr
         }
         for (int r = 0; r < 15; r++) for (int q = 0; q < 15; q++) pr.prior_H[15 * r + q] = c->H(r, q);
     }
-    static thread_local liba_solver* solver = nullptr;
-    if (!solver) orbslam3_hip::check(liba_create(0, &solver));
+    liba_solver* solver = orbslam3_hip::thread_handle<liba_solver, liba_create>();
     double R[9], t[3], v[3], bg[3], ba[3], H[900];
     std::vector<uint8_t> outlier(feat.size() + 1);
     int32_t inliers = 0, nBad = 0;
@@ -1238,51 +1188,68 @@ private:
     orbv_vocab* h_ = nullptr;
 };
 
-// int Optimizer::PoseOptimization(Frame* pFrame) (src/Optimizer.cc:814-1115), conventional (non-rigid-body) cameras:
-// one PoseProblem edge per feature holding a MapPoint, in feature order (= g2o's addEdge order).
-inline int PoseOptimizationHIP(Frame* pFrame)
-{
-    if (pFrame->mpCamera2) return Optimizer::PoseOptimization(pFrame);              // rigid-body stereo-fisheye rig: not on this path
-    const int N = pFrame->N;
+// int Optimizer::PoseOptimization(Frame* pFrame) (src/Optimizer.cc:814-1115), conventional (non-rigid-body) cameras, in three steps:
+// PoseGraph = one edge per feature holding a MapPoint, in feature order (= g2o's addEdge order).
+struct PoseGraph {
     std::vector<double> Xw, obs, w;
     std::vector<uint8_t> stereo;
     std::vector<int> feat;
-    {
-        std::unique_lock<std::mutex> lock(MapPoint::mGlobalMutex);                  // :857
-        for (int i = 0; i < N; i++) {
-            MapPoint* pMP = pFrame->mvpMapPoints[i];
-            if (!pMP) continue;
-            pFrame->mvbOutlier[i] = false;                                          // :870, :898
-            const cv::KeyPoint& kpUn = pFrame->mvKeysUn[i];
-            const float ur = pFrame->mvuRight[i];
-            const Eigen::Vector3d X = pMP->GetWorldPos().cast<double>();
-            Xw.push_back(X.x()); Xw.push_back(X.y()); Xw.push_back(X.z());
-            obs.push_back(kpUn.pt.x); obs.push_back(kpUn.pt.y); obs.push_back(ur < 0 ? -1.0 : (double)ur);
-            w.push_back((double)pFrame->mvInvLevelSigma2[kpUn.octave]);
-            stereo.push_back(ur < 0 ? 0 : 1);
-            feat.push_back(i);
-        }
+};
+
+inline void PoseOptimizationFlatten(Frame* pFrame, PoseGraph& g)
+{
+    std::unique_lock<std::mutex> lock(MapPoint::mGlobalMutex);                      // :857
+    for (int i = 0; i < pFrame->N; i++) {
+        MapPoint* pMP = pFrame->mvpMapPoints[i];
+        if (!pMP) continue;
+        pFrame->mvbOutlier[i] = false;                                              // :870, :898
+        const cv::KeyPoint& kpUn = pFrame->mvKeysUn[i];
+        const Eigen::Vector3d X = pMP->GetWorldPos().cast<double>();
+        g.Xw.push_back(X.x()); g.Xw.push_back(X.y()); g.Xw.push_back(X.z());
+        orbslam3_hip::push_edge_obs(kpUn, pFrame->mvuRight[i], g.obs, g.stereo);
+        g.w.push_back((double)pFrame->mvInvLevelSigma2[kpUn.octave]);
+        g.feat.push_back(i);
     }
+}
+
+// cam: the frame's one monocular KannalaBrandt8 camera (orbslam3_shim_kb8.hpp), set on the handle around the call; nullptr: the pinhole
+// parameters of the frame.  outlier has one entry per edge of g, and one to spare.
+inline void PoseOptimizationSolve(Frame* pFrame, const PoseGraph& g, const OrbxKB8* cam, PoseResult& res, std::vector<uint8_t>& outlier)
+{
     PoseProblem pr;
-    const Sophus::SE3<float> Tcw = pFrame->GetPose();
-    const Eigen::Quaterniond qd = Tcw.unit_quaternion().cast<double>();
-    const Eigen::Vector3d td = Tcw.translation().cast<double>();
-    pr.q[0] = qd.x(); pr.q[1] = qd.y(); pr.q[2] = qd.z(); pr.q[3] = qd.w();
-    pr.t[0] = td.x(); pr.t[1] = td.y(); pr.t[2] = td.z();
-    pr.n = (int)feat.size(); pr.Xw = Xw.data(); pr.obs = obs.data(); pr.inv_sigma2 = w.data(); pr.stereo = stereo.data();
-    pr.fx = pFrame->fx; pr.fy = pFrame->fy; pr.cx = pFrame->cx; pr.cy = pFrame->cy; pr.bf = pFrame->mbf;
-    const float deltaMono = sqrt(5.991), deltaStereo = sqrt(7.815);                 // :838-839 (through float)
-    pr.huber_mono = deltaMono; pr.huber_stereo = deltaStereo;
-    static thread_local pose_solver* solver = nullptr;
-    if (!solver) orbslam3_hip::check(pose_create(0, &solver));
-    PoseResult res;
-    std::vector<uint8_t> outlier(feat.size() + 1);
+    orbslam3_hip::pose_in(pFrame->GetPose(), pr.q, pr.t);
+    pr.n = (int)g.feat.size(); pr.Xw = g.Xw.data(); pr.obs = g.obs.data(); pr.inv_sigma2 = g.w.data(); pr.stereo = g.stereo.data();
+    if (cam) { pr.fx = cam->fx; pr.fy = cam->fy; pr.cx = cam->cx; pr.cy = cam->cy; pr.bf = 0.0; }     // bf is not read while a KB8 camera is set
+    else { pr.fx = pFrame->fx; pr.fy = pFrame->fy; pr.cx = pFrame->cx; pr.cy = pFrame->cy; pr.bf = pFrame->mbf; }
+    pr.huber_mono = orbslam3_hip::huber_mono(); pr.huber_stereo = orbslam3_hip::huber_stereo();         // :838-839
+    pose_solver* solver = orbslam3_hip::thread_handle<pose_solver, pose_create>();
+    outlier.assign(g.feat.size() + 1, 0);
+    orbslam3_hip::CameraScope<pose_solver, pose_set_camera_kb8> scope(solver, cam);
     orbslam3_hip::check(pose_optimize(solver, &pr, &res, outlier.data()));
-    if (pr.n < 3) return 0;                                                         // :998-999 (pose untouched)
-    for (size_t k = 0; k < feat.size(); k++) pFrame->mvbOutlier[feat[k]] = outlier[k] != 0;
-    const Eigen::Quaterniond qo(res.q[3], res.q[0], res.q[1], res.q[2]);
-    pFrame->SetPose(Sophus::SE3f(qo.cast<float>(), Eigen::Vector3d(res.t[0], res.t[1], res.t[2]).cast<float>()));   // :1107-1110
+}
+
+inline int PoseOptimizationWriteBack(Frame* pFrame, const PoseGraph& g, const PoseResult& res, const std::vector<uint8_t>& outlier)
+{
+    if (g.feat.size() < 3) return 0;                                                // :998-999 (pose untouched)
+    for (size_t k = 0; k < g.feat.size(); k++) pFrame->mvbOutlier[g.feat[k]] = outlier[k] != 0;
+    pFrame->SetPose(orbslam3_hip::pose_out(res.q, res.t));                          // :1107-1110
     return res.inliers;
+}
+
+inline int PoseOptimizationWithCamera(Frame* pFrame, const OrbxKB8* cam)
+{
+    PoseGraph g;
+    PoseOptimizationFlatten(pFrame, g);
+    PoseResult res;
+    std::vector<uint8_t> outlier;
+    PoseOptimizationSolve(pFrame, g, cam, res, outlier);
+    return PoseOptimizationWriteBack(pFrame, g, res, outlier);
+}
+
+inline int PoseOptimizationHIP(Frame* pFrame)
+{
+    if (pFrame->mpCamera2) return Optimizer::PoseOptimization(pFrame);              // rigid-body stereo-fisheye rig: not on this path
+    return PoseOptimizationWithCamera(pFrame, nullptr);
 }
 
 }  // namespace ORB_SLAM3

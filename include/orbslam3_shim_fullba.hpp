@@ -89,27 +89,8 @@ void FlattenFullInertialBA(MapT* pMap, bool bFixLocal, FullBAFlat<KF, MP>& g)
         pInt->SetNewBias(pKFi->mPrevKF->GetImuBias());                              // :491 (before the vertex lookup)
         const auto i1 = index.find(static_cast<ObsKF>(pKFi->mPrevKF)), i2 = index.find(static_cast<ObsKF>(pKFi));
         if (i1 == index.end() || i2 == index.end()) continue;                       // optimizer.vertex() == NULL: "Error", no edge
-        LibaLink L;
-        std::memset(&L, 0, sizeof(L));
-        L.kf1 = i1->second; L.kf2 = i2->second;
-        auto put3x3 = [](float* dst, const Eigen::Matrix3f& M) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = M(r, c); };
-        put3x3(L.dR, pInt->dR); put3x3(L.JRg, pInt->JRg); put3x3(L.JVg, pInt->JVg); put3x3(L.JVa, pInt->JVa); put3x3(L.JPg, pInt->JPg); put3x3(L.JPa, pInt->JPa);
-        for (int r = 0; r < 3; r++) { L.dV[r] = pInt->dV(r); L.dP[r] = pInt->dP(r); }
-        L.dT = pInt->dT;
-        const IMU::Bias b = pInt->GetOriginalBias();
-        L.bias0[0] = b.bax; L.bias0[1] = b.bay; L.bias0[2] = b.baz; L.bias0[3] = b.bwx; L.bias0[4] = b.bwy; L.bias0[5] = b.bwz;
-        Eigen::Matrix<double, 9, 9> Info = pInt->C.template block<9, 9>(0, 0).template cast<double>().inverse();     // EdgeInertial ctor, G2oTypes.cc:510-518
-        Info = (Info + Info.transpose()) / 2;
-        Eigen::SelfAdjointEigenSolver<Eigen::Matrix<double, 9, 9> > es(Info);
-        Eigen::Matrix<double, 9, 1> eigs = es.eigenvalues();
-        for (int k = 0; k < 9; k++) if (eigs[k] < 1e-12) eigs[k] = 0;
-        Info = es.eigenvectors() * eigs.asDiagonal() * es.eigenvectors().transpose();
-        for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) L.info9[9 * r + c] = Info(r, c);      // no factor 1e-2 in this function
-        const Eigen::Matrix3d InfoG = pInt->C.template block<3, 3>(9, 9).template cast<double>().inverse();           // :551, :559 (read without bInit only)
-        const Eigen::Matrix3d InfoA = pInt->C.template block<3, 3>(12, 12).template cast<double>().inverse();
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { L.info_gyro[3 * r + c] = InfoG(r, c); L.info_acc[3 * r + c] = InfoA(r, c); }
-        L.robust = 1;                                                               // :540-542
-        g.links.push_back(L);
+        g.links.push_back(orbslam3_hip::imu_link(pInt, i1->second, i2->second, 1.0, pInt, true));    // no factor 1e-2 in this function; Huber :540-542;
+                                                                                                    // the random-walk informations :551, :559 are read without bInit only
     }
     g.not_included.assign(vpMPs.size(), false);
     for (size_t i = 0; i < vpMPs.size(); i++) {                                     // :599-719
@@ -131,9 +112,8 @@ void FlattenFullInertialBA(MapT* pMap, bool bFixLocal, FullBAFlat<KF, MP>& g)
             const cv::KeyPoint& kpUn = pKFi->mvKeysUn[leftIndex];
             const float ur = pKFi->mvuRight[leftIndex];
             g.edge_kf.push_back(it->second); g.edge_point.push_back((int32_t)i);
-            g.edge_obs.push_back(kpUn.pt.x); g.edge_obs.push_back(kpUn.pt.y); g.edge_obs.push_back(ur >= 0 ? (double)ur : -1.0);
+            orbslam3_hip::push_edge_obs(kpUn, ur, g.edge_obs, g.edge_stereo);
             g.edge_w.push_back((double)pKFi->mvInvLevelSigma2[kpUn.octave]);       // (no uncertainty2 in this function)
-            g.edge_stereo.push_back(ur >= 0);
         }
         if (bAllFixed) g.not_included[i] = true;
     }
@@ -141,35 +121,21 @@ void FlattenFullInertialBA(MapT* pMap, bool bFixLocal, FullBAFlat<KF, MP>& g)
 
 namespace fullba_detail {
 
-// one handle per calling thread: a handle owns one stream and must not be shared between threads
-inline fiba_solver* solver()
-{
-    static thread_local fiba_solver* s = nullptr;
-    if (!s) orbslam3_hip::check(fiba_create(0, &s));
-    return s;
-}
-
-struct Calib { double Rcb[9], tcb[3], tbc[3]; };
-
 template <class KF, class MP>
-inline void fill(const FullBAFlat<KF, MP>& g, int its, bool* pbStopFlag, bool bInit, float priorG, float priorA, Calib& cal, FibaProblem& p)
+inline void fill(const FullBAFlat<KF, MP>& g, int its, bool* pbStopFlag, bool bInit, float priorG, float priorA, FibaProblem& p)
 {
     std::memset(&p, 0, sizeof(p));
     KF* k0 = g.pIncKF;
     p.n_kf = (int32_t)g.kfs.size();
     p.Rwb = g.Rwb.data(); p.twb = g.twb.data(); p.vel = g.vel.data(); p.bg = g.bg.data(); p.ba = g.ba.data();
     p.pose_fixed = g.pose_fixed.data(); p.has_imu = g.has_imu.data(); p.imu_fixed = g.imu_fixed.data();
-    const Eigen::Matrix3d Rcb = k0->mImuCalib.mTcb.rotationMatrix().template cast<double>();
-    const Eigen::Vector3d tcb = k0->mImuCalib.mTcb.translation().template cast<double>(), tbc = k0->mImuCalib.mTbc.translation().template cast<double>();
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) cal.Rcb[3 * r + c] = Rcb(r, c); cal.tcb[r] = tcb[r]; cal.tbc[r] = tbc[r]; }
-    std::memcpy(p.Rcb, cal.Rcb, sizeof(p.Rcb)); std::memcpy(p.tcb, cal.tcb, sizeof(p.tcb)); std::memcpy(p.tbc, cal.tbc, sizeof(p.tbc));
+    orbslam3_hip::imu_calib(k0->mImuCalib, p.Rcb, p.tcb, p.tbc);
     p.fx = k0->fx; p.fy = k0->fy; p.cx = k0->cx; p.cy = k0->cy; p.bf = k0->mbf;
     p.n_points = (int32_t)g.mps.size(); p.points = g.X.data();
     p.n_edges = (int32_t)g.edge_kf.size(); p.edge_kf = g.edge_kf.data(); p.edge_point = g.edge_point.data(); p.edge_obs = g.edge_obs.data();
     p.edge_inv_sigma2 = g.edge_w.data(); p.edge_stereo = g.edge_stereo.data();
     p.n_links = (int32_t)g.links.size(); p.links = g.links.data();
-    const float thHuberMono = std::sqrt(5.991), thHuberStereo = std::sqrt(7.815);   // :592-593 (through float)
-    p.huber_mono = thHuberMono; p.huber_stereo = thHuberStereo; p.huber_inertial = std::sqrt(16.92);
+    p.huber_mono = orbslam3_hip::huber_mono(); p.huber_stereo = orbslam3_hip::huber_stereo(); p.huber_inertial = std::sqrt(16.92);   // :592-593
     p.lambda_init = 1e-5; p.max_iters = its;                                        // :407, :727
     p.shared_bias = bInit;
     if (bInit) {                                                                    // :456-466, :570-590
@@ -180,21 +146,14 @@ inline void fill(const FullBAFlat<KF, MP>& g, int its, bool* pbStopFlag, bool bI
     p.stop_flag = reinterpret_cast<const volatile uint8_t*>(pbStopFlag);
 }
 
-// :730-810
+// :730-810; p: the problem of g, for its camera-body calibration
 template <class MapT, class KF, class MP>
-inline void write_back(MapT* pMap, const FullBAFlat<KF, MP>& g, const Calib& cal, unsigned long nLoopId, const double* Ro, const double* to, const double* vo,
+inline void write_back(MapT* pMap, const FullBAFlat<KF, MP>& g, const FibaProblem& p, unsigned long nLoopId, const double* Ro, const double* to, const double* vo,
                        const double* go, const double* ao, const double* Xo)
 {
-    Eigen::Matrix3d Rcb;
-    Eigen::Vector3d tcb;
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcb(r, c) = cal.Rcb[3 * r + c]; tcb[r] = cal.tcb[r]; }
     for (size_t i = 0; i < g.kfs.size(); i++) {
         KF* pKFi = g.kfs[i];
-        Eigen::Matrix3d R; Eigen::Vector3d t;
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R(r, c) = Ro[9 * i + 3 * r + c]; t[r] = to[3 * i + r]; }
-        const Eigen::Matrix3d Rcw = Rcb * R.transpose();                            // ImuCamPose: Rcw = Rcb Rbw, tcw = Rcb tbw + tcb
-        const Eigen::Vector3d tcw = Rcb * (-R.transpose() * t) + tcb;
-        const Sophus::SE3f Tcw(Rcw.template cast<float>(), tcw.template cast<float>());
+        const Sophus::SE3f Tcw = orbslam3_hip::camera_pose(p.Rcb, p.tcb, &Ro[9 * i], &to[3 * i]);
         if (nLoopId == 0) pKFi->SetPose(Tcw);
         else { pKFi->mTcwGBA = Tcw; pKFi->mnBAGlobalForKF = nLoopId; }
         if (!pKFi->bImu) continue;
@@ -227,10 +186,9 @@ void FullInertialBAHIP(MapT* pMap, int its, const bool bFixLocal = false, const 
     FlattenFullInertialBA(pMap, bFixLocal, g);
     if (g.too_few) return;                                                          // :468-472
     FibaProblem p;
-    fullba_detail::Calib cal;
     bool device = !g.camera2 && !g.refused && g.pIncKF;
     if (device) {
-        fullba_detail::fill(g, its, pbStopFlag, bInit, priorG, priorA, cal, p);
+        fullba_detail::fill(g, its, pbStopFlag, bInit, priorG, priorA, p);
         const int ok = fiba_check(&p);                                              // before a handle (and with it a device) is asked for
         device = ok != ORBX_ERR_ARG && ok != ORBX_ERR_CAPACITY;
     }
@@ -240,8 +198,8 @@ void FullInertialBAHIP(MapT* pMap, int its, const bool bFixLocal = false, const 
     FibaOutputs o;
     o.Rwb = Ro.data(); o.twb = to.data(); o.vel = vo.data(); o.bg = go.data(); o.ba = ao.data(); o.points = Xo.data();
     LbaStats st;
-    orbslam3_hip::check(fiba_solve(fullba_detail::solver(), &p, &o, &st));
-    fullba_detail::write_back(pMap, g, cal, nLoopId, Ro.data(), to.data(), vo.data(), go.data(), ao.data(), Xo.data());
+    orbslam3_hip::check(fiba_solve(orbslam3_hip::thread_handle<fiba_solver, fiba_create>(), &p, &o, &st));
+    fullba_detail::write_back(pMap, g, p, nLoopId, Ro.data(), to.data(), vo.data(), go.data(), ao.data(), Xo.data());
 }
 
 }  // namespace ORB_SLAM3

@@ -66,36 +66,11 @@ void FlattenInertialOptimization(MapT* pMap, ImuInitFlat<KF>& g, bool set_new_bi
         auto* pInt = pKFi->mpImuPreintegrated;
         if (set_new_bias) pInt->SetNewBias(pKFi->mPrevKF->GetImuBias());                    // :3145 (before the vertex lookup)
         if (i1 == index.end() || i2 == index.end()) continue;                               // optimizer.vertex() == NULL: "Error", no edge
-        LibaLink L;
-        std::memset(&L, 0, sizeof(L));
-        L.kf1 = i1->second; L.kf2 = i2->second;
-        auto put3x3 = [](float* dst, const Eigen::Matrix3f& M) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = M(r, c); };
-        put3x3(L.dR, pInt->dR); put3x3(L.JRg, pInt->JRg); put3x3(L.JVg, pInt->JVg); put3x3(L.JVa, pInt->JVa); put3x3(L.JPg, pInt->JPg); put3x3(L.JPa, pInt->JPa);
-        for (int r = 0; r < 3; r++) { L.dV[r] = pInt->dV(r); L.dP[r] = pInt->dP(r); }
-        L.dT = pInt->dT;
-        const IMU::Bias b = pInt->GetOriginalBias();
-        L.bias0[0] = b.bax; L.bias0[1] = b.bay; L.bias0[2] = b.baz; L.bias0[3] = b.bwx; L.bias0[4] = b.bwy; L.bias0[5] = b.bwz;
-        Eigen::Matrix<double, 9, 9> Info = pInt->C.template block<9, 9>(0, 0).template cast<double>().inverse();     // EdgeInertialGS ctor, G2oTypes.cc:604-612
-        Info = (Info + Info.transpose()) / 2;
-        Eigen::SelfAdjointEigenSolver<Eigen::Matrix<double, 9, 9> > es(Info);
-        Eigen::Matrix<double, 9, 1> eigs = es.eigenvalues();
-        for (int k = 0; k < 9; k++) if (eigs[k] < 1e-12) eigs[k] = 0;
-        Info = es.eigenvectors() * eigs.asDiagonal() * es.eigenvectors().transpose();
-        for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) L.info9[9 * r + c] = Info(r, c);      // no factor 1e-2 here
-        L.robust = robust ? 1 : 0;
-        g.links.push_back(L);
+        g.links.push_back(orbslam3_hip::imu_link(pInt, i1->second, i2->second, 1.0, nullptr, robust));   // EdgeInertialGS: no factor 1e-2, no random-walk edges
     }
 }
 
 namespace imu_init_detail {
-
-// one handle per calling thread: a handle owns one stream and must not be shared between threads
-inline imu_init_solver* solver()
-{
-    static thread_local imu_init_solver* s = nullptr;
-    if (!s) orbslam3_hip::check(imu_init_create(0, &s));
-    return s;
-}
 
 struct Settings {
     bool free_vel, free_bias, free_gdir, free_scale, gauss_newton;
@@ -131,7 +106,7 @@ inline bool run(const ImuInitFlat<KF>& g, const Settings& s, const double* Rwg, 
     fill(g, s, Rwg, scale, vel_out, p, r);
     const int ok = imu_init_check(&p, &r);              // before a handle (and with it a device) is asked for
     if (ok == ORBX_ERR_ARG || ok == ORBX_ERR_CAPACITY) return false;
-    orbslam3_hip::check(imu_init_optimize_batch(solver(), &p, 1, &r));
+    orbslam3_hip::check(imu_init_optimize_batch(orbslam3_hip::thread_handle<imu_init_solver, imu_init_create>(), &p, 1, &r));
     return true;
 }
 

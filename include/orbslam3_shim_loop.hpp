@@ -29,13 +29,7 @@ namespace loop_detail {
 
 inline bool single_pinhole(KeyFrame* pKF) { return !pKF->mpCamera2 && pKF->mpCamera && pKF->mpCamera->GetType() == GeometricCamera::CAM_PINHOLE; }
 
-// one handle per calling thread: a handle owns one stream and must not be shared between threads (orbslam3_hip.h)
-inline sim3_solver* solver()
-{
-    static thread_local sim3_solver* s = nullptr;
-    if (!s) orbslam3_hip::check(sim3_create(0, &s));
-    return s;
-}
+inline sim3_solver* solver() { return orbslam3_hip::thread_handle<sim3_solver, sim3_create>(); }
 
 inline void intrinsics(KeyFrame* pKF, float* K)      // fx fy cx cy as the camera model holds them (Pinhole::toK_)
 {
@@ -440,12 +434,7 @@ struct Builder {
     }
 };
 
-inline essg_solver* solver()        // one handle per calling thread (orbslam3_hip.h)
-{
-    static thread_local essg_solver* s = nullptr;
-    if (!s) orbslam3_hip::check(essg_create(0, &s));
-    return s;
-}
+inline essg_solver* solver() { return orbslam3_hip::thread_handle<essg_solver, essg_create>(); }
 
 }  // namespace essential_detail
 

@@ -39,13 +39,7 @@ typedef NewMapPointCandidateT<KeyFrame> NewMapPointCandidate;
 
 namespace mapping_detail {
 
-// one handle per calling thread: a handle owns one stream and must not be shared between threads (orbslam3_hip.h)
-inline orbm_matcher* matcher()
-{
-    static thread_local orbm_matcher* m = nullptr;
-    if (!m) orbslam3_hip::check(orbm_create(0, &m));
-    return m;
-}
+inline orbm_matcher* matcher() { return orbslam3_hip::thread_handle<orbm_matcher, orbm_create>(); }
 
 template <class KF>
 struct FlatKeyFrame {           // the arrays an OrbmMapKeyFrame points into

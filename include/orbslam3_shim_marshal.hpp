@@ -1,0 +1,137 @@
+// orbslam3_shim_marshal.hpp -- the marshalling every drop-in adapter of orbslam3_shim*.hpp shares: the solver handle of the calling
+// thread, poses and calibrations between the reference's float types and the C ABI's doubles, one pre-integration as a LibaLink,
+// one observation as an edge record, the Huber deltas, the LbaProblem of a flattened window.
+// Included by orbslam3_shim.hpp, after orbslam3_hip::check and the reference's headers (Eigen, Sophus, cv::KeyPoint): include that
+// header, not this one.  Whatever touches a reference class takes it as a template parameter, so that the helpers serve the
+// adapters that are templates themselves (orbslam3_shim_fullba.hpp, orbslam3_shim_imu_init.hpp) and compile against stand-in types.
+// A problem struct holds raw pointers: a helper that returns one takes the arrays by reference, from an owner that has to outlive
+// the solve -- never hand it a temporary.
+#pragma once
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace orbslam3_hip {
+
+// The one handle of a solver type on the calling thread, created on first use: a handle owns one stream and must not be shared
+// between threads (orbslam3_hip.h).  Adapters that name the same Create share the handle.
+template <class T, int (*Create)(int, T**)>
+inline T* thread_handle()
+{
+    static thread_local T* h = nullptr;
+    if (!h) check(Create(0, &h));
+    return h;
+}
+
+// Sets a KannalaBrandt8 camera on a handle for the lifetime of the object; with cam == nullptr nothing is set and the handle keeps
+// its pinhole model.  The reset must happen on every way out (check() throws).
+template <class Handle, int (*Set)(Handle*, const OrbxKB8*)>
+struct CameraScope {
+    Handle* h;
+    CameraScope(Handle* h_, const OrbxKB8* cam) : h(cam ? h_ : nullptr) { if (h) check(Set(h, cam)); }
+    ~CameraScope() { if (h) (void)Set(h, nullptr); }
+    CameraScope(const CameraScope&) = delete;
+    CameraScope& operator=(const CameraScope&) = delete;
+};
+
+// Tcw -> q[4] (x y z w), t[3]: cast to double component by component, as g2o::SE3Quat is built from the float pose
+inline void pose_in(const Sophus::SE3f& Tcw, double* q, double* t)
+{
+    const Eigen::Quaterniond qd = Tcw.unit_quaternion().cast<double>();
+    const Eigen::Vector3d td = Tcw.translation().cast<double>();
+    q[0] = qd.x(); q[1] = qd.y(); q[2] = qd.z(); q[3] = qd.w();
+    t[0] = td.x(); t[1] = td.y(); t[2] = td.z();
+}
+inline Sophus::SE3f pose_out(const double* q, const double* t)
+{
+    const Eigen::Quaterniond qd(q[3], q[0], q[1], q[2]);
+    return Sophus::SE3f(qd.cast<float>(), Eigen::Vector3d(t[0], t[1], t[2]).cast<float>());
+}
+
+inline Eigen::Vector3f point_out(const double* X) { return Eigen::Vector3d(X[0], X[1], X[2]).cast<float>(); }
+
+template <class M>
+inline void put3x3(const M& m, double* dst) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = m(r, c); }
+
+// IMU::Calib -> Rcb[9] (row major), tcb[3], tbc[3]
+template <class Calib>
+inline void imu_calib(const Calib& calib, double* Rcb, double* tcb, double* tbc)
+{
+    const Eigen::Matrix3d R = calib.mTcb.rotationMatrix().template cast<double>();
+    const Eigen::Vector3d c = calib.mTcb.translation().template cast<double>(), b = calib.mTbc.translation().template cast<double>();
+    put3x3(R, Rcb);
+    for (int r = 0; r < 3; r++) { tcb[r] = c[r]; tbc[r] = b[r]; }
+}
+
+// ImuCamPose: the camera pose of a body pose, Rcw = Rcb Rbw, tcw = Rcb tbw + tcb
+inline Sophus::SE3f camera_pose(const double* Rcb_, const double* tcb_, const double* Rwb, const double* twb)
+{
+    Eigen::Matrix3d Rcb, R;
+    Eigen::Vector3d tcb, t;
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) { Rcb(r, c) = Rcb_[3 * r + c]; R(r, c) = Rwb[3 * r + c]; } tcb[r] = tcb_[r]; t[r] = twb[r]; }
+    const Eigen::Matrix3d Rcw = Rcb * R.transpose();
+    const Eigen::Vector3d tcw = Rcb * (-R.transpose() * t) + tcb;
+    return Sophus::SE3f(Rcw.cast<float>(), tcw.cast<float>());
+}
+
+// One IMU::Preintegrated between the slots kf1 -> kf2 as a LibaLink: the pre-integrated terms, the original bias, and the
+// EdgeInertial information of its constructor (G2oTypes.cc:510-518, EdgeInertialGS :604-612): C's 9 x 9 block cast to double,
+// inverted, symmetrised, eigenvalues below 1e-12 set to 0; info_scale is the factor 1e-2 of Optimizer.cc:2651.
+// random_walk_from = the pre-integration whose C gives the EdgeGyroRW / EdgeAccRW informations; nullptr leaves them zero.
+template <class Pre>
+inline LibaLink imu_link(Pre* pInt, int kf1, int kf2, double info_scale, decltype(pInt) random_walk_from, bool robust)
+{
+    LibaLink L;
+    std::memset(&L, 0, sizeof(L));
+    L.kf1 = kf1; L.kf2 = kf2;
+    auto put = [](float* dst, const Eigen::Matrix3f& M) { for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dst[3 * r + c] = M(r, c); };
+    put(L.dR, pInt->dR); put(L.JRg, pInt->JRg); put(L.JVg, pInt->JVg); put(L.JVa, pInt->JVa); put(L.JPg, pInt->JPg); put(L.JPa, pInt->JPa);
+    for (int r = 0; r < 3; r++) { L.dV[r] = pInt->dV(r); L.dP[r] = pInt->dP(r); }
+    L.dT = pInt->dT;
+    const auto b = pInt->GetOriginalBias();
+    L.bias0[0] = b.bax; L.bias0[1] = b.bay; L.bias0[2] = b.baz; L.bias0[3] = b.bwx; L.bias0[4] = b.bwy; L.bias0[5] = b.bwz;
+    Eigen::Matrix<double, 9, 9> Info = pInt->C.template block<9, 9>(0, 0).template cast<double>().inverse();
+    Info = (Info + Info.transpose()) / 2;
+    Eigen::SelfAdjointEigenSolver<Eigen::Matrix<double, 9, 9> > es(Info);
+    Eigen::Matrix<double, 9, 1> eigs = es.eigenvalues();
+    for (int k = 0; k < 9; k++) if (eigs[k] < 1e-12) eigs[k] = 0;
+    Info = es.eigenvectors() * eigs.asDiagonal() * es.eigenvectors().transpose();
+    Info *= info_scale;
+    for (int r = 0; r < 9; r++) for (int c = 0; c < 9; c++) L.info9[9 * r + c] = Info(r, c);
+    if (random_walk_from) {
+        const Eigen::Matrix3d InfoG = random_walk_from->C.template block<3, 3>(9, 9).template cast<double>().inverse();
+        const Eigen::Matrix3d InfoA = random_walk_from->C.template block<3, 3>(12, 12).template cast<double>().inverse();
+        put3x3(InfoG, L.info_gyro); put3x3(InfoA, L.info_acc);
+    }
+    L.robust = robust;
+    return L;
+}
+
+// one observation as an edge record: x, y, and the right coordinate of a stereo observation (mvuRight >= 0), else -1
+inline void push_edge_obs(const cv::KeyPoint& kpUn, float ur, std::vector<double>& obs, std::vector<uint8_t>& stereo)
+{
+    obs.push_back(kpUn.pt.x); obs.push_back(kpUn.pt.y); obs.push_back(ur >= 0 ? (double)ur : -1.0);
+    stereo.push_back(ur >= 0);
+}
+
+// the reference keeps its Huber deltas in floats (const float thHuberMono = sqrt(5.991), Optimizer.cc:838-839, :1275-1276, ...)
+inline double huber_mono() { const float d = std::sqrt(5.991); return d; }
+inline double huber_stereo() { const float d = std::sqrt(7.815); return d; }
+
+// The LbaProblem of a flattened window.  cam = fx fy cx cy bf.  The problem points into the arrays.
+inline LbaProblem lba_problem(const std::vector<double>& q, const std::vector<double>& t, const std::vector<uint8_t>& fixed, const double* points, int n_points,
+                              const std::vector<int32_t>& ePoint, const std::vector<int32_t>& ePose, const std::vector<double>& eObs, const std::vector<double>& eW,
+                              const std::vector<uint8_t>& eStereo, const double (&cam)[5], double huber_mono_, double huber_stereo_)
+{
+    LbaProblem pr;
+    pr.n_poses = (int)fixed.size(); pr.pose_q = q.data(); pr.pose_t = t.data(); pr.pose_fixed = fixed.data();
+    pr.n_points = n_points; pr.points = points;
+    pr.n_edges = (int)ePoint.size(); pr.edge_point = ePoint.data(); pr.edge_pose = ePose.data(); pr.edge_obs = eObs.data();
+    pr.edge_inv_sigma2 = eW.data(); pr.edge_stereo = eStereo.data();
+    pr.fx = cam[0]; pr.fy = cam[1]; pr.cx = cam[2]; pr.cy = cam[3]; pr.bf = cam[4];
+    pr.huber_mono = huber_mono_; pr.huber_stereo = huber_stereo_;
+    return pr;
+}
+
+}  // namespace orbslam3_hip

@@ -9,6 +9,7 @@
 #define ORBSLAM3_HIP_WITH_REFERENCE
 #include "standin_fullba.hpp"
 #include "orbslam3_shim_fullba.hpp"
+#include "record_abi.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +46,7 @@ extern "C" int fiba_check(const FibaProblem* p) { return p->n_kf > 1000 ? ORBX_E
 extern "C" int fiba_solve(fiba_solver*, const FibaProblem* p, const FibaOutputs* o, LbaStats* st)
 {
     g_solve_calls++;
+    record_abi::dump(*p);           // stderr: the whole struct, for tests/test_shim_abi_golden.py
     std::printf("call n_kf %d n_points %d n_edges %d n_links %d shared %d its %d lambda %a priors %a %a stop %d huber %a %a %a cam %a %a %a %a %a\n", p->n_kf, p->n_points,
                 p->n_edges, p->n_links, (int)p->shared_bias, p->max_iters, p->lambda_init, p->prior_g, p->prior_a, p->stop_flag ? (int)*p->stop_flag : -1, p->huber_mono,
                 p->huber_stereo, p->huber_inertial, p->fx, p->fy, p->cx, p->cy, p->bf);

@@ -11,6 +11,7 @@
 #define ORBSLAM3_HIP_WITH_REFERENCE
 #include "standin_imu_init.hpp"
 #include "orbslam3_shim_imu_init.hpp"
+#include "record_abi.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -101,6 +102,15 @@ int main(int argc, char** argv)
         ImuInitFlat<ImiKeyFrame> g;
         FlattenInertialOptimization(&map, g, overload != 3, overload == 3);
         std::printf("key_frames %zu links %zu refused %d\n", g.kfs.size(), g.links.size(), (int)g.refused);
+        {   // stderr: the problem struct made of this walk, for tests/test_shim_abi_golden.py (this toy has no fake of the solve to record it)
+            const imu_init_detail::Settings s = {overload != 3, overload == 2, overload != 2, overload == 1, overload == 3, 1e2, 1e6, overload == 3 ? 1.0 : 0.0, 1e3, 200};
+            const double Rwg[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1};
+            std::vector<double> vel_out;
+            ImuInitProblem p;
+            ImuInitResult r;
+            imu_init_detail::fill(g, s, Rwg, 1.5, vel_out, p, r);
+            record_abi::dump(p);
+        }
         std::printf("bias %a %a %a %a %a %a\n", g.bg[0], g.bg[1], g.bg[2], g.ba[0], g.ba[1], g.ba[2]);
         for (size_t k = 0; k < g.kfs.size(); k++) {
             std::printf("kf %lu", g.kfs[k]->mnId);

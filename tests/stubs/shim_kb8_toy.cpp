@@ -1,11 +1,13 @@
 // TEST INFRASTRUCTURE -- drives include/orbslam3_shim_kb8.hpp (PoseOptimizationAnyCamHIP, LocalBundleAdjustmentAnyCamHIP) on toy
 // frames and a toy window made of the stand-in types (tests/stubs/standin_*.hpp) against a RECORDING FAKE of the C entry points
-// defined here: every call prints a line, the solves return the inputs moved by fixed amounts.  No device is needed.
+// defined here: every call prints a line (and dumps its whole argument on stderr through record_abi.hpp, for tests/test_shim_abi_golden.py),
+// the solves return the inputs moved by fixed amounts.  No device is needed.
 //   shim_kb8_toy <scenario>      pose_kb8 | pose_pinhole | pose_rig | pose_stereo_obs | lba_kb8 | lba_mixed | lba_rig | lba_fixed_pinhole | lba_stereo_obs
 // tests/test_shim_kb8_typed.py checks the order of the calls, the camera parameters and what was written back.
 #define ORBSLAM3_HIP_WITH_REFERENCE
 #include "standin_kb8.hpp"
 #include "orbslam3_shim_kb8.hpp"
+#include "record_abi.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +38,7 @@ extern "C" const char* orbx_last_error(void) { return "fake"; }
 static int id_of(const void* h) { return (int)reinterpret_cast<size_t>(h); }
 static void print_camera(const char* what, const void* h, const OrbxKB8* c)
 {
+    record_abi::dump(c);
     if (!c) { std::printf("%s handle %d NULL\n", what, id_of(h)); return; }
     std::printf("%s handle %d %a %a %a %a %a %a %a %a\n", what, id_of(h), c->fx, c->fy, c->cx, c->cy, c->k[0], c->k[1], c->k[2], c->k[3]);
 }
@@ -46,6 +49,7 @@ extern "C" int lba_set_camera_kb8(lba_solver* s, const OrbxKB8* c) { print_camer
 extern "C" int pose_optimize(pose_solver* s, const PoseProblem* p, PoseResult* r, uint8_t* outlier)
 {
     int n_stereo = 0;
+    record_abi::dump(*p);
     for (int i = 0; i < p->n; i++) n_stereo += p->stereo[i];
     std::printf("pose_optimize handle %d n %d stereo %d huber %a first_obs %a %a %a\n", id_of(s), p->n, n_stereo, p->huber_mono, p->n ? p->obs[0] : 0.0, p->n ? p->obs[1] : 0.0,
                 p->n ? p->obs[2] : 0.0);
@@ -59,6 +63,8 @@ extern "C" int lba_solve(lba_solver* s, const LbaProblem* p, const volatile uint
                          uint8_t* depth, LbaStats*)
 {
     int n_stereo = 0, n_fixed = 0;
+    record_abi::dump(*p);
+    record_abi::scalar("max_iters", max_iters); record_abi::scalar("lambda_init", lambda_init);
     for (int e = 0; e < p->n_edges; e++) n_stereo += p->edge_stereo[e];
     for (int i = 0; i < p->n_poses; i++) n_fixed += p->pose_fixed[i];
     std::printf("lba_solve handle %d poses %d fixed %d points %d edges %d stereo %d iters %d lambda %a\n", id_of(s), p->n_poses, n_fixed, p->n_points, p->n_edges, n_stereo, max_iters,

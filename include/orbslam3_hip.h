@@ -662,7 +662,8 @@ int  orbv_transform_batch_device(orbv_vocab* v, const uint8_t* d_desc, const int
  * Optimizer::LocalInertialBA(KeyFrame*, bool*, Map*, int&, int&, int&, int&, bool bLarge, bool bRecInit)
  * (include/Optimizer.h, src/Optimizer.cc:2383-2958).  The graph walk (:2383-2500) and the map
  * write-back (:2862-2957) stay in the host shim, which also reads the pre-integrated terms off IMU::Preintegrated
- * (IntegrateNewMeasurement stays on the host) and forms the information matrices (G2oTypes.cc:510-518, Optimizer.cc:2651-2668).
+ * and forms the information matrices (G2oTypes.cc:510-518, Optimizer.cc:2651-2668); imu_preintegrate_batch and imu_links_batch of
+ * orbslam3_hip_imu_preint.h do both on the device (IntegrateNewMeasurement, and a state as the LibaLink read here).
  * Vertices: per key frame a body pose (VertexPose / ImuCamPose, 6), velocity, gyro bias, accelerometer bias (3 each);
  * landmarks marginalised.  Edges: EdgeMono / EdgeStereo, EdgeInertial, EdgeGyroRW, EdgeAccRW.
  * ------------------------------------------------------------------------------------------------------------------ */
@@ -968,6 +969,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 #include "orbslam3_hip_imu_init.h"
 #include "orbslam3_hip_fullba.h"
 #include "orbslam3_hip_kb8.h"
+#include "orbslam3_hip_imu_preint.h"
 
 #ifdef __cplusplus
 }

@@ -1901,3 +1901,159 @@ class FullInertialBA:
 
     def last_device_ms(self):
         return lib.fiba_last_device_ms(self._h)
+
+
+# ---- IMU pre-integration on the device (include/orbslam3_hip_imu_preint.h) ----
+class ImuMeasurement(C.Structure):
+    _fields_ = [("a", C.c_float * 3), ("w", C.c_float * 3), ("dt", C.c_float)]
+
+
+class ImuPreintState(C.Structure):
+    _fields_ = [("dT", C.c_float), ("b", C.c_float * 6), ("bu", C.c_float * 6), ("nga", C.c_float * 6), ("nga_walk", C.c_float * 6),
+                ("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9),
+                ("JVa", C.c_float * 9), ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("avgA", C.c_float * 3), ("avgW", C.c_float * 3),
+                ("C", C.c_float * 225), ("n_meas", C.c_int32)]
+
+
+class ImuPreintJob(C.Structure):
+    _fields_ = [("state", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("reset", C.c_uint8), ("bias", C.c_float * 6)]
+
+
+class ImuLinkSpec(C.Structure):
+    _fields_ = [("state", C.c_int32), ("walk_state", C.c_int32), ("kf1", C.c_int32), ("kf2", C.c_int32), ("info_scale", C.c_double),
+                ("robust", C.c_uint8)]
+
+
+class ImuPredictJob(C.Structure):
+    _fields_ = [("state", C.c_int32), ("Rwb1", C.c_float * 9), ("twb1", C.c_float * 3), ("Vwb1", C.c_float * 3), ("bias", C.c_float * 6)]
+
+
+class ImuPredictOut(C.Structure):
+    _fields_ = [("Rwb2", C.c_float * 9), ("twb2", C.c_float * 3), ("Vwb2", C.c_float * 3)]
+
+
+def _np_dtype(cls, shapes=None):
+    """the numpy record of a ctypes struct: same offsets, same size"""
+    names, formats, offsets = [], [], []
+    for name, ct in cls._fields_:
+        names.append(name); offsets.append(getattr(cls, name).offset)
+        if hasattr(ct, "_length_"):
+            n = ct._length_
+            shape = (shapes or {}).get(name, (n,))
+            formats.append((np.dtype(ct._type_), shape))
+        else:
+            formats.append(np.dtype(ct))
+    return np.dtype(dict(names=names, formats=formats, offsets=offsets, itemsize=C.sizeof(cls)))
+
+
+_M33 = {k: (3, 3) for k in ("dR", "JRg", "JVg", "JVa", "JPg", "JPa", "Rwb1", "Rwb2")}
+IMU_MEAS_DTYPE = _np_dtype(ImuMeasurement)
+IMU_STATE_DTYPE = _np_dtype(ImuPreintState, dict(_M33, C=(15, 15)))
+IMU_JOB_DTYPE = _np_dtype(ImuPreintJob)
+IMU_LINK_SPEC_DTYPE = _np_dtype(ImuLinkSpec)
+IMU_PREDICT_JOB_DTYPE = _np_dtype(ImuPredictJob, _M33)
+IMU_PREDICT_OUT_DTYPE = _np_dtype(ImuPredictOut, _M33)
+LIBA_LINK_DTYPE = _np_dtype(_LibaLink, dict(_M33, info9=(9, 9), info_gyro=(3, 3), info_acc=(3, 3)))
+
+lib.imu_preint_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+lib.imu_preint_destroy.argtypes = [C.c_void_p]
+lib.imu_preint_last_device_ms.argtypes = [C.c_void_p]
+lib.imu_preint_last_device_ms.restype = C.c_double
+lib.imu_preint_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+lib.imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+lib.imu_preintegrate_batch_device.argtypes = lib.imu_preintegrate_batch.argtypes + [C.c_void_p]
+lib.imu_frame_measurements_batch.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+lib.imu_frame_measurements_batch_device.argtypes = lib.imu_frame_measurements_batch.argtypes + [C.c_void_p]
+lib.imu_links_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+lib.imu_links_batch_device.argtypes = lib.imu_links_batch.argtypes + [C.c_void_p]
+lib.imu_predict_state_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+lib.imu_predict_state_batch_device.argtypes = lib.imu_predict_state_batch.argtypes + [C.c_void_p]
+
+
+def imu_state_new(n, nga, nga_walk):
+    """n states as Preintegrated(Bias(), calib) leaves them: Initialize(0), nga / nga_walk = the diagonals of Calib::Cov / CovWalk"""
+    s = np.zeros(n, IMU_STATE_DTYPE)
+    s["nga"] = np.asarray(nga, np.float32); s["nga_walk"] = np.asarray(nga_walk, np.float32)
+    s["dR"] = np.eye(3, dtype=np.float32)
+    return s
+
+
+def imu_preint_check(states, jobs, meas):
+    """the host-only argument checks of imu_preintegrate_batch: the ORBX code"""
+    return lib.imu_preint_check(_p(states), len(states), _p(jobs), len(jobs), _p(meas), len(meas))
+
+
+class ImuPreintegrator:
+    """IMU::Preintegrated on the device (include/orbslam3_hip_imu_preint.h): Initialize / IntegrateNewMeasurement batched over states,
+    the interpolation loop of Tracking::PreintegrateIMU, the LibaLink of a state and Tracking::PredictStateIMU.  The host entries
+    take numpy records (IMU_STATE_DTYPE, IMU_JOB_DTYPE, ...); the *_device entries take device addresses (int) and only enqueue.
+    One handle serves one call at a time."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        _check(lib.imu_preint_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.imu_preint_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def preintegrate(self, states, jobs, meas):
+        """states is updated in place; returns the per-job status"""
+        assert states.dtype == IMU_STATE_DTYPE and states.flags.c_contiguous
+        jobs = np.ascontiguousarray(jobs, IMU_JOB_DTYPE); meas = np.ascontiguousarray(meas, IMU_MEAS_DTYPE)
+        st = np.zeros(len(jobs), np.int32)
+        _check(lib.imu_preintegrate_batch(self._h, _p(states), len(states), _p(jobs), len(jobs), _p(meas), len(meas), _p(st)))
+        return st
+
+    def preintegrate_device(self, d_states, n_states, d_jobs, n_jobs, d_meas, n_meas, d_status, stream=None):
+        _check(lib.imu_preintegrate_batch_device(self._h, C.c_void_p(d_states), int(n_states), C.c_void_p(d_jobs), int(n_jobs), C.c_void_p(d_meas or 0),
+                                                 int(n_meas), C.c_void_p(d_status), C.c_void_p(stream or 0)))
+
+    def frame_measurements(self, samples, n_imu, t_prev_ns, t_cur_ns):
+        """samples [B][imu_cap] IMU_DTYPE; returns (meas [B][imu_cap] IMU_MEAS_DTYPE, count [B])"""
+        samples = np.ascontiguousarray(samples, IMU_DTYPE)
+        B, cap = samples.shape
+        n_imu = np.ascontiguousarray(n_imu, np.int32); tp = np.ascontiguousarray(t_prev_ns, np.int64); tc = np.ascontiguousarray(t_cur_ns, np.int64)
+        assert n_imu.shape == tp.shape == tc.shape == (B,)
+        meas = np.zeros((B, cap), IMU_MEAS_DTYPE); cnt = np.zeros(B, np.int32)
+        _check(lib.imu_frame_measurements_batch(self._h, _p(samples), _p(n_imu), _p(tp), _p(tc), B, cap, _p(meas), _p(cnt)))
+        return meas, cnt
+
+    def frame_measurements_device(self, d_samples, d_n_imu, d_t_prev_ns, d_t_cur_ns, batch, imu_cap, d_meas_out, d_count_out, stream=None):
+        _check(lib.imu_frame_measurements_batch_device(self._h, C.c_void_p(d_samples), C.c_void_p(d_n_imu), C.c_void_p(d_t_prev_ns), C.c_void_p(d_t_cur_ns),
+                                                       int(batch), int(imu_cap), C.c_void_p(d_meas_out), C.c_void_p(d_count_out), C.c_void_p(stream or 0)))
+
+    def links(self, states, specs):
+        """returns (links LIBA_LINK_DTYPE [n], status [n])"""
+        assert states.dtype == IMU_STATE_DTYPE and states.flags.c_contiguous
+        specs = np.ascontiguousarray(specs, IMU_LINK_SPEC_DTYPE)
+        out = np.zeros(len(specs), LIBA_LINK_DTYPE); st = np.zeros(len(specs), np.int32)
+        _check(lib.imu_links_batch(self._h, _p(states), len(states), _p(specs), len(specs), _p(out), _p(st)))
+        return out, st
+
+    def links_device(self, d_states, n_states, d_specs, n_links, d_links_out, d_status, stream=None):
+        _check(lib.imu_links_batch_device(self._h, C.c_void_p(d_states), int(n_states), C.c_void_p(d_specs), int(n_links), C.c_void_p(d_links_out),
+                                          C.c_void_p(d_status), C.c_void_p(stream or 0)))
+
+    def predict(self, states, jobs):
+        """returns (out IMU_PREDICT_OUT_DTYPE [n], status [n])"""
+        assert states.dtype == IMU_STATE_DTYPE and states.flags.c_contiguous
+        jobs = np.ascontiguousarray(jobs, IMU_PREDICT_JOB_DTYPE)
+        out = np.zeros(len(jobs), IMU_PREDICT_OUT_DTYPE); st = np.zeros(len(jobs), np.int32)
+        _check(lib.imu_predict_state_batch(self._h, _p(states), len(states), _p(jobs), len(jobs), _p(out), _p(st)))
+        return out, st
+
+    def predict_device(self, d_states, n_states, d_jobs, n_jobs, d_out, d_status, stream=None):
+        _check(lib.imu_predict_state_batch_device(self._h, C.c_void_p(d_states), int(n_states), C.c_void_p(d_jobs), int(n_jobs), C.c_void_p(d_out),
+                                                  C.c_void_p(d_status), C.c_void_p(stream or 0)))
+
+    def last_device_ms(self):
+        return lib.imu_preint_last_device_ms(self._h)

@@ -365,7 +365,8 @@ int orbx_extractor::setup_geometry(int w, int h)
             max_nch = std::max(max_nch, (qoff + 4 * ngx + 4 + 15) >> 4);
             for (int j = 0; j < sd.ncell; j++) { const CellDesc& c = cells[sd.cell0 + j]; max_int = std::max(max_int, (c.x1 - c.x0 - 6) * ih); }
             max_ngx = std::max(max_ngx, ngx); max_sth = std::max(max_sth, sth);
-            max_ent = std::max(max_ent, ((ih + 3) / 4) * ngx);
+            // (the minThFAST pass lists the wave's rows cell by cell: a quad that straddles two cells is listed with both)
+            max_ent = std::max(max_ent, ((ih + 3) / 4) * (ngx + sd.ncell - 1));
             max_ncell = std::max(max_ncell, (int)sd.ncell);
         }
         if (max_int > 8191) return fail(ORBX_ERR_ARG, "FAST cell interior of %d px exceeds the 8191-px bitmask", max_int);

@@ -4,9 +4,9 @@
 // The cell interiors of a level tile its detection area exactly (SURVEY E2), so a strip is processed as ONE image region and
 // the cell structure only enters where the reference's semantics need it: the 3x3 non-maximum suppression treats everything
 // outside a pixel's own cell interior as 0, the iniThFAST -> minThFAST fallback is per cell, and the output order is
-// cell-major / row-major.  Per threshold t ("phase"; iniThFAST over the whole strip, then minThFAST over each cell of the
-// strip that found nothing, :843-846), every WAVE owns the rows y = wave, wave + 4, ... of the strip and keeps its lists
-// to itself (counters in SGPRs, no LDS atomics, no workgroup barrier until the score map is needed by the neighbours):
+// cell-major / row-major.  At iniThFAST, over the whole strip, every WAVE owns the rows y = wave, wave + 4, ... of the strip and
+// keeps its lists to itself (counters in SGPRs, no LDS atomics, no workgroup barrier until the score map is needed by the
+// neighbours):
 //
 //   stage 1  dense, 4 pixels per lane in packed u16 pairs: the COMPASS quick test -- a 9-arc of the ring contains ring pixel
 //            0 or 8 and ring pixel 4 or 12, so a corner at t has, with one polarity, one pixel of each of these two opposite
@@ -24,9 +24,19 @@
 //   rank     per cell (one wave each): exclusive prefix of the mask's word popcounts -> cell count (0 => fallback phase)
 //   emit     one lane per corner whose bit is set: rank = prefix[word] + popcount(lower bits) -> the cell's slots in HBM.
 //
-// A corner list that overflows (more than corner_cap corners in a quarter of a strip: pathological images, or the debug
-// knob of the tests) sends its wave through the same nms / emit code over ALL the pixels of its rows instead.  Everything is
-// integer; the result is the reference's vToDistributeKeys order and content bit for bit.
+// Then minThFAST for each cell of the strip that found nothing (:843-846; 9 % of the cells of the synthetic frames, a handful of
+// corners each).  The quick test is the wide part and is shared out as before: every wave lists the entries of its rows, cell
+// by cell.  After ONE workgroup barrier the k-th such cell of the strip is the work of wave k & 3 alone, which expands the
+// cell's segment of all four entry lists and runs stage 2, nms, rank and emit of that cell, ordered by its own LDS queue
+// (wave_lds_fence).  No further barrier is needed because a cell is self-contained: the suppression masks everything outside
+// the cell interior, and the cell's mask words, prefix words, total and map bytes have no other writer -- a quad that
+// straddles two cells is scored by both owners, which store the same score in the same byte.  The cells of a strip run side
+// by side, and a strip without such a cell (three in four) pays nothing.
+//
+// A corner list that overflows (more than corner_cap corners of a wave: pathological images, or the debug knob of the tests)
+// sends its wave through the same nms / emit code over ALL the pixels it scored instead (its rows of the strip; in the
+// minThFAST pass, the rows and quads of its cell).  Everything is integer; the result is the reference's vToDistributeKeys order and
+// content bit for bit.
 
 struct StripDesc {
     int16_t level;
@@ -40,7 +50,7 @@ struct FastLds {                // byte offsets into the dynamic LDS block (host
     int32_t tile_pitch;         // bytes per tile row (multiple of 16)
     int32_t map_off, map_pitch; // M map: (ih + 2) rows, 4 bytes of margin left of the first quad
     int32_t colcell_off;        // u8 per map column: cell of the strip that owns it, 0xFF = none
-    int32_t ent_off, ent_cap;   // u16 entries of stage 1, ent_cap per wave (worst case: every quad of the wave's rows)
+    int32_t ent_off, ent_cap;   // u16 entries of stage 1, ent_cap per wave (worst case: every quad of the wave's rows, cell by cell)
     int32_t px_off;             // u16 surviving pixels of one batch, kPxCap per wave
     int32_t corner_off, corner_cap;   // u16 corners, corner_cap per wave
     int32_t bits_off, pre_off, wpc;   // u32 bitmasks and their word prefix sums, wpc words per cell
@@ -51,7 +61,7 @@ constexpr int kStripMaxCells = 8;
 constexpr int kStripWidth = 160;      // target strip width in pixels: four 36-px cells
 constexpr int kEntBatch = 128;        // entries expanded at a time ...
 constexpr int kPxCap = 4 * kEntBatch; // ... into at most this many pixels
-constexpr int kCornerCap = 256;       // corners a wave lists before it falls back to scanning its rows
+constexpr int kCornerCap = 256;       // corners a wave lists before it falls back to scanning the pixels it scored
 
 __device__ __forceinline__ int fast_m_tree(const uint8_t* __restrict__ t, int pitch)
 {
@@ -114,6 +124,7 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_cx0[kStripMaxCells], s_iw[kStripMaxCells], s_total[kStripMaxCells], s_slot_off[kStripMaxCells], s_slot_cap[kStripMaxCells];
+    __shared__ int s_seg[4][kStripMaxCells + 1];        // minThFAST: where the segment of the k-th fallback cell starts in a wave's entry list
 #ifdef ORBX_FAST_TIMING
     long long t_prev = clock64();
     int fallback_slot = 0;
@@ -124,6 +135,9 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     const StripDesc S = strips[strip_idx];
     const LevelDesc L = levels[S.level];
     const int frame = blockIdx.y;
+#if defined(ORBX_FAST_CUT)      // a cut variant emits nothing: the stages downstream see empty cells, not whatever the buffer held
+    if ((int)threadIdx.x < S.ncell) cell_count[(size_t)frame * n_cells + S.cell0 + threadIdx.x] = 0;
+#endif
     const bool ext = S.level == 0 && lvl0.base != nullptr;       // level 0 read from the caller's image in place
     const uint8_t* img = ext ? lvl0.base + (size_t)frame * lvl0.frame_stride : pyr + (size_t)frame * frame_stride + L.off;
     const int istride = ext ? lvl0.stride : L.stride;
@@ -212,15 +226,17 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     int ncorner = 0;                // wave-uniform: corners this wave found in the current phase (> corner_cap: overflow)
     int gA = 0, ng = 1;             // active quads of the current phase
 
-    // stages 1 + 2 of one phase = the score side of cv::FAST(cell, t, true) for the cells [cA, cB) of the strip
-    auto score_phase = [&](const int t, const int cA, const int cB) {
+    // the quads that hold the columns of the cells [cA, cB)
+    auto set_cols = [&](const int cA, const int cB) {
         const int mA = s_cx0[cA], mB = s_cx0[cB - 1] + s_iw[cB - 1] - 1;       // first / last active map column
         gA = (mA - 4) >> 2;
         ng = ((mB - 4) >> 2) - gA + 1;
-        const int nrow_w = (ih - wave + 3) >> 2;              // rows wave, wave + 4, ...
+    };
+    const int nrow_w = (ih - wave + 3) >> 2;              // the wave's rows: wave, wave + 4, ...
+    // stage 1 of cv::FAST(cell, t, true) over the active quads of the wave's rows: the entries join the wave's list behind the nent
+    // it holds; returns the new length
+    auto stage1 = [&](const int t, int nent) {
         const int n_items = nrow_w * ng;
-        int nent = 0;
-        // ---- stage 1 ----
         {
             const uint32_t T2 = (uint32_t)t | ((uint32_t)t << 16);
             const int q64 = 64 / ng, r64 = 64 - q64 * ng;     // 64 items further on: q64 rows down, r64 quads right
@@ -265,22 +281,24 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
             }
         }
         wave_lds_fence();
-        ORBX_FTICK(1)
-#if defined(ORBX_FAST_CUT) && ORBX_FAST_CUT == 1
-        if (nent >= 0) return;
-#endif
-        // ---- expand + stage 2 ----
-        ncorner = 0;
+        return nent;
+    };
+    // expand + stage 2 over nent entries, which may come from all four waves' lists: entry i is entry i + (d & 0xFFFF) of the lists'
+    // block and was listed by wave d >> 16, d = d0 below c1, d1 below c2, d2 below c3, d3 from there; the corners join the wave's list
+    const uint16_t* ent_all = (const uint16_t*)(smem + Z.ent_off);
+    auto stage2 = [&](const int t, const int nent, const int c1, const int c2, const int c3, const int d0, const int d1, const int d2, const int d3) {
         for (int e0 = 0; e0 < nent; e0 += kEntBatch) {
             const int e1 = min(e0 + kEntBatch, nent);
             int npx = 0;
             for (int base = e0; base < e1; base += 64) {
                 const int i = base + lane;
-                const uint32_t en = (i < e1) ? (uint32_t)ent[i] : 0u;
+                int d = d0;
+                d = i >= c1 ? d1 : d; d = i >= c2 ? d2 : d; d = i >= c3 ? d3 : d;
+                const uint32_t en = (i < e1) ? (uint32_t)ent_all[i + (d & 0xFFFF)] | ((uint32_t)d & 0x30000u) : 0u;
                 const int cnt = __popc(en & 0xFu);
                 const int incl = wave_incl_scan(cnt);
                 if (cnt) {
-                    const uint32_t id = ((((en >> 4) & 31u) * 4u + (uint32_t)wave) << 8) | (((en >> 9) & 63u) << 2);     // (y << 8) | (4 * gx)
+                    const uint32_t id = ((((en >> 4) & 31u) * 4u + (en >> 16)) << 8) | (((en >> 9) & 63u) << 2);     // (y << 8) | (4 * gx)
                     int p = npx + incl - cnt;
                     if (en & 1u) pxl[p++] = (uint16_t)(id | 0u);
                     if (en & 2u) pxl[p++] = (uint16_t)(id | 1u);
@@ -310,70 +328,114 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
             wave_lds_fence();
         }
     };
-    // nms or emission over the wave's corners -- or, after an overflow, over every pixel of its rows
-    auto for_corners = [&](auto&& fn) {
+    // nms or emission over the wave's corners -- or, after an overflow, over every pixel of the active quads of the nrows rows
+    // y0, y0 + ystep, ... that the list was made from
+    auto for_corners = [&](const int y0, const int ystep, const int nrows, auto&& fn) {
         if (ncorner <= Z.corner_cap) {
             for (int base = 0; base < ncorner; base += 64) {
                 const int i = base + lane;
                 if (i < ncorner) { const int id = corners[i]; fn(id >> 8, (id & 0xFF) + 4); }
             }
         } else {
-            const int wpx = 4 * ng, n = ((ih - wave + 3) >> 2) * wpx;
+            const int wpx = 4 * ng, n = nrows * wpx;
             const float inv = 1.0f / (float)wpx;
             for (int i = lane; i < n; i += 64) {
                 const int ry = (int)(((float)i + 0.5f) * inv), xq = 4 * gA + i - ry * wpx;
-                fn(4 * ry + wave, xq + 4);
+                fn(ystep * ry + y0, xq + 4);
             }
         }
     };
-    // per-cell exclusive prefix of the mask's word popcounts, one wave per cell
-    auto rank_cells = [&](const int cA, const int cB) {
-        for (int j = cA + wave; j < cB; j += 4) {
-            const int nwords = (s_iw[j] * ih + 31) >> 5;
-            int run = 0;
-            for (int w0 = 0; w0 < nwords; w0 += 64) {
-                const int i = w0 + lane;
-                const int my = (i < nwords) ? __popc(bits[j * WPC + i]) : 0;
-                const int incl = wave_incl_scan(my);
-                if (i < nwords) pre[j * WPC + i] = (uint32_t)(run + incl - my);
-                run += __builtin_amdgcn_readlane(incl, 63);
-            }
-            if (lane == 0) s_total[j] = run;
+    // exclusive prefix of the word popcounts of cell j's mask, by one wave
+    auto rank_cell = [&](const int j) {
+        const int nwords = (s_iw[j] * ih + 31) >> 5;
+        int run = 0;
+        for (int w0 = 0; w0 < nwords; w0 += 64) {
+            const int i = w0 + lane;
+            const int my = (i < nwords) ? __popc(bits[j * WPC + i]) : 0;
+            const int incl = wave_incl_scan(my);
+            if (i < nwords) pre[j * WPC + i] = (uint32_t)(run + incl - my);
+            run += __builtin_amdgcn_readlane(incl, 63);
         }
+        if (lane == 0) s_total[j] = run;
     };
-    auto phase = [&](const int t, const int cA, const int cB) {
-        score_phase(t, cA, cB);
-        ORBX_FTICK(2)
-#if defined(ORBX_FAST_CUT) && ORBX_FAST_CUT < 3
-        if (t >= 0) return;
+    // ---- iniThFAST over the whole strip ----
+    uint32_t fb_cells = 0u;         // workgroup-uniform: bit j = cell j found nothing at iniThFAST
+    set_cols(0, S.ncell);
+    {
+        const int nent = stage1(ini_th, 0);
+        ORBX_FTICK(1)
+#if !defined(ORBX_FAST_CUT) || ORBX_FAST_CUT >= 2
+        const int d = (wave * Z.ent_cap) | (wave << 16);         // the wave's own list
+        stage2(ini_th, nent, nent, nent, nent, d, d, d, d);
 #endif
-        __syncthreads();                                          // every wave's scores are in the map
-        ORBX_FTICK(3)
-        for_corners([&](int y, int mc) { nms_pixel(y, mc, t, cA, cB); });
-        __syncthreads();                                          // every winner's bit is set
-        ORBX_FTICK(4)
-        rank_cells(cA, cB);
-        __syncthreads();
-        ORBX_FTICK(5)
-        for_corners([&](int y, int mc) { emit_pixel(y, mc, cA, cB); });
-        ORBX_FTICK(6)
-    };
-
-    // ---- iniThFAST over the whole strip; then, per cell without a single keypoint, minThFAST (:843-846) ----
-    phase(ini_th, 0, S.ncell);
+    }
+    ORBX_FTICK(2)
+#if !defined(ORBX_FAST_CUT) || ORBX_FAST_CUT >= 3
+    __syncthreads();                                              // every wave's scores are in the map
+    ORBX_FTICK(3)
+    for_corners(wave, 4, nrow_w, [&](int y, int mc) { nms_pixel(y, mc, ini_th, 0, S.ncell); });
+    __syncthreads();                                              // every winner's bit is set
+    ORBX_FTICK(4)
+    for (int j = wave; j < S.ncell; j += 4) rank_cell(j);
+    __syncthreads();
+    ORBX_FTICK(5)
+    // (read here, between two barriers: the owner of a fallback cell writes s_total[j] again after the next one)
+    fb_cells = (uint32_t)__ballot(lane < S.ncell && s_total[min(lane, kStripMaxCells - 1)] == 0);
+    for_corners(wave, 4, nrow_w, [&](int y, int mc) { emit_pixel(y, mc, 0, S.ncell); });
+    ORBX_FTICK(6)
+#endif
 #if defined(ORBX_FAST_CUT)      // instruction-budget experiments (tools/fast_cuts.sh): the kernel ends after a prefix of its stages
     if (ini_th >= 0) return;
 #endif
 #ifdef ORBX_FAST_TIMING
     fallback_slot = 8;
 #endif
-    for (int j = 0; j < S.ncell; j++) {
-        if (s_total[j] != 0) continue;                            // uniform: written before the last barrier of the phase that ranked it
-        __syncthreads();                                          // other waves may still be emitting from the previous phase
+    // ---- per cell without a single keypoint, minThFAST (:843-846).  The quick test, which is wide, is shared out like the first
+    // one: every wave lists the entries of its rows, one segment per fallback cell (its entry list is its own and free by now).
+    // Everything behind it is small (a handful of corners per cell), so after ONE barrier the k-th fallback cell is the work of wave
+    // k & 3 alone: it expands the cell's segment of all four lists, scores, suppresses, ranks and emits, ordered by its own LDS queue.
+    // That is safe because a cell is self-contained: the suppression masks everything outside its interior, and its mask words, prefix
+    // words, total and the map bytes of its columns are written by its owner only (a quad shared with the neighbour cell gets the
+    // same scores from both owners, in bytes of their own). ----
+    if (fb_cells) {
+        int k = 0, nent = 0;
+        if (lane == 0) s_seg[wave][0] = 0;
+        for (uint32_t rest = fb_cells; rest; rest &= rest - 1u, k++) {
+            const int j = __builtin_ctz(rest);
+            set_cols(j, j + 1);
+            nent = stage1(min_th, nent);
+            if (lane == 0) s_seg[wave][k + 1] = nent;
+        }
+        ORBX_FTICK(1)
+        // every wave's entries and segment ends are in LDS -- and no wave is still emitting from the iniThFAST pass (its overflow
+        // scan reads every cell's mask, which the owners are about to write)
+        __syncthreads();
+        ORBX_FTICK(3)
+        k = 0;
+        for (uint32_t rest = fb_cells; rest; rest &= rest - 1u, k++) {
+            if ((k & 3) != wave) continue;
+            const int j = __builtin_ctz(rest);
 #ifdef ORBX_FAST_TIMING
-        if (threadIdx.x == 0) atomicAdd(&d_fast_prof[15], 1ull);
+            if (threadIdx.x == 0) atomicAdd(&d_fast_prof[15], 1ull);
 #endif
-        phase(min_th, j, j + 1);
+            set_cols(j, j + 1);
+            // entry i of the cell = entry i + d[w] of wave w's list, w = the number of c[] that i has reached
+            auto seg = [&](int w, int kk) { return __builtin_amdgcn_readfirstlane(s_seg[w][kk]); };          // (uniform: into SGPRs)
+            const int b0 = seg(0, k), b1 = seg(1, k), b2 = seg(2, k), b3 = seg(3, k);
+            const int c1 = seg(0, k + 1) - b0, c2 = c1 + seg(1, k + 1) - b1, c3 = c2 + seg(2, k + 1) - b2, n = c3 + seg(3, k + 1) - b3;
+            const int d0 = b0, d1 = (Z.ent_cap + b1 - c1) | (1 << 16), d2 = (2 * Z.ent_cap + b2 - c2) | (2 << 16), d3 = (3 * Z.ent_cap + b3 - c3) | (3 << 16);
+            ncorner = 0;
+            stage2(min_th, n, c1, c2, c3, d0, d1, d2, d3);
+            ORBX_FTICK(2)
+            for_corners(0, 1, ih, [&](int y, int mc) { nms_pixel(y, mc, min_th, j, j + 1); });
+            wave_lds_fence();
+            ORBX_FTICK(4)
+            rank_cell(j);
+            wave_lds_fence();
+            ORBX_FTICK(5)
+            for_corners(0, 1, ih, [&](int y, int mc) { emit_pixel(y, mc, j, j + 1); });
+            ORBX_FTICK(6)
+        }
     }
     __syncthreads();
     if (tid < S.ncell) cell_count[(size_t)frame * n_cells + S.cell0 + tid] = min(s_total[tid], s_slot_cap[tid]);

@@ -24,4 +24,6 @@ v = list(out)
 names = ["load + clears + tables", "stage 1 (compass test)", "expand + stage 2 (scores)", "barrier", "nms", "rank", "emit"]
 tot = sum(v[:15])
 print("iniThFAST pass:   " + ", ".join("%s %.1f%%" % (n, 100.0 * c / tot) for n, c in zip(names, v[:7])))
-print("minThFAST passes: " + ", ".join("%s %.1f%%" % (n, 100.0 * c / tot) for n, c in zip(names[1:], v[9:15])) + " (%d cells fell back)" % v[15])
+# (every wave runs the quick test of its rows; everything behind the barrier is the work of the cell's owner: thread 0 times the cells
+# that wave 0 owns, the first and the fifth of a strip)
+print("minThFAST passes: " + ", ".join("%s %.1f%%" % (n, 100.0 * c / tot) for n, c in zip(names[1:], v[9:15])) + " (%d cells fell back on wave 0)" % v[15])

@@ -970,6 +970,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 #include "orbslam3_hip_fullba.h"
 #include "orbslam3_hip_kb8.h"
 #include "orbslam3_hip_imu_preint.h"
+#include "orbslam3_hip_fisheye.h"
 
 #ifdef __cplusplus
 }

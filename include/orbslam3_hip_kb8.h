@@ -11,14 +11,16 @@
  *
  * While a KB8 camera is set on a handle:
  *   - pose_optimize, pose_optimize_batch, lba_solve and lba_solve_batch use it; fx, fy, cx, cy and bf of the problem are not read;
- *   - a stereo edge is ORBX_ERR_ARG (KB8 frames are monocular, or a two-camera rig, which is not built);
+ *   - a stereo edge is ORBX_ERR_ARG (KB8 frames are monocular, or a two-camera rig, whose edges are not built);
  *   - pose_optimize_batch_device returns ORBX_ERR_ARG (it has no KB8 path and must not project as a pinhole);
  *   - fx <= 0 or fy <= 0 in a setter is ORBX_ERR_ARG and leaves the handle's camera as it was.
  * These checks are made before anything touches a device, and the handle stays usable.  A setter with cam == NULL returns the
  * handle to the pinhole camera of the problems; results are then bit-identical to those of a fresh handle.
  * lba_solve_batch keeps its contract: window i equals lba_solve of that window bit for bit.
- * Not built: the stereo-fisheye rig (mpCamera2, EdgeSE3ProjectXYZToBody), the matcher's device-side projections, the inertial
- * solvers, the sharded global BA (lba_shard_*) and the pose graphs. */
+ * The stereo step of a two-camera rig, Frame::ComputeStereoFishEyeMatches, is built: orbslam3_hip_fisheye.h.
+ * Not built: what reads its outputs (the Nleft != -1 branches of the matchers, the EdgeSE3ProjectXYZToBody edges with mpCamera2,
+ * KeyFrame::UnprojectStereoFishEye), the matcher's device-side projections, the inertial solvers, the sharded global BA
+ * (lba_shard_*) and the pose graphs. */
 typedef struct OrbxKB8 { double fx, fy, cx, cy, k[4]; } OrbxKB8;   /* mvParameters[0..7], floats promoted to double */
 
 int pose_set_camera_kb8(pose_solver* s, const OrbxKB8* cam);        /* NULL: back to pinhole */

@@ -31,9 +31,7 @@ namespace kb8_detail {
 inline bool camera_of(GeometricCamera* pCamera, OrbxKB8& out)
 {
     if (!pCamera || pCamera->GetType() != GeometricCamera::CAM_FISHEYE) return false;
-    KannalaBrandt8* kb = static_cast<KannalaBrandt8*>(pCamera);
-    out.fx = kb->getParameter(0); out.fy = kb->getParameter(1); out.cx = kb->getParameter(2); out.cy = kb->getParameter(3);
-    for (int k = 0; k < 4; k++) out.k[k] = kb->getParameter(4 + k);
+    orbslam3_hip::kb8_in(static_cast<KannalaBrandt8*>(pCamera), out);
     return true;
 }
 

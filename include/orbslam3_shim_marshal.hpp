@@ -1,6 +1,7 @@
 // orbslam3_shim_marshal.hpp -- the marshalling every drop-in adapter of orbslam3_shim*.hpp shares: the solver handle of the calling
 // thread, poses and calibrations between the reference's float types and the C ABI's doubles, one pre-integration as a LibaLink,
-// one observation as an edge record, the Huber deltas, the LbaProblem of a flattened window.
+// one observation as an edge record, key points, descriptors and a fisheye rig as the C ABI reads them, the Huber deltas, the LbaProblem of a
+// flattened window.
 // Included by orbslam3_shim.hpp, after orbslam3_hip::check and the reference's headers (Eigen, Sophus, cv::KeyPoint): include that
 // header, not this one.  Whatever touches a reference class takes it as a template parameter, so that the helpers serve the
 // adapters that are templates themselves (orbslam3_shim_fullba.hpp, orbslam3_shim_imu_init.hpp) and compile against stand-in types.
@@ -113,6 +114,47 @@ inline void push_edge_obs(const cv::KeyPoint& kpUn, float ur, std::vector<double
 {
     obs.push_back(kpUn.pt.x); obs.push_back(kpUn.pt.y); obs.push_back(ur >= 0 ? (double)ur : -1.0);
     stereo.push_back(ur >= 0);
+}
+
+// mvKeys as the C ABI's key points: cv::KeyPoint has OrbxKeyPoint's layout (orbslam3_hip.h), so the vector is read in place
+inline const OrbxKeyPoint* keypoints_in(const std::vector<cv::KeyPoint>& keys)
+{
+    static_assert(sizeof(cv::KeyPoint) == sizeof(OrbxKeyPoint), "cv::KeyPoint layout");
+    return keys.empty() ? nullptr : reinterpret_cast<const OrbxKeyPoint*>(keys.data());
+}
+
+// the first n rows of a descriptor matrix (CV_8U, 32 columns) as one contiguous array: read in place where the rows already are,
+// else copied into `copy`, which has to outlive the call that reads the pointer
+inline const uint8_t* descriptors_in(const cv::Mat& desc, int n, std::vector<uint8_t>& copy)
+{
+    if (n <= 0) return nullptr;
+    if (desc.isContinuous()) return desc.data;
+    copy.resize((size_t)n * 32);
+    for (int r = 0; r < n; r++) std::memcpy(copy.data() + (size_t)r * 32, desc.ptr<uint8_t>(r), 32);
+    return copy.data();
+}
+
+// the eight parameters of a KannalaBrandt8 camera (mvParameters: fx fy cx cy k0 k1 k2 k3, floats) promoted to double
+template <class Fisheye>
+inline void kb8_in(Fisheye* kb, OrbxKB8& out)
+{
+    out.fx = kb->getParameter(0); out.fy = kb->getParameter(1); out.cx = kb->getParameter(2); out.cy = kb->getParameter(3);
+    for (int k = 0; k < 4; k++) out.k[k] = kb->getParameter(4 + k);
+}
+
+// A two-camera fisheye rig as an OrbxFisheyeRig: the eight parameters of each camera (floats promoted to double), their Newton
+// precision, and Tlr as mRlr (row major) and mtlr.  Fisheye = KannalaBrandt8 (getParameter, GetPrecision)
+template <class Fisheye>
+inline OrbxFisheyeRig fisheye_rig_in(Fisheye* left, Fisheye* right, const Sophus::SE3f& Tlr)
+{
+    OrbxFisheyeRig rig;
+    std::memset(&rig, 0, sizeof(rig));
+    kb8_in(left, rig.left); kb8_in(right, rig.right);
+    rig.precision_l = left->GetPrecision(); rig.precision_r = right->GetPrecision();
+    const Eigen::Matrix3f R = Tlr.rotationMatrix();
+    const Eigen::Vector3f t = Tlr.translation();
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) rig.Rlr[3 * r + c] = R(r, c); rig.tlr[r] = t(r); }
+    return rig;
 }
 
 // the reference keeps its Huber deltas in floats (const float thHuberMono = sqrt(5.991), Optimizer.cc:838-839, :1275-1276, ...)

@@ -565,6 +565,37 @@ class Matcher:
         lib.orbm_create_new_map_points_last_kernel_ms.argtypes = [C.c_void_p]
         return float(lib.orbm_create_new_map_points_last_kernel_ms(self._h))
 
+    # ---- Frame::ComputeStereoFishEyeMatches (include/orbslam3_hip_fisheye.h) ----
+    def stereo_fisheye(self, rig, kps_l, desc_l, mono_l, kps_r, desc_r, mono_r, level_sigma2):
+        """orbm_stereo_fisheye on host arrays: kps = KP_DTYPE arrays (mvKeys / mvKeysRight), mono = monoLeft / monoRight, rig as
+        fisheye_rig() takes it.  Returns dict(matches, left_to_right, right_to_left, depth, p3d, knn_right, knn_d0, knn_d1)."""
+        kps_l = np.ascontiguousarray(kps_l, KP_DTYPE); kps_r = np.ascontiguousarray(kps_r, KP_DTYPE)
+        desc_l = np.ascontiguousarray(desc_l, np.uint8); desc_r = np.ascontiguousarray(desc_r, np.uint8)
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        n_l, n_r = len(kps_l), len(kps_r)
+        out = dict(left_to_right=np.full(n_l, -1, np.int32), right_to_left=np.full(n_r, -1, np.int32), depth=np.full(n_l, -1, np.float32),
+                   p3d=np.zeros((n_l, 3), np.float32), knn_right=np.full(n_l, -1, np.int32), knn_d0=np.full(n_l, -1, np.int32),
+                   knn_d1=np.full(n_l, -1, np.int32))
+        _fisheye_argtypes()
+        out["matches"] = _check(lib.orbm_stereo_fisheye(self._h, _p(kps_l), _p(desc_l), n_l, int(mono_l), _p(kps_r), _p(desc_r), n_r, int(mono_r),
+                                                        _p(sig), len(sig), C.byref(fisheye_rig(rig)), _p(out["left_to_right"]), _p(out["right_to_left"]),
+                                                        _p(out["depth"]), _p(out["p3d"]), _p(out["knn_right"]), _p(out["knn_d0"]), _p(out["knn_d1"])))
+        return out
+
+    def stereo_fisheye_last_kernel_ms(self):
+        _fisheye_argtypes()
+        return float(lib.orbm_stereo_fisheye_last_kernel_ms(self._h))
+
+    def stereo_fisheye_device(self, rig, batch, cap, d_kps_l, d_desc_l, d_n_l, d_mono_l, d_kps_r, d_desc_r, d_n_r, d_mono_r, level_sigma2,
+                              d_left_to_right, d_right_to_left, d_depth, d_p3d, d_knn_right=None, d_knn_d0=None, d_knn_d1=None, stream=None):
+        """orbm_stereo_fisheye_batch_device: raw device pointers (ints, e.g. torch.Tensor.data_ptr()); asynchronous"""
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        _fisheye_argtypes()
+        v = lambda q: C.c_void_p(q or 0)
+        _check(lib.orbm_stereo_fisheye_batch_device(self._h, int(batch), int(cap), v(d_kps_l), v(d_desc_l), v(d_n_l), v(d_mono_l), v(d_kps_r), v(d_desc_r),
+                                                    v(d_n_r), v(d_mono_r), _p(sig), len(sig), C.byref(fisheye_rig(rig)), v(d_left_to_right),
+                                                    v(d_right_to_left), v(d_depth), v(d_p3d), v(d_knn_right), v(d_knn_d0), v(d_knn_d1), v(stream)))
+
 
 ORBM_MAX_NEIGHBOURS = 64
 
@@ -732,6 +763,53 @@ def kb8_project(cam, Xc, want_jac=True, device=0):
     jac = np.zeros((len(X), 6)) if want_jac else None
     _check(lib.orbx_kb8_project(device, C.byref(_kb8(cam)), _p(X), len(X), _p(uv), _p(jac)))
     return (uv, jac.reshape(-1, 2, 3)) if want_jac else uv
+
+
+class OrbxFisheyeRig(C.Structure):
+    """OrbxFisheyeRig of include/orbslam3_hip_fisheye.h: mpCamera, mpCamera2, their precision, mRlr (row major), mtlr"""
+    _fields_ = [("left", OrbxKB8), ("right", OrbxKB8), ("precision_l", C.c_float), ("precision_r", C.c_float), ("Rlr", C.c_float * 9), ("tlr", C.c_float * 3)]
+
+
+ORBM_FISHEYE_KNN_CHUNK = 128        # right key points the k-NN kernel stages per pass (include/orbslam3_hip_fisheye.h)
+
+
+def fisheye_rig(rig):
+    """dict(left, right (as _kb8 takes them), precision_l, precision_r, Rlr (3, 3), tlr (3,)) -> OrbxFisheyeRig"""
+    if isinstance(rig, OrbxFisheyeRig):
+        return rig
+    r = OrbxFisheyeRig(_kb8(rig["left"]), _kb8(rig["right"]), float(rig.get("precision_l", 1e-6)), float(rig.get("precision_r", 1e-6)))
+    r.Rlr[:] = [float(v) for v in np.asarray(rig["Rlr"], np.float32).reshape(9)]
+    r.tlr[:] = [float(v) for v in np.asarray(rig["tlr"], np.float32).reshape(3)]
+    return r
+
+
+def _fisheye_argtypes():
+    side = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.orbm_stereo_fisheye_check.argtypes = side + side + [C.c_void_p, C.c_int, C.POINTER(OrbxFisheyeRig)]
+    lib.orbm_stereo_fisheye.argtypes = [C.c_void_p] + side + side + [C.c_void_p, C.c_int, C.POINTER(OrbxFisheyeRig)] + [C.c_void_p] * 7
+    lib.orbm_stereo_fisheye_last_kernel_ms.restype = C.c_float
+    lib.orbm_stereo_fisheye_last_kernel_ms.argtypes = [C.c_void_p]
+    lib.orbm_stereo_fisheye_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.POINTER(OrbxFisheyeRig)] + [C.c_void_p] * 8
+    lib.orbx_kb8_triangulate_matches.argtypes = [C.c_int, C.POINTER(OrbxFisheyeRig)] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+
+
+def stereo_fisheye_check(rig, kps_l, desc_l, n_l, mono_l, kps_r, desc_r, n_r, mono_r, level_sigma2, n_levels):
+    """orbm_stereo_fisheye_check with the arguments as given (arrays or None; rig a dict, an OrbxFisheyeRig or None): the code"""
+    _fisheye_argtypes()
+    return int(lib.orbm_stereo_fisheye_check(_p(kps_l), _p(desc_l), int(n_l), int(mono_l), _p(kps_r), _p(desc_r), int(n_r), int(mono_r), _p(level_sigma2),
+                                             int(n_levels), None if rig is None else C.byref(fisheye_rig(rig))))
+
+
+def kb8_triangulate_matches(rig, pts_l, pts_r, sigma_l, sigma_r, device=0):
+    """orbx_kb8_triangulate_matches: KannalaBrandt8::TriangulateMatches of n pixel pairs on the device -> (code or depth [n], p3d [n, 3])"""
+    pl = np.ascontiguousarray(pts_l, np.float32).reshape(-1, 2); pr = np.ascontiguousarray(pts_r, np.float32).reshape(-1, 2)
+    sl = np.ascontiguousarray(sigma_l, np.float32); sr = np.ascontiguousarray(sigma_r, np.float32)
+    n = len(pl)
+    assert len(pr) == len(sl) == len(sr) == n
+    code = np.zeros(n, np.float32); p3d = np.zeros((n, 3), np.float32)
+    _fisheye_argtypes()
+    _check(lib.orbx_kb8_triangulate_matches(device, C.byref(fisheye_rig(rig)), _p(pl), _p(pr), _p(sl), _p(sr), n, _p(code), _p(p3d)))
+    return code, p3d
 
 
 def _lba_problem(w):

@@ -63,6 +63,8 @@ struct orbm_matcher {
     float h_scale[32] = {};             // ... staged here: the asynchronous copy must not read the caller's array after the call returned
     hipEvent_t nmp_ev[2] = {nullptr, nullptr};      // orbm_create_new_map_points: events around its one kernel (created on first use)
     float nmp_kernel_ms = 0.f;
+    hipEvent_t sfe_ev[2] = {nullptr, nullptr};      // orbm_stereo_fisheye: events around its two kernels (created on first use)
+    float sfe_kernel_ms = 0.f;
 
     int ensure(size_t bytes)
     {

@@ -1929,6 +1929,8 @@ void orbm_destroy(orbm_matcher* m)
     if (m->d_scale) (void)hipFree(m->d_scale);
     for (hipEvent_t e : m->nmp_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : m->sfe_ev)
+        if (e) (void)hipEventDestroy(e);
     delete m;
 }
 

@@ -34,7 +34,15 @@ struct CellDesc {
 };
 
 struct TileDesc {
-    int16_t level, x0, y0, pad;
+    int16_t level, x0, y0;     // x0: a multiple of the tile width
+    int16_t edge;              // bit 0: a stored output reads columns left of column 0, bit 1: right of the last column
+};
+
+// One destination row of the table-driven resize (k_resize, k_resize_tail): the two source rows clamped to the source image
+// (sy0 | sy1 << 16) and the two vertical coefficients (0 .. 2048) shifted left by 12.  The host pads the table to whole tiles of
+// 64 rows with copies of the last row, so that a thread reads its rows without a bound test.
+struct __attribute__((aligned(16))) ResizeRow {
+    uint32_t sy, b0, b1, pad;
 };
 
 // Workgroups are dispatched round-robin over the 8 XCDs, so workgroups b and b+8 share an L2 (MI355X_MICROARCH.md,

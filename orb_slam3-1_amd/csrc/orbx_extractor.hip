@@ -116,11 +116,12 @@ struct orbx_extractor {
     DevBuf<TileDesc> d_tiles;
     DevBuf<StripDesc> d_strips;
     // resize tables per destination level: per quad of columns the first source column, 4 v_perm selectors, 4 coefficient pairs
-    std::vector<DevBuf<int> > d_qsx0, d_yofs;
+    // and per destination row the two source rows and the two coefficients (ResizeRow)
+    std::vector<DevBuf<int> > d_qsx0;
     std::vector<DevBuf<uint4> > d_qsel, d_qalpha;
-    std::vector<DevBuf<short> > d_ibeta;
-    std::vector<DevBuf<int> > d_xofs;            // per-column tables of the levels that take k_resize_generic (resize_generic[l])
-    std::vector<DevBuf<short> > d_ialpha;
+    std::vector<DevBuf<ResizeRow> > d_rows;
+    std::vector<DevBuf<int> > d_xofs, d_yofs;    // per-column / per-row tables of the levels that take k_resize_generic (resize_generic[l])
+    std::vector<DevBuf<short> > d_ialpha, d_ibeta;
     std::vector<uint8_t> resize_generic;
 
     // per-batch scratch
@@ -216,7 +217,7 @@ int orbx_extractor::setup_geometry(int w, int h)
     size_t off = 0;
     int cand_off = 0, sel_off = 0, max_tw = 0, max_th = 0, max_nfeat = 0;
     std::vector<int> node_need(nlevels, 0);
-    d_qsx0.resize(nlevels); d_yofs.resize(nlevels); d_qsel.resize(nlevels); d_qalpha.resize(nlevels); d_ibeta.resize(nlevels);
+    d_qsx0.resize(nlevels); d_yofs.resize(nlevels); d_qsel.resize(nlevels); d_qalpha.resize(nlevels); d_ibeta.resize(nlevels); d_rows.resize(nlevels);
     d_xofs.resize(nlevels); d_ialpha.resize(nlevels); resize_generic.assign(nlevels, 0);
     for (int l = 0; l < nlevels; l++) {
         LevelDesc& L = levels[l];
@@ -295,7 +296,9 @@ int orbx_extractor::setup_geometry(int w, int h)
         // blur tiles
         for (int y0 = 0; y0 < L.h; y0 += kBlurTH)
             for (int x0 = 0; x0 < L.w; x0 += kBlurTW) {
-                TileDesc t; t.level = (int16_t)l; t.x0 = (int16_t)x0; t.y0 = (int16_t)y0; t.pad = 0;
+                TileDesc t; t.level = (int16_t)l; t.x0 = (int16_t)x0; t.y0 = (int16_t)y0;
+                // (the 7 taps of the tile's last column, x0 + 63, reach column x0 + 66)
+                t.edge = (int16_t)((x0 == 0 ? 1 : 0) | (L.w <= x0 + kBlurTW + 2 ? 2 : 0));
                 tiles.push_back(t);
             }
         // resize tables (cv::resize INTER_LINEAR 8UC1); level l is made from level l-1
@@ -345,13 +348,24 @@ int orbx_extractor::setup_geometry(int w, int h)
                 qsel[q] = make_uint4(se[0], se[1], se[2], se[3]);
                 qal[q] = make_uint4(al[0], al[1], al[2], al[3]);
             }
+            // per destination row: the source rows clamped to the image and the coefficients as k_resize multiplies them (b << 12)
+            std::vector<ResizeRow> rows((size_t)round_up(L.h, kResizeRows));
+            for (size_t dy = 0; dy < rows.size(); dy++) {
+                const int y = std::min((int)dy, L.h - 1);
+                const int sy0 = std::min(std::max(yofs[y], 0), P.h - 1), sy1 = std::min(std::max(yofs[y] + 1, 0), P.h - 1);
+                if (ib[2 * y] < 0 || ib[2 * y] > 2048 || ib[2 * y + 1] < 0 || ib[2 * y + 1] > 2048)
+                    return fail(ORBX_ERR_INTERNAL, "resize table: row coefficients %d %d", ib[2 * y], ib[2 * y + 1]);
+                rows[dy].sy = (uint32_t)sy0 | ((uint32_t)sy1 << 16);
+                rows[dy].b0 = (uint32_t)ib[2 * y] << 12; rows[dy].b1 = (uint32_t)ib[2 * y + 1] << 12; rows[dy].pad = 0;
+            }
             int r;
-            if (resize_generic[l] && ((r = d_xofs[l].upload(xofs)) || (r = d_ialpha[l].upload(ia)))) return r;
-            if ((r = d_qsx0[l].upload(qsx0)) || (r = d_yofs[l].upload(yofs)) || (r = d_qsel[l].upload(qsel)) || (r = d_qalpha[l].upload(qal)) ||
-                (r = d_ibeta[l].upload(ib))) return r;
+            if (resize_generic[l] && ((r = d_xofs[l].upload(xofs)) || (r = d_ialpha[l].upload(ia)) || (r = d_yofs[l].upload(yofs)) || (r = d_ibeta[l].upload(ib)))) return r;
+            if ((r = d_qsx0[l].upload(qsx0)) || (r = d_qsel[l].upload(qsel)) || (r = d_qalpha[l].upload(qal)) || (r = d_rows[l].upload(rows))) return r;
         }
     }
     pyr_frame_bytes = off;
+    // (k_resize and k_blur address the levels of one frame with 32-bit byte offsets)
+    if (off >= ((size_t)1 << 31)) return fail(ORBX_ERR_ARG, "the pyramid of a %dx%d image exceeds 2 GiB per frame", w, h);
     cand_frame_entries = std::max(cand_off, 1);
     sel_frame_entries = sel_off;
     // FAST kernel LDS: sized for the largest strip (orbx_fast_strips.inc)
@@ -550,7 +564,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
                                    d_xofs[l].p, d_ialpha[l].p, d_yofs[l].p, d_ibeta[l].p);
             else
             hipLaunchKernelGGL(k_resize, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
-                               d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_yofs[l].p, d_ibeta[l].p);
+                               d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
             ORBX_LAUNCHED("k_resize");
         }
         if (chain_beside) ORBX_HIP(hipEventRecord(ev_resize, rs));
@@ -597,7 +611,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
         if (l_tail < nlevels) {
             ResizeTables T;
             std::memset(&T, 0, sizeof(T));
-            for (int l = l_tail; l < nlevels; l++) { T.q_sx0[l] = d_qsx0[l].p; T.q_sel[l] = d_qsel[l].p; T.q_alpha[l] = d_qalpha[l].p; T.yofs[l] = d_yofs[l].p; T.ibeta[l] = d_ibeta[l].p; }
+            for (int l = l_tail; l < nlevels; l++) { T.q_sx0[l] = d_qsx0[l].p; T.q_sel[l] = d_qsel[l].p; T.q_alpha[l] = d_qalpha[l].p; T.rows[l] = d_rows[l].p; }
             // With side streams the tail -- one latency-bound workgroup per frame -- and FAST on its levels run BESIDE FAST on the
             // lower levels (which only need the levels before the tail) instead of in front of it.
             const bool beside = blur_s && oct_stream && n_cells > 0 && tail_strip > 0;
@@ -812,6 +826,7 @@ void orbx_destroy(orbx_extractor* e)
     for (auto& b : e->d_qsel) b.release();
     for (auto& b : e->d_qalpha) b.release();
     for (auto& b : e->d_ibeta) b.release();
+    for (auto& b : e->d_rows) b.release();
     for (auto& b : e->d_xofs) b.release();
     for (auto& b : e->d_ialpha) b.release();
     e->d_pyr.release(); e->d_blur.release(); e->d_cand.release(); e->d_scratch.release(); e->d_sel.release(); e->d_oct_nodes.release();
@@ -866,6 +881,9 @@ int orbx_extract_batch_device(orbx_extractor* e, const uint8_t* d_imgs, int batc
 {
     if (!e || !d_imgs || !d_kps || !d_desc || !d_n || !d_mono || !d_status) return fail(ORBX_ERR_ARG, "NULL argument");
     if (batch < 1 || width < 1 || height < 1 || row_stride < width || cap < 1) return fail(ORBX_ERR_ARG, "bad batch/geometry");
+    // (k_resize and k_blur address the pixels of one frame with 32-bit byte offsets, row x stride as a 24-bit product)
+    if (row_stride >= (1 << 24) || (uint64_t)row_stride * (uint64_t)height >= (1ull << 31))
+        return fail(ORBX_ERR_ARG, "a frame of %d rows of %d bytes exceeds 2 GiB (or a row 16 MiB)", height, row_stride);
     ORBX_HIP(hipSetDevice(e->device));
     int r;
     if ((r = e->setup_geometry(width, height)) || (r = e->ensure_batch(batch))) return r;

@@ -45,57 +45,65 @@ struct SrcImage {
     int32_t stride, w, h;       // row stride in bytes (multiple of 4), size
 };
 
+// high dword of the 48-bit product of two 24-bit factors (v_mul_hi_u32_u24)
+__device__ __forceinline__ uint32_t mul_hi_u24(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu)) >> 32); }
+
 struct __attribute__((aligned(4))) Dwords3 { uint32_t x, y, z; };     // 12 bytes at dword alignment: one global_load_dwordx3
 struct __attribute__((aligned(4))) Dwords4 { uint32_t x, y, z, w; };  // 16 bytes at dword alignment: one global_load_dwordx4
 constexpr int kResizeRows = 64, kResizeTW = 64;      // output tile of a workgroup: 64 x 64 (16 rows per wave, 64-pixel segments of four rows per wave step)
 
-// one tile of 64 x 64 outputs of level `dst` of frame `frame` by 4 waves (`wave` 0..3, 16 rows each).  A wave covers 16 quads
+// one tile of 64 x 64 outputs of level `dst` of one frame by 4 waves (`wave` 0..3, 16 rows each).  A wave covers 16 quads
 // (64 pixels) of FOUR rows at a time: levels are 179..533 pixels wide, and whole waves per row (256 pixels) left a third of the
 // lanes idle on average (533 px = 2.08 waves); with 64-pixel segments the idle share is a few percent.
-__device__ __forceinline__ void resize_tile(const SrcImage& src, uint8_t* __restrict__ pyr, size_t frame_stride, const LevelDesc& dst,
+// `S` and `D` are the frame's source image and destination level (wave-uniform: scalar registers); a thread addresses both with
+// 32-bit byte offsets (the host refuses frames of 2 GiB and more).  Everything that depends on the output row only is the
+// host-built `rows` table (ResizeRow, padded to whole tiles): the two source rows, already clamped, and the two coefficients.
+__device__ __forceinline__ void resize_tile(const uint8_t* __restrict__ S, int s_stride, uint8_t* __restrict__ D, const LevelDesc& dst,
                                             const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
-                                            const int* __restrict__ yofs, const short* __restrict__ ibeta, int tile, int frame, int lane, int wave)
+                                            const ResizeRow* __restrict__ rows, int tile, int lane, int wave)
 {
     const int tiles_x = (dst.w + kResizeTW - 1) / kResizeTW;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int q = tx * (kResizeTW / 4) + (lane & 15), rsel = lane >> 4;
     if (4 * q >= dst.w) return;
+    constexpr int NR = kResizeRows / 16;                        // row groups of 4 per wave
+    const int dy0 = ty * kResizeRows + wave * (kResizeRows / 4) + rsel;
+    ResizeRow rw[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) rw[r] = *(const ResizeRow*)((const uint8_t*)rows + (((uint32_t)dy0 << 4) + 64u * r));
     const int sx0 = q_sx0[q];
     const uint4 sel = q_sel[q], al = q_alpha[q];
     const uint32_t sels[4] = {sel.x, sel.y, sel.z, sel.w}, als[4] = {al.x, al.y, al.z, al.w};
-    const int a = sx0 & ~3;
+    const uint32_t a = (uint32_t)(sx0 & ~3);
     const uint32_t sh = (uint32_t)(sx0 & 3);
-    const int last = src.stride - 4;                            // last dword of a row: bytes past the row's pixels only meet coefficient 0
-    const int o0 = a, o1 = min(a + 4, last), o2 = min(a + 8, last);
-    const uint8_t* S = src.base + (size_t)frame * src.frame_stride;
-    uint8_t* D = pyr + (size_t)frame * frame_stride + dst.off + 4 * q;
-    constexpr int NR = kResizeRows / 16;                        // row groups of 4 per wave
-    const int dy0 = ty * kResizeRows + wave * (kResizeRows / 4) + rsel;
+    const uint32_t last = (uint32_t)(s_stride - 4);             // last dword of a row: bytes past the row's pixels only meet coefficient 0
     // all the loads of the wave's rows are issued before the first result is stored (the compiler cannot move a load above a
     // store through pointers it cannot tell apart)
-    uint32_t u[NR][3], v[NR][3], bb[NR];
+    uint32_t u[NR][3], v[NR][3], r0[NR], r1[NR];
 #pragma unroll
-    for (int r = 0; r < NR; r++) {
-        const int dy = min(dy0 + 4 * r, dst.h - 1);
-        const int sy = yofs[dy];
-        const int sy0 = min(max(sy, 0), src.h - 1), sy1 = min(max(sy + 1, 0), src.h - 1);
-        bb[r] = ((const uint32_t*)ibeta)[dy];                      // (ibeta0, ibeta1) as one dword
-        const uint8_t* r0p = S + (size_t)sy0 * src.stride;
-        const uint8_t* r1p = S + (size_t)sy1 * src.stride;
-        if (a + 8 <= last) {        // one 12-byte load per row: the address unit handles 4 lanes per clock whatever the width
-            const Dwords3 tu = *(const Dwords3*)(r0p + a), tv = *(const Dwords3*)(r1p + a);
+    for (int r = 0; r < NR; r++) { r0[r] = __umul24(rw[r].sy & 0xFFFFu, (uint32_t)s_stride) + a; r1[r] = __umul24(rw[r].sy >> 16, (uint32_t)s_stride) + a; }
+    if (a + 8 <= last) {            // one 12-byte load per row: the address unit handles 4 lanes per clock whatever the width
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+            const Dwords3 tu = *(const Dwords3*)(S + r0[r]), tv = *(const Dwords3*)(S + r1[r]);
             u[r][0] = tu.x; u[r][1] = tu.y; u[r][2] = tu.z;
             v[r][0] = tv.x; v[r][1] = tv.y; v[r][2] = tv.z;
-        } else {                    // the last quads of a row: never read past the row's last dword
-            u[r][0] = *(const uint32_t*)(r0p + o0); u[r][1] = *(const uint32_t*)(r0p + o1); u[r][2] = *(const uint32_t*)(r0p + o2);
-            v[r][0] = *(const uint32_t*)(r1p + o0); v[r][1] = *(const uint32_t*)(r1p + o1); v[r][2] = *(const uint32_t*)(r1p + o2);
+        }
+    } else {                        // the last quads of a row: never read past the row's last dword
+        const uint32_t d1 = min(a + 4, last) - a, d2 = min(a + 8, last) - a;
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+            u[r][0] = *(const uint32_t*)(S + r0[r]); u[r][1] = *(const uint32_t*)(S + (r0[r] + d1)); u[r][2] = *(const uint32_t*)(S + (r0[r] + d2));
+            v[r][0] = *(const uint32_t*)(S + r1[r]); v[r][1] = *(const uint32_t*)(S + (r1[r] + d1)); v[r][2] = *(const uint32_t*)(S + (r1[r] + d2));
         }
     }
+    const uint32_t off0 = __umul24((uint32_t)dy0, (uint32_t)dst.stride) + 4u * (uint32_t)q;
 #pragma unroll
     for (int r = 0; r < NR; r++) {
-        const int dy = dy0 + 4 * r;
-        if (dy >= dst.h) continue;
-        const uint32_t b0 = bb[r] & 0xFFFFu, b1 = bb[r] >> 16;
+        if (dy0 + 4 * r >= dst.h) continue;
+        // (b * (h >> 4)) >> 16 is the high dword of (b << 12) * (h & ~15): b <= 2048 and h <= 255 * 2048 keep both factors inside
+        // 24 bits (v_mul_hi_u32_u24); the table holds b << 12
+        const uint32_t b0 = rw[r].b0, b1 = rw[r].b1;
         // the 8 source bytes from column sx0 on, per row
         const uint32_t ulo = __builtin_amdgcn_alignbyte(u[r][1], u[r][0], sh), uhi = __builtin_amdgcn_alignbyte(u[r][2], u[r][1], sh);
         const uint32_t vlo = __builtin_amdgcn_alignbyte(v[r][1], v[r][0], sh), vhi = __builtin_amdgcn_alignbyte(v[r][2], v[r][1], sh);
@@ -105,25 +113,26 @@ __device__ __forceinline__ void resize_tile(const SrcImage& src, uint8_t* __rest
             const us2 ak = as_us2(als[k]);
             const uint32_t h0 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(uhi, ulo, sels[k])), ak, 0u, false);    // S0[sx] a0 + S0[sx+1] a1
             const uint32_t h1 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(vhi, vlo, sels[k])), ak, 0u, false);
-            const uint32_t val = ((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2u) >> 2;
-            out[k] = min(val, 255u);
+            out[k] = min((mul_hi_u24(b0, h0 & ~15u) + mul_hi_u24(b1, h1 & ~15u) + 2u) >> 2, 255u);
         }
+        // (gfx950's v_ashr_pk_u8_i32 does shift, saturation and packing of two pixels in one instruction, but issues every 8.2
+        // cycles against 4.2-4.3 for each of these: not used)
         // columns past dst.w: coefficients 0 -> 0; the row padding absorbs the tail of the last dword
-        *(uint32_t*)(D + (size_t)dy * dst.stride) = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+        *(uint32_t*)(D + (off0 + (uint32_t)(4 * r) * (uint32_t)dst.stride)) = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
     }
 }
 
 __global__ __launch_bounds__(256) void k_resize(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst,
                                                 const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
-                                                const int* __restrict__ yofs, const short* __restrict__ ibeta)
+                                                const ResizeRow* __restrict__ rows)
 {
     // tiles of 64 x 64 outputs are numbered row-major and handed to the XCDs in contiguous bands (xcd_remap), so the source
     // rows a band of destination rows needs are fetched by one L2 only
     const int tiles_x = (dst.w + kResizeTW - 1) / kResizeTW, tiles_y = (dst.h + kResizeRows - 1) / kResizeRows;
     const int tile = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);
     if (tile >= tiles_x * tiles_y) return;
-    resize_tile(src, pyr, frame_stride, dst, q_sx0, q_sel, q_alpha, yofs, ibeta, tile, blockIdx.y, threadIdx.x & 63,
-                __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+    resize_tile(src.base + (size_t)blockIdx.y * src.frame_stride, src.stride, pyr + (size_t)blockIdx.y * frame_stride + dst.off, dst,
+                q_sx0, q_sel, q_alpha, rows, tile, threadIdx.x & 63, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
 // Fallback for levels whose four-column source span exceeds the 8-byte window of the table-driven kernel above (scale factors of
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(256) void k_resize_generic(SrcImage src, uint8_t* _
 // tiles at a time, a workgroup barrier between levels: the level just written is read back by the same CU).
 struct ResizeTables {
     const int* q_sx0[kMaxLevels]; const uint4* q_sel[kMaxLevels]; const uint4* q_alpha[kMaxLevels];
-    const int* yofs[kMaxLevels]; const short* ibeta[kMaxLevels];
+    const ResizeRow* rows[kMaxLevels];
 };
 __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr, size_t frame_stride, const LevelDesc* __restrict__ levels,
                                                       ResizeTables T, int l_first, int n_levels)
@@ -163,11 +172,10 @@ __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr,
     const int lane = threadIdx.x & 63;
     for (int l = l_first; l < n_levels; l++) {
         const LevelDesc D = levels[l], P = levels[l - 1];
-        SrcImage src;
-        src.base = pyr + P.off; src.frame_stride = frame_stride; src.stride = P.stride; src.w = P.w; src.h = P.h;
+        uint8_t* fp = pyr + (size_t)frame * frame_stride;
         const int tiles = ((D.w + kResizeTW - 1) / kResizeTW) * ((D.h + kResizeRows - 1) / kResizeRows);
         for (int t = sub; t < tiles; t += 4)
-            resize_tile(src, pyr, frame_stride, D, T.q_sx0[l], T.q_sel[l], T.q_alpha[l], T.yofs[l], T.ibeta[l], t, frame, lane, wave);
+            resize_tile(fp + P.off, P.stride, fp + D.off, D, T.q_sx0[l], T.q_sel[l], T.q_alpha[l], T.rows[l], t, lane, wave);
         __syncthreads();            // the level is complete (and visible to this CU) before it becomes the next one's source
     }
 }
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(64) void k_index(const LevelDesc* __restrict__ leve
 // ------------------------------------------------------------------------------------------------
 // E6: GaussianBlur 7x7, sigma 2, BORDER_REFLECT_101 -- OpenCV 4.x fixed-point path:
 // horizontal u8 x Q8.8 taps -> Q8.8 (u16), vertical Q8.8 x Q8.8 -> Q16.16, (v + 0x8000) >> 16.
-// 256 threads per 64x32 output tile; the (64+6) x (32+6) source window is staged in LDS.
+// 256 threads per 64x58 output tile; the (64+6) x (58+6) source window is staged in LDS (k_blur).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -713,22 +721,67 @@ __device__ __forceinline__ int reflect101(int p, int len)
 }
 
 constexpr int kBlurTW = 64, kBlurTH = 58;        // outputs per tile; 58 + 6 = 64 staged rows = 32 row pairs
+constexpr int kBlurSP = 96;                      // LDS row pitch: source column x0 - 4 is byte 12, so the 16-byte chunks of the tile start at byte 16
 
-// 256 threads per 64 x 58 output tile.  The (64 + 6) x (58 + 6) source window is staged in LDS as 16-byte chunks (rows start
-// 16 bytes left of the tile so that every chunk is an aligned dwordx4 load; chunks that touch the image border are
-// assembled byte by byte with BORDER_REFLECT_101).
-//   horizontal  one work item = 2 rows x 4 columns: per output two byte dot products (v_dot4_u32_u8) on v_alignbyte windows;
-//               the Q8.8 results of the two rows are stored as ONE dword per column (row 2p | row 2p+1 << 16)
-//   vertical    one work item = 2 rows x 4 columns: the 7 taps of an output are 4 x v_dot2_u32_u16 on those row pairs
-//               (even output row: (t0 t1)(t2 t3)(t2 t1)(t0 0), odd: (0 t0)(t1 t2)(t3 t2)(t1 t0)), rounding folded into the
-//               first accumulator, the four result bytes gathered with v_perm.
+// one horizontal work item: rows 2p, 2p+1 of the staged window x columns 4q .. 4q+3 -> four (row 2p | row 2p+1 << 16) Q8.8 pairs.
+// Output column 4q+k of a row uses source bytes k+1 .. k+7 of the 12 bytes w0 w1 w2 (taps (t0 t1 t2 t3) on k+1..k+4, (t2 t1 t0 0)
+// on k+5..k+8).  The taps sum to 256, so a sum never exceeds 255 * 256 = 65280: it fits 16 bits.
+__device__ __forceinline__ void blur_h_item(const uint8_t* __restrict__ src /* row 2p, byte 12 + 4q */, uint32_t* __restrict__ hp, uint32_t tapA, uint32_t tapB)
+{
+    uint32_t o[2][4];
+#pragma unroll
+    for (int rr = 0; rr < 2; rr++) {
+        const uint32_t* w = (const uint32_t*)(src + rr * kBlurSP);
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+        o[rr][0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), tapB, 0u, false), false);
+        o[rr][1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), tapB, 0u, false), false);
+        o[rr][2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), tapB, 0u, false), false);
+        o[rr][3] = __builtin_amdgcn_udot4(w1, tapA, __builtin_amdgcn_udot4(w2, tapB, 0u, false), false);
+    }
+    // (row 2p | row 2p+1 << 16): the low halves of two sums in one v_perm
+    *(uint4*)hp = make_uint4(__builtin_amdgcn_perm(o[1][0], o[0][0], 0x05040100u), __builtin_amdgcn_perm(o[1][1], o[0][1], 0x05040100u),
+                             __builtin_amdgcn_perm(o[1][2], o[0][2], 0x05040100u), __builtin_amdgcn_perm(o[1][3], o[0][3], 0x05040100u));
+}
+
+struct BlurTaps { us2 e0, e1, e2, e3, o0, o1, o2, o3; };
+
+// one vertical work item: output rows 2m, 2m+1 x columns 4q .. 4q+3 from the row pairs m .. m+3 (`hp`: pair m, column 4q).
+// The 7 taps of an output are 4 x v_dot2_u32_u16 on those pairs (even row: (t0 t1)(t2 t3)(t2 t1)(t0 0), odd: (0 t0)(t1 t2)(t3 t2)(t1 t0)),
+// rounding folded into the first accumulator, the four result bytes gathered with v_perm.
+__device__ __forceinline__ void blur_v_item(const uint32_t* __restrict__ hp, const BlurTaps& c, uint8_t* __restrict__ dst, uint32_t off, uint32_t stride, bool odd_row)
+{
+    const uint4 P0 = *(const uint4*)hp, P1 = *(const uint4*)(hp + kBlurTW), P2 = *(const uint4*)(hp + 2 * kBlurTW), P3 = *(const uint4*)(hp + 3 * kBlurTW);
+    const uint32_t a0[4] = {P0.x, P0.y, P0.z, P0.w}, a1[4] = {P1.x, P1.y, P1.z, P1.w}, a2[4] = {P2.x, P2.y, P2.z, P2.w}, a3[4] = {P3.x, P3.y, P3.z, P3.w};
+    uint32_t e[4], o[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {       // Q16.16 sums + 0x8000: the result byte is bits 16..23 (at most 255 * 65536 + 32768)
+        e[k] = __builtin_amdgcn_udot2(as_us2(a3[k]), c.e3, __builtin_amdgcn_udot2(as_us2(a2[k]), c.e2, __builtin_amdgcn_udot2(as_us2(a1[k]), c.e1,
+               __builtin_amdgcn_udot2(as_us2(a0[k]), c.e0, 0x8000u, false), false), false), false);
+        o[k] = __builtin_amdgcn_udot2(as_us2(a3[k]), c.o3, __builtin_amdgcn_udot2(as_us2(a2[k]), c.o2, __builtin_amdgcn_udot2(as_us2(a1[k]), c.o1,
+               __builtin_amdgcn_udot2(as_us2(a0[k]), c.o0, 0x8000u, false), false), false), false);
+    }
+    // bytes 2 of four accumulators -> one dword
+    const uint32_t pe = __builtin_amdgcn_perm(__builtin_amdgcn_perm(e[3], e[2], 0x0C0C0602u), __builtin_amdgcn_perm(e[1], e[0], 0x0C0C0602u), 0x05040100u);
+    const uint32_t po = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[3], o[2], 0x0C0C0602u), __builtin_amdgcn_perm(o[1], o[0], 0x0C0C0602u), 0x05040100u);
+    *(uint32_t*)(dst + off) = pe;                       // the row padding absorbs the tail of the last dword
+    if (odd_row) *(uint32_t*)(dst + (off + stride)) = po;
+}
+
+// 256 threads per 64 x 58 output tile at a multiple of 64 columns.  The (64 + 6) x (58 + 6) source window is staged in LDS as the
+// four aligned 16-byte chunks of the tile's columns plus the dword on either side (columns x0-4 .. x0+67): thread (row, chunk) =
+// (tid >> 2, tid & 3) loads one chunk, the threads of chunks 0 and 3 the side dwords as well, all before one wait.  Loaded bytes past
+// the last column are row padding; they only reach outputs that are not stored.  The three columns left of column 0 and right of
+// column w - 1 (BORDER_REFLECT_101) are byte copies inside LDS, in the tiles that the host marks as touching that edge (TileDesc::edge).
+//   horizontal  512 work items of 2 rows x 4 columns, two per thread (blur_h_item)
+//   vertical    464 work items of 2 rows x 4 columns, two per thread (blur_v_item)
+// Work items outside the image (quads at or beyond w, rows that no stored output reads) are skipped in all three phases.
 // raw_out != nullptr (level 0 taken from the caller's image): the tile's own pixels are also copied into the pyramid, which
 // is what later readers of level 0 (descriptors, stereo matching, the mvImagePyramid getter) use.
 __global__ __launch_bounds__(256) void k_blur(SrcImage lvl0, const uint8_t* __restrict__ pyr, uint8_t* __restrict__ raw_out, uint8_t* __restrict__ blur,
                                               size_t frame_stride, const LevelDesc* __restrict__ levels, const TileDesc* __restrict__ tiles, int n_tiles,
                                               int t0, int t1, int t2, int t3)
 {
-    constexpr int SP = kBlurTW + 32, SR = kBlurTH + 6;      // LDS row = source columns x0-16 .. x0+79 (6 chunks); staged rows
+    constexpr int SP = kBlurSP, SR = kBlurTH + 6;
     __shared__ __align__(16) uint8_t s_src[SR * SP];
     __shared__ __align__(16) uint32_t s_hp[(SR / 2) * kBlurTW];
     const int tile_idx = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);     // contiguous tile range per XCD (see k_fast_strips)
@@ -736,85 +789,72 @@ __global__ __launch_bounds__(256) void k_blur(SrcImage lvl0, const uint8_t* __re
     const TileDesc T = tiles[tile_idx];
     const LevelDesc L = levels[T.level];
     const bool ext = T.level == 0 && lvl0.base != nullptr;
+    // per-frame bases are wave-uniform (scalar registers); everything per thread is a 32-bit offset inside the frame's level
     const uint8_t* img = ext ? lvl0.base + (size_t)blockIdx.y * lvl0.frame_stride : pyr + (size_t)blockIdx.y * frame_stride + L.off;
-    const int istride = ext ? lvl0.stride : L.stride;
+    const uint32_t istride = (uint32_t)(ext ? lvl0.stride : L.stride), ostride = (uint32_t)L.stride;
     uint8_t* dst = blur + (size_t)blockIdx.y * frame_stride + L.off;
     const int tid = threadIdx.x;
-    const int x0 = T.x0, y0 = T.y0;
-    for (int i = tid; i < SR * (SP / 16); i += 256) {
-        const int r = i / (SP / 16), q = i - r * (SP / 16);
-        const int sy = reflect101(y0 + r - 3, L.h), cx = x0 - 16 + 16 * q;
-        // A chunk that starts inside the row is one aligned load (its bytes past the last column are row padding: they only reach
-        // outputs that are not stored).  Only the three columns left of column 0 and the three right of column w - 1 can be read by
-        // stored outputs without being pixels: they are patched in with BORDER_REFLECT_101 (six byte tests per border chunk --
-        // a byte-by-byte assembly of such chunks cost more than the whole filter of an inner tile).
+    const int x0 = T.x0, y0 = T.y0, w = L.w, h = L.h;
+    const int rows_in = min(h - y0, kBlurTH);           // output rows of this tile; staged rows 0 .. rows_in + 5 feed them
+    {
+        const int r = tid >> 2, c = tid & 3;
+        const int cx = x0 + 16 * c, y = y0 + r - 3;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        const uint8_t* rowp = img + (size_t)sy * istride;
-        if (cx >= 0 && cx < L.w) v = *(const uint4*)(rowp + cx);
-        if (cx < 0 || cx + 16 > L.w) {
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 1; k <= 3; k++) {
-                const int bl = -k - cx, br = L.w - 1 + k - cx;              // byte positions of columns -k and w - 1 + k in this chunk
-                if (bl >= 0 && bl < 16) { const uint32_t px = rowp[reflect101(-k, L.w)]; w[bl >> 2] = (w[bl >> 2] & ~(0xFFu << (8 * (bl & 3)))) | (px << (8 * (bl & 3))); }
-                if (br >= 0 && br < 16) { const uint32_t px = rowp[reflect101(L.w - 1 + k, L.w)]; w[br >> 2] = (w[br >> 2] & ~(0xFFu << (8 * (br & 3)))) | (px << (8 * (br & 3))); }
+        uint32_t left = 0u, right = 0u;
+        if (r < rows_in + 6) {
+            const uint32_t ro = __umul24((uint32_t)reflect101(y, h), istride);
+            if (cx < w) v = *(const uint4*)(img + (ro + (uint32_t)cx));
+            if (c == 0 && x0 > 0) left = *(const uint32_t*)(img + (ro + (uint32_t)(x0 - 4)));
+            if (c == 3 && x0 + kBlurTW < w) right = *(const uint32_t*)(img + (ro + (uint32_t)(x0 + kBlurTW)));
+            *(uint4*)(s_src + r * SP + 16 + 16 * c) = v;
+            if (c == 0) *(uint32_t*)(s_src + r * SP + 12) = left;
+            if (c == 3) *(uint32_t*)(s_src + r * SP + 16 + kBlurTW) = right;
+            // level 0 of the pyramid = the caller's image (what k_copy_level0 would have written): the tile's own rows, dword by dword
+            // up to the last pixel's
+            if (ext && raw_out != nullptr && r >= 3 && r < rows_in + 3 && cx < w) {
+                uint8_t* rp = raw_out + (size_t)blockIdx.y * frame_stride + L.off + (__umul24((uint32_t)y, ostride) + (uint32_t)cx);
+                if (cx + 12 < w) *(uint4*)rp = v;
+                else {
+                    *(uint32_t*)rp = v.x;
+                    if (cx + 4 < w) *(uint32_t*)(rp + 4) = v.y;
+                    if (cx + 8 < w) *(uint32_t*)(rp + 8) = v.z;
+                }
             }
-            v = make_uint4(w[0], w[1], w[2], w[3]);
         }
-        *(uint4*)(s_src + r * SP + 16 * q) = v;
     }
     __syncthreads();
-    if (ext && raw_out != nullptr) {        // level 0 of the pyramid = the caller's image (what k_copy_level0 would have written)
-        uint8_t* raw = raw_out + (size_t)blockIdx.y * frame_stride + L.off;
-        for (int i = tid; i < kBlurTH * (kBlurTW / 4); i += 256) {
-            const int r = i >> 4, q = i & 15;
-            if (y0 + r < L.h && x0 + 4 * q < L.w) *(uint32_t*)(raw + (size_t)(y0 + r) * L.stride + x0 + 4 * q) = *(const uint32_t*)(s_src + (r + 3) * SP + 16 + 4 * q);
+    if (T.edge) {       // (uniform) columns -3 .. -1 and w .. w+2 of every staged row: wave j copies column -1-j and / or w+j
+        const int r = tid & 63, j = __builtin_amdgcn_readfirstlane(tid >> 6);
+        if (j < 3) {
+            uint8_t* row = s_src + r * SP + 16 - x0;        // byte of column 0
+            if (T.edge & 1) row[-1 - j] = row[reflect101(-1 - j, w)];
+            if ((T.edge & 2) && w + j < x0 + kBlurTW + 4) row[w + j] = row[reflect101(w + j, w)];
         }
+        __syncthreads();
     }
     const uint32_t tapA = (uint32_t)t0 | ((uint32_t)t1 << 8) | ((uint32_t)t2 << 16) | ((uint32_t)t3 << 24);
     const uint32_t tapB = (uint32_t)t2 | ((uint32_t)t1 << 8) | ((uint32_t)t0 << 16);
-    // ---- horizontal: output column 4q+k of a row uses source bytes k+1 .. k+7 of the 12 bytes w0 w1 w2 (taps (t0 t1 t2 t3) on
-    // k+1..k+4, (t2 t1 t0 0) on k+5..k+8).  The taps sum to 256, so a sum never exceeds 255 * 256 = 65280: it fits 16 bits. ----
-    for (int i = tid; i < (SR / 2) * (kBlurTW / 4); i += 256) {
-        const int p = i >> 4, q = i & 15;
-        uint32_t o[2][4];
-#pragma unroll
-        for (int rr = 0; rr < 2; rr++) {
-            const uint32_t* w = (const uint32_t*)(s_src + (2 * p + rr) * SP + 12) + q;
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-            o[rr][0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), tapB, 0u, false), false);
-            o[rr][1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), tapB, 0u, false), false);
-            o[rr][2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), tapA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), tapB, 0u, false), false);
-            o[rr][3] = __builtin_amdgcn_udot4(w1, tapA, __builtin_amdgcn_udot4(w2, tapB, 0u, false), false);
-        }
-        *(uint4*)(s_hp + p * kBlurTW + 4 * q) = make_uint4(o[0][0] | (o[1][0] << 16), o[0][1] | (o[1][1] << 16), o[0][2] | (o[1][2] << 16), o[0][3] | (o[1][3] << 16));
+    const int q = tid & 15, pm = tid >> 4;              // this thread's quad of columns; its row pairs are pm and pm + 16 in both passes
+    const bool q_in = x0 + 4 * q < w;
+    // ---- horizontal: row pair p holds staged rows 2p, 2p+1; the last pair a stored output reads is (rows_in + 5) >> 1 ----
+    {
+        const uint8_t* sp = s_src + 2 * pm * SP + 12 + 4 * q;
+        uint32_t* hp = s_hp + pm * kBlurTW + 4 * q;
+        if (q_in && 2 * pm < rows_in + 6) blur_h_item(sp, hp, tapA, tapB);
+        if (q_in && 2 * pm + 32 < rows_in + 6) blur_h_item(sp + 32 * SP, hp + 16 * kBlurTW, tapA, tapB);
     }
     __syncthreads();
     // ---- vertical ----
-    const us2 cE0 = as_us2((uint32_t)t0 | ((uint32_t)t1 << 16)), cE1 = as_us2((uint32_t)t2 | ((uint32_t)t3 << 16)),
-              cE2 = as_us2((uint32_t)t2 | ((uint32_t)t1 << 16)), cE3 = as_us2((uint32_t)t0);
-    const us2 cO0 = as_us2((uint32_t)t0 << 16), cO1 = as_us2((uint32_t)t1 | ((uint32_t)t2 << 16)),
-              cO2 = as_us2((uint32_t)t3 | ((uint32_t)t2 << 16)), cO3 = as_us2((uint32_t)t1 | ((uint32_t)t0 << 16));
-    for (int i = tid; i < (kBlurTH / 2) * (kBlurTW / 4); i += 256) {
-        const int m = i >> 4, q = i & 15;
-        const int oy = y0 + 2 * m, ox = x0 + 4 * q;
-        if (oy >= L.h || ox >= L.w) continue;
-        const uint4 P0 = *(const uint4*)(s_hp + m * kBlurTW + 4 * q), P1 = *(const uint4*)(s_hp + (m + 1) * kBlurTW + 4 * q),
-                    P2 = *(const uint4*)(s_hp + (m + 2) * kBlurTW + 4 * q), P3 = *(const uint4*)(s_hp + (m + 3) * kBlurTW + 4 * q);
-        const uint32_t a0[4] = {P0.x, P0.y, P0.z, P0.w}, a1[4] = {P1.x, P1.y, P1.z, P1.w}, a2[4] = {P2.x, P2.y, P2.z, P2.w}, a3[4] = {P3.x, P3.y, P3.z, P3.w};
-        uint32_t e[4], o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {       // Q16.16 sums + 0x8000: the result byte is bits 16..23 (at most 255 * 65536 + 32768)
-            e[k] = __builtin_amdgcn_udot2(as_us2(a3[k]), cE3, __builtin_amdgcn_udot2(as_us2(a2[k]), cE2, __builtin_amdgcn_udot2(as_us2(a1[k]), cE1,
-                   __builtin_amdgcn_udot2(as_us2(a0[k]), cE0, 0x8000u, false), false), false), false);
-            o[k] = __builtin_amdgcn_udot2(as_us2(a3[k]), cO3, __builtin_amdgcn_udot2(as_us2(a2[k]), cO2, __builtin_amdgcn_udot2(as_us2(a1[k]), cO1,
-                   __builtin_amdgcn_udot2(as_us2(a0[k]), cO0, 0x8000u, false), false), false), false);
-        }
-        // bytes 2 of four accumulators -> one dword
-        const uint32_t pe = __builtin_amdgcn_perm(__builtin_amdgcn_perm(e[3], e[2], 0x0C0C0602u), __builtin_amdgcn_perm(e[1], e[0], 0x0C0C0602u), 0x05040100u);
-        const uint32_t po = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[3], o[2], 0x0C0C0602u), __builtin_amdgcn_perm(o[1], o[0], 0x0C0C0602u), 0x05040100u);
-        *(uint32_t*)(dst + (size_t)oy * L.stride + ox) = pe;                       // the row padding absorbs the tail of the last dword
-        if (oy + 1 < L.h) *(uint32_t*)(dst + (size_t)(oy + 1) * L.stride + ox) = po;
+    {
+        BlurTaps c;
+        c.e0 = as_us2((uint32_t)t0 | ((uint32_t)t1 << 16)); c.e1 = as_us2((uint32_t)t2 | ((uint32_t)t3 << 16));
+        c.e2 = as_us2((uint32_t)t2 | ((uint32_t)t1 << 16)); c.e3 = as_us2((uint32_t)t0);
+        c.o0 = as_us2((uint32_t)t0 << 16); c.o1 = as_us2((uint32_t)t1 | ((uint32_t)t2 << 16));
+        c.o2 = as_us2((uint32_t)t3 | ((uint32_t)t2 << 16)); c.o3 = as_us2((uint32_t)t1 | ((uint32_t)t0 << 16));
+        const uint32_t* hp = s_hp + pm * kBlurTW + 4 * q;
+        const uint32_t off = __umul24((uint32_t)(y0 + 2 * pm), ostride) + (uint32_t)(x0 + 4 * q);
+        if (q_in && 2 * pm < rows_in) blur_v_item(hp, c, dst, off, ostride, 2 * pm + 1 < rows_in);
+        if (q_in && 2 * pm + 32 < rows_in) blur_v_item(hp + 16 * kBlurTW, c, dst, off + 32u * ostride, ostride, 2 * pm + 33 < rows_in);
     }
 }
 

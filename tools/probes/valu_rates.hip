@@ -40,6 +40,7 @@ KERNEL(sub_u16, OP2("v_sub_u16"), "memory")
 KERNEL(mul_u24, OP2("v_mul_u32_u24"), "memory")
 KERNEL(mul_i24, OP2("v_mul_i32_i24"), "memory")
 KERNEL(mul_lo_u32, OP2("v_mul_lo_u32"), "memory")     // the full 32-bit product of index arithmetic such as y * pitch
+KERNEL(mul_hi_u32_u24, OP2("v_mul_hi_u32_u24"), "memory")     // k_resize: (b * (h >> 4)) >> 16 as one high multiply
 KERNEL(add_f32, OP2("v_add_f32"), "memory")
 KERNEL(min_f32, OP2("v_min_f32"), "memory")
 KERNEL(max_f16, OP2("v_max_f16"), "memory")
@@ -75,6 +76,7 @@ KERNEL(cvt_pk_u8_f32, OP3("v_cvt_pk_u8_f32"), "memory")
 KERNEL(bfi, OP3("v_bfi_b32"), "memory")
 KERNEL(xad, OP3("v_xad_u32"), "memory")
 KERNEL(lerp_u8, OP3("v_lerp_u8"), "memory")
+KERNEL(ashr_pk_u8_i32, OP3C("v_ashr_pk_u8_i32"), "memory")    // gfx950: shift, saturate to a byte and pack, two pixels at a time
 
 int main()
 {
@@ -98,9 +100,9 @@ int main()
         printf("%-18s %.3f ns per wave-instruction and SIMD = %.2f cycles at %.2f GHz\n", #id, ns, ns * ghz, ghz);          \
     }
     RUN(add_u32) RUN(sub_u32) RUN(and_b32) RUN(or_b32) RUN(xor_b32) RUN(lshlrev) RUN(min_i32) RUN(max_u32) RUN(min_u16) RUN(add_u16) RUN(sub_u16)
-    RUN(mul_u24) RUN(mul_i24) RUN(mul_lo_u32) RUN(add_f32) RUN(min_f32) RUN(max_f16) RUN(pk_add_u16) RUN(pk_min_u16) RUN(pk_max_i16) RUN(pk_add_f16) RUN(pk_min_f16) RUN(pk_mul_lo_u16)
+    RUN(mul_u24) RUN(mul_i24) RUN(mul_lo_u32) RUN(mul_hi_u32_u24) RUN(add_f32) RUN(min_f32) RUN(max_f16) RUN(pk_add_u16) RUN(pk_min_u16) RUN(pk_max_i16) RUN(pk_add_f16) RUN(pk_min_f16) RUN(pk_mul_lo_u16)
     RUN(cmp_gt_u32) RUN(cndmask) RUN(mov) RUN(fma_f32) RUN(mad_u24) RUN(add3) RUN(and_or) RUN(lshl_or) RUN(bfe) RUN(perm) RUN(alignbyte)
     RUN(min3_i32) RUN(max3_u32) RUN(med3_i32) RUN(min3_f32) RUN(sad_u8) RUN(msad_u8) RUN(sad_u16) RUN(sad_u32) RUN(dot4_u32_u8) RUN(dot2_u32_u16)
-    RUN(pk_mad_u16) RUN(cvt_pk_u8_f32) RUN(bfi) RUN(xad) RUN(lerp_u8)
+    RUN(pk_mad_u16) RUN(cvt_pk_u8_f32) RUN(bfi) RUN(xad) RUN(lerp_u8) RUN(ashr_pk_u8_i32)
     return 0;
 }

@@ -100,6 +100,7 @@ struct orbx_extractor {
     size_t pyr_frame_bytes = 0;
     int cand_frame_entries = 0, sel_frame_entries = 0;
     std::vector<StripDesc> strips;       // FAST work items: runs of adjacent cells of one cell row
+    std::vector<StripRec> strip_recs;    // ... and what the kernel reads of each: one record per strip, in the same order
     FastLds fast_layout;
     int fast_corner_cap = 0;             // 0 = kCornerCap; tests shrink it to drive the overflow path (orbx_debug_set_fast_corner_cap)
     size_t fast_lds = 0, oct_lds = 0;
@@ -114,7 +115,7 @@ struct orbx_extractor {
     DevBuf<LevelDesc> d_levels;
     DevBuf<CellDesc> d_cells;
     DevBuf<TileDesc> d_tiles;
-    DevBuf<StripDesc> d_strips;
+    DevBuf<StripRec> d_strips;
     // resize tables per destination level: per quad of columns the first source column, 4 v_perm selectors, 4 coefficient pairs
     // and per destination row the two source rows and the two coefficients (ResizeRow)
     std::vector<DevBuf<int> > d_qsx0;
@@ -214,6 +215,7 @@ int orbx_extractor::setup_geometry(int w, int h)
     cells.clear();
     tiles.clear();
     strips.clear();
+    strip_recs.clear();
     size_t off = 0;
     int cand_off = 0, sel_off = 0, max_tw = 0, max_th = 0, max_nfeat = 0;
     std::vector<int> node_need(nlevels, 0);
@@ -391,7 +393,6 @@ int orbx_extractor::setup_geometry(int w, int h)
         o = al16((size_t)max_sth * Z.tile_pitch);
         Z.map_off = (int)o; Z.map_pitch = 4 * max_ngx + 8;
         o = al16(o + (size_t)(max_sth - 6 + 2) * Z.map_pitch);
-        Z.colcell_off = (int)o; o = al16(o + Z.map_pitch);
         Z.ent_cap = (max_ent + 7) & ~7;
         Z.ent_off = (int)o; o = al16(o + 2 * 4 * (size_t)Z.ent_cap);
         Z.px_off = (int)o; o = al16(o + 2 * 4 * (size_t)kPxCap);
@@ -403,6 +404,35 @@ int orbx_extractor::setup_geometry(int w, int h)
         Z.total = (int)o;
         fast_lds = o;
         if (fast_lds > 150 * 1024) return fail(ORBX_ERR_ARG, "FAST strip of %d quads x %d rows does not fit LDS", max_ngx, max_sth);
+        // the strips' records (orbx_fast_strips.inc: StripRec): what the kernel's set-up would otherwise compute or fetch per workgroup
+        strip_recs.assign(strips.size(), StripRec());
+        for (size_t si = 0; si < strips.size(); si++) {
+            const StripDesc& sd = strips[si];
+            const LevelDesc& L = levels[sd.level];
+            StripRec& R = strip_recs[si];
+            const int g0 = (sd.x0 + 3) >> 2, g1 = (sd.x1 - 4) >> 2, ngx = g1 - g0 + 1;       // first / last image dword that holds a detection column
+            const int xa = (4 * (g0 - 1)) & ~15, qoff = 4 * g0 - xa, nch = (qoff + 4 * ngx + 4 + 15) >> 4, sth = sd.y1 - sd.y0;
+            R.src_off = (uint32_t)((size_t)L.off + (size_t)sd.y0 * L.stride + xa);          // (the frame is below 2 GiB)
+            R.stride = (uint32_t)L.stride;
+            auto pair = [](int lo, int hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
+            if (sd.y0 < 0 || xa < 0 || sd.cell0 < 0) return fail(ORBX_ERR_INTERNAL, "FAST strip at row %d, column %d, cell %d", sd.y0, xa, sd.cell0);
+            R.y0_xa = pair(sd.y0, xa); R.th_nch = pair(sth, nch); R.g0_qoff = pair(g0, qoff); R.ncell_cell0 = pair(sd.ncell, sd.cell0);
+            R.level = (uint32_t)sd.level;
+            // chunk i of the tile is chunk i % nch of row i / nch: the division as a multiplication, exact for every chunk of the strip
+            R.inv_nch = (65536u + (uint32_t)nch - 1u) / (uint32_t)nch;
+            for (uint32_t i = 0; i < (uint32_t)(sth * nch); i++)
+                if (((i * R.inv_nch) >> 16) != i / (uint32_t)nch)
+                    return fail(ORBX_ERR_INTERNAL, "FAST strip of %d rows x %d chunks: the row of chunk %u is not exact", sth, nch, i);
+            std::memset(R.tab.colcell, 0xFF, sizeof(R.tab.colcell));
+            for (int j = 0; j < sd.ncell; j++) {
+                const CellDesc& c = cells[sd.cell0 + j];
+                R.tab.cx0[j] = c.x0 + 3 - 4 * g0 + 4; R.tab.iw[j] = c.x1 - c.x0 - 6;
+                R.tab.slot_off[j] = c.slot_off; R.tab.slot_cap[j] = c.slot_cap;
+                if (R.tab.cx0[j] < 0 || R.tab.cx0[j] + R.tab.iw[j] > Z.map_pitch)
+                    return fail(ORBX_ERR_INTERNAL, "FAST cell columns %d + %d outside the strip's %d map columns", R.tab.cx0[j], R.tab.iw[j], Z.map_pitch);
+                for (int i = 0; i < R.tab.iw[j]; i++) R.tab.colcell[R.tab.cx0[j] + i] = (uint8_t)j;
+            }
+        }
     }
     // octree kernel LDS
     oct_pool = max_nfeat + 16;
@@ -458,7 +488,7 @@ int orbx_extractor::setup_geometry(int w, int h)
     }
     ORBX_HIP(hipFuncSetAttribute((const void*)k_fast_strips, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds));
     int r;
-    if ((r = d_levels.upload(levels)) || (r = d_cells.upload(cells)) || (r = d_tiles.upload(tiles)) || (r = d_strips.upload(strips))) return r;
+    if ((r = d_levels.upload(levels)) || (r = d_cells.upload(cells)) || (r = d_tiles.upload(tiles)) || (r = d_strips.upload(strip_recs))) return r;
     geo_w = w; geo_h = h;
     batch_cap = 0;      // scratch must be re-sized for the new geometry
     return ORBX_OK;
@@ -520,7 +550,8 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
     // level 1, FAST and the blur read it where it lies, and the blur -- which touches every pixel anyway -- leaves the copy in
     // the pyramid that the later readers of level 0 (descriptors, stereo matching, orbx_pyramid_level) use.  Otherwise it is
     // copied first (k_copy_level0), as it is when the host-pointer entry points have uploaded it into the pyramid themselves.
-    const bool in_place = !level0_ready && ((uintptr_t)d_imgs % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0);
+    // (... and when a tile's rows are within 32-bit offsets of its first one, as k_fast_strips addresses them)
+    const bool in_place = !level0_ready && ((uintptr_t)d_imgs % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) && row_stride < (1 << 23);
     const int n_cells = (int)cells.size();
     const int quads = (sel_frame_entries + 7) / 8;       // workgroups of k_orient_desc per frame: 8 key points each (two per wave)
 
@@ -602,7 +633,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
         int* cell_cnt = d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1);
         auto launch_fast = [&](hipStream_t fs, int s0, int s1) {
             if (s1 > s0)
-                hipLaunchKernelGGL(k_fast_strips, dim3(xcd_grid(s1 - s0), nB), dim3(256), fast_lds, fs, lvl0, pyr, pyr_frame_bytes, d_levels.p, d_cells.p,
+                hipLaunchKernelGGL(k_fast_strips, dim3(xcd_grid(s1 - s0), nB), dim3(256), fast_lds, fs, lvl0, pyr, pyr_frame_bytes,
                                    d_strips.p + s0, s1 - s0, n_cells, ini_th, min_th, fast_layout, cand, (size_t)cand_frame_entries, cell_cnt);
         };
         // first strip of the levels the resize tail produces (the strips are in level order)

@@ -33,12 +33,19 @@
 // straddles two cells is scored by both owners, which store the same score in the same byte.  The cells of a strip run side
 // by side, and a strip without such a cell (three in four) pays nothing.
 //
+// Set-up.  Everything a workgroup needs before the first pixel, except the pixels, is known when the geometry is set up, so the host
+// builds one record per strip (StripRec): where the tile lies in the pyramid, its size in 16-byte chunks with an exact reciprocal for
+// chunk -> (row, chunk of the row), and the cells' columns, slots and the finished column -> cell row exactly as they lie in LDS.  The
+// record is addressed by the strip index alone: 32 bytes through the scalar unit, the table as one 16-byte load per lane of wave 0.
+// Two dependent global round trips remain (record, tile).  A thread has its chunks of the tile in flight together, three at a time, and
+// zeroes the score map and the bitmasks with 16-byte LDS stores while they travel; then one wait, the LDS stores, ONE barrier.
+//
 // A corner list that overflows (more than corner_cap corners of a wave: pathological images, or the debug knob of the tests)
 // sends its wave through the same nms / emit code over ALL the pixels it scored instead (its rows of the strip; in the
 // minThFAST pass, the rows and quads of its cell).  Everything is integer; the result is the reference's vToDistributeKeys order and
 // content bit for bit.
 
-struct StripDesc {
+struct StripDesc {               // (host: the strip geometry, from which the layout of the LDS and the records below are made)
     int16_t level;
     int16_t cell0, ncell;       // cells [cell0, cell0 + ncell) of the cell table, left to right
     int16_t x0, x1;             // columns [x0, x1) spanned by the cells' sub-images (first cell's x0 .. last cell's x1)
@@ -46,10 +53,37 @@ struct StripDesc {
     int16_t pad;
 };
 
+constexpr int kStripMaxCells = 8;
+constexpr int kStripMapPitchMax = 4 * 64 + 8;         // map columns of the widest strip the host accepts (64 quads)
+
+// What a workgroup keeps about its cells in LDS, exactly as the host lays it out in the strip's record: one 16-byte copy per lane.
+struct __attribute__((aligned(16))) StripTab {
+    int32_t cx0[kStripMaxCells];        // first map column of the cell's interior
+    int32_t iw[kStripMaxCells];         // interior width
+    int32_t slot_off[kStripMaxCells], slot_cap[kStripMaxCells];     // the cell's slots in the per-frame candidate buffer
+    uint8_t colcell[(kStripMapPitchMax + 15) & ~15];                // u8 per map column: cell of the strip that owns it, 0xFF = none
+};
+
+// One record per strip, built when the geometry is set up: everything the kernel's set-up needs, addressed by the strip index alone
+// (no load depends on another).  The first 32 bytes are read with scalar loads, the table with one 16-byte load per lane.
+struct __attribute__((aligned(16))) StripRec {
+    // (pairs of 16-bit values, all non-negative: low half | high half << 16 -- the scalar unit loads whole dwords)
+    uint32_t src_off;           // pyramid byte of tile row 0, tile column 0 inside the frame (level offset + y0 * stride + xa)
+    uint32_t stride;            // row stride of the level in the pyramid
+    uint32_t y0_xa;             // first row of the sub-images | image column of tile column 0 (16-B aligned: dwordx4 loads)
+    uint32_t th_nch;            // tile rows | 16-B chunks per tile row (up to the dword after the last quad)
+    uint32_t g0_qoff;           // first image dword that holds a detection column | tile byte of quad 0's own dword (4 .. 16)
+    uint32_t ncell_cell0;       // cells of the strip | the first one's index in the cell table
+    uint32_t level;
+    uint32_t inv_nch;           // (i * inv_nch) >> 16 == i / nch for every i < th * nch (proved by the host for every strip)
+    StripTab tab;
+};
+static_assert(sizeof(StripTab) % 16 == 0 && sizeof(StripRec) == 32 + sizeof(StripTab), "StripRec: 32 header bytes, then the table");
+constexpr int kStripTabChunks = (int)(sizeof(StripTab) / 16);
+
 struct FastLds {                // byte offsets into the dynamic LDS block (host-computed from the largest strip)
     int32_t tile_pitch;         // bytes per tile row (multiple of 16)
-    int32_t map_off, map_pitch; // M map: (ih + 2) rows, 4 bytes of margin left of the first quad
-    int32_t colcell_off;        // u8 per map column: cell of the strip that owns it, 0xFF = none
+    int32_t map_off, map_pitch; // M map: (ih + 2) rows, 4 bytes of margin left of the first quad; padded to whole 16-byte stores
     int32_t ent_off, ent_cap;   // u16 entries of stage 1, ent_cap per wave (worst case: every quad of the wave's rows, cell by cell)
     int32_t px_off;             // u16 surviving pixels of one batch, kPxCap per wave
     int32_t corner_off, corner_cap;   // u16 corners, corner_cap per wave
@@ -57,7 +91,6 @@ struct FastLds {                // byte offsets into the dynamic LDS block (host
     int32_t total;
 };
 
-constexpr int kStripMaxCells = 8;
 constexpr int kStripWidth = 160;      // target strip width in pixels: four 36-px cells
 constexpr int kEntBatch = 128;        // entries expanded at a time ...
 constexpr int kPxCap = 4 * kEntBatch; // ... into at most this many pixels
@@ -117,13 +150,13 @@ __device__ unsigned long long d_fast_prof[16];
 #define ORBX_FTICK(k)
 #endif
 __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_t* __restrict__ pyr, size_t frame_stride,
-                                                     const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
-                                                     const StripDesc* __restrict__ strips, int n_strips, int n_cells,
+                                                     const StripRec* __restrict__ recs, int n_strips, int n_cells,
                                                      int ini_th, int min_th, FastLds Z,
                                                      uint32_t* __restrict__ cand, size_t cand_frame_stride, int* __restrict__ cell_count)
 {
     extern __shared__ __align__(16) uint8_t smem[];
-    __shared__ int s_cx0[kStripMaxCells], s_iw[kStripMaxCells], s_total[kStripMaxCells], s_slot_off[kStripMaxCells], s_slot_cap[kStripMaxCells];
+    __shared__ StripTab s_tab;
+    __shared__ int s_total[kStripMaxCells];
     __shared__ int s_seg[4][kStripMaxCells + 1];        // minThFAST: where the segment of the k-th fallback cell starts in a wave's entry list
 #ifdef ORBX_FAST_TIMING
     long long t_prev = clock64();
@@ -132,27 +165,31 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
 
     const int strip_idx = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);
     if (strip_idx >= n_strips) return;
-    const StripDesc S = strips[strip_idx];
-    const LevelDesc L = levels[S.level];
+    const StripRec* S = recs + strip_idx;
     const int frame = blockIdx.y;
-#if defined(ORBX_FAST_CUT)      // a cut variant emits nothing: the stages downstream see empty cells, not whatever the buffer held
-    if ((int)threadIdx.x < S.ncell) cell_count[(size_t)frame * n_cells + S.cell0 + threadIdx.x] = 0;
-#endif
-    const bool ext = S.level == 0 && lvl0.base != nullptr;       // level 0 read from the caller's image in place
-    const uint8_t* img = ext ? lvl0.base + (size_t)frame * lvl0.frame_stride : pyr + (size_t)frame * frame_stride + L.off;
-    const int istride = ext ? lvl0.stride : L.stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the strip's record: 32 bytes through the scalar unit, the table by wave 0, one 16-byte chunk per lane; both addresses need
+    // nothing but the strip index
+    const uint4 h0 = ((const uint4*)S)[0], h1 = ((const uint4*)S)[1];
+    uint4 tab_chunk = make_uint4(0u, 0u, 0u, 0u);
+    if (wave == 0) tab_chunk = ((const uint4*)&S->tab)[min(lane, kStripTabChunks - 1)];
+    const int sy0 = (int)(h0.z & 0xFFFFu), xa = (int)(h0.z >> 16);
+    const int th = (int)(h0.w & 0xFFFFu), nch = (int)(h0.w >> 16), ih = th - 6;
+    const int g0 = (int)(h1.x & 0xFFFFu), qoff = (int)(h1.x >> 16);
+    const int ncell = (int)(h1.y & 0xFFFFu), cell0 = (int)(h1.y >> 16);
+    const uint32_t inv_nch = h1.w;
+#if defined(ORBX_FAST_CUT)      // a cut variant emits nothing: the stages downstream see empty cells, not whatever the buffer held
+    if ((int)threadIdx.x < ncell) cell_count[(size_t)frame * n_cells + cell0 + threadIdx.x] = 0;
+#endif
+    const bool ext = h1.z == 0u && lvl0.base != nullptr;         // level 0 read from the caller's image in place
+    // tile row 0, tile column 0 of this frame: a scalar base, the threads add 32-bit offsets
+    const uint8_t* img = (ext ? lvl0.base : pyr) + (size_t)frame * (ext ? lvl0.frame_stride : frame_stride) +
+                         (ext ? (size_t)sy0 * (size_t)lvl0.stride + (size_t)xa : (size_t)h0.x);
+    const uint32_t istride = ext ? (uint32_t)lvl0.stride : h0.y;
 
-    const int th = S.y1 - S.y0, ih = th - 6;
-    const int g0 = (S.x0 + 3) >> 2, g1 = (S.x1 - 4) >> 2;      // first / last image dword that holds a detection column
-    const int ngx = g1 - g0 + 1;
-    const int xa = (4 * (g0 - 1)) & ~15;                         // image column of tile column 0 (16-B aligned: dwordx4 loads)
-    const int qoff = 4 * g0 - xa;                                // tile byte of quad 0's own dword (4 .. 16)
-    const int nch = (qoff + 4 * ngx + 4 + 15) >> 4;              // 16-B chunks per tile row: up to the dword after the last quad
     const int TP = Z.tile_pitch, MP = Z.map_pitch;
     uint8_t* tile = smem;
     uint8_t* mmap = smem + Z.map_off;                            // map column = 4 * gx + k + 4, map row = y + 1
-    uint8_t* colcell = smem + Z.colcell_off;
     uint16_t* ent = (uint16_t*)(smem + Z.ent_off) + wave * Z.ent_cap;
     uint16_t* pxl = (uint16_t*)(smem + Z.px_off) + wave * kPxCap;
     uint16_t* corners = (uint16_t*)(smem + Z.corner_off) + wave * Z.corner_cap;
@@ -160,25 +197,33 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     uint32_t* pre = (uint32_t*)(smem + Z.pre_off);
     const int WPC = Z.wpc;
 
-    // ---- tile load (16-B chunks; the pyramid rows are 64-B aligned), clears, per-cell tables ----
-    {
-        const float inv = 1.0f / (float)nch;
-        for (int i = tid; i < th * nch; i += 256) {
-            const int r = (int)(((float)i + 0.5f) * inv), q = i - r * nch;
-            *(uint4*)(tile + r * TP + 16 * q) = *(const uint4*)(img + (size_t)(S.y0 + r) * istride + xa + 16 * q);
-        }
+    // ---- tile load (16-B chunks; the pyramid rows are 64-B aligned): chunk i = tid + 256 * k is chunk i % nch of tile row i / nch.
+    // A thread issues the loads of a group of three chunks back to back (a chunk past the end is the last one again, so no load sits
+    // behind a branch) and stores what it owns after ONE wait.  Under the first group's loads: the clears.  (Strips of 640 x 480
+    // frames are one group; ten chunks per thread is the most the host accepts: 133 rows of 18.) ----
+    const int n_chunk = th * nch;
+    uint4 c0, c1, c2;
+    uint32_t d0, d1, d2;
+    auto issue = [&](const int k, uint32_t& dst) {
+        const uint32_t i = (uint32_t)min(tid + 256 * k, n_chunk - 1);
+        // (24-bit multiplies: i < 4096, inv_nch <= 65536, r < 256, the pitches below 2^23)
+        const uint32_t r = __umul24(i, inv_nch) >> 16, q = i - __umul24(r, (uint32_t)nch);
+        dst = __umul24(r, (uint32_t)TP) + 16u * q;
+        return *(const uint4*)(img + (__umul24(r, istride) + 16u * q));
+    };
+    auto land = [&](const int k, const uint32_t dst, const uint4& c) { if (tid + 256 * k < n_chunk) *(uint4*)(tile + dst) = c; };
+    c0 = issue(0, d0); c1 = issue(1, d1); c2 = issue(2, d2);
+    {   // (the host pads both regions to whole 16-byte stores)
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+        for (int i = tid; i < ((ih + 2) * MP + 15) >> 4; i += 256) ((uint4*)mmap)[i] = zero;
+        for (int i = tid; i < (ncell * WPC + 3) >> 2; i += 256) ((uint4*)bits)[i] = zero;
     }
-    for (int i = tid; i < ((ih + 2) * MP) >> 2; i += 256) ((uint32_t*)mmap)[i] = 0u;
-    for (int i = tid; i < S.ncell * WPC; i += 256) bits[i] = 0u;
-    for (int i = tid; i < MP; i += 256) colcell[i] = 0xFF;
-    if (tid < S.ncell) {
-        const CellDesc c = cells[S.cell0 + tid];
-        s_cx0[tid] = c.x0 + 3 - 4 * g0 + 4; s_iw[tid] = c.x1 - c.x0 - 6;
-        s_slot_off[tid] = c.slot_off; s_slot_cap[tid] = c.slot_cap;     // (the emission must not wait for a global load per corner)
+    if (wave == 0 && lane < kStripTabChunks) ((uint4*)&s_tab)[lane] = tab_chunk;
+    land(0, d0, c0); land(1, d1, c1); land(2, d2, c2);
+    for (int k = 3; 256 * k < n_chunk; k += 3) {
+        c0 = issue(k, d0); c1 = issue(k + 1, d1); c2 = issue(k + 2, d2);
+        land(k, d0, c0); land(k + 1, d1, c1); land(k + 2, d2, c2);
     }
-    __syncthreads();
-    for (int j = 0; j < S.ncell; j++)
-        for (int i = tid; i < s_iw[j]; i += 256) colcell[s_cx0[j] + i] = (uint8_t)j;
     __syncthreads();
 
     ORBX_FTICK(0)
@@ -189,9 +234,9 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     auto nms_pixel = [&](const int y, const int mc, const int t, const int cA, const int cB) {
         const uint8_t* p = mmap + (y + 1) * MP + mc;
         const int m = p[0];
-        const int j = colcell[mc];
+        const int j = s_tab.colcell[mc];
         if (m > t && j >= cA && j < cB) {
-            const int xl = mc - s_cx0[j], iw = s_iw[j];
+            const int xl = mc - s_tab.cx0[j], iw = s_tab.iw[j];
             // neighbours outside the cell interior count as 0, and so do those that are no corners at t: the pixel survives when its
             // score beats the largest of the eight (branch-free: a short-circuit chain costs a branch per neighbour in SIMD)
             const bool hl = xl > 0, hr = xl < iw - 1, hu = y > 0, hd = y < ih - 1;
@@ -208,17 +253,17 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     };
     // emission of one pixel if its bit is set
     auto emit_pixel = [&](const int y, const int mc, const int cA, const int cB) {
-        const int j = colcell[mc];
+        const int j = s_tab.colcell[mc];
         if (j >= cA && j < cB) {
-            const int iw = s_iw[j], q = y * iw + (mc - s_cx0[j]);
+            const int iw = s_tab.iw[j], q = y * iw + (mc - s_tab.cx0[j]);
             const uint32_t wd = bits[j * WPC + (q >> 5)];
             if ((wd >> (q & 31)) & 1u) {
                 const int rk = (int)pre[j * WPC + (q >> 5)] + __popc(wd & ((1u << (q & 31)) - 1u));
                 const int m = mmap[(y + 1) * MP + mc];
                 // coordinates relative to minBorder (= level coordinates - 16), as vToDistributeKeys holds them (:865-866)
-                if (rk < s_slot_cap[j])
-                    cand[(size_t)frame * cand_frame_stride + s_slot_off[j] + rk] =
-                        pack_key((uint32_t)(4 * g0 + mc - 4 - 16), (uint32_t)(S.y0 + 3 + y - 16), (uint32_t)(m - 1));
+                if (rk < s_tab.slot_cap[j])
+                    cand[(size_t)frame * cand_frame_stride + s_tab.slot_off[j] + rk] =
+                        pack_key((uint32_t)(4 * g0 + mc - 4 - 16), (uint32_t)(sy0 + 3 + y - 16), (uint32_t)(m - 1));
             }
         }
     };
@@ -228,7 +273,7 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
 
     // the quads that hold the columns of the cells [cA, cB)
     auto set_cols = [&](const int cA, const int cB) {
-        const int mA = s_cx0[cA], mB = s_cx0[cB - 1] + s_iw[cB - 1] - 1;       // first / last active map column
+        const int mA = s_tab.cx0[cA], mB = s_tab.cx0[cB - 1] + s_tab.iw[cB - 1] - 1;       // first / last active map column
         gA = (mA - 4) >> 2;
         ng = ((mB - 4) >> 2) - gA + 1;
     };
@@ -347,7 +392,7 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     };
     // exclusive prefix of the word popcounts of cell j's mask, by one wave
     auto rank_cell = [&](const int j) {
-        const int nwords = (s_iw[j] * ih + 31) >> 5;
+        const int nwords = (s_tab.iw[j] * ih + 31) >> 5;
         int run = 0;
         for (int w0 = 0; w0 < nwords; w0 += 64) {
             const int i = w0 + lane;
@@ -360,7 +405,7 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     };
     // ---- iniThFAST over the whole strip ----
     uint32_t fb_cells = 0u;         // workgroup-uniform: bit j = cell j found nothing at iniThFAST
-    set_cols(0, S.ncell);
+    set_cols(0, ncell);
     {
         const int nent = stage1(ini_th, 0);
         ORBX_FTICK(1)
@@ -373,15 +418,15 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
 #if !defined(ORBX_FAST_CUT) || ORBX_FAST_CUT >= 3
     __syncthreads();                                              // every wave's scores are in the map
     ORBX_FTICK(3)
-    for_corners(wave, 4, nrow_w, [&](int y, int mc) { nms_pixel(y, mc, ini_th, 0, S.ncell); });
+    for_corners(wave, 4, nrow_w, [&](int y, int mc) { nms_pixel(y, mc, ini_th, 0, ncell); });
     __syncthreads();                                              // every winner's bit is set
     ORBX_FTICK(4)
-    for (int j = wave; j < S.ncell; j += 4) rank_cell(j);
+    for (int j = wave; j < ncell; j += 4) rank_cell(j);
     __syncthreads();
     ORBX_FTICK(5)
     // (read here, between two barriers: the owner of a fallback cell writes s_total[j] again after the next one)
-    fb_cells = (uint32_t)__ballot(lane < S.ncell && s_total[min(lane, kStripMaxCells - 1)] == 0);
-    for_corners(wave, 4, nrow_w, [&](int y, int mc) { emit_pixel(y, mc, 0, S.ncell); });
+    fb_cells = (uint32_t)__ballot(lane < ncell && s_total[min(lane, kStripMaxCells - 1)] == 0);
+    for_corners(wave, 4, nrow_w, [&](int y, int mc) { emit_pixel(y, mc, 0, ncell); });
     ORBX_FTICK(6)
 #endif
 #if defined(ORBX_FAST_CUT)      // instruction-budget experiments (tools/fast_cuts.sh): the kernel ends after a prefix of its stages
@@ -438,5 +483,5 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
         }
     }
     __syncthreads();
-    if (tid < S.ncell) cell_count[(size_t)frame * n_cells + S.cell0 + tid] = min(s_total[tid], s_slot_cap[tid]);
+    if (tid < ncell) cell_count[(size_t)frame * n_cells + cell0 + tid] = min(s_total[tid], s_tab.slot_cap[tid]);
 }

@@ -1113,6 +1113,33 @@ int orbx_debug_wave_sort(int32_t* count, int32_t* ulx, int32_t* node, int n)
     return ORBX_OK;
 }
 
+// the FAST score tree of k_fast_strips alone, on n row-major 7 x 7 patches in host memory: M (OpenCV's corner score + 1, 0 where no
+// arc of nine is all brighter or all darker) per patch.  Pinned against the definition by tests/test_fast_score_tree_gpu.py.
+int orbx_debug_fast_scores(const uint8_t* patches, int n, int pitch, int* out)
+{
+    if (n < 0 || n > (1 << 22)) return fail(ORBX_ERR_ARG, "n %d outside 0..2^22", n);
+    if (pitch < 8 || pitch > 1024) return fail(ORBX_ERR_ARG, "pitch %d outside 8..1024", pitch);
+    if (n == 0) return ORBX_OK;
+    if (!patches || !out) return fail(ORBX_ERR_ARG, "NULL argument");
+    const int per_band = std::min(pitch / 8, 64), bands = (64 + per_band - 1) / per_band;
+    const size_t lds = (size_t)bands * 7 * pitch;               // a few KB: 64 bands at pitch 8 .. 15, one at pitch >= 512
+    uint8_t* d_in = nullptr;
+    int* d_out = nullptr;
+    ORBX_HIP(hipMalloc(&d_in, (size_t)n * 49));
+    int r = ORBX_OK;
+    if (hipMalloc(&d_out, sizeof(int) * (size_t)n) != hipSuccess) r = ORBX_ERR_HIP;
+    if (!r && hipMemcpy(d_in, patches, (size_t)n * 49, hipMemcpyHostToDevice) != hipSuccess) r = ORBX_ERR_HIP;
+    if (!r) {
+        hipLaunchKernelGGL(k_debug_fast_scores, dim3((n + 63) / 64), dim3(64), lds, 0, d_in, n, pitch, per_band, d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) r = ORBX_ERR_HIP;
+    }
+    if (!r && hipMemcpy(out, d_out, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) r = ORBX_ERR_HIP;
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (r) return fail(r, "device score tree failed");
+    return ORBX_OK;
+}
+
 // Frame::ComputeStereoMatches (src/Frame.cc:931-1101) on the pyramids both extractors hold from their LAST extract call.
 static int stereo_enqueue(orbx_extractor* l, orbx_extractor* r, int frame0, int batch,
                           const OrbxKeyPoint* d_kps_l, const uint8_t* d_desc_l, const int32_t* d_n_l,

@@ -14,9 +14,9 @@
 //            survivor becomes ONE 16-bit entry of the wave's list (ballot + mbcnt).  On the synthetic frames 5.7 % of the
 //            pixels survive at t = 20 (the exact 8-pair test: 3.8 %, at 3.4x the instructions).
 //   expand   128 entries at a time -> list of surviving pixels (DPP prefix sum of the popcounts)
-//   stage 2  one lane per surviving pixel: M = max over the 16 arcs of min(+-(v - ring)) (min3 / max3 trees); OpenCV's corner
-//            test at t is M > t and its response M - 1 (SURVEY App. A.1).  M goes into a byte map with a zero halo; pixels
-//            with M > t join the wave's corner list.
+//   stage 2  one lane per surviving pixel: M = max over the 16 arcs of min(+-(v - ring)), both polarities in one packed-f16
+//            min3 / max3 tree (fast_m_tree); OpenCV's corner test at t is M > t and its response M - 1 (SURVEY App. A.1).  M goes
+//            into a byte map with a zero halo; pixels with M > t join the wave's corner list.
 //   -------- workgroup barrier --------
 //   nms      one lane per corner: strict 3x3 maximum over the neighbours that are corners at t AND lie in the same cell
 //            interior; winners set a bit in their cell's row-major bitmask.
@@ -96,30 +96,48 @@ constexpr int kEntBatch = 128;        // entries expanded at a time ...
 constexpr int kPxCap = 4 * kEntBatch; // ... into at most this many pixels
 constexpr int kCornerCap = 256;       // corners a wave lists before it falls back to scanning the pixels it scored
 
+// The score tree in packed f16, both polarities at once.  A byte b read as f16 is the subnormal b * 2^-24; differences, minima and maxima of
+// such values are exact, and the raw 16 bits of a non-negative result are the integer itself.  This needs the kernel's f16 denormal mode
+// "preserve" (hipcc's default, .amdhsa_float_denorm_mode_16_64 3) and opcodes that do not flush; tests/test_fast_score_tree_gpu.py runs
+// this function alone (orbx_debug_fast_scores) over every difference.
+typedef _Float16 fast_h2 __attribute__((ext_vector_type(2)));
+// v_pk_minimum3_f16 / v_pk_maximum3_f16 (gfx950)
+__device__ __forceinline__ fast_h2 fast_pk_min3(fast_h2 a, fast_h2 b, fast_h2 c) { return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c); }
+__device__ __forceinline__ fast_h2 fast_pk_max3(fast_h2 a, fast_h2 b, fast_h2 c) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c); }
+// (v - r, r - v) from two zero-extended bytes: low half v.lo + -r.lo, high half -v.lo + r.lo.  Round to nearest: x - x is +0 in both halves.
+__device__ __forceinline__ fast_h2 fast_pk_diff(uint32_t v, uint32_t r)
+{
+    uint32_t d;
+    asm("v_pk_add_f16 %0, %1, %2 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(d) : "v"(v), "v"(r));
+    return __builtin_bit_cast(fast_h2, d);
+}
+
+// M = max(0, max over the 16 arcs of min(d), max over the arcs of min(-d)), d = centre - ring pixel: OpenCV's corner score + 1
 __device__ __forceinline__ int fast_m_tree(const uint8_t* __restrict__ t, int pitch)
 {
-    const int v = t[0];
-    int d[16];
-    d[0] = v - t[3 * pitch];       d[1] = v - t[3 * pitch + 1];   d[2] = v - t[2 * pitch + 2];   d[3] = v - t[pitch + 3];
-    d[4] = v - t[3];               d[5] = v - t[-pitch + 3];      d[6] = v - t[-2 * pitch + 2];  d[7] = v - t[-3 * pitch + 1];
-    d[8] = v - t[-3 * pitch];      d[9] = v - t[-3 * pitch - 1];  d[10] = v - t[-2 * pitch - 2]; d[11] = v - t[-pitch - 3];
-    d[12] = v - t[-3];             d[13] = v - t[pitch - 3];      d[14] = v - t[2 * pitch - 2];  d[15] = v - t[3 * pitch - 1];
-    // min / max of every run of 3, then of every run of 9 as three runs of 3: v_min3 / v_max3 all the way
-    int lo3[16], hi3[16];
+    const uint32_t v = t[0];
+    fast_h2 d[16];                // (d, -d)
+    d[0] = fast_pk_diff(v, t[3 * pitch]);       d[1] = fast_pk_diff(v, t[3 * pitch + 1]);   d[2] = fast_pk_diff(v, t[2 * pitch + 2]);   d[3] = fast_pk_diff(v, t[pitch + 3]);
+    d[4] = fast_pk_diff(v, t[3]);               d[5] = fast_pk_diff(v, t[-pitch + 3]);      d[6] = fast_pk_diff(v, t[-2 * pitch + 2]);  d[7] = fast_pk_diff(v, t[-3 * pitch + 1]);
+    d[8] = fast_pk_diff(v, t[-3 * pitch]);      d[9] = fast_pk_diff(v, t[-3 * pitch - 1]);  d[10] = fast_pk_diff(v, t[-2 * pitch - 2]); d[11] = fast_pk_diff(v, t[-pitch - 3]);
+    d[12] = fast_pk_diff(v, t[-3]);             d[13] = fast_pk_diff(v, t[pitch - 3]);      d[14] = fast_pk_diff(v, t[2 * pitch - 2]);  d[15] = fast_pk_diff(v, t[3 * pitch - 1]);
+    // minimum of every run of 3, then of every run of 9 as three runs of 3: (min of d[k .. k+8], min of -d[k .. k+8])
+    fast_h2 lo3[16], lo9[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        lo3[k] = min(min(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-        hi3[k] = max(max(d[k], d[(k + 1) & 15]), d[(k + 2) & 15]);
-    }
-    int best_dark = -256, best_bright = 256;
+    for (int k = 0; k < 16; k++) lo3[k] = fast_pk_min3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int lo9 = min(min(lo3[k], lo3[(k + 3) & 15]), lo3[(k + 6) & 15]);      // min of d[k .. k+8]
-        const int hi9 = max(max(hi3[k], hi3[(k + 3) & 15]), hi3[(k + 6) & 15]);
-        best_dark = max(best_dark, lo9);
-        best_bright = min(best_bright, hi9);
-    }
-    return max(max(best_dark, -best_bright), 0);
+    for (int k = 0; k < 16; k++) lo9[k] = fast_pk_min3(lo3[k], lo3[(k + 3) & 15], lo3[(k + 6) & 15]);
+    // maximum over the arcs, 16 -> 6 -> 2, the last one together with +0: (best_dark, -best_bright), both clamped at 0.  The +0 also
+    // keeps a -0 from the bit-level read-out below (none can arise: every d is +0 or non-zero, and minimum / maximum order -0 below +0).
+    const fast_h2 a0 = fast_pk_max3(lo9[0], lo9[1], lo9[2]), a1 = fast_pk_max3(lo9[3], lo9[4], lo9[5]), a2 = fast_pk_max3(lo9[6], lo9[7], lo9[8]);
+    const fast_h2 a3 = fast_pk_max3(lo9[9], lo9[10], lo9[11]), a4 = fast_pk_max3(lo9[12], lo9[13], lo9[14]);
+    const fast_h2 b0 = fast_pk_max3(a0, a1, a2), b1 = fast_pk_max3(a3, a4, lo9[15]);
+    const fast_h2 zero = {(_Float16)0.0f, (_Float16)0.0f};
+    const fast_h2 m = fast_pk_max3(b0, b1, zero);
+    // low half against high half; the raw bits of the non-negative subnormal are M
+    uint32_t r;
+    asm("v_pk_max_f16 %0, %1, %1 op_sel:[0,1]" : "=v"(r) : "v"(__builtin_bit_cast(uint32_t, m)));
+    return (int)(r & 0xFFFFu);
 }
 
 // inclusive prefix sum over the 64 lanes without LDS traffic (row_shr 1 / 2 / 4 / 8, row_bcast 15 / 31)

@@ -665,6 +665,21 @@ __global__ __launch_bounds__(64) void k_debug_wave_sort(SortNode* __restrict__ d
     for (int i = threadIdx.x; i < n; i += 64) data[i] = out[i];
 }
 
+// test hook: fast_m_tree alone (orbx_debug_fast_scores).  One lane per 7 x 7 patch; the patches of a workgroup lie in LDS as the strips'
+// tiles do, at row pitch `pitch`: per_band = pitch / 8 of them side by side, eight columns apart, in bands of seven rows.
+__global__ __launch_bounds__(64) void k_debug_fast_scores(const uint8_t* __restrict__ patches, int n, int pitch, int per_band, int* __restrict__ out)
+{
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int band = (int)threadIdx.x / per_band, col = 8 * ((int)threadIdx.x - band * per_band);
+    uint8_t* const p = smem + band * 7 * pitch + col;           // rows 0..6, columns col .. col + 6 <= 8 * per_band - 2 < pitch
+    for (int r = 0; r < 7; r++)
+        for (int c = 0; c < 7; c++) p[r * pitch + c] = patches[(size_t)i * 49 + r * 7 + c];
+    wave_lds_fence();                                           // a lane reads what it wrote itself
+    out[i] = fast_m_tree(p + 3 * pitch + 3, pitch);
+}
+
 // ------------------------------------------------------------------------------------------------
 // E8 (index part): slot of every selected keypoint in the output arrays.  Level-major order; keypoints
 // whose scaled x lies in [lap0, lap1] are written from the back (stereoIndex--), the rest from the front.

@@ -10,12 +10,17 @@
 #define OP3(name) name " %0, %0, %8, %1\n " name " %1, %1, %8, %2\n " name " %2, %2, %8, %3\n " name " %3, %3, %8, %4\n " name " %4, %4, %8, %5\n " name " %5, %5, %8, %6\n " name " %6, %6, %8, %7\n " name " %7, %7, %8, %0\n"
 #define OP3C(name) name " %0, %0, %8, 1\n " name " %1, %1, %8, 1\n " name " %2, %2, %8, 1\n " name " %3, %3, %8, 1\n " name " %4, %4, %8, 1\n " name " %5, %5, %8, 1\n " name " %6, %6, %8, 1\n " name " %7, %7, %8, 1\n"
 #define OP1(name) name " %0, %8\n " name " %1, %8\n " name " %2, %8\n " name " %3, %8\n " name " %4, %8\n " name " %5, %8\n " name " %6, %8\n " name " %7, %8\n"
+// the subtraction of the packed FAST score tree: (x, .) -> (k.lo - x.lo, x.lo - k.lo); applied twice it gives x.lo back, so bytes stay f16 subnormals for the whole run
+#define OP2SUB(name) name " %0, %8, %0 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %1, %8, %1 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %2, %8, %2 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %3, %8, %3 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %4, %8, %4 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %5, %8, %5 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %6, %8, %6 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n " name " %7, %8, %7 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]\n"
 #define CMP(name) name " vcc, %0, %8\n " name " vcc, %1, %8\n " name " vcc, %2, %8\n " name " vcc, %3, %8\n " name " vcc, %4, %8\n " name " vcc, %5, %8\n " name " vcc, %6, %8\n " name " vcc, %7, %8\n"
 
-#define KERNEL(id, body, clob)                                                                                          \
+#define KERNEL(id, body, clob) KERNELM(id, body, clob, 0xFFFFFFFFu)
+// (mask: the registers start as (threadIdx.x + j) & mask -- 0xFF: raw bytes, i.e. f16 subnormals b * 2^-24 in the low half)
+#define KERNELM(id, body, clob, mask)                                                                                      \
     __global__ __launch_bounds__(1024) void k_##id(uint32_t* out, int iters, unsigned long long* cyc)                   \
     {                                                                                                                   \
         uint32_t a0 = threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7; \
+        a0 &= mask; a1 &= mask; a2 &= mask; a3 &= mask; a4 &= mask; a5 &= mask; a6 &= mask; a7 &= mask;                 \
         const uint32_t k1 = 0x00010001u + blockIdx.x;                                                                   \
         const unsigned long long w0 = wall_clock64(), t0 = clock64();                                                   \
         for (int i = 0; i < iters; i++) {                                                                               \
@@ -77,6 +82,11 @@ KERNEL(bfi, OP3("v_bfi_b32"), "memory")
 KERNEL(xad, OP3("v_xad_u32"), "memory")
 KERNEL(lerp_u8, OP3("v_lerp_u8"), "memory")
 KERNEL(ashr_pk_u8_i32, OP3C("v_ashr_pk_u8_i32"), "memory")    // gfx950: shift, saturate to a byte and pack, two pixels at a time
+// gfx950: three-input packed f16 minimum / maximum, and the packed subtraction in the form the FAST score tree uses, all on subnormal operands
+KERNELM(pk_minimum3_f16, OP3("v_pk_minimum3_f16"), "memory", 0xFFu)
+KERNELM(pk_maximum3_f16, OP3("v_pk_maximum3_f16"), "memory", 0xFFu)
+KERNELM(pk_add_f16_sub_denorm, OP2SUB("v_pk_add_f16"), "memory", 0xFFu)
+KERNELM(pk_max_f16_denorm, OP2("v_pk_max_f16"), "memory", 0xFFu)
 
 int main()
 {
@@ -104,5 +114,6 @@ int main()
     RUN(cmp_gt_u32) RUN(cndmask) RUN(mov) RUN(fma_f32) RUN(mad_u24) RUN(add3) RUN(and_or) RUN(lshl_or) RUN(bfe) RUN(perm) RUN(alignbyte)
     RUN(min3_i32) RUN(max3_u32) RUN(med3_i32) RUN(min3_f32) RUN(sad_u8) RUN(msad_u8) RUN(sad_u16) RUN(sad_u32) RUN(dot4_u32_u8) RUN(dot2_u32_u16)
     RUN(pk_mad_u16) RUN(cvt_pk_u8_f32) RUN(bfi) RUN(xad) RUN(lerp_u8) RUN(ashr_pk_u8_i32)
+    RUN(pk_minimum3_f16) RUN(pk_maximum3_f16) RUN(pk_add_f16_sub_denorm) RUN(pk_max_f16_denorm)
     return 0;
 }

@@ -847,6 +847,7 @@ int orb_oracle_stereo_matches(void* hL, void* hR, const OracleKeyPoint* kpsL, co
             }
         }
         if (bestDist < thOrbDist) {
+            if (kpL.octave < 0 || kpL.octave >= eL->nlevels) return -2;      // mvInvScaleFactors / mvImagePyramid have no such level
             const float uR0 = kpsR[bestIdxR].x;
             const float scaleFactor = eL->inv_scale[kpL.octave];
             const float scaleduL = std::round(kpL.x * scaleFactor);

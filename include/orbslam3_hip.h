@@ -131,6 +131,10 @@ int orbx_debug_set_tail_delay(orbx_extractor* h, int microseconds);
  * LDS, 2 keys in the L2-resident scratch, 3 per level and frame: keys in LDS when the level's candidates fit), 4 two octree launches, 8 level-0 octree started early, 16 level 0 read in place,
  * 32 resize tail on the side stream, 64 the whole resize chain on the side stream beside FAST on level 0. */
 int orbx_debug_last_schedule(orbx_extractor* h);
+/* Test hook: the waves per workgroup (1, 2 or 4) of the LAST extract call's octree launches -- launch 0 level 0 started early, 1 the
+ * lower levels (or all levels, when there is one launch), 2 the upper levels; 0 when the call had no such launch.  ORBX_OCT_WAVES =
+ * 1 | 2 | 4 (read at construction) forces the value for every launch. */
+int orbx_debug_octree_waves(orbx_extractor* h, int launch);
 /* Test hook: the FAST score tree of the extractor's corner kernel alone.  `patches` holds n row-major 7 x 7 patches (49 bytes each,
  * host memory); out[i] = M of patch i's centre = max(0, max over the 16 arcs of nine of min(d), of min(-d)), d = centre - ring
  * pixel: OpenCV's corner score + 1.  `pitch` (8..1024) is the row pitch at which the kernel lays the patches out in LDS. */

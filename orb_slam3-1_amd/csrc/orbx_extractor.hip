@@ -164,6 +164,18 @@ struct orbx_extractor {
     bool oct_dyn_off = false;            // ORBX_OCT_DYN=0: small batches keep the scratch instantiation (measurement / tests)
     int oct_dyn_max_batch = 64;          // largest batch that takes k_octree_dyn (ORBX_OCT_DYN_MAXB; measured: one frame 0.163 -> 0.136 ms,
                                          // 64 frames 0.412 -> 0.352 ms per call, 256 frames 0.99 -> 1.12 ms: the LDS is the blur's there; LDS keys for the early level-0 launch alone: 0.993 -> 1.008)
+    // Waves per octree workgroup (k_octree: one control wave, W - 1 helpers): ORBX_OCT_WAVES = 1 | 2 | 4 forces every launch; otherwise
+    // a launch that runs on a mostly empty chip (up to 64 frames) takes 4 and the launches beside FAST / the blur take oct_waves_beside.
+    // Measured at B = 256 (ms per step, medians of three; W of the three launches): 1/1/1 0.897, 2/2/2 0.868, 4/4/4 0.912, 4/1/1 0.892,
+    // 4/2/2 0.871, 2/1/2 0.900, 2/2/1 0.878, 1/2/2 0.875, 2/2/4 0.925: helpers that wait at a barrier still hold the wave slots that the
+    // blur's workgroups need, and two waves per workgroup is where that stops paying.  B = 64: 1 wave 0.315 ms per call, 2 0.299, 4 0.290.
+    int oct_waves_env = 0;
+    int oct_waves_beside[3] = {2, 2, 2};  // level 0 started early, the lower levels, the upper levels
+    // k_octree's lane-per-node threshold for launches of more than one wave (ORBX_OCT_SMALL_MAX; one wave: 32).  Re-measured with
+    // helpers: 16 / 8 / 0 leave the B = 256 step where it is (0.868 / 0.868 / 0.868 against 0.868) and take a single frame from 0.115 to
+    // 0.107 / 0.105 / 0.103 ms, but the serial octree stage of 64 frames went from 0.23 to 0.67 ms with each of them; not understood, so 32 stays.
+    int oct_small_max_waves = 32;
+    int last_oct_waves[3] = {0, 0, 0};    // W of the last enqueue's launches, same order; 0: no such launch (orbx_debug_octree_waves)
     int oct_dyn_keys_beside = 6144;      // LDS keys per workgroup when the blur runs beside the octree (batches of 32 frames and more)
     bool resize_beside = true;           // the whole resize chain on the side stream beside FAST on level 0 (ORBX_RESIZE_BESIDE=0: in front of it)
     std::vector<hipStream_t> aux_streams;
@@ -616,12 +628,17 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
         // (keys in LDS: one launch, the buffers are sized for the largest level anyway)
         const bool two_launches = !oct_nodes_hbm && (o_keys == 0 || dyn_keys) && oct_split > 0 && oct_stream && blur_s;
         const int lv_lo = two_launches ? oct_split : nlevels;
-        auto launch_octree = [&](hipStream_t qs, int lv0, int lv1, size_t lds, int pool, int keys) {
+        // `which`: 0 level 0 started early, 1 the lower levels (or all of them), 2 the upper levels
+        const bool oct_beside = B > 64;                  // the launch shares a full chip: with FAST / the blur, or with its own 2 000 workgroups
+        last_oct_waves[0] = last_oct_waves[1] = last_oct_waves[2] = 0;
+        auto launch_octree = [&](hipStream_t qs, int lv0, int lv1, size_t lds, int pool, int keys, int which) {
+            const int W = oct_waves_env ? oct_waves_env : (oct_beside ? oct_waves_beside[which] : 4);
+            if (lv1 > lv0) last_oct_waves[which] = W;
             if (lv1 > lv0)
-                hipLaunchKernelGGL(oct_kernel, dim3(lv1 - lv0, nB), dim3(64), lds, qs, d_levels.p, d_cells.p, d_cand.p + (size_t)f0 * cand_frame_entries, (size_t)cand_frame_entries,
+                hipLaunchKernelGGL(oct_kernel, dim3(lv1 - lv0, nB), dim3(64 * W), lds, qs, d_levels.p, d_cells.p, d_cand.p + (size_t)f0 * cand_frame_entries, (size_t)cand_frame_entries,
                                    d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1), n_cells, d_scratch.p + (size_t)f0 * 2 * cand_frame_entries, (size_t)2 * cand_frame_entries, pool, keys,
                                    sel, sel_frame_entries, sel_cnt, nlevels, o_status + f0,
-                                   d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0);
+                                   d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0, W > 1 ? oct_small_max_waves : 32);
         };
         auto launch_blur = [&](hipStream_t bs) {
             hipLaunchKernelGGL(k_blur, dim3(xcd_grid((int)tiles.size()), nB), dim3(256), 0, bs, lvl0, pyr, in_place ? pyr : nullptr, blr, pyr_frame_bytes,
@@ -666,7 +683,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
                     launch_fast(s, 0, l1_strip);
                     ORBX_HIP(hipEventRecord(ev_fast0, s));
                     ORBX_HIP(hipStreamWaitEvent(blur_s, ev_fast0, 0));
-                    launch_octree(blur_s, 0, 1, o_lds, oct_pool, o_keys);
+                    launch_octree(blur_s, 0, 1, o_lds, oct_pool, o_keys, 0);
                     oct0_early = true;
                     if (chain_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_resize, 0));
                     launch_fast(s, l1_strip, tail_strip);
@@ -701,11 +718,11 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             ORBX_HIP(hipStreamWaitEvent(oct_stream, ev_fork, 0));
             {   // (dynamic LDS keys: the upper levels hold fewer candidates -- half the allotment)
                 const int k_hi = dyn_keys ? std::max(64, o_keys / 2) : 0;
-                launch_octree(oct_stream, oct_split, nlevels, oct_lds_hi + 8 * (size_t)k_hi, oct_pool_hi, k_hi);
+                launch_octree(oct_stream, oct_split, nlevels, oct_lds_hi + 8 * (size_t)k_hi, oct_pool_hi, k_hi, 2);
             }
             ORBX_HIP(hipEventRecord(ev_oct_join, oct_stream));
         }
-        launch_octree(os, oct0_early ? 1 : 0, lv_lo, o_lds, oct_pool, o_keys);
+        launch_octree(os, oct0_early ? 1 : 0, lv_lo, o_lds, oct_pool, o_keys, 1);
         if (blur_s) {
             if (tail_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_tail, 0));
             launch_blur(s);
@@ -822,6 +839,11 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
     if (const char* env = getenv("ORBX_RESIZE_BESIDE")) e->resize_beside = atoi(env) != 0;
     if (const char* env = getenv("ORBX_OCT_DYN")) e->oct_dyn_off = atoi(env) == 0;
     if (const char* env = getenv("ORBX_OCT_DYN_MAXB")) e->oct_dyn_max_batch = atoi(env);
+    if (const char* env = getenv("ORBX_OCT_WAVES")) { const int wv = atoi(env); if (wv == 1 || wv == 2 || wv == 4) e->oct_waves_env = wv; }
+    if (const char* env = getenv("ORBX_OCT_SMALL_MAX")) e->oct_small_max_waves = std::max(0, std::min(64, atoi(env)));
+    if (const char* env = getenv("ORBX_OCT_WAVES_BESIDE")) {       // A/B runs: three digits, e.g. 412 (early level 0, lower, upper levels)
+        for (int i = 0; i < 3 && env[i]; i++) { const int wv = env[i] - '0'; if (wv == 1 || wv == 2 || wv == 4) e->oct_waves_beside[i] = wv; }
+    }
     if (const char* env = getenv("ORBX_OCT_DYN_KEYS_BESIDE")) e->oct_dyn_keys_beside = std::max(64, atoi(env));
     for (int i = 0; i + 1 < e->split_parts; i++) {
         hipStream_t s = nullptr; hipEvent_t ev = nullptr;
@@ -1062,6 +1084,12 @@ int orbx_debug_set_tail_delay(orbx_extractor* e, int microseconds)
     return ORBX_OK;
 }
 
+int orbx_debug_octree_waves(orbx_extractor* e, int launch)
+{
+    if (!e || launch < 0 || launch > 2) return fail(ORBX_ERR_ARG, "NULL handle or launch outside 0..2");
+    return e->last_oct_waves[launch];
+}
+
 int orbx_debug_last_schedule(orbx_extractor* e)
 {
     if (!e) return fail(ORBX_ERR_ARG, "NULL handle");
@@ -1226,9 +1254,9 @@ int orbx_debug_fast_prof(unsigned long long* out16)
 }
 #endif
 #ifdef ORBX_OCT_TIMING
-int orbx_debug_oct_prof(unsigned long long* out10)
+int orbx_debug_oct_prof(unsigned long long* out11)
 {
-    if (hipMemcpyFromSymbol(out10, HIP_SYMBOL(d_oct_prof), 10 * sizeof(unsigned long long)) != hipSuccess) return ORBX_ERR_HIP;
+    if (hipMemcpyFromSymbol(out11, HIP_SYMBOL(d_oct_prof), 11 * sizeof(unsigned long long)) != hipSuccess) return ORBX_ERR_HIP;
     return ORBX_OK;
 }
 #endif

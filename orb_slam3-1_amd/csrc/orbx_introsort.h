@@ -201,6 +201,25 @@ ORBX_SORT_HD inline void introsort_nodes(SortNode* v, int n, int* stack)
 // `out` receives the sorted array; it doubles as scratch while partitioning (3 ints per element: left stops, right stops,
 // segment bounds).  `rank_tmp`: n shorts.  `stack`: 3 * kIntrosortStack ints.  All four live in the caller's LDS (or an HBM
 // scratch); every lane of the wave must call this with the same arguments.
+//
+// The wave orders its own accesses with wave_mem_fence: the wave may be one of several in its workgroup (k_octree's control wave),
+// so no workgroup barrier may stand here.  LDS operations of one wave execute in order, only the compiler has to be held back;
+// arrays in global memory (GLOBAL) additionally need the wave's stores to have completed before other lanes load them.
+template <bool GLOBAL>
+__device__ __forceinline__ void wave_mem_fence()
+{
+    if constexpr (GLOBAL) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+template <bool GLOBAL = true>
 __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* stack, short* rank_tmp)
 {
     using namespace detail;
@@ -215,7 +234,7 @@ __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* s
         while (last - first > 16) {
             if (depth == 0) {           // __partial_sort(first, last, last): heapsort, one lane (adversarial inputs only)
                 if (lane == 0) heap_sort(v, first, last);
-                __syncthreads();
+                wave_mem_fence<GLOBAL>();
                 break;
             }
             --depth;
@@ -241,9 +260,9 @@ __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* s
                 if (le) posR[nR + __popcll(ml & lt)] = p;           // ascending; the right cursor's k-th stop is posR[nR - 1 - k]
                 nL += __popcll(mg); nR += __popcll(ml);
             }
-            __syncthreads();
+            wave_mem_fence<GLOBAL>();
             if (lane == 0) { v[first] = piv; v[ch] = F; }
-            __syncthreads();
+            wave_mem_fence<GLOBAL>();
             // K = number of swaps; the pairs are monotone (L ascending, R descending), so the test holds on a prefix
             int K = 0, cutL = 0x7fffffff, cutR = 0x7fffffff;
             const int kmax = nL < nR ? nL : nR;
@@ -266,7 +285,7 @@ __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* s
                     v[a] = y; v[b] = x;
                 }
             }
-            __syncthreads();
+            wave_mem_fence<GLOBAL>();
             // __introsort_loop(cut, last, depth) -- later; continue with [first, cut)
             if (sp < kIntrosortStack) { stack_first[sp] = cut; stack_last[sp] = last; stack_depth[sp] = depth; ++sp; }
             last = cut;
@@ -274,11 +293,11 @@ __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* s
         // [first, last) is a leaf: every element's final place lies inside it
         for (int p = first + lane; p < last; p += 64) seg[p] = first | (last << 16);
         if (sp == 0) break;
-        __syncthreads();
+        wave_mem_fence<GLOBAL>();
         --sp;
         first = stack_first[sp]; last = stack_last[sp]; depth = stack_depth[sp];
     }
-    __syncthreads();
+    wave_mem_fence<GLOBAL>();
     // __final_insertion_sort: stable rank inside the leaf
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
@@ -295,9 +314,9 @@ __device__ inline void wave_sort_nodes(SortNode* v, SortNode* out, int n, int* s
         }
         if (i < n) rank_tmp[i] = (short)(lo + rank);
     }
-    __syncthreads();
+    wave_mem_fence<GLOBAL>();
     for (int i = lane; i < n; i += 64) out[rank_tmp[i]] = v[i];
-    __syncthreads();
+    wave_mem_fence<GLOBAL>();
 }
 #endif
 

@@ -4,7 +4,8 @@
 //   k_resize        level l-1 -> l, fixed-point bilinear; k_resize_tail: the upper levels in one launch (E1, ComputePyramid :1170-1195)
 //   k_fast_strips   FAST-9/16 score + per-cell NMS / threshold fallback / ordered compaction, a workgroup per strip of cells
 //                                                                    (E2, ComputeKeyPointsOctTree :787-872)
-//   k_octree        quadtree keypoint selection, one wave per (frame, level), a lane per node within a pass
+//   k_octree        quadtree keypoint selection, a workgroup of 1 / 2 / 4 waves per (frame, level): one control wave, a lane per node
+//                   within a pass; the helper waves share the key partition of large nodes, the gather and the final selection
 //                                                                    (E3, DistributeOctTree :555-779)
 //   k_index         output slot of every keypoint (lapping-area split) (E8, operator() :1140-1167)
 //   k_blur          7x7 sigma-2 Gaussian, Q8.8 fixed point             (E6, :1132-1133)
@@ -186,14 +187,40 @@ __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr,
 #include "orbx_fast_strips.inc"
 
 // ------------------------------------------------------------------------------------------------
-// E3: DistributeOctTree.  One wave per (frame, level).  The std::list of nodes is an index-linked list
+// E3: DistributeOctTree.  One control wave per (frame, level), plus up to three helper waves (see OctJob).  The std::list of nodes is an index-linked list
 // in LDS; a node's keys are a contiguous, order-preserving segment of a ping-pong key array (LDS when
 // the level's candidates fit, HBM scratch otherwise).  A pass of the reference's loops is a batch of up to 64
 // DivideNode calls, a lane per node (see k_octree); std::sort is wave-parallel (orbx_introsort.h).
 // ------------------------------------------------------------------------------------------------
 #ifdef ORBX_OCT_TIMING      // cycle split of the (level 0, frame 0) wave (tools/oct_timing.py); never defined in the product build
-__device__ unsigned long long d_oct_prof[10];
+__device__ unsigned long long d_oct_prof[11];
 #endif
+// A workgroup is W = 1, 2 or 4 waves (the host chooses per launch).  Wave 0 is the CONTROL wave: it runs octree_body and owns all the
+// sequential state.  The other waves are helpers that run oct_helper_loop and nothing else.  Wave 0 hands them the parts of a pass
+// whose items are independent -- the key partition of the nodes the whole wave takes one by one, the initial gather, the final
+// selection -- as JOBS through this LDS record.  Workgroup barriers stand at exactly two points:
+//   A  wave 0 has written the job (oct_post_job)    | the helpers wait here between jobs
+//   B  every wave, wave 0 included, has done its share of the job
+// The record is written by wave 0 only between B and the next A and read by the helpers only between A and B.  Everything else that
+// was a barrier when the workgroup was one wave is a fence of the control wave alone (wave_mem_fence).
+enum { kOctJobExit = 0, kOctJobPartition = 1, kOctJobGather = 2, kOctJobSelect = 3 };
+constexpr int kOctMaxJobs = 1 << 24;    // the helpers' loop bound; wave 0 stops posting one short of it, so that the EXIT job always fits
+struct OctJob {
+    int op, n, lds_keys, pad;
+    int list[64];           // PARTITION: (batch lane << 16) | node id;  GATHER: the first key slot of every block of 64 cells
+    int cnt[4 * 64];        // PARTITION: the four child sizes of the node of batch lane l at cnt[4 l ..]
+};
+struct OctArgs {
+    const LevelDesc* levels; const CellDesc* cells;
+    const uint32_t* cand; size_t cand_frame_stride;
+    const int* cell_count; int n_cells;
+    uint32_t* scratch; size_t scratch_frame_stride;
+    int pool, lds_keys_cap;
+    uint32_t* sel; int sel_frame_stride;
+    int* sel_count; int n_levels; int* status;
+    uint8_t* node_scratch; size_t node_stride; int level_first;
+    int small_max;          // a node of at most this many keys is partitioned by its lane, a larger one by the whole wave(s)
+};
 struct OctLds {
     short* ulx; short* uly; short* brx; short* bry;
     int* beg; int* cnt;
@@ -214,23 +241,248 @@ struct OctLds {
 // child its node slot, its place in the push log and in the next to-expand vector in exactly the order the sequential loop
 // would have produced, and -- in the sorted phase -- the lane at which the running size reaches N (the reference breaks
 // there: later lanes do not divide).
+struct OctMem {
+    OctLds S;
+    SortNode* ex_new;       // the to-expand vector being appended to
+    SortNode* ex_sorted;    // the sorted previous one (and the sort's scratch)
+    uint32_t* kb;           // the two key buffers: kb[0 .. cap) and kb[cap .. 2 cap)
+    int cap;
+};
+
+// carve the node pool and the key buffers of this (frame, level); every wave of the workgroup computes the same pointers
 template <bool LDS_KEYS, bool LDS_NODES>
-__device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
-                                            const uint32_t* __restrict__ cand, size_t cand_frame_stride,
-                                            const int* __restrict__ cell_count, int n_cells,
-                                            uint32_t* __restrict__ scratch, size_t scratch_frame_stride,
-                                            int pool, int lds_keys_cap,
-                                            uint32_t* __restrict__ sel, int sel_frame_stride,
-                                            int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
-                                            uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first,
-                                            uint8_t* __restrict__ smem, int* __restrict__ s_sort_stack)
+__device__ __forceinline__ OctMem oct_carve(const OctArgs& A, const LevelDesc& L, uint8_t* __restrict__ smem)
+{
+    const int pool = A.pool;
+    OctMem M;
+    OctLds& S = M.S;
+    uint8_t* p;
+    if constexpr (LDS_NODES) p = smem;
+    else p = A.node_scratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * A.node_stride;
+    M.ex_new = (SortNode*)p; p += sizeof(SortNode) * pool;
+    M.ex_sorted = (SortNode*)p; p += sizeof(SortNode) * pool;
+    S.beg = (int*)p; p += 4 * pool;
+    S.cnt = (int*)p; p += 4 * pool;
+    S.ulx = (short*)p; p += 2 * pool;  S.uly = (short*)p; p += 2 * pool;
+    S.brx = (short*)p; p += 2 * pool;  S.bry = (short*)p; p += 2 * pool;
+    S.pidx = (int*)p; p += 4 * pool;
+    S.freelist = (short*)p; p += 2 * pool; S.order = (short*)p; p += 2 * pool;
+    S.plog = (short*)p; p += 2 * kOctLogFactor * pool;
+    S.flg = p; p += (pool + 15) & ~15;
+    if constexpr (LDS_KEYS) { M.kb = (uint32_t*)p; M.cap = A.lds_keys_cap; }
+    else { M.kb = A.scratch + (size_t)blockIdx.y * A.scratch_frame_stride + 2 * (size_t)L.cand_off; M.cap = L.cand_cap; }
+    return M;
+}
+
+// what DivideNode needs of the node of this lane
+struct OctNodeBox { int ulx, uly, brx, bry, beg, cnt, src, midx, midy, in_off, out_off; };
+__device__ __forceinline__ OctNodeBox oct_node_box(const OctLds& S, int cap, int id)
+{
+    OctNodeBox b = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (id >= 0) {
+        b.ulx = S.ulx[id]; b.uly = S.uly[id]; b.brx = S.brx[id]; b.bry = S.bry[id];
+        b.beg = S.beg[id]; b.cnt = S.cnt[id]; b.src = (S.flg[id] >> 1) & 1;
+    }
+    const int halfX = (b.brx - b.ulx + 1) >> 1;     // ceil(float(w)/2), w >= 0
+    const int halfY = (b.bry - b.uly + 1) >> 1;
+    b.midx = b.ulx + halfX; b.midy = b.uly + halfY;
+    b.in_off = (b.src ? cap : 0) + b.beg; b.out_off = (b.src ? 0 : cap) + b.beg;
+    return b;
+}
+
+// The whole wave partitions the nodes of the lanes in `mb` (wave-uniform), one node at a time: ballot + prefix popcount, stable.
+// Lane b holds its node's key ranges, key count and mid point; it receives the four child sizes.  The first 64 keys of the NEXT node
+// are read before the current one is consumed (two nodes in flight: a node's ranges of the two buffers are its own, so the early
+// read cannot meet another node's scatter).
+__device__ __forceinline__ void oct_partition_nodes(uint32_t* __restrict__ kb, unsigned long long mb, const int lane, const unsigned long long lt,
+                                                    const int in_off, const int out_off, const int cnt, const int midx, const int midy,
+                                                    int& c0, int& c1, int& c2, int& c3)
+{
+    if (mb == 0ull) return;
+    int b = __builtin_ctzll(mb);
+    int bin = __builtin_amdgcn_readlane(in_off, b), bcnt = __builtin_amdgcn_readlane(cnt, b);
+    uint32_t e = (bcnt <= 64 && lane < bcnt) ? kb[bin + lane] : 0u;
+    for (;;) {
+        const int bout = __builtin_amdgcn_readlane(out_off, b);
+        const int bmx = __builtin_amdgcn_readlane(midx, b), bmy = __builtin_amdgcn_readlane(midy, b);
+        mb &= mb - 1ull;
+        int nb = b, nbin = 0, nbcnt = 0;
+        uint32_t e_next = 0;
+        if (mb != 0ull) {
+            nb = __builtin_ctzll(mb);
+            nbin = __builtin_amdgcn_readlane(in_off, nb); nbcnt = __builtin_amdgcn_readlane(cnt, nb);
+            if (nbcnt <= 64 && lane < nbcnt) e_next = kb[nbin + lane];
+        }
+        int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+        if (bcnt <= 64) {
+            int cls = -1;
+            if (lane < bcnt) cls = ((int)key_x(e) >= bmx ? 1 : 0) + ((int)key_y(e) >= bmy ? 2 : 0);
+            const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2), m3 = __ballot(cls == 3);
+            s0 = __popcll(m0); s1 = __popcll(m1); s2 = __popcll(m2); s3 = __popcll(m3);
+            const unsigned long long mm = (cls == 0) ? m0 : (cls == 1) ? m1 : (cls == 2) ? m2 : m3;
+            const int basec = (cls == 0) ? 0 : (cls == 1) ? s0 : (cls == 2) ? s0 + s1 : s0 + s1 + s2;
+            if (cls >= 0) kb[bout + basec + __popcll(mm & lt)] = e;
+        } else {
+            // pass 1: child sizes (four chunks of 64 keys in flight)
+            for (int k0 = 0; k0 < bcnt; k0 += 256) {
+                uint32_t ev[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int k = k0 + 64 * u + lane; ev[u] = (k < bcnt) ? kb[bin + k] : 0u; }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int k = k0 + 64 * u + lane;
+                    const int cls = (k < bcnt) ? ((int)key_x(ev[u]) >= bmx ? 1 : 0) + ((int)key_y(ev[u]) >= bmy ? 2 : 0) : -1;
+                    s0 += __popcll(__ballot(cls == 0)); s1 += __popcll(__ballot(cls == 1));
+                    s2 += __popcll(__ballot(cls == 2)); s3 += __popcll(__ballot(cls == 3));
+                }
+            }
+            // pass 2: stable scatter into the other buffer
+            int w0 = bout, w1 = bout + s0, w2 = w1 + s1, w3 = w2 + s2;
+            for (int k0 = 0; k0 < bcnt; k0 += 256) {
+                uint32_t ev[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int k = k0 + 64 * u + lane; ev[u] = (k < bcnt) ? kb[bin + k] : 0u; }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int k = k0 + 64 * u + lane;
+                    const int cls = (k < bcnt) ? ((int)key_x(ev[u]) >= bmx ? 1 : 0) + ((int)key_y(ev[u]) >= bmy ? 2 : 0) : -1;
+                    const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2), m3 = __ballot(cls == 3);
+                    const unsigned long long mm = (cls == 0) ? m0 : (cls == 1) ? m1 : (cls == 2) ? m2 : m3;
+                    const int wc = (cls == 0) ? w0 : (cls == 1) ? w1 : (cls == 2) ? w2 : w3;
+                    if (cls >= 0) kb[wc + __popcll(mm & lt)] = ev[u];
+                    w0 += __popcll(m0); w1 += __popcll(m1); w2 += __popcll(m2); w3 += __popcll(m3);
+                }
+            }
+        }
+        if (lane == b) { c0 = s0; c1 = s1; c2 = s2; c3 = s3; }
+        if (mb == 0ull) break;
+        b = nb; bin = nbin; bcnt = nbcnt; e = e_next;
+    }
+}
+
+// ---- a wave's share of a job (wave w of W; wave 0 calls these too)
+// PARTITION: list entries w, w + W, ...; lane l loads the box of entry l, exactly as the control wave's lane did
+__device__ __forceinline__ void oct_job_partition(const OctMem& M, OctJob* __restrict__ J, const int w, const int W, const int lane, const unsigned long long lt)
+{
+    const int n = min(__builtin_amdgcn_readfirstlane(J->n), 64);
+    int id = -1, bl = 0;
+    if (lane < n) { const int v = J->list[lane]; id = v & 0xFFFF; bl = v >> 16; }
+    const OctNodeBox nb = oct_node_box(M.S, M.cap, id);
+    const unsigned long long all = (n >= 64) ? ~0ull : (1ull << n) - 1ull;
+    const unsigned long long stripe = ((W == 4) ? 0x1111111111111111ull : (W == 2) ? 0x5555555555555555ull : ~0ull) << w;
+    const unsigned long long mine = all & stripe;
+    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    oct_partition_nodes(M.kb, mine, lane, lt, nb.in_off, nb.out_off, nb.cnt, nb.midx, nb.midy, c0, c1, c2, c3);
+    if ((mine >> lane) & 1ull) { int* o = J->cnt + 4 * (bl & 63); o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3; }
+}
+
+// GATHER: blocks of 64 cells w, w + W, ...; J->list[block] is the block's first key slot
+__device__ __forceinline__ void oct_gather_block(const LevelDesc& L, const CellDesc* __restrict__ cells, const uint32_t* __restrict__ fc, const int* __restrict__ cc,
+                                                 uint32_t* __restrict__ kb, const int cap, const int c0, const int first, const int lane, int& block_total)
+{
+    const int ci = c0 + lane;
+    int n = 0, slot_off = 0;
+    if (ci < L.cell_count) { n = cc[L.cell_begin + ci]; slot_off = cells[L.cell_begin + ci].slot_off; }
+    const int incl = wave_incl_scan(n);
+    const int base = first + incl - n;
+    if (base < 0 || base + n > cap) n = 0;          // cannot happen (the buffers hold a whole level); reported by the control wave
+    for (int k = 0; __ballot(k < n) != 0ull; k += 8) {
+        uint32_t e[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) e[u] = (k + u < n) ? fc[slot_off + k + u] : 0u;
+#pragma unroll
+        for (int u = 0; u < 8; u++) if (k + u < n) kb[base + k + u] = e[u];
+    }
+    block_total = __builtin_amdgcn_readlane(incl, 63);
+}
+__device__ __forceinline__ void oct_job_gather(const OctArgs& A, const LevelDesc& L, const OctMem& M, const OctJob* __restrict__ J, const int w, const int W, const int lane)
+{
+    const uint32_t* fc = A.cand + (size_t)blockIdx.y * A.cand_frame_stride;
+    const int* cc = A.cell_count + (size_t)blockIdx.y * A.n_cells;
+    const int nblk = min(__builtin_amdgcn_readfirstlane(J->n), 64);
+    for (int blk = w; blk < nblk; blk += W) {
+        int unused;
+        oct_gather_block(L, A.cells, fc, cc, M.kb, M.cap, 64 * blk, __builtin_amdgcn_readfirstlane(J->list[blk]), lane, unused);
+    }
+}
+
+// SELECT: the best-response key of every node, first wins ties (:758-776); blocks of 64 nodes w, w + W, ..., a lane per node
+__device__ __forceinline__ void oct_select_blocks(const OctMem& M, uint32_t* __restrict__ out, const int n_out, const int w, const int W, const int lane)
+{
+    const OctLds& S = M.S;
+    for (int k0 = 64 * w; k0 < n_out; k0 += 64 * W) {
+        const int k = k0 + lane;
+        int off = 0, cnt = 0;
+        if (k < n_out) { const int id = S.order[k]; off = (((S.flg[id] >> 1) & 1) ? M.cap : 0) + S.beg[id]; cnt = S.cnt[id]; }
+        uint32_t best = 0;
+        for (int i = 0; __ballot(i < cnt) != 0ull; i += 4) {
+            uint32_t e[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) e[u] = (i + u < cnt) ? M.kb[off + i + u] : 0u;
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (i + u < cnt && (i + u == 0 || key_resp(e[u]) > key_resp(best))) best = e[u];
+        }
+        if (k < n_out) out[k] = best;
+    }
+}
+
+template <bool LDS_KEYS, bool LDS_NODES>
+__device__ __forceinline__ void oct_do_job(const int op, const OctArgs& A, const LevelDesc& L, uint8_t* __restrict__ smem, OctJob* __restrict__ J,
+                                           const int w, const int W, const int lane, const unsigned long long lt)
+{
+    const OctMem M = oct_carve<LDS_KEYS, LDS_NODES>(A, L, smem);
+    if (op == kOctJobPartition) oct_job_partition(M, J, w, W, lane, lt);
+    else if (op == kOctJobGather) oct_job_gather(A, L, M, J, w, W, lane);
+    else if (op == kOctJobSelect)
+        oct_select_blocks(M, A.sel + (size_t)blockIdx.y * A.sel_frame_stride + L.sel_off, min(__builtin_amdgcn_readfirstlane(J->n), L.sel_cap), w, W, lane);
+}
+
+// The helpers' whole life: wait at A, leave on EXIT, do the share, meet at B.  KEYS: 0 scratch, 1 LDS, 2 as the job says (k_octree_dyn:
+// the control wave chose the body).  The loop bound is a backstop only: wave 0 posts fewer than kOctMaxJobs jobs, EXIT included.
+template <int KEYS, bool LDS_NODES>
+__device__ __forceinline__ void oct_helper_loop(const OctArgs& A, uint8_t* __restrict__ smem, OctJob* __restrict__ J, const int w, const int W)
+{
+    const LevelDesc L = A.levels[A.level_first + blockIdx.x];
+    const int lane = (int)(threadIdx.x & 63u);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int j = 0; j < kOctMaxJobs; j++) {
+        __syncthreads();                                    // A
+        const int op = __builtin_amdgcn_readfirstlane(J->op);
+        if (op == kOctJobExit) break;
+        if constexpr (KEYS == 2) {
+            if (__builtin_amdgcn_readfirstlane(J->lds_keys) != 0) oct_do_job<true, true>(op, A, L, smem, J, w, W, lane, lt);
+            else oct_do_job<false, true>(op, A, L, smem, J, w, W, lane, lt);
+        } else {
+            oct_do_job<KEYS == 1, LDS_NODES>(op, A, L, smem, J, w, W, lane, lt);
+        }
+        __syncthreads();                                    // B
+    }
+}
+
+// wave 0 posts a job: barrier A.  (Wave 0 calls this in wave-uniform control flow only.)
+__device__ __forceinline__ void oct_post_job(OctJob* __restrict__ J, const int op, const int n, const int lds_keys, const int lane, int& jobs)
+{
+    if (lane == 0) { J->op = op; J->n = n; J->lds_keys = lds_keys; }
+    jobs++;
+    __syncthreads();                                        // A
+}
+
+// The control wave.  Returns on every exit path; the caller posts the EXIT job.
+template <bool LDS_KEYS, bool LDS_NODES>
+__device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restrict__ smem, int* __restrict__ s_sort_stack, OctJob* __restrict__ J, const int W, int& jobs)
 {
     static_assert(LDS_NODES || !LDS_KEYS, "a pool too large for LDS leaves no room for LDS keys");
-    const int level = level_first + blockIdx.x, frame = blockIdx.y;     // (a launch covers the levels level_first ..: see enqueue())
+    const LevelDesc* __restrict__ levels = A.levels; const CellDesc* __restrict__ cells = A.cells;
+    const int pool = A.pool, n_levels = A.n_levels;
+    int* __restrict__ status = A.status;
+    const int level = A.level_first + blockIdx.x, frame = blockIdx.y;     // (a launch covers the levels level_first ..: see enqueue())
     const int lane = threadIdx.x;
     const LevelDesc L = levels[level];
     const int N = L.nfeat;
     const unsigned long long lt = (1ull << lane) - 1ull;
+    // this wave's own ordering of what its lanes write and other lanes read: never a workgroup barrier (the helpers are not here)
+    auto fence = [] { wave_mem_fence<!(LDS_KEYS && LDS_NODES)>(); };
+    auto can_post = [&] { return W > 1 && jobs < kOctMaxJobs - 1; };
 #ifdef ORBX_OCT_TIMING
     long long tq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const bool timed = level == 0 && frame == 0 && lane == 0;
@@ -242,56 +494,48 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
 #define ORBX_OTICK(k)
 #endif
 
-    // carve the node pool
-    OctLds S;
-    uint8_t* p;
-    if constexpr (LDS_NODES) p = smem;
-    else p = node_scratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * node_stride;
-    SortNode* const ex_new = (SortNode*)p; p += sizeof(SortNode) * pool;    // the to-expand vector being appended to
-    SortNode* const ex_sorted = (SortNode*)p; p += sizeof(SortNode) * pool; // the sorted previous one (and the sort's scratch)
-    S.beg = (int*)p; p += 4 * pool;
-    S.cnt = (int*)p; p += 4 * pool;
-    S.ulx = (short*)p; p += 2 * pool;  S.uly = (short*)p; p += 2 * pool;
-    S.brx = (short*)p; p += 2 * pool;  S.bry = (short*)p; p += 2 * pool;
-    S.pidx = (int*)p; p += 4 * pool;
-    S.freelist = (short*)p; p += 2 * pool; S.order = (short*)p; p += 2 * pool;
-    S.plog = (short*)p; p += 2 * kOctLogFactor * pool;
-    S.flg = p; p += (pool + 15) & ~15;
-    // the two key buffers: kb[0 .. cap) and kb[cap .. 2 cap)
-    uint32_t* kb;
-    int cap;
-    if constexpr (LDS_KEYS) { kb = (uint32_t*)p; cap = lds_keys_cap; }
-    else { kb = scratch + (size_t)frame * scratch_frame_stride + 2 * (size_t)L.cand_off; cap = L.cand_cap; }
+    const OctMem M = oct_carve<LDS_KEYS, LDS_NODES>(A, L, smem);
+    const OctLds& S = M.S;
+    SortNode* const ex_new = M.ex_new;
+    SortNode* const ex_sorted = M.ex_sorted;
+    uint32_t* const kb = M.kb;
+    const int cap = M.cap;
 
-    int* out_count = sel_count + (size_t)frame * n_levels + level;
-    uint32_t* out = sel + (size_t)frame * sel_frame_stride + L.sel_off;
+    int* out_count = A.sel_count + (size_t)frame * n_levels + level;
+    uint32_t* out = A.sel + (size_t)frame * A.sel_frame_stride + L.sel_off;
 
     // ---- gather the level's candidates in vToDistributeKeys order (cell row-major, row-major inside a cell): one lane per
     // cell, the in-wave prefix of the cell counts gives each cell its place in the ordered list
-    const uint32_t* fc = cand + (size_t)frame * cand_frame_stride;
-    const int* cc = cell_count + (size_t)frame * n_cells;
+    const uint32_t* fc = A.cand + (size_t)frame * A.cand_frame_stride;
+    const int* cc = A.cell_count + (size_t)frame * A.n_cells;
     int total = 0;
-    for (int c0 = 0; c0 < L.cell_count; c0 += 64) {
-        const int ci = c0 + lane;
-        int n = 0, slot_off = 0;
-        if (ci < L.cell_count) { n = cc[L.cell_begin + ci]; slot_off = cells[L.cell_begin + ci].slot_off; }
-        const int incl = wave_incl_scan(n);
-        const int base = total + incl - n;
-        if (base + n > cap) n = 0;          // cannot happen (the buffers hold a whole level); reported below
-        for (int k = 0; __ballot(k < n) != 0ull; k += 8) {
-            uint32_t e[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) e[u] = (k + u < n) ? fc[slot_off + k + u] : 0u;
-#pragma unroll
-            for (int u = 0; u < 8; u++) if (k + u < n) kb[base + k + u] = e[u];
+    const int n_blocks = (L.cell_count + 63) >> 6;
+    if (can_post() && n_blocks > 1 && n_blocks <= 64) {
+        // the running total per block of 64 cells first, so that every wave knows where its blocks begin
+        for (int blk = 0; blk < n_blocks; blk++) {
+            const int ci = 64 * blk + lane;
+            int n = (ci < L.cell_count) ? cc[L.cell_begin + ci] : 0;
+            for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+            if (lane == 0) J->list[blk] = total;
+            total += __builtin_amdgcn_readfirstlane(n);
         }
-        total += __builtin_amdgcn_readlane(incl, 63);
+        oct_post_job(J, kOctJobGather, n_blocks, LDS_KEYS ? 1 : 0, lane, jobs);
+        oct_job_gather(A, L, M, J, 0, W, lane);
+        ORBX_OTICK(0)
+        __syncthreads();                                    // B
+        ORBX_OTICK(7)
+    } else {
+        for (int c0 = 0; c0 < L.cell_count; c0 += 64) {
+            int block_total;
+            oct_gather_block(L, cells, fc, cc, kb, cap, c0, total, lane, block_total);
+            total += block_total;
+        }
     }
     if (total > cap) {
         if (lane == 0) { atomicExch(status + frame, ORBX_ERR_INTERNAL); *out_count = 0; }
         return;
     }
-    __syncthreads();
+    fence();
     ORBX_OTICK(0)
 
     const int width = (L.w - kEdge + 3) - (kEdge - 3), height = (L.h - kEdge + 3) - (kEdge - 3);
@@ -310,7 +554,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
     const int plog_cap = kOctLogFactor * pool;
     int np = 0, size = 0, nfree = pool, n_ex = 0;
     for (int i = lane; i < pool; i += 64) S.freelist[i] = (short)(pool - 1 - i);
-    __syncthreads();
+    fence();
     bool overflow = false;
     auto compact = [&]() {          // drop tombstones, order preserved (wave-parallel, in place)
         int w = 0;
@@ -322,7 +566,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
             w += __popcll(m);
         }
         np = w;
-        __syncthreads();
+        fence();
     };
 
     // ---- root nodes (:564-586): nIni vertical strips of width hX
@@ -336,7 +580,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
             S.plog[0] = (short)id; S.pidx[id] = 0;
         }
         nfree--; np = 1; size = 1;
-        __syncthreads();
+        fence();
     } else {
         // stable partition of the keys by strip into buffer 1
         int strip_beg = 0;
@@ -364,13 +608,13 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
             if (lane == 0) S.order[s] = (short)id;
             strip_beg += cnt;
         }
-        __syncthreads();
+        fence();
         // the reference push_back()s the roots in strip order; in push-log terms the first strip is pushed last
         for (int s = nIni - 1; s >= 0; s--) {
             const int id = S.order[s];
             if (id >= 0) { if (lane == 0) { S.plog[np] = (short)id; S.pidx[id] = np; } np++; size++; }
         }
-        __syncthreads();
+        fence();
     }
     ORBX_OTICK(1)
 
@@ -379,20 +623,21 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
     // whether that happened.
     auto divide_batch = [&](const int id, const bool sorted_phase, int& n_to_expand) -> bool {
         const bool act = id >= 0;
-        int ulx = 0, uly = 0, brx = 0, bry = 0, beg = 0, cnt = 0, src = 0;
-        if (act) {
-            ulx = S.ulx[id]; uly = S.uly[id]; brx = S.brx[id]; bry = S.bry[id];
-            beg = S.beg[id]; cnt = S.cnt[id]; src = (S.flg[id] >> 1) & 1;
-        }
-        const int halfX = (brx - ulx + 1) >> 1;     // ceil(float(w)/2), w >= 0
-        const int halfY = (bry - uly + 1) >> 1;
-        const int midx = ulx + halfX, midy = uly + halfY;
-        const int in_off = (src ? cap : 0) + beg, out_off = (src ? 0 : cap) + beg;
+        const OctNodeBox nb = oct_node_box(S, cap, id);
+        const int ulx = nb.ulx, uly = nb.uly, brx = nb.brx, bry = nb.bry, beg = nb.beg, cnt = nb.cnt, src = nb.src;
+        const int midx = nb.midx, midy = nb.midy, in_off = nb.in_off, out_off = nb.out_off;
         // Scattering a node's keys into the other buffer is harmless when the node ends up not being divided (its range of
         // the other buffer is dead space of its own), so counting and scattering do not wait for the cut.
         const unsigned long long m_act = __ballot(act);
-        const int small_max = (__popcll(m_act) <= 6) ? 0 : 32;       // a handful of nodes: the whole wave takes them one by one
+        const int small_max = (__popcll(m_act) <= 6) ? 0 : A.small_max;       // a handful of nodes: the whole wave takes them one by one
         const bool small = act && cnt <= small_max;
+        // the nodes the whole wave takes one by one: with helpers, and more than one such node, they are a PARTITION job
+        const unsigned long long m_big = __ballot(act && !small);
+        const bool job = __popcll(m_big) > 1 && can_post();
+        if (job) {
+            if (act && !small) J->list[__popcll(m_big & lt)] = (lane << 16) | id;
+            oct_post_job(J, kOctJobPartition, __popcll(m_big), LDS_KEYS ? 1 : 0, lane, jobs);
+        }
         int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
         if (__ballot(small) != 0ull) {
             // a lane per node: count, then stable scatter
@@ -422,55 +667,15 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
                 }
             }
         }
-        for (unsigned long long mb = __ballot(act && !small); mb != 0ull; mb &= mb - 1ull) {
-            // the wave per node: ballot + prefix popcount
-            const int b = __builtin_ctzll(mb);
-            const int bin = __builtin_amdgcn_readlane(in_off, b), bout = __builtin_amdgcn_readlane(out_off, b);
-            const int bcnt = __builtin_amdgcn_readlane(cnt, b);
-            const int bmx = __builtin_amdgcn_readlane(midx, b), bmy = __builtin_amdgcn_readlane(midy, b);
-            int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-            if (bcnt <= 64) {
-                int cls = -1;
-                uint32_t e = 0;
-                if (lane < bcnt) { e = kb[bin + lane]; cls = ((int)key_x(e) >= bmx ? 1 : 0) + ((int)key_y(e) >= bmy ? 2 : 0); }
-                const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2), m3 = __ballot(cls == 3);
-                s0 = __popcll(m0); s1 = __popcll(m1); s2 = __popcll(m2); s3 = __popcll(m3);
-                const unsigned long long mm = (cls == 0) ? m0 : (cls == 1) ? m1 : (cls == 2) ? m2 : m3;
-                const int basec = (cls == 0) ? 0 : (cls == 1) ? s0 : (cls == 2) ? s0 + s1 : s0 + s1 + s2;
-                if (cls >= 0) kb[bout + basec + __popcll(mm & lt)] = e;
-            } else {
-                // pass 1: child sizes (four chunks of 64 keys in flight)
-                for (int k0 = 0; k0 < bcnt; k0 += 256) {
-                    uint32_t e[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const int k = k0 + 64 * u + lane; e[u] = (k < bcnt) ? kb[bin + k] : 0u; }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int k = k0 + 64 * u + lane;
-                        const int cls = (k < bcnt) ? ((int)key_x(e[u]) >= bmx ? 1 : 0) + ((int)key_y(e[u]) >= bmy ? 2 : 0) : -1;
-                        s0 += __popcll(__ballot(cls == 0)); s1 += __popcll(__ballot(cls == 1));
-                        s2 += __popcll(__ballot(cls == 2)); s3 += __popcll(__ballot(cls == 3));
-                    }
-                }
-                // pass 2: stable scatter into the other buffer
-                int w0 = bout, w1 = bout + s0, w2 = w1 + s1, w3 = w2 + s2;
-                for (int k0 = 0; k0 < bcnt; k0 += 256) {
-                    uint32_t e[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const int k = k0 + 64 * u + lane; e[u] = (k < bcnt) ? kb[bin + k] : 0u; }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int k = k0 + 64 * u + lane;
-                        const int cls = (k < bcnt) ? ((int)key_x(e[u]) >= bmx ? 1 : 0) + ((int)key_y(e[u]) >= bmy ? 2 : 0) : -1;
-                        const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2), m3 = __ballot(cls == 3);
-                        const unsigned long long mm = (cls == 0) ? m0 : (cls == 1) ? m1 : (cls == 2) ? m2 : m3;
-                        const int wc = (cls == 0) ? w0 : (cls == 1) ? w1 : (cls == 2) ? w2 : w3;
-                        if (cls >= 0) kb[wc + __popcll(mm & lt)] = e[u];
-                        w0 += __popcll(m0); w1 += __popcll(m1); w2 += __popcll(m2); w3 += __popcll(m3);
-                    }
-                }
-            }
-            if (lane == b) { c0 = s0; c1 = s1; c2 = s2; c3 = s3; }
+        if (job) {
+            // (the lane-per-node loops above ran beside the helpers' share)
+            oct_job_partition(M, J, 0, W, lane, lt);
+            ORBX_OTICK(2)
+            __syncthreads();                                // B
+            ORBX_OTICK(7)
+            if (act && !small) { const int* o = J->cnt + 4 * lane; c0 = o[0]; c1 = o[1]; c2 = o[2]; c3 = o[3]; }
+        } else {
+            oct_partition_nodes(kb, m_big, lane, lt, in_off, out_off, cnt, midx, midy, c0, c1, c2, c3);
         }
         ORBX_OTICK(2)
 
@@ -515,7 +720,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
                 }
                 S.plog[S.pidx[id]] = -1;        // erase the parent
             }
-            __syncthreads();                    // the free-list reads above come before the writes below
+            fence();                    // the free-list reads above come before the writes below
             np += tot_e; size += tot_e - tot_a; nfree -= tot_e;
             if (take) S.freelist[nfree + incl_a - 1] = (short)id;
             nfree += tot_a;
@@ -524,7 +729,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
             n_div += tot_a;
 #endif
             rem &= ~m_take;
-            __syncthreads();        // key scatter and node records visible before the next round / batch reads them
+            fence();        // key scatter and node records visible before the next round / batch reads them
         }
         ORBX_OTICK(3)
         return reached;
@@ -553,7 +758,7 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
                 compact();
                 const int n_prev = min(n_ex, pool);
                 ORBX_OTICK(4)
-                wave_sort_nodes(ex_new, ex_sorted, n_prev, s_sort_stack, S.order);     // std::sort(..., compareNodes) (:700)
+                wave_sort_nodes<!LDS_NODES>(ex_new, ex_sorted, n_prev, s_sort_stack, S.order);     // std::sort(..., compareNodes) (:700)
                 ORBX_OTICK(5)
                 n_ex = 0;
                 int dummy = 0;
@@ -575,21 +780,16 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
     // ---- final list order, then the best-response key of every node, first wins ties (:758-776)
     compact();
     for (int k = lane; k < np && k < pool; k += 64) S.order[k] = S.plog[np - 1 - k];
-    __syncthreads();
+    fence();
     const int n_out = min(size, L.sel_cap);
-    for (int k0 = 0; k0 < n_out; k0 += 64) {
-        const int k = k0 + lane;
-        int off = 0, cnt = 0;
-        if (k < n_out) { const int id = S.order[k]; off = (((S.flg[id] >> 1) & 1) ? cap : 0) + S.beg[id]; cnt = S.cnt[id]; }
-        uint32_t best = 0;
-        for (int i = 0; __ballot(i < cnt) != 0ull; i += 4) {
-            uint32_t e[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) e[u] = (i + u < cnt) ? kb[off + i + u] : 0u;
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (i + u < cnt && (i + u == 0 || key_resp(e[u]) > key_resp(best))) best = e[u];
-        }
-        if (k < n_out) out[k] = best;
+    if (n_out > 64 && can_post()) {
+        oct_post_job(J, kOctJobSelect, n_out, LDS_KEYS ? 1 : 0, lane, jobs);
+        oct_select_blocks(M, out, n_out, 0, W, lane);
+        ORBX_OTICK(6)
+        __syncthreads();                                    // B
+        ORBX_OTICK(7)
+    } else {
+        oct_select_blocks(M, out, n_out, 0, 1, lane);
     }
     if (lane == 0) {
         *out_count = n_out;
@@ -599,56 +799,65 @@ __device__ __forceinline__ void octree_body(const LevelDesc* __restrict__ levels
 #ifdef ORBX_OCT_TIMING
     if (timed) {
         for (int i = 0; i < 7; i++) d_oct_prof[i] = (unsigned long long)tq[i];
+        d_oct_prof[10] = (unsigned long long)tq[7];         // waiting at the job barriers
         d_oct_prof[7] = (unsigned long long)(clock64() - t_kernel0);
         d_oct_prof[8] = (unsigned long long)total; d_oct_prof[9] = (unsigned long long)n_div;
     }
 #endif
 }
 
+// Launched with W x 64 threads.  Wave 0 runs the body and then posts EXIT -- at ONE place, whichever way the body returned; the other
+// waves run the helpers' loop.  With W = 1 no job is ever posted and no workgroup barrier is executed.
 template <bool LDS_KEYS, bool LDS_NODES = true>
-__global__ __launch_bounds__(64) void k_octree(const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
-                                               const uint32_t* __restrict__ cand, size_t cand_frame_stride,
-                                               const int* __restrict__ cell_count, int n_cells,
-                                               uint32_t* __restrict__ scratch, size_t scratch_frame_stride,
-                                               int pool, int lds_keys_cap,
-                                               uint32_t* __restrict__ sel, int sel_frame_stride,
-                                               int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
-                                               uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first)
+__global__ __launch_bounds__(256) void k_octree(const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
+    const uint32_t* __restrict__ cand, size_t cand_frame_stride, const int* __restrict__ cell_count, int n_cells,
+    uint32_t* __restrict__ scratch, size_t scratch_frame_stride, int pool, int lds_keys_cap,
+    uint32_t* __restrict__ sel, int sel_frame_stride, int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
+    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_sort_stack[3 * kIntrosortStack];       // the sort's explicit stack (in LDS, not in private scratch)
-    octree_body<LDS_KEYS, LDS_NODES>(levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
-                                     sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, smem, s_sort_stack);
+    __shared__ OctJob s_job;
+    const OctArgs A = {levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
+                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max};
+    const int W = (int)(blockDim.x >> 6);                                   // 1, 2 or 4 waves (the host's choice per launch)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave != 0) { oct_helper_loop<LDS_KEYS ? 1 : 0, LDS_NODES>(A, smem, &s_job, wave, W); return; }
+    int jobs = 0;
+    octree_body<LDS_KEYS, LDS_NODES>(A, smem, s_sort_stack, &s_job, W, jobs);
+    if (W > 1) oct_post_job(&s_job, kOctJobExit, 0, 0, (int)threadIdx.x, jobs);
 }
 
 // Small batches (a single frame: the reference's own use) are bound by the latency of the level-0 wave, and a level's key buffers are
 // SIZED for the 3x3-NMS worst case (a quarter of the pixels: 614 KB for two buffers at 640 x 480) while a real level holds a few
 // thousand candidates.  This kernel counts the level's candidates first and takes the keys-in-LDS body when they fit the LDS it was
 // given (no L2 round trip per key-partition step: 0.079 -> 0.062 ms for the octree of one 320 x 200 frame), the scratch body otherwise;
-// both bodies are compiled in, each with its own static addressing (no flat accesses).
-__global__ __launch_bounds__(64) void k_octree_dyn(const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
-                                                   const uint32_t* __restrict__ cand, size_t cand_frame_stride,
-                                                   const int* __restrict__ cell_count, int n_cells,
-                                                   uint32_t* __restrict__ scratch, size_t scratch_frame_stride,
-                                                   int pool, int lds_keys_cap,
-                                                   uint32_t* __restrict__ sel, int sel_frame_stride,
-                                                   int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
-                                                   uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first)
+// both bodies are compiled in, each with its own static addressing (no flat accesses).  The control wave alone counts and chooses;
+// every job tells the helpers which key home it is about.
+__global__ __launch_bounds__(256) void k_octree_dyn(const LevelDesc* __restrict__ levels, const CellDesc* __restrict__ cells,
+    const uint32_t* __restrict__ cand, size_t cand_frame_stride, const int* __restrict__ cell_count, int n_cells,
+    uint32_t* __restrict__ scratch, size_t scratch_frame_stride, int pool, int lds_keys_cap,
+    uint32_t* __restrict__ sel, int sel_frame_stride, int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
+    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_sort_stack[3 * kIntrosortStack];
+    __shared__ OctJob s_job;
+    const OctArgs A = {levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
+                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max};
+    const int W = (int)(blockDim.x >> 6);                                   // 1, 2 or 4 waves (the host's choice per launch)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave != 0) { oct_helper_loop<2, true>(A, smem, &s_job, wave, W); return; }
     const LevelDesc L = levels[level_first + blockIdx.x];
     const int* cc = cell_count + (size_t)blockIdx.y * n_cells + L.cell_begin;
     int total = 0;
     for (int ci = threadIdx.x; ci < L.cell_count; ci += 64) total += cc[ci];
     for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
     total = __builtin_amdgcn_readfirstlane(total);
-    if (total <= lds_keys_cap)
-        octree_body<true, true>(levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
-                                sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, smem, s_sort_stack);
-    else
-        octree_body<false, true>(levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
-                                 sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, smem, s_sort_stack);
+    int jobs = 0;
+    if (total <= lds_keys_cap) octree_body<true, true>(A, smem, s_sort_stack, &s_job, W, jobs);
+    else octree_body<false, true>(A, smem, s_sort_stack, &s_job, W, jobs);
+    if (W > 1) oct_post_job(&s_job, kOctJobExit, 0, 0, (int)threadIdx.x, jobs);
 }
 
 // test hook: wave_sort_nodes on one array (orbx_debug_wave_sort)

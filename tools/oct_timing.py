@@ -14,9 +14,10 @@ synth = importlib.import_module("orb_slam3-1_amd.synth")
 ex = pkg.Extractor()
 img = synth.make_frame(0)
 ex(img); ex(img)
-out = (C.c_ulonglong * 10)()
+out = (C.c_ulonglong * 11)()
 pkg.lib.orbx_debug_oct_prof(out)
 v = list(out)
 names = ["gather", "roots", "count+scatter", "bookkeeping", "compact/other", "sort", "final selection"]
 print("level-0 wave: %d cycles, %d candidates, %d divides" % (v[7], v[8], v[9]))
 print("  " + ", ".join("%s %d" % (n, c) for n, c in zip(names, v[:7])))
+print("  waiting at the job barriers %d (control wave, %d waves per workgroup)" % (v[10], ex.debug_octree_waves(1)))

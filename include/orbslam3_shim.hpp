@@ -608,9 +608,25 @@ inline bool LbaWindowIsPinhole(KeyFrame* pKF)
     return true;
 }
 
+// the edge of one observation by a conventional camera (:1302-1364): monocular, or stereo where mvuRight >= 0
+inline void LbaConventionalEdge(KeyFrame* pKFi, MapPoint* pMP, const std::tuple<int, int>& idx, LbaGraph& g)
+{
+    const int leftIndex = std::get<0>(idx);
+    if (leftIndex == -1) return;
+    const cv::KeyPoint& kpUn = pKFi->mvKeysUn[leftIndex];
+    const float ur = pKFi->mvuRight[leftIndex];
+    g.ePoint.push_back(g.mpIndex.at(pMP)); g.ePose.push_back(g.kfIndex.at(pKFi));      // .at(): an observer outside the window is a bug, not vertex 0
+    orbslam3_hip::push_edge_obs(kpUn, ur, g.eObs, g.eStereo);
+    g.eW.push_back((double)pKFi->mvInvLevelSigma2[kpUn.octave]);
+    g.eKF.push_back(pKFi); g.eMP.push_back(pMP);
+    g.fx = pKFi->fx; g.fy = pKFi->fy; g.cx = pKFi->cx; g.cy = pKFi->cy; g.bf = pKFi->mbf;
+}
+
 // src/Optimizer.cc:1118-1404.  Returns false on the reference's silent early return (no fixed key frame, :1182-1186); the
-// counters are then what the reference leaves in its out-parameters at that point.
-inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g)
+// counters are then what the reference leaves in its out-parameters at that point.  add_edges(pKFi, pMP, indices, g) appends the
+// edges of one observation: LbaConventionalEdge, or the left and right edges of a rig key frame (orbslam3_shim_rig.hpp).
+template <class EdgeFn>
+inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g, EdgeFn add_edges)
 {
     g.lLocalKeyFrames.push_back(pKF);
     pKF->mnBALocalForKF = pKF->mnId;
@@ -662,23 +678,17 @@ inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g)
         for (auto& obs : pMP->GetObservations()) {
             KeyFrame* pKFi = obs.first;
             if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;
-            const int leftIndex = std::get<0>(obs.second);
-            if (leftIndex == -1) continue;
-            const cv::KeyPoint& kpUn = pKFi->mvKeysUn[leftIndex];
-            const float ur = pKFi->mvuRight[leftIndex];
-            g.ePoint.push_back(g.mpIndex.at(pMP)); g.ePose.push_back(g.kfIndex.at(pKFi));      // .at(): an observer outside the window is a bug, not vertex 0
-            orbslam3_hip::push_edge_obs(kpUn, ur, g.eObs, g.eStereo);
-            g.eW.push_back((double)pKFi->mvInvLevelSigma2[kpUn.octave]);
-            g.eKF.push_back(pKFi); g.eMP.push_back(pMP);
-            g.fx = pKFi->fx; g.fy = pKFi->fy; g.cx = pKFi->cx; g.cy = pKFi->cy; g.bf = pKFi->mbf;
+            add_edges(pKFi, pMP, obs.second, g);
         }
     g.num_edges = (int)g.ePoint.size();                                             // :1404
     return true;
 }
+inline bool LocalBundleAdjustmentGraph(KeyFrame* pKF, Map* pMap, LbaGraph& g) { return LocalBundleAdjustmentGraph(pKF, pMap, g, LbaConventionalEdge); }
 
 // The steps after the walk (:1406-1497), for a pinhole window (cam == nullptr) and for a window of one monocular KannalaBrandt8
 // camera (orbslam3_shim_kb8.hpp) alike: the problem and the solve with the camera set around it, the write-back, and
-// LocalBundleAdjustmentFinish, which sets the counters and runs the two.
+// LocalBundleAdjustmentFinish, which sets the counters and runs the two.  A window of a two-camera rig (orbslam3_shim_rig.hpp) comes
+// here with cam == nullptr, rig == true, eStereo holding 0 or ORBX_EDGE_RIGHT, and its rig already set on this thread's handle.
 inline void LocalBundleAdjustmentSolve(const LbaGraph& g, bool* pbStopFlag, Map* pMap, const OrbxKB8* cam, std::vector<double>& qo, std::vector<double>& to,
                                        std::vector<double>& Xo, std::vector<double>& chi2, std::vector<uint8_t>& depthPos)
 {
@@ -694,13 +704,15 @@ inline void LocalBundleAdjustmentSolve(const LbaGraph& g, bool* pbStopFlag, Map*
 }
 
 inline void LocalBundleAdjustmentWriteBack(const LbaGraph& g, Map* pMap, const std::vector<double>& qo, const std::vector<double>& to, const std::vector<double>& Xo,
-                                           const std::vector<double>& chi2, const std::vector<uint8_t>& depthPos)
+                                           const std::vector<double>& chi2, const std::vector<uint8_t>& depthPos, bool rig = false)
 {
     std::vector<std::pair<KeyFrame*, MapPoint*> > vToErase;                         // :1413-1460 (a KB8 window has no stereo edge)
-    for (int e = 0; e < g.num_edges; e++) {
-        if (g.eMP[e]->isBad()) continue;
-        if (chi2[e] > (g.eStereo[e] ? 7.815 : 5.991) || !depthPos[e]) vToErase.push_back(std::make_pair(g.eKF[e], g.eMP[e]));
-    }
+    for (int pass = 0; pass < (rig ? 2 : 1); pass++)                                // a rig: the left edges, then the right ones (:1417-1445), all against 5.991
+        for (int e = 0; e < g.num_edges; e++) {
+            if (rig && (g.eStereo[e] != 0) != (pass == 1)) continue;
+            if (g.eMP[e]->isBad()) continue;
+            if (chi2[e] > (!rig && g.eStereo[e] ? 7.815 : 5.991) || !depthPos[e]) vToErase.push_back(std::make_pair(g.eKF[e], g.eMP[e]));
+        }
     std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                       // :1464
     for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
     for (KeyFrame* pKFi : g.lLocalKeyFrames) {
@@ -715,7 +727,8 @@ inline void LocalBundleAdjustmentWriteBack(const LbaGraph& g, Map* pMap, const s
 }
 
 // ok = what LocalBundleAdjustmentGraph returned for g
-inline void LocalBundleAdjustmentFinish(const LbaGraph& g, bool ok, bool* pbStopFlag, Map* pMap, const OrbxKB8* cam, int& num_fixedKF, int& num_OptKF, int& num_edges)
+inline void LocalBundleAdjustmentFinish(const LbaGraph& g, bool ok, bool* pbStopFlag, Map* pMap, const OrbxKB8* cam, int& num_fixedKF, int& num_OptKF, int& num_edges,
+                                        bool rig = false)
 {
     num_fixedKF = g.num_fixedKF;                                                    // num_MPs is never assigned by the reference overload either
     if (!ok) return;                                                                // :1182-1186: the other counters keep the caller's values
@@ -724,7 +737,7 @@ inline void LocalBundleAdjustmentFinish(const LbaGraph& g, bool ok, bool* pbStop
     std::vector<double> qo, to, Xo, chi2;
     std::vector<uint8_t> depthPos;
     LocalBundleAdjustmentSolve(g, pbStopFlag, pMap, cam, qo, to, Xo, chi2, depthPos);
-    LocalBundleAdjustmentWriteBack(g, pMap, qo, to, Xo, chi2, depthPos);
+    LocalBundleAdjustmentWriteBack(g, pMap, qo, to, Xo, chi2, depthPos, rig);
 }
 
 inline void LocalBundleAdjustmentHIP(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges)
@@ -1213,7 +1226,8 @@ inline void PoseOptimizationFlatten(Frame* pFrame, PoseGraph& g)
 }
 
 // cam: the frame's one monocular KannalaBrandt8 camera (orbslam3_shim_kb8.hpp), set on the handle around the call; nullptr: the pinhole
-// parameters of the frame.  outlier has one entry per edge of g, and one to spare.
+// parameters of the frame -- or a frame of a two-camera rig (orbslam3_shim_rig.hpp), whose rig is already set on this thread's handle and
+// whose g.stereo holds 0 or ORBX_EDGE_RIGHT.  outlier has one entry per edge of g, and one to spare.
 inline void PoseOptimizationSolve(Frame* pFrame, const PoseGraph& g, const OrbxKB8* cam, PoseResult& res, std::vector<uint8_t>& outlier)
 {
     PoseProblem pr;

@@ -25,16 +25,20 @@ inline T* thread_handle()
     return h;
 }
 
-// Sets a KannalaBrandt8 camera on a handle for the lifetime of the object; with cam == nullptr nothing is set and the handle keeps
+// Sets a KannalaBrandt8 camera (or a rig of two: RigScope) on a handle for the lifetime of the object; with cam == nullptr nothing is set and the handle keeps
 // its pinhole model.  The reset must happen on every way out (check() throws).
-template <class Handle, int (*Set)(Handle*, const OrbxKB8*)>
-struct CameraScope {
+template <class Handle, class Cam, int (*Set)(Handle*, const Cam*)>
+struct CameraScopeOf {
     Handle* h;
-    CameraScope(Handle* h_, const OrbxKB8* cam) : h(cam ? h_ : nullptr) { if (h) check(Set(h, cam)); }
-    ~CameraScope() { if (h) (void)Set(h, nullptr); }
-    CameraScope(const CameraScope&) = delete;
-    CameraScope& operator=(const CameraScope&) = delete;
+    CameraScopeOf(Handle* h_, const Cam* cam) : h(cam ? h_ : nullptr) { if (h) check(Set(h, cam)); }
+    ~CameraScopeOf() { if (h) (void)Set(h, nullptr); }
+    CameraScopeOf(const CameraScopeOf&) = delete;
+    CameraScopeOf& operator=(const CameraScopeOf&) = delete;
 };
+template <class Handle, int (*Set)(Handle*, const OrbxKB8*)>
+using CameraScope = CameraScopeOf<Handle, OrbxKB8, Set>;            // one KannalaBrandt8 camera (*_set_camera_kb8)
+template <class Handle, int (*Set)(Handle*, const OrbxKB8Rig*)>
+using RigScope = CameraScopeOf<Handle, OrbxKB8Rig, Set>;            // a rig of two (*_set_rig_kb8)
 
 // Tcw -> q[4] (x y z w), t[3]: cast to double component by component, as g2o::SE3Quat is built from the float pose
 inline void pose_in(const Sophus::SE3f& Tcw, double* q, double* t)
@@ -154,6 +158,17 @@ inline OrbxFisheyeRig fisheye_rig_in(Fisheye* left, Fisheye* right, const Sophus
     const Eigen::Matrix3f R = Tlr.rotationMatrix();
     const Eigen::Vector3f t = Tlr.translation();
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) rig.Rlr[3 * r + c] = R(r, c); rig.tlr[r] = t(r); }
+    return rig;
+}
+
+// A two-camera fisheye rig as an OrbxKB8Rig: the eight parameters of each camera and Trl as the g2o::SE3Quat the reference builds
+// from it (Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>(), src/Optimizer.cc:984, :1388-1389)
+template <class Fisheye>
+inline OrbxKB8Rig kb8_rig_in(Fisheye* left, Fisheye* right, const Sophus::SE3f& Trl)
+{
+    OrbxKB8Rig rig;
+    kb8_in(left, rig.left); kb8_in(right, rig.right);
+    pose_in(Trl, rig.q_rl, rig.t_rl);
     return rig;
 }
 

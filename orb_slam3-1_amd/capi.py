@@ -762,6 +762,27 @@ def _set_camera_kb8(fn, handle, cam):
     _check(fn(handle, C.byref(_kb8(cam)) if cam is not None else None))
 
 
+class OrbxKB8Rig(C.Structure):
+    """OrbxKB8Rig of include/orbslam3_hip_kb8.h: mpCamera, mpCamera2 and GetRelativePoseTrl() as a g2o::SE3Quat (q xyzw, t)"""
+    _fields_ = [("left", OrbxKB8), ("right", OrbxKB8), ("q_rl", C.c_double * 4), ("t_rl", C.c_double * 3)]
+
+
+EDGE_RIGHT = 2      # ORBX_EDGE_RIGHT: the stereo byte of a right-camera edge while a rig is set
+
+
+def _kb8_rig(rig):
+    """dict(left, right (as _kb8 takes them), q_rl (xyzw), t_rl) -> OrbxKB8Rig"""
+    r = OrbxKB8Rig(_kb8(rig["left"]), _kb8(rig["right"]))
+    r.q_rl[:] = [float(v) for v in rig["q_rl"]]
+    r.t_rl[:] = [float(v) for v in rig["t_rl"]]
+    return r
+
+
+def _set_rig_kb8(fn, handle, rig):
+    fn.argtypes = [C.c_void_p, C.POINTER(OrbxKB8Rig)]
+    _check(fn(handle, C.byref(_kb8_rig(rig)) if rig is not None else None))
+
+
 def kb8_project(cam, Xc, want_jac=True, device=0):
     """orbx_kb8_project: KannalaBrandt8::project (and projectJac, 2 x 3 row-major) of camera-frame points on the device"""
     lib.orbx_kb8_project.argtypes = [C.c_int, C.POINTER(OrbxKB8), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -862,6 +883,10 @@ class LbaSolver:
         """lba_set_camera_kb8: dict(fx, fy, cx, cy, k) or None (back to the pinhole camera of the windows)"""
         _set_camera_kb8(lib.lba_set_camera_kb8, self._h, cam)
 
+    def set_rig_kb8(self, rig):
+        """lba_set_rig_kb8: dict(left, right, q_rl, t_rl) or None (back to the pinhole camera); edge_stereo then holds 0 or EDGE_RIGHT"""
+        _set_rig_kb8(lib.lba_set_rig_kb8, self._h, rig)
+
     def solve(self, w, max_iters=10, lambda_init=0.0, stop_flag=None):
         pr = _lba_problem(w)
         k = pr._keep
@@ -904,6 +929,10 @@ class LbaBatch:
     def set_camera_kb8(self, cam):
         """lba_batch_set_camera_kb8: one fisheye camera for every window of a call, or None"""
         _set_camera_kb8(lib.lba_batch_set_camera_kb8, self._h, cam)
+
+    def set_rig_kb8(self, rig):
+        """lba_batch_set_rig_kb8: one rig of two fisheye cameras for every window of a call, or None"""
+        _set_rig_kb8(lib.lba_batch_set_rig_kb8, self._h, rig)
 
     def prepare(self, windows, want_outputs=True):
         """marshal once (a benchmark re-solves the same windows): problem structs, output arrays, stats"""
@@ -1121,6 +1150,10 @@ class PoseSolver:
     def set_camera_kb8(self, cam):
         """pose_set_camera_kb8: dict(fx, fy, cx, cy, k) or None (back to the pinhole camera of the problems)"""
         _set_camera_kb8(lib.pose_set_camera_kb8, self._h, cam)
+
+    def set_rig_kb8(self, rig):
+        """pose_set_rig_kb8: dict(left, right, q_rl, t_rl) or None (back to the pinhole camera); stereo then holds 0 or EDGE_RIGHT"""
+        _set_rig_kb8(lib.pose_set_rig_kb8, self._h, rig)
 
     def optimize_one(self, w):
         """pose_optimize: the single-frame entry"""

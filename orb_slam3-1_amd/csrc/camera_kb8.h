@@ -74,4 +74,67 @@ __device__ __forceinline__ void pose_rows(const Cam& c, const double* Xc, double
     }
 }
 
+// ---- a rig of two such cameras: the right-camera edges EdgeSE3ProjectXYZOnlyPoseToBody / EdgeSE3ProjectXYZToBody
+// (src/OptimizableTypes.cpp:91-107, 192-213): error obs - right.project(X_r), X_r = Trl X_l; pose Jacobian
+// -right.projectJac(X_r) R_rl SE3deriv(X_l); point Jacobian -right.projectJac(X_r) R_rl R_lw ----
+struct Rig {
+    Cam left, right;                    // mpCamera, mpCamera2
+    double R_rl[9], t_rl[3];            // GetRelativePoseTrl(), the rotation row major
+    const uint8_t* kind;                // LBA: [nE] camera of an edge, 0 left, else right (the pose solver reads the problem's stereo byte)
+    const uint8_t* const* kind_tab;     // batched LBA: the kind array of window w at kind_tab[w]
+};
+struct RigEdge { const Rig& g; bool right; };      // the camera argument of one edge
+
+// The camera and the camera-frame point of one edge, by selection: a wave that holds left and right edges then makes ONE pass through
+// the f64 atan2 / sincos / polynomial code of project and project_jac instead of two under divergence.  A left edge gets the left
+// camera and X_l untouched, so it computes what the monocular kb8 edge computes, bit for bit.
+__device__ __forceinline__ void rig_select(const Rig& g, bool right, const double* Xl, Cam& c, double* Xp)
+{
+    c.fx = right ? g.right.fx : g.left.fx; c.fy = right ? g.right.fy : g.left.fy;
+    c.cx = right ? g.right.cx : g.left.cx; c.cy = right ? g.right.cy : g.left.cy;
+#pragma unroll
+    for (int k = 0; k < 4; k++) c.k[k] = right ? g.right.k[k] : g.left.k[k];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double xr = g.R_rl[3 * a] * Xl[0] + g.R_rl[3 * a + 1] * Xl[1] + g.R_rl[3 * a + 2] * Xl[2] + g.t_rl[a];
+        Xp[a] = right ? xr : Xl[a];
+    }
+}
+
+// project of the edge's own camera; Xp[3] receives the point in that camera's frame (isDepthPositive reads Xp[2])
+__device__ __forceinline__ void rig_project(const Rig& g, bool right, const double* Xl, double* Xp, double* uv)
+{
+    Cam c;
+    rig_select(g, right, Xl, c, Xp);
+    project(c, Xp, uv);
+}
+
+// N[6] = -projectJac(Xp), times R_rl on a right edge; Jj[12] = N * SE3deriv(X_l).  The caller's point Jacobian is N * R_lw for both kinds.
+__device__ __forceinline__ void rig_pose_rows(const Rig& g, bool right, const double* Xl, double* N, double* Jj)
+{
+    Cam c;
+    double Xp[3], J[6];
+    rig_select(g, right, Xl, c, Xp);
+    project_jac(c, Xp, J);
+    for (int k = 0; k < 6; k++) N[k] = -J[k];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const double a0 = N[3 * q], a1 = N[3 * q + 1], a2 = N[3 * q + 2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double m = a0 * g.R_rl[k] + a1 * g.R_rl[3 + k] + a2 * g.R_rl[6 + k];
+            N[3 * q + k] = right ? m : N[3 * q + k];
+        }
+    }
+    const double x = Xl[0], y = Xl[1], z = Xl[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const double a0 = N[3 * q], a1 = N[3 * q + 1], a2 = N[3 * q + 2];
+        Jj[6 * q + 0] = a1 * (-z) + a2 * y;
+        Jj[6 * q + 1] = a0 * z + a2 * (-x);
+        Jj[6 * q + 2] = a0 * (-y) + a1 * x;
+        Jj[6 * q + 3] = a0; Jj[6 * q + 4] = a1; Jj[6 * q + 5] = a2;
+    }
+}
+
 }  // namespace kb8

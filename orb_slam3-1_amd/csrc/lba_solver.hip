@@ -32,6 +32,7 @@
 #include "../../include/orbslam3_hip.h"
 #include "batch_stage.h"
 #include "camera_kb8.h"
+#include "camera_kb8_host.h"
 #include "dense_chol.h"
 #include "device_scope.h"
 #include "lm_control.h"
@@ -82,12 +83,22 @@ __device__ __forceinline__ void edge_residual(const Cam& c, const double* Xc, co
 // exactly where they were read before the parameter existed -- handing the bodies a reference to d.cam instead made k_lin_all
 // spill its whole Dev to scratch) or a kb8::Cam, which the _kb8 kernels receive by value.
 struct ProblemCam {};
-__device__ __forceinline__ const Cam& camera(const Dev& d, const ProblemCam&) { return d.cam; }
-__device__ __forceinline__ const kb8::Cam& camera(const Dev&, const kb8::Cam& c) { return c; }
+// (a kb8::Rig, which the _rig kernels receive by value, finds the camera of edge e in its own array: RigEdge)
+__device__ __forceinline__ const Cam& camera(const Dev& d, const ProblemCam&, int) { return d.cam; }
+__device__ __forceinline__ const kb8::Cam& camera(const Dev&, const kb8::Cam& c, int) { return c; }
+__device__ __forceinline__ kb8::RigEdge camera(const Dev&, const kb8::Rig& g, int e) { return kb8::RigEdge{g, g.kind[e] != 0}; }
 __device__ __forceinline__ void edge_residual(const kb8::Cam& c, const double* Xc, const double* obs, int, double* r)
 {
     double uv[2];
     kb8::project(c, Xc, uv);
+    r[0] = obs[0] - uv[0]; r[1] = obs[1] - uv[1]; r[2] = 0;
+}
+
+// a left or right edge of a two-camera rig (lba_set_rig_kb8): obs - project of the edge's own camera (OptimizableTypes.h:127-132)
+__device__ __forceinline__ void edge_residual(const kb8::RigEdge& c, const double* Xc, const double* obs, int, double* r)
+{
+    double uv[2], Xp[3];
+    kb8::rig_project(c.g, c.right, Xc, Xp, uv);
     r[0] = obs[0] - uv[0]; r[1] = obs[1] - uv[1]; r[2] = 0;
 }
 
@@ -174,6 +185,20 @@ __device__ inline void edge_jacobians(const kb8::Cam& c, const double* T, const 
     for (int k = 12; k < 18; k++) Jj[k] = 0;
 }
 
+// EdgeSE3ProjectXYZToBody::linearizeOplus on a right edge of a rig (OptimizableTypes.cpp:192-213), the mono edge above on a left one
+__device__ inline void edge_jacobians(const kb8::RigEdge& c, const double* T, const double* Xc, int, double* Ji, double* Jj)
+{
+    double R[9], N[6];
+    quat_to_R(T, R);
+    kb8::rig_pose_rows(c.g, c.right, Xc, N, Jj);
+    for (int k = 0; k < 3; k++) {
+        Ji[k] = N[0] * R[k] + N[1] * R[3 + k] + N[2] * R[6 + k];
+        Ji[3 + k] = N[3] * R[k] + N[4] * R[3 + k] + N[5] * R[6 + k];
+        Ji[6 + k] = 0;
+    }
+    for (int k = 12; k < 18; k++) Jj[k] = 0;
+}
+
 // ---- errors of a state (SparseOptimizer::computeActiveErrors + per-edge robust chi2) ----
 template <class CamT>
 __device__ __forceinline__ void errors_body(Dev d, const CamT& cam, const double* __restrict__ poses, const double* __restrict__ pts, const int bx)
@@ -183,7 +208,7 @@ __device__ __forceinline__ void errors_body(Dev d, const CamT& cam, const double
     double Xc[3], r[3];
     pose_map(poses + 7 * (size_t)d.e_pose[e], pts + 3 * (size_t)d.e_point[e], Xc);
     const int st = d.e_stereo[e];
-    edge_residual(camera(d, cam), Xc, d.e_obs + 3 * (size_t)e, st, r);
+    edge_residual(camera(d, cam, e), Xc, d.e_obs + 3 * (size_t)e, st, r);
     const double w = d.e_w[e];
     double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
     if (st) chi += r[2] * (w * r[2]);
@@ -199,6 +224,11 @@ __global__ __launch_bounds__(256) void k_errors(Dev d, const double* __restrict_
 __global__ __launch_bounds__(256) void k_errors_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts)
 {
     errors_body(d, cam, poses, pts, (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_errors_rig(Dev d, kb8::Rig rig, const double* __restrict__ poses, const double* __restrict__ pts)
+{
+    errors_body(d, rig, poses, pts, (int)blockIdx.x);
 }
 
 // ---- buildSystem, landmark side: Hll, bl and the Hpl blocks W_e = B^T (rho1 Omega) A (6x3) ----
@@ -248,7 +278,7 @@ __device__ __forceinline__ void lin_landmarks_body(const Dev& d, const CamT& cam
             const int st = d.e_stereo[e];
             double Xc[3], Ji[9], Jj[18];
             pose_map(T, X, Xc);
-            edge_jacobians(camera(d, cam), T, Xc, st, Ji, Jj);
+            edge_jacobians(camera(d, cam, e), T, Xc, st, Ji, Jj);
             const double* r = d.err + 3 * (size_t)e;
             const double w = d.e_w[e];
             double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
@@ -322,7 +352,7 @@ __device__ __forceinline__ void lin_all_body(Dev d, const CamT& cam, const doubl
         const int st = d.e_stereo[e];
         double Xc[3], Ji[9], Jj[18];
         pose_map(T, pts + 3 * (size_t)d.e_point[e], Xc);
-        edge_jacobians(camera(d, cam), T, Xc, st, Ji, Jj);
+        edge_jacobians(camera(d, cam, e), T, Xc, st, Ji, Jj);
         const double* r = d.err + 3 * (size_t)e;
         const double w = d.e_w[e];
         double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
@@ -370,6 +400,11 @@ __global__ __launch_bounds__(256) void k_lin_all(Dev d, const double* __restrict
 __global__ __launch_bounds__(256) void k_lin_all_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
 {
     lin_all_body(d, cam, poses, pts, lambda, (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_lin_all_rig(Dev d, kb8::Rig rig, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
+{
+    lin_all_body(d, rig, poses, pts, lambda, (int)blockIdx.x);
 }
 
 // ---- deterministic scalar reductions (single workgroup) ----
@@ -624,7 +659,7 @@ __device__ __forceinline__ void update_errors_body(const Dev& d, const CamT& cam
             double Xc[3], r[3];
             pose_map(poses_new + 7 * (size_t)d.e_pose[e], Xn, Xc);
             const int st = d.e_stereo[e];
-            edge_residual(camera(d, cam), Xc, d.e_obs + 3 * (size_t)e, st, r);
+            edge_residual(camera(d, cam, e), Xc, d.e_obs + 3 * (size_t)e, st, r);
             const double w = d.e_w[e];
             double chi = r[0] * (w * r[0]) + r[1] * (w * r[1]);
             if (st) chi += r[2] * (w * r[2]);
@@ -673,6 +708,11 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_errors_kb8(Dev d, kb8::C
 {
     update_errors_body(d, cam, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
 }
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors_rig(Dev d, kb8::Rig rig, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
+                                                                   double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
+{
+    update_errors_body(d, rig, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Batched windows (lba_solve_batch): the SAME kernel bodies, one launch per stage for W independent windows, grid.y = window.
@@ -712,6 +752,22 @@ __global__ __launch_bounds__(256) void k_errors_b_kb8(const BWin* __restrict__ w
     const int st = trial_state ? 1 - y.cur : y.cur;
     errors_body(w.d, cam, w.poses[st], w.pts[st], (int)blockIdx.x);
 }
+// (the rig of a batch is one for all windows; each window's edge kinds are found through the pointer table the rig carries)
+__device__ __forceinline__ kb8::Rig rig_of_window(const kb8::Rig& rig, int w)
+{
+    kb8::Rig g = rig;
+    g.kind = rig.kind_tab[w];
+    return g;
+}
+__global__ __launch_bounds__(256) void k_errors_b_rig(const BWin* __restrict__ wins, BDynAll dyn, int trial_state, kb8::Rig rig)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & (trial_state ? kBwTrial : kBwErrors))) return;
+    const BWin& w = wins[blockIdx.y];
+    if ((int)blockIdx.x * 256 >= w.d.nE) return;
+    const int st = trial_state ? 1 - y.cur : y.cur;
+    errors_body(w.d, rig_of_window(rig, (int)blockIdx.y), w.poses[st], w.pts[st], (int)blockIdx.x);
+}
 __global__ __launch_bounds__(256) void k_lin_all_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
     const BDyn y = dyn.w[blockIdx.y];
@@ -727,6 +783,14 @@ __global__ __launch_bounds__(256) void k_lin_all_b_kb8(const BWin* __restrict__ 
     const BWin& w = wins[blockIdx.y];
     if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
     lin_all_body(w.d, cam, w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_lin_all_b_rig(const BWin* __restrict__ wins, BDynAll dyn, kb8::Rig rig)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & kBwLin)) return;
+    const BWin& w = wins[blockIdx.y];
+    if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
+    lin_all_body(w.d, rig_of_window(rig, (int)blockIdx.y), w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(1024) void k_reduce_b(const BWin* __restrict__ wins, BDynAll dyn, int mode)
 {
@@ -815,6 +879,15 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_errors_b_kb8(const BWin*
     if ((int)blockIdx.x >= nb) return;
     update_errors_body(w.d, cam, y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
 }
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b_rig(const BWin* __restrict__ wins, BDynAll dyn, kb8::Rig rig)
+{
+    const BDyn y = dyn.w[blockIdx.y];
+    if (!(y.flags & kBwTrial)) return;
+    const BWin& w = wins[blockIdx.y];
+    const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
+    if ((int)blockIdx.x >= nb) return;
+    update_errors_body(w.d, rig_of_window(rig, (int)blockIdx.y), y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
+}
 
 __global__ __launch_bounds__(256) void k_epilogue(Dev d, const double* __restrict__ poses, const double* __restrict__ pts,
                                                   double* __restrict__ chi2, uint8_t* __restrict__ depth_pos)
@@ -829,6 +902,22 @@ __global__ __launch_bounds__(256) void k_epilogue(Dev d, const double* __restric
     double Xc[3];
     pose_map(poses + 7 * (size_t)d.e_pose[e], pts + 3 * (size_t)d.e_point[e], Xc);
     depth_pos[e] = Xc[2] > 0.0;
+}
+
+// the epilogue of a rig window: two residual rows on every edge, and isDepthPositive of a right edge reads X_r.z (OptimizableTypes.h:134-138)
+__global__ __launch_bounds__(256) void k_epilogue_rig(Dev d, kb8::Rig rig, const double* __restrict__ poses, const double* __restrict__ pts,
+                                                      double* __restrict__ chi2, uint8_t* __restrict__ depth_pos)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= d.nE) return;
+    const double* r = d.err + 3 * (size_t)e;
+    const double w = d.e_w[e];
+    chi2[e] = r[0] * (w * r[0]) + r[1] * (w * r[1]);
+    double Xc[3], Xp[3];
+    kb8::Cam c;
+    pose_map(poses + 7 * (size_t)d.e_pose[e], pts + 3 * (size_t)d.e_point[e], Xc);
+    kb8::rig_select(rig, rig.kind[e] != 0, Xc, c, Xp);
+    depth_pos[e] = Xp[2] > 0.0;
 }
 
 __global__ void k_normalize_poses(double* poses, int n)
@@ -853,6 +942,8 @@ struct lba_shard {
     lba::Dev d;
     bool kb8_on = false;        // the window's camera is the fisheye one of its solver handle (lba_set_camera_kb8): the _kb8 kernels run
     kb8::Cam kb8;
+    bool rig_on = false;        // ... or the rig of two (lba_set_rig_kb8): the _rig kernels run, rig.kind = this window's per-edge cameras
+    kb8::Rig rig;
     int nblk = 0;
     std::vector<void*> allocs;
     double *poses[2] = {nullptr, nullptr}, *pts[2] = {nullptr, nullptr};
@@ -979,6 +1070,15 @@ static int kb8_reject_stereo(const LbaProblem* p)
     return ORBX_OK;
 }
 
+// a window of a handle with a rig holds left (0) and right (ORBX_EDGE_RIGHT) edges only (host check, before any device work)
+static int rig_reject_kinds(const LbaProblem* p)
+{
+    for (int e = 0; e < p->n_edges; e++)
+        if (p->edge_stereo[e] != 0 && p->edge_stereo[e] != ORBX_EDGE_RIGHT)
+            return fail(ORBX_ERR_ARG, "edge %d has kind %d, the handle's camera is a KannalaBrandt8 rig (0 or %d)", e, (int)p->edge_stereo[e], ORBX_EDGE_RIGHT);
+    return ORBX_OK;
+}
+
 static int kb8_from_abi(const OrbxKB8* cam, kb8::Cam* out)
 {
     if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
@@ -997,6 +1097,8 @@ struct lba_solver {                 // also a window slot of an lba_batch, with 
     size_t stage_cap = 0;
     bool kb8_on = false;            // lba_set_camera_kb8
     kb8::Cam kb8;
+    bool rig_on = false;            // lba_set_rig_kb8
+    kb8::Rig rig;
     ~lba_solver()
     {
         if (arena) (void)hipFree(arena);
@@ -1030,12 +1132,14 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     *out = nullptr;
     int r = shard_validate(p);
     if (!r && owner && owner->kb8_on) r = kb8_reject_stereo(p);
+    if (!r && owner && owner->rig_on) r = rig_reject_kinds(p);
     if (r || (r = stage::check_device(device))) return r;
     ORBX_HIP(hipSetDevice(device));
     lba_shard* s = new lba_shard();
     s->device = device;
     if (owner) {
         s->kb8_on = owner->kb8_on; s->kb8 = owner->kb8;
+        s->rig_on = owner->rig_on; s->rig = owner->rig;
         s->arena = owner->arena; s->arena_cap = owner->arena_cap;
         s->stream = owner->stream; s->owns_stream = false;
         s->hs = owner->hs.view();
@@ -1147,7 +1251,13 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     LBA_TRY(s->upload(&d.pose_col, pose_col)); LBA_TRY(s->upload(&d.col_pose, col_pose));
     LBA_TRY(s->upload_raw(&d.e_point, p->edge_point, (size_t)d.nE)); LBA_TRY(s->upload_raw(&d.e_pose, p->edge_pose, (size_t)d.nE));
     LBA_TRY(s->upload_raw(&d.e_obs, p->edge_obs, 3 * (size_t)d.nE));
-    LBA_TRY(s->upload_raw(&d.e_w, p->edge_inv_sigma2, (size_t)d.nE)); LBA_TRY(s->upload_raw(&d.e_stereo, p->edge_stereo, (size_t)d.nE));
+    LBA_TRY(s->upload_raw(&d.e_w, p->edge_inv_sigma2, (size_t)d.nE)); 
+    if (!s->rig_on) LBA_TRY(s->upload_raw(&d.e_stereo, p->edge_stereo, (size_t)d.nE));
+    else {      // a rig edge has two residual rows: the kernels' "third row" flag is 0, the camera of an edge travels in an array of its own
+        const std::vector<uint8_t> zeros((size_t)d.nE, 0);
+        LBA_TRY(s->upload(&d.e_stereo, zeros));
+        LBA_TRY(s->upload_raw(&s->rig.kind, p->edge_stereo, (size_t)d.nE));
+    }
     LBA_TRY(s->upload(&d.l_off, l_off)); LBA_TRY(s->upload(&d.l_edge, l_edge)); LBA_TRY(s->upload(&d.p_off, p_off)); LBA_TRY(s->upload(&d.p_edge, p_edge));
     LBA_TRY(s->upload(&d.b_i, b_i)); LBA_TRY(s->upload(&d.b_j, b_j)); LBA_TRY(s->upload(&d.b_off, b_off)); LBA_TRY(s->upload(&d.b_pair, pairs));
     LBA_TRY(s->dalloc(&s->poses[0], 7 * (size_t)p->n_poses)); LBA_TRY(s->dalloc(&s->pts[0], 3 * (size_t)d.nL));
@@ -1361,14 +1471,16 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
     const bool reuse = s->err_current;
     s->mark(lba::kStageLinearize);
     if (!reuse && d.nE > 0) {
-        if (s->kb8_on) hipLaunchKernelGGL(lba::k_errors_kb8, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->kb8, P, X);
+        if (s->rig_on) hipLaunchKernelGGL(lba::k_errors_rig, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->rig, P, X);
+        else if (s->kb8_on) hipLaunchKernelGGL(lba::k_errors_kb8, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->kb8, P, X);
         else hipLaunchKernelGGL(lba::k_errors, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, P, X);
     }
     // one launch for both sides; with a lambda hint (lba_shard_hint_lambda) the landmark workgroups also do their part of the Schur complement
     const double hint = s->hint_lambda;
     s->hint_lambda = -1.0;
     if (d.nP + d.nL > 0) {
-        if (s->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_kb8, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->kb8, P, X, hint);
+        if (s->rig_on) hipLaunchKernelGGL(lba::k_lin_all_rig, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->rig, P, X, hint);
+        else if (s->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_kb8, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->kb8, P, X, hint);
         else hipLaunchKernelGGL(lba::k_lin_all, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, P, X, hint);
     }
     s->schur_lambda = hint;
@@ -1444,7 +1556,8 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     }
     s->mark(lba::kStageUpdate);
     const dim3 upd_grid(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1));
-    if (s->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_kb8, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->kb8, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    if (s->rig_on) hipLaunchKernelGGL(lba::k_update_errors_rig, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->rig, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    else if (s->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_kb8, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->kb8, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
     else hipLaunchKernelGGL(lba::k_update_errors, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
     s->mark(lba::kStageIdle);
     ORBX_HIP(hipGetLastError());
@@ -1479,7 +1592,9 @@ int lba_shard_download(lba_shard* s, double* pose_q, double* pose_t, double* poi
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
     ORBX_HIP(hipSetDevice(s->device));
     const lba::Dev& d = s->d;
-    if (d.nE > 0)
+    if (d.nE > 0 && s->rig_on)
+        hipLaunchKernelGGL(lba::k_epilogue_rig, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->rig, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
+    else if (d.nE > 0)
         hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
     ORBX_HIP(hipGetLastError());
     std::vector<double> poses(7 * (size_t)d.nPoses);
@@ -1608,10 +1723,20 @@ void lba_destroy(lba_solver* s)
 int lba_set_camera_kb8(lba_solver* s, const OrbxKB8* cam)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!cam) { s->kb8_on = false; return ORBX_OK; }
+    if (!cam) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
     kb8::Cam c;
     if (int r = kb8_from_abi(cam, &c)) return r;
-    s->kb8 = c; s->kb8_on = true;
+    s->kb8 = c; s->kb8_on = true; s->rig_on = false;        // the last setter wins
+    return ORBX_OK;
+}
+
+int lba_set_rig_kb8(lba_solver* s, const OrbxKB8Rig* rig)
+{
+    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
+    if (!rig) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
+    kb8::Rig g;
+    if (int r = kb8::rig_from_abi(rig, &g)) return r;
+    s->rig = g; s->rig_on = true; s->kb8_on = false;
     return ORBX_OK;
 }
 
@@ -1660,11 +1785,15 @@ struct lba_batch : stage::Batch {       // its stream, the two events around the
     double last_device_ms = 0.0;
     bool kb8_on = false;                // lba_batch_set_camera_kb8: one fisheye camera for every window of a call
     kb8::Cam kb8;
+    bool rig_on = false;                // lba_batch_set_rig_kb8: one rig for every window of a call
+    kb8::Rig rig;
+    const uint8_t** d_kinds = nullptr;  // [kMaxBatch] the per-edge camera array of each window of a rig call (kb8::Rig::kind_tab)
     stage::PinnedOut out;               // the results of all windows (one synchronisation per call)
     ~lba_batch()
     {
         for (lba_solver* sv : slots) delete sv;
         if (d_wins) (void)hipFree(d_wins);
+        if (d_kinds) (void)hipFree(d_kinds);
         hs.release();
         out.release();
     }
@@ -1692,10 +1821,20 @@ double lba_batch_last_device_ms(const lba_batch* b) { return b ? b->last_device_
 int lba_batch_set_camera_kb8(lba_batch* b, const OrbxKB8* cam)
 {
     if (!b) return fail(ORBX_ERR_ARG, "NULL batch");
-    if (!cam) { b->kb8_on = false; return ORBX_OK; }
+    if (!cam) { b->kb8_on = false; b->rig_on = false; return ORBX_OK; }
     kb8::Cam c;
     if (int r = kb8_from_abi(cam, &c)) return r;
-    b->kb8 = c; b->kb8_on = true;
+    b->kb8 = c; b->kb8_on = true; b->rig_on = false;        // the last setter wins
+    return ORBX_OK;
+}
+
+int lba_batch_set_rig_kb8(lba_batch* b, const OrbxKB8Rig* rig)
+{
+    if (!b) return fail(ORBX_ERR_ARG, "NULL batch");
+    if (!rig) { b->kb8_on = false; b->rig_on = false; return ORBX_OK; }
+    kb8::Rig g;
+    if (int r = kb8::rig_from_abi(rig, &g)) return r;
+    b->rig = g; b->rig_on = true; b->kb8_on = false;
     return ORBX_OK;
 }
 
@@ -1710,14 +1849,20 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             int rc = shard_validate(&problems[i]);
             if (rc || (rc = kb8_reject_stereo(&problems[i]))) return rc;
         }
+    if (b->rig_on)
+        for (int i = 0; i < n_windows; i++) {
+            int rc = shard_validate(&problems[i]);
+            if (rc || (rc = rig_reject_kinds(&problems[i]))) return rc;
+        }
     ORBX_HIP(hipSetDevice(b->device));
+    if (b->rig_on && !b->d_kinds) ORBX_HIP(hipMalloc((void**)&b->d_kinds, lba::kMaxBatch * sizeof(const uint8_t*)));
     const int W = n_windows;
     while ((int)b->slots.size() < W) {
         lba_solver* sv = new lba_solver();
         sv->device = b->device; sv->stream = b->stream; sv->hs = b->hs.view((int)b->slots.size());
         b->slots.push_back(sv);
     }
-    for (int i = 0; i < W; i++) { b->slots[i]->kb8_on = b->kb8_on; b->slots[i]->kb8 = b->kb8; }
+    for (int i = 0; i < W; i++) { b->slots[i]->kb8_on = b->kb8_on; b->slots[i]->kb8 = b->kb8; b->slots[i]->rig_on = b->rig_on; b->slots[i]->rig = b->rig; }
     std::vector<lba_shard*> sh((size_t)W, nullptr);
     std::vector<size_t> wanted((size_t)W, 0), wanted_stage((size_t)W, 0);
     int r = ORBX_OK;
@@ -1728,6 +1873,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         }
     };
     std::vector<lba::BWin> hw((size_t)W);
+    std::vector<const uint8_t*> hkinds((size_t)W, nullptr);
     int max_lin = 1, max_e = 1, max_lm = 1, max_sb = 1, max_nblk = 1, max_upd = 1, max_n = 0;
     static const bool timing = std::getenv("ORBX_LBA_TIMING") != nullptr;
     const auto t_start = stage::Clock::now();
@@ -1741,6 +1887,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         lba::BWin& w = hw[i];
         w.d = s->d; w.poses[0] = s->poses[0]; w.poses[1] = s->poses[1]; w.pts[0] = s->pts[0]; w.pts[1] = s->pts[1];
         w.S = s->S(); w.bs = s->bs(); w.bpf = s->bpf(); w.diag = s->diag(); w.Lp = s->Lp; w.Linv = s->Linv; w.hmap = s->hs.d; w.flow = s->flow; w.nblk = s->nblk;
+        hkinds[i] = s->rig.kind;
         const lba::Dev& d = s->d;
         max_lin = std::max(max_lin, d.nP + (d.nL + 31) / 32); max_e = std::max(max_e, (d.nE + 255) / 256); max_lm = std::max(max_lm, (d.nL + 7) / 8);
         max_sb = std::max(max_sb, d.nBlocks + d.nP); max_nblk = std::max(max_nblk, s->nblk); max_upd = std::max(max_upd, (d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks);
@@ -1750,10 +1897,13 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     const size_t solve_lds = chol::solve_lds_bytes(max_n);      // (<= kFusedSolveLds: the windows are on the fused path)
     if (chol::allow_lds(lba::k_chol_step_b, chol::kStepLds) || chol::allow_lds(lba::k_chol_flow_b, chol::kStepLds) ||
         chol::allow_lds(lba::k_chol_solve_update_b, chol::kFusedSolveLds) ||
-        hipMemcpyAsync(b->d_wins, hw.data(), (size_t)W * sizeof(lba::BWin), hipMemcpyHostToDevice, b->stream) != hipSuccess) {
+        hipMemcpyAsync(b->d_wins, hw.data(), (size_t)W * sizeof(lba::BWin), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
+        (b->rig_on && hipMemcpyAsync(b->d_kinds, hkinds.data(), (size_t)W * sizeof(const uint8_t*), hipMemcpyHostToDevice, b->stream) != hipSuccess)) {
         cleanup();
         return fail(ORBX_ERR_HIP, "batch setup failed");
     }
+    kb8::Rig brig = b->rig;
+    brig.kind = nullptr; brig.kind_tab = b->d_kinds;
     (void)hipEventRecord(b->ev0, b->stream);
 
     // ---- one Levenberg controller per window (the control flow of lba_shard_optimize, cut at the points where it waits for the device);
@@ -1789,11 +1939,13 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         if (!any_lin && !any_trial) break;
         hipStream_t st = b->stream;
         if (any_err) {
-            if (b->kb8_on) hipLaunchKernelGGL(lba::k_errors_b_kb8, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, b->kb8);
+            if (b->rig_on) hipLaunchKernelGGL(lba::k_errors_b_rig, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, brig);
+            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_errors_b_kb8, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, b->kb8);
             else hipLaunchKernelGGL(lba::k_errors_b, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
         }
         if (any_lin) {
-            if (b->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_b_kb8, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
+            if (b->rig_on) hipLaunchKernelGGL(lba::k_lin_all_b_rig, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, brig);
+            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_b_kb8, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
             else hipLaunchKernelGGL(lba::k_lin_all_b, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
         }
         if (any_err) hipLaunchKernelGGL(lba::k_reduce_b, dim3(1, W), dim3(1024), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
@@ -1813,7 +1965,8 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
                 }
             }
             hipLaunchKernelGGL(lba::k_chol_solve_update_b, dim3(1, W), dim3(1024), solve_lds, st, (const lba::BWin*)b->d_wins, dyn);
-            if (b->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_b_kb8, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
+            if (b->rig_on) hipLaunchKernelGGL(lba::k_update_errors_b_rig, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, brig);
+            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_b_kb8, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
             else hipLaunchKernelGGL(lba::k_update_errors_b, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn);
         }
         if (hipGetLastError() != hipSuccess) { r = fail(ORBX_ERR_HIP, "batched launch failed"); break; }
@@ -1863,7 +2016,9 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             const lba::Dev& d = s->d;
             const LbaOutputs& o = outputs[i];
             const stage::PinnedOut::Slice h = po.slice(po.h + po.off[i], 7 * (size_t)d.nPoses * 8, d.nL, d.nE);
-            if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive))
+            if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive) && s->rig_on)
+                hipLaunchKernelGGL(lba::k_epilogue_rig, dim3((d.nE + 255) / 256), dim3(256), 0, b->stream, d, s->rig, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
+            else if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive))
                 hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, b->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
             ORBX_HIP_FIRST(r, hipMemcpyAsync(h.state, s->poses[s->cur], 7 * (size_t)d.nPoses * 8, hipMemcpyDeviceToHost, b->stream));
             if (o.points && d.nL > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.points, s->pts[s->cur], 3 * (size_t)d.nL * 8, hipMemcpyDeviceToHost, b->stream));

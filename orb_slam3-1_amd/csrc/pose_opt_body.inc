@@ -1,5 +1,5 @@
 // pose_opt_body.inc -- the body of k_pose_opt (pose_solver.hip), included once per camera: the text of a kernel, not a function.
-// Expects: problems (const ProblemDev*), cam (a camera policy: Pinhole or Fisheye), STEREO (bool constant), kRegEdges (int constant).
+// Expects: problems (const ProblemDev*), cam (a camera policy: Pinhole, Fisheye or RigCam), STEREO (bool constant), kRegEdges (int constant).
 // (As a __device__ function template shared by the two kernels the same statements compiled to other code for the pinhole kernels:
 // other register allocation throughout, DESIGN.md 4f / 4g.  Included as text, the pinhole kernels are the ones they were.)
     __shared__ double s_acc[28][kAccRow];       // per-thread partials of H (21), b (6), chi2 (1), transposed
@@ -25,7 +25,7 @@
     for (int j = 0; j < kRegEdges; j++) {
         const int e = tid + j * 256;
         cvalid[j] = e < n;
-        if (cvalid[j]) ce[j] = load_edge<STEREO>(P, e);
+        if (cvalid[j]) ce[j] = load_edge<STEREO>(cam, P, e);
         else { ce[j].X[0] = 0; ce[j].X[1] = 0; ce[j].X[2] = 1; ce[j].o[0] = 0; ce[j].o[1] = 0; ce[j].o[2] = 0; ce[j].w = 0; ce[j].st = 0; }
         cact[j] = cvalid[j]; cout_[j] = false;
         cerr[j][0] = 0; cerr[j][1] = 0; cerr[j][2] = 0;
@@ -65,7 +65,7 @@
                     if (cact[j]) edge_build<STEREO>(cam, P, T, ce[j], rb, cerr[j], acc);
                 for (int e = e_rest; e < n; e += 256) {
                     if (!P.active[e]) continue;
-                    const Edge d = load_edge<STEREO>(P, e);
+                    const Edge d = load_edge<STEREO>(cam, P, e);
                     double r[3];
                     edge_build<STEREO>(cam, P, T, d, rb, r, acc);
                     P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
@@ -113,7 +113,7 @@
                         if (cact[j]) tchi += edge_trial<STEREO>(cam, P, Tt, ce[j], rb, cerr[j]);
                     for (int e = e_rest; e < n; e += 256) {
                         if (!P.active[e]) continue;
-                        const Edge d = load_edge<STEREO>(P, e);
+                        const Edge d = load_edge<STEREO>(cam, P, e);
                         double r[3];
                         tchi += edge_trial<STEREO>(cam, P, Tt, d, rb, r);
                         P.err[3 * (size_t)e] = r[0]; P.err[3 * (size_t)e + 1] = r[1]; P.err[3 * (size_t)e + 2] = r[2];
@@ -143,7 +143,7 @@
             cout_[j] = o; cact[j] = !o; bad += o ? 1.0 : 0.0;
         }
         for (int e = e_rest; e < n; e += 256) {
-            const Edge d = load_edge<STEREO>(P, e);
+            const Edge d = load_edge<STEREO>(cam, P, e);
             double r[3];
             if (P.outlier[e]) {
                 double Xc[3];

@@ -17,6 +17,7 @@
 #include "../../include/orbslam3_hip.h"
 #include "batch_stage.h"
 #include "camera_kb8.h"
+#include "camera_kb8_host.h"
 #include "dense_lm_device.h"
 #include "se3_device.h"
 
@@ -37,8 +38,10 @@ struct ProblemDev {
 
 // camera policies of the edge bodies: the pinhole one reads fx .. bf of the problem, the fisheye one carries its own eight parameters
 // (monocular edges only; pose_set_camera_kb8)
-struct Pinhole { static constexpr bool kFisheye = false; };
-struct Fisheye { static constexpr bool kFisheye = true; kb8::Cam c; };
+struct Pinhole { static constexpr bool kFisheye = false, kRig = false; };
+struct Fisheye { static constexpr bool kFisheye = true, kRig = false; kb8::Cam c; };
+// a rig of two fisheye cameras (pose_set_rig_kb8): Edge::st is the camera of the edge, 0 left, ORBX_EDGE_RIGHT right; two residual rows
+struct RigCam { static constexpr bool kFisheye = true, kRig = true; kb8::Rig g; };
 
 // one edge in registers
 struct Edge {
@@ -58,6 +61,13 @@ __device__ __forceinline__ Edge load_edge(const ProblemDev& P, int e)
     d.st = STEREO ? (int)P.stereo[e] : 0;
     return d;
 }
+template <bool STEREO, class CamT>
+__device__ __forceinline__ Edge load_edge(const CamT&, const ProblemDev& P, int e)
+{
+    Edge d = load_edge<STEREO>(P, e);
+    if constexpr (CamT::kRig) d.st = (int)P.stereo[e];
+    return d;
+}
 
 // EdgeSE3ProjectXYZOnlyPose::computeError (include/OptimizableTypes.h:46-50) and
 // EdgeStereoSE3ProjectXYZOnlyPose::computeError (types_six_dof_expmap.h:203-207, cam_project .cpp:339-346)
@@ -65,7 +75,11 @@ template <bool STEREO, class CamT>
 __device__ __forceinline__ void edge_eval(const CamT& cam, const ProblemDev& P, const double* T, const Edge& d, double* Xc, double* r)
 {
     pose_map(T, d.X, Xc);
-    if constexpr (CamT::kFisheye) {                             // obs - pCamera->project(Xc) (OptimizableTypes.h:46-50)
+    if constexpr (CamT::kRig) {                                 // a right edge: obs - pCamera->project(Trl Xc) (OptimizableTypes.h:69-73)
+        double uv[2], Xp[3];
+        kb8::rig_project(cam.g, d.st != 0, Xc, Xp, uv);
+        r[0] = d.o[0] - uv[0]; r[1] = d.o[1] - uv[1]; r[2] = 0;
+    } else if constexpr (CamT::kFisheye) {                      // obs - pCamera->project(Xc) (OptimizableTypes.h:46-50)
         double uv[2];
         kb8::project(cam.c, Xc, uv);
         r[0] = d.o[0] - uv[0]; r[1] = d.o[1] - uv[1]; r[2] = 0;
@@ -107,7 +121,10 @@ __device__ __forceinline__ void edge_build(const CamT& cam, const ProblemDev& P,
     dlm::huber(rb.on, chi, delta, dsq, rho0, rho1);
     acc[27] += rho0;
     const double x = Xc[0], y = Xc[1], z = Xc[2];
-    if constexpr (CamT::kFisheye) {                             // -projectJac(Xc) * SE3deriv (OptimizableTypes.cpp:24-38)
+    if constexpr (CamT::kRig) {                                 // -projectJac(X_r) * R_rl * SE3deriv(X_l) on a right edge (OptimizableTypes.cpp:91-107)
+        double N[6];
+        kb8::rig_pose_rows(cam.g, d.st != 0, Xc, N, J);
+    } else if constexpr (CamT::kFisheye) {                      // -projectJac(Xc) * SE3deriv (OptimizableTypes.cpp:24-38)
         double N[6];
         kb8::pose_rows(cam.c, Xc, N, J);
     } else if (!STEREO || !d.st) {
@@ -185,7 +202,13 @@ __global__ __launch_bounds__(256) void k_pose_opt_kb8(const ProblemDev* __restri
     constexpr bool STEREO = false;
 #include "pose_opt_body.inc"
 }
-
+// the rig instantiation: left and right fisheye edges interleaved, the kind of an edge in the problem's stereo byte
+template <int kRegEdges>
+__global__ __launch_bounds__(256) void k_pose_opt_rig(const ProblemDev* __restrict__ problems, const RigCam cam)
+{
+    constexpr bool STEREO = false;
+#include "pose_opt_body.inc"
+}
 
 // ---- device-resident entry (pose_optimize_batch_device): the frame's edges are gathered ON THE DEVICE from the arrays the extractor
 // and the projection search left there, in feature order (the order Optimizer::PoseOptimization walks mvpMapPoints, :861-996) ----
@@ -297,13 +320,19 @@ struct pose_solver : stage::Batch {
     size_t dev_cap = 0;
     bool kb8_on = false;            // pose_set_camera_kb8: the fisheye camera replaces fx .. bf of every problem
     poseopt::Fisheye kb8;
+    bool rig_on = false;            // pose_set_rig_kb8: two fisheye cameras, the stereo byte of an edge names its camera
+    poseopt::RigCam rig;
     ~pose_solver() { if (d_dev) (void)hipFree(d_dev); }
 };
 
 namespace {
-inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p, const poseopt::Fisheye* kb8 = nullptr)
+inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p, const poseopt::Fisheye* kb8 = nullptr,
+                        const poseopt::RigCam* rig = nullptr)
 {
-    if (kb8) {
+    if (rig) {
+        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt_rig<4>), dim3(n), dim3(256), 0, st, p, *rig);
+        else hipLaunchKernelGGL((poseopt::k_pose_opt_rig<2>), dim3(n), dim3(256), 0, st, p, *rig);
+    } else if (kb8) {
         if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<4>), dim3(n), dim3(256), 0, st, p, *kb8);
         else hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<2>), dim3(n), dim3(256), 0, st, p, *kb8);
     } else if (stereo) {
@@ -322,6 +351,11 @@ int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, 
         for (int i = 0; i < n_problems; i++)
             for (int k = 0; k < problems[i].n && problems[i].stereo; k++)
                 if (problems[i].stereo[k]) return fail(ORBX_ERR_ARG, "problem %d: edge %d is stereo, the handle's camera is KannalaBrandt8", i, k);
+    if (s->rig_on)          // a rig frame holds left (0) and right (ORBX_EDGE_RIGHT) edges only: before any device work
+        for (int i = 0; i < n_problems; i++)
+            for (int k = 0; k < problems[i].n && problems[i].stereo; k++)
+                if (problems[i].stereo[k] != 0 && problems[i].stereo[k] != ORBX_EDGE_RIGHT)
+                    return fail(ORBX_ERR_ARG, "problem %d: edge %d has kind %d, the handle's camera is a KannalaBrandt8 rig (0 or %d)", i, k, (int)problems[i].stereo[k], ORBX_EDGE_RIGHT);
     ORBX_HIP(hipSetDevice(s->device));
     // layout: [ProblemDev x N][per problem: Xw obs w stereo]  ||  [PoseResult x N][per problem: outlier]  ||  scratch
     struct Off { size_t Xw, obs, w, st, outl, err, act; };
@@ -374,7 +408,8 @@ int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, 
         descs[i] = d;
     }
     const int rr = stage::run(*s, up_bytes, res_off, down_end,
-                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base, s->kb8_on ? &s->kb8 : nullptr); });
+                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base, s->kb8_on ? &s->kb8 : nullptr,
+                                                 s->rig_on ? &s->rig : nullptr); });
     if (rr != ORBX_OK) return rr;
     std::memcpy(results, s->h_blob + res_off, sizeof(PoseResult) * (size_t)n_problems);
     if (outlier_out)
@@ -401,6 +436,7 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
                                uint8_t* d_outlier, PoseResult* d_results, void* stream)
 {
     if (!s || !f || batch < 1) return fail(ORBX_ERR_ARG, "bad arguments");
+    if (s->rig_on) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 rig path: reset the camera (pose_set_rig_kb8(s, NULL)) or use pose_optimize_batch");
     if (s->kb8_on) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 path: reset the camera (pose_set_camera_kb8(s, NULL)) or use pose_optimize_batch");
     if (!f->d_kps || !f->d_n || !f->d_assign || !f->d_mp_xyz || !f->d_pose || !f->inv_level_sigma2) return fail(ORBX_ERR_ARG, "NULL arrays");
     if (f->cap < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap / mp_cap / n_levels");
@@ -448,11 +484,22 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
 int pose_set_camera_kb8(pose_solver* s, const OrbxKB8* cam)
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!cam) { s->kb8_on = false; return ORBX_OK; }
+    if (!cam) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
     if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
     s->kb8.c.fx = cam->fx; s->kb8.c.fy = cam->fy; s->kb8.c.cx = cam->cx; s->kb8.c.cy = cam->cy;
     for (int k = 0; k < 4; k++) s->kb8.c.k[k] = cam->k[k];
-    s->kb8_on = true;
+    s->kb8_on = true; s->rig_on = false;        // the last setter wins
+    return ORBX_OK;
+}
+
+int pose_set_rig_kb8(pose_solver* s, const OrbxKB8Rig* rig)
+{
+    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
+    if (!rig) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
+    kb8::Rig g;
+    if (int r = kb8::rig_from_abi(rig, &g)) return r;
+    s->rig.g = g;
+    s->rig_on = true; s->kb8_on = false;
     return ORBX_OK;
 }
 

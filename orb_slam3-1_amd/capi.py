@@ -604,6 +604,127 @@ class Matcher:
                                                     v(d_right_to_left), v(d_depth), v(d_p3d), v(d_knn_right), v(d_knn_d0), v(d_knn_d1), v(stream)))
 
 
+    # ---- the tracking searches of a two-camera fisheye rig frame, Nleft != -1 (include/orbslam3_hip_rig_match.h) ----
+    def search_by_projection_rig(self, rig, mp, th, assign, occupied, far_points=False, th_far=0.0):
+        """SearchByProjection(Frame&, vector<MapPoint*>&, th, bFarPoints, thFarPoints) of a rig frame.  rig: dict(left, right
+        (grid dicts as _frame takes them, with "desc" and optionally "angle"), scale, left_to_right, right_to_left); mp: dict of
+        the OrbmRigMapPoints arrays.  assign / occupied: in/out, left.n + right.n slots.  Returns nmatches."""
+        _rig_match_argtypes()
+        r, keep = rig_frame(rig)
+        p = rig_map_points(mp)
+        return _check(lib.orbm_search_by_projection_rig(self._h, C.byref(r), C.byref(p), th, int(far_points), th_far, self.nnratio, _p(assign), _p(occupied)))
+
+    def search_by_projection_last_rig(self, rig, last, th, assign, occupied):
+        """SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) of a rig frame; last: dict of the
+        OrbmRigLastPoints arrays and "level_window".  Returns nmatches."""
+        _rig_match_argtypes()
+        r, keep = rig_frame(rig)
+        p = rig_last_points(last)
+        return _check(lib.orbm_search_by_projection_last_rig(self._h, C.byref(r), C.byref(p), th, int(last.get("level_window", 0)), int(self.check_ori),
+                                                             _p(assign), _p(occupied)))
+
+    def search_by_projection_rig_batch(self, queries, th, far_points=False, th_far=0.0):
+        """queries: list of dict(rig, pts, assign, occupied) -> list of nmatches; ONE launch"""
+        _rig_match_argtypes()
+        arr = (OrbmRigMapQuery * len(queries))()
+        keep = []
+        for i, q in enumerate(queries):
+            r, k = rig_frame(q["rig"]); p = rig_map_points(q["pts"])
+            keep.append((r, k, p))
+            arr[i] = OrbmRigMapQuery(C.pointer(r), C.pointer(p), q["assign"].ctypes.data, q["occupied"].ctypes.data, 0)
+        _check(lib.orbm_search_by_projection_rig_batch(self._h, arr, len(queries), th, int(far_points), th_far, self.nnratio))
+        return [int(arr[i].n_matches) for i in range(len(queries))]
+
+    def search_by_projection_last_rig_batch(self, queries, th):
+        """queries: list of dict(rig, pts (with "level_window"), assign, occupied) -> list of nmatches; ONE launch"""
+        _rig_match_argtypes()
+        arr = (OrbmRigLastQuery * len(queries))()
+        keep = []
+        for i, q in enumerate(queries):
+            r, k = rig_frame(q["rig"]); p = rig_last_points(q["pts"])
+            keep.append((r, k, p))
+            arr[i] = OrbmRigLastQuery(C.pointer(r), C.pointer(p), int(q["pts"].get("level_window", 0)), q["assign"].ctypes.data, q["occupied"].ctypes.data, 0)
+        _check(lib.orbm_search_by_projection_last_rig_batch(self._h, arr, len(queries), th, int(self.check_ori)))
+        return [int(arr[i].n_matches) for i in range(len(queries))]
+
+    def rig_search_last_kernel_ms(self):
+        _rig_match_argtypes()
+        return float(lib.orbm_rig_search_last_kernel_ms(self._h))
+
+
+class OrbmRigFrame(C.Structure):
+    """OrbmRigFrame of include/orbslam3_hip_rig_match.h"""
+    _fields_ = [("left", Frame), ("right", Frame), ("left_to_right", C.c_void_p), ("right_to_left", C.c_void_p)]
+
+
+class OrbmRigMapPoints(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "in_view", "proj_u", "proj_v", "pred_level", "view_cos", "in_view_r", "proj_u_r", "proj_v_r", "pred_level_r", "view_cos_r",
+        "track_depth", "bad", "has_obs", "desc")]
+
+
+class OrbmRigLastPoints(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k in ("valid", "proj_u", "proj_v", "proj_u_r", "proj_v_r", "octave", "angle", "has_obs", "desc")]
+
+
+class OrbmRigMapQuery(C.Structure):
+    _fields_ = [("rig", C.POINTER(OrbmRigFrame)), ("pts", C.POINTER(OrbmRigMapPoints)), ("assign", C.c_void_p), ("occupied", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+class OrbmRigLastQuery(C.Structure):
+    _fields_ = [("rig", C.POINTER(OrbmRigFrame)), ("pts", C.POINTER(OrbmRigLastPoints)), ("level_window", C.c_int32), ("assign", C.c_void_p),
+                ("occupied", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+def _rig_match_argtypes():
+    lib.orbm_rig_search_check.argtypes = [C.POINTER(OrbmRigFrame), C.POINTER(OrbmRigMapPoints), C.POINTER(OrbmRigLastPoints), C.c_void_p, C.c_void_p]
+    lib.orbm_search_by_projection_rig.argtypes = [C.c_void_p, C.POINTER(OrbmRigFrame), C.POINTER(OrbmRigMapPoints), C.c_float, C.c_int, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_void_p]
+    lib.orbm_search_by_projection_last_rig.argtypes = [C.c_void_p, C.POINTER(OrbmRigFrame), C.POINTER(OrbmRigLastPoints), C.c_float, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_void_p]
+    lib.orbm_search_by_projection_rig_batch.argtypes = [C.c_void_p, C.POINTER(OrbmRigMapQuery), C.c_int, C.c_float, C.c_int, C.c_float, C.c_float]
+    lib.orbm_search_by_projection_last_rig_batch.argtypes = [C.c_void_p, C.POINTER(OrbmRigLastQuery), C.c_int, C.c_float, C.c_int]
+    lib.orbm_rig_search_last_kernel_ms.restype = C.c_float
+    lib.orbm_rig_search_last_kernel_ms.argtypes = [C.c_void_p]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def rig_frame(rig):
+    """dict(left, right, scale, left_to_right, right_to_left) -> (OrbmRigFrame, the arrays it points to).  A side is a grid dict
+    (x, y, octave, min_x .. max_y, cols, rows) with "desc" and optionally "angle"; a side may carry its own "scale"."""
+    sides = []
+    for s in ("left", "right"):
+        g = rig[s]
+        sc = g.get("scale", rig.get("scale"))
+        n = int(g["n"]) if "n" in g else next((len(g[k]) for k in ("x", "y", "octave", "desc") if g.get(k) is not None), 0)
+        sides.append(Frame(n, _ptr(g["x"]), _ptr(g["y"]), _ptr(g["octave"]), _ptr(g.get("angle")), _ptr(g["desc"]),
+                           g["min_x"], g["min_y"], g["max_x"], g["max_y"], g.get("cols", 64), g.get("rows", 48), _ptr(sc), g.get("n_levels", 0 if sc is None else len(sc)),
+                           _ptr(g.get("u_right"))))
+    return OrbmRigFrame(sides[0], sides[1], _ptr(rig["left_to_right"]), _ptr(rig["right_to_left"])), rig
+
+
+def rig_map_points(mp):
+    return OrbmRigMapPoints(int(mp.get("n", len(mp["proj_u"]) if mp.get("proj_u") is not None else 0)),
+                            *[_ptr(mp.get(k)) for k, _ in OrbmRigMapPoints._fields_[1:]])
+
+
+def rig_last_points(last):
+    return OrbmRigLastPoints(int(last.get("n", len(last["proj_u"]) if last.get("proj_u") is not None else 0)),
+                             *[_ptr(last.get(k)) for k, _ in OrbmRigLastPoints._fields_[1:]])
+
+
+def rig_search_check(rig, mp=None, last=None, assign=None, occupied=None):
+    """orbm_rig_search_check with the arguments as given (dicts, ctypes structs or None): the code"""
+    _rig_match_argtypes()
+    r = None if rig is None else C.byref(rig if isinstance(rig, OrbmRigFrame) else rig_frame(rig)[0])
+    a = None if mp is None else C.byref(rig_map_points(mp))
+    b = None if last is None else C.byref(rig_last_points(last))
+    return int(lib.orbm_rig_search_check(r, a, b, _p(assign), _p(occupied)))
+
+
 ORBM_MAX_NEIGHBOURS = 64
 
 

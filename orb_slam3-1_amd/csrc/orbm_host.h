@@ -65,6 +65,8 @@ struct orbm_matcher {
     float nmp_kernel_ms = 0.f;
     hipEvent_t sfe_ev[2] = {nullptr, nullptr};      // orbm_stereo_fisheye: events around its two kernels (created on first use)
     float sfe_kernel_ms = 0.f;
+    hipEvent_t rig_ev[2] = {nullptr, nullptr};      // the rig-frame tracking searches: events around k_grid + k_rig (created on first use)
+    float rig_kernel_ms = 0.f;
 
     int ensure(size_t bytes)
     {

@@ -1896,6 +1896,8 @@ static int run_projection(orbm_matcher* m, const OrbmFrame* f, int last_mode, in
     return r ? r : q.n_matches;
 }
 
+#include "orbm_rig_search.inc"      // the same two searches for a two-camera fisheye rig frame (include/orbslam3_hip_rig_match.h)
+
 extern "C" {
 
 int orbm_hamming(const uint8_t a[32], const uint8_t b[32])
@@ -1930,6 +1932,8 @@ void orbm_destroy(orbm_matcher* m)
     for (hipEvent_t e : m->nmp_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : m->sfe_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : m->rig_ev)
         if (e) (void)hipEventDestroy(e);
     delete m;
 }

@@ -1,0 +1,569 @@
+// orbm_rig_search.inc -- the two tracking searches for a two-camera fisheye rig frame (F.Nleft != -1): kernel, host driver and
+// the C ABI of include/orbslam3_hip_rig_match.h.  Included by orbm_matcher.hip (once, after run_projection), whose
+// search_window, key helpers, rot_bin, three_maxima, ProjFrameDev, k_grid and build_grid it uses as they are.
+// Reference: src/ORBmatcher.cc:43-213 (Frame x map points) and :1676-1887 (last frame).  DESIGN.md 4k.
+namespace orbm {
+
+struct RigArgs {
+    ProjFrameDev L, R;                      // mvKeys + mGrid, mvKeysRight + mGridRight (u_right == nullptr on both)
+    const int32_t* l2r; const int32_t* r2l; // mvLeftToRightMatch, mvRightToLeftMatch
+    int32_t n_pts;
+    const uint8_t* valid; const float* u; const float* v; const int32_t* level; const float* view_cos;             // left camera (map points) / the entry (last frame)
+    const uint8_t* valid_r; const float* u_r; const float* v_r; const int32_t* level_r; const float* view_cos_r;   // right camera; the last-frame search reads u_r, v_r only
+    const float* depth; const uint8_t* bad;         // map points only
+    const float* angle;                             // last frame only
+    const uint8_t* desc; const uint8_t* has_obs;
+    float th, th_far, nnratio;
+    int32_t far_points, check_ori, level_window;
+    int32_t last_mode;                      // 0: Frame x map points (:43), 1: last frame (:1676)
+    int32_t* assign; uint8_t* occupied;     // [L.n + R.n], left slots first
+    int32_t* log_slot; int32_t* log_bin;    // last frame: rotation log, 2 * n_pts entries (wave w owns [w * n_pts, (w + 1) * n_pts))
+    int32_t* n_matches;
+};
+
+constexpr int kRigThreads = 128;            // two waves: one per side
+
+// LDS bytes of one staged side: descriptors, x, y, octave, CSR entries (48 B per feature) + the cell table
+__host__ __device__ inline size_t rig_side_bytes(int n, int ncell) { return (size_t)n * 48 + ((((size_t)ncell + 1) * 4 + 15) & ~(size_t)15); }
+
+__device__ __forceinline__ uint8_t* rig_stage_side(ProjFrameDev& F, uint8_t* p, int tid)
+{
+    const int n = F.n, ncell = F.cols * F.rows;
+    uint8_t* s_desc = p; p += (size_t)n * 32;
+    float* s_x = (float*)p; p += (size_t)n * 4;
+    float* s_y = (float*)p; p += (size_t)n * 4;
+    int32_t* s_oct = (int32_t*)p; p += (size_t)n * 4;
+    int32_t* s_cfeat = (int32_t*)p; p += (size_t)n * 4;
+    int32_t* s_coff = (int32_t*)p; p += (((size_t)ncell + 1) * 4 + 15) & ~(size_t)15;
+    for (int i = tid; i < n * 8; i += kRigThreads) ((uint32_t*)s_desc)[i] = ((const uint32_t*)F.desc)[i];
+    for (int i = tid; i < n; i += kRigThreads) { s_x[i] = F.x[i]; s_y[i] = F.y[i]; s_oct[i] = F.octave[i]; }
+    const int nfeat_cells = min(F.cell_off[ncell], n);
+    for (int i = tid; i < nfeat_cells; i += kRigThreads) s_cfeat[i] = F.cell_feat[i];
+    for (int i = tid; i <= ncell; i += kRigThreads) s_coff[i] = F.cell_off[i];
+    F.desc = s_desc; F.x = s_x; F.y = s_y; F.octave = s_oct; F.cell_feat = s_cfeat; F.cell_off = s_coff;
+    return p;
+}
+
+// `!vIndices2.empty()` of :1735 for the calling wave: does Frame::GetFeaturesInArea return anything?  Cells, level filter and
+// the |dx|, |dy| < r test only -- occupancy plays no part and no descriptor is read.  Stops at the first 64 cells that hold a hit.
+__device__ __forceinline__ bool rig_window_nonempty(const ProjFrameDev& F, float x, float y, float r, int minLevel, int maxLevel, int lane)
+{
+    const int nMinCellX = max(0, (int)floorf((x - F.min_x - r) * F.winv));
+    if (nMinCellX >= F.cols) return false;
+    const int nMaxCellX = min(F.cols - 1, (int)ceilf((x - F.min_x + r) * F.winv));
+    if (nMaxCellX < 0) return false;
+    const int nMinCellY = max(0, (int)floorf((y - F.min_y - r) * F.hinv));
+    if (nMinCellY >= F.rows) return false;
+    const int nMaxCellY = min(F.rows - 1, (int)ceilf((y - F.min_y + r) * F.hinv));
+    if (nMaxCellY < 0) return false;
+    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
+    const int ny = nMaxCellY - nMinCellY + 1, nx = nMaxCellX - nMinCellX + 1;
+    const int ncell = nx * ny;
+    for (int c0 = 0; c0 < ncell; c0 += 64) {
+        const int c = c0 + lane;
+        bool hit = false;
+        if (c < ncell) {
+            const int cq = c / ny;
+            const int cell = (nMinCellX + cq) * F.rows + nMinCellY + (c - cq * ny);
+            const int e1 = F.cell_off[cell + 1];
+            for (int e = F.cell_off[cell]; e < e1 && !hit; e++) {
+                const int idx = F.cell_feat[e];
+                if (bCheckLevels) {
+                    const int oc = F.octave[idx];
+                    if (oc < minLevel) continue;
+                    if (maxLevel >= 0 && oc > maxLevel) continue;
+                }
+                hit = fabsf(F.x[idx] - x) < r && fabsf(F.y[idx] - y) < r;
+            }
+        }
+        if (__ballot(hit) != 0ull) return true;
+    }
+    return false;
+}
+
+__device__ __forceinline__ void rig_load_desc(const uint8_t* desc, int i, unsigned long long d[4])
+{
+    const unsigned long long* dp = (const unsigned long long*)(desc + (size_t)i * 32);
+    d[0] = dp[0]; d[1] = dp[1]; d[2] = dp[2]; d[3] = dp[3];
+}
+
+// One workgroup of two waves per rig frame; the points go in the reference's order.
+//  last frame: the two passes of an entry touch disjoint slots (left [0, L.n), right [L.n, ..)) and the right pass's gate --
+//   entry valid, LEFT projection inside the image, LEFT window not empty -- is geometry only.  So wave 0 runs the whole left
+//   loop and wave 1 the whole right loop (evaluating the gate itself with rig_window_nonempty), each against its own half of
+//   the occupancy table and with its own log; they meet at the one histogram (LDS atomics), one three_maxima, and each
+//   filters its own log.  The filter is a set operation and nmatches a count, so the order of log entries does not matter.
+//  map points: the sides are coupled through l2r / r2l, so the points stay strictly in order, but the two windows of ONE point
+//   are walked at once, both against the occupancy as it stands before the point.  The left outcome is final.  The right one
+//   is final unless (a) the left pass took the `continue` of :125-126 -- then it is discarded --, or (b) the left pass's
+//   partner write CHANGED the occupancy of right slot L.n + l2r in a way the right window can see: the slot became free
+//   (has_obs = 0 over an occupied slot: it may now be a candidate), or it became occupied and is the right wave's best or
+//   second candidate (any other candidate is irrelevant to the outcome: the dirty rule of k_proj_par within a point).  Then
+//   the right window is searched again against the exact occupancy.  Wave 1's first lane commits everything in the
+//   reference's order (left slot, its partner, r2l partner, right slot), so a later write to the same slot wins.
+template <bool STAGE>
+__global__ __launch_bounds__(kRigThreads) void k_rig(const RigArgs* __restrict__ jobs)
+{
+    const RigArgs A = jobs[blockIdx.x];
+    extern __shared__ __align__(16) uint8_t s_dyn[];
+    __shared__ int s_hist[HISTO_LENGTH];
+    __shared__ int s_keep[3];
+    __shared__ int s_nm[2];
+    __shared__ float s_scale[32];
+    __shared__ int s_col[2][32];
+    __shared__ unsigned long long s_res[2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    ProjFrameDev L = A.L, R = A.R;
+    const int nl = L.n, nr = R.n;
+    uint8_t* s_occ = s_dyn;
+    if (STAGE) {
+        uint8_t* p = s_dyn + (((size_t)nl + nr + 15) & ~(size_t)15);
+        p = rig_stage_side(L, p, tid);
+        p = rig_stage_side(R, p, tid);
+    }
+    if (tid < L.n_levels && tid < 32) s_scale[tid] = L.scale_factors[tid];      // one table per frame (checked on the host)
+    L.scale_factors = s_scale; R.scale_factors = s_scale;
+    for (int i = tid; i < nl + nr; i += kRigThreads) s_occ[i] = A.occupied[i];
+    if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+    __syncthreads();
+
+    if (A.last_mode) {
+        uint8_t* occ = s_occ + (wave ? nl : 0);
+        const int slot0 = wave ? nl : 0;
+        const float* side_angle = wave ? R.angle : L.angle;
+        int32_t* log_slot = A.log_slot + (size_t)wave * A.n_pts;
+        int32_t* log_bin = A.log_bin + (size_t)wave * A.n_pts;
+        int nm = 0, nlog = 0;
+        for (int i = 0; i < A.n_pts; i++) {
+            if (!A.valid[i]) continue;
+            const float x = A.u[i], y = A.v[i];
+            if (x < L.min_x || x > L.max_x) continue;                  // :1715-1718: the LEFT projection gates both passes
+            if (y < L.min_y || y > L.max_y) continue;
+            const int oct = A.level[i];
+            const float r = A.th * s_scale[oct];                       // :1724, :1802
+            int minLevel, maxLevel;
+            if (A.level_window == ORBM_LEVELS_FORWARD) { minLevel = oct; maxLevel = -1; }          // :1729, :1807
+            else if (A.level_window == ORBM_LEVELS_BACKWARD) { minLevel = 0; maxLevel = oct; }     // :1731, :1809
+            else { minLevel = oct - 1; maxLevel = oct + 1; }                                        // :1733, :1811
+            unsigned long long d[4], kb, ks;
+            rig_load_desc(A.desc, i, d);
+            if (wave == 0) {
+                search_window<true>(L, occ, x, y, r, minLevel, maxLevel, 0.f, d, lane, s_col[0], kb, ks);     // (an empty window has no best: :1735 needs no test of its own here)
+            } else {
+                if (!rig_window_nonempty(L, x, y, r, minLevel, maxLevel, lane)) continue;                      // :1735
+                search_window<true>(R, occ, A.u_r[i], A.v_r[i], r, minLevel, maxLevel, 0.f, d, lane, s_col[1], kb, ks);   // no bounds test on the right projection
+            }
+            if (kb == kNoKey) continue;
+            const int bestIdx = key_idx(kb);
+            if (key_dist(kb) > TH_HIGH) continue;                      // :1770, :1836
+            if (lane == 0) {
+                A.assign[slot0 + bestIdx] = i;
+                occ[bestIdx] = A.has_obs[i];
+                if (A.check_ori) {
+                    const int bin = rot_bin(A.angle[i], side_angle[bestIdx]);
+                    log_slot[nlog] = slot0 + bestIdx; log_bin[nlog] = bin;
+                    atomicAdd(&s_hist[bin], 1);
+                }
+            }
+            nlog++; nm++;
+            wave_lds_sync();        // this wave's next window must see the occupancy update (the other wave never reads this half)
+        }
+        __syncthreads();
+        if (A.check_ori) {          // ONE histogram over both sides (:1865-1884)
+            if (tid == 0) {
+                int i1, i2, i3;
+                three_maxima(s_hist, HISTO_LENGTH, i1, i2, i3);
+                s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
+            }
+            __syncthreads();
+            const int i1 = s_keep[0], i2 = s_keep[1], i3 = s_keep[2];
+            for (int k0 = 0; k0 < nlog; k0 += 64) {
+                const int k = k0 + lane;
+                bool drop = false;
+                if (k < nlog) {
+                    const int b = log_bin[k];
+                    drop = b != i1 && b != i2 && b != i3;
+                    if (drop) { const int s = log_slot[k]; A.assign[s] = -1; s_occ[s] = 0; }        // mvpMapPoints[...] = NULL (:1879)
+                }
+                nm -= __popcll(__ballot(drop));
+            }
+        }
+        if (lane == 0) s_nm[wave] = nm;
+        __syncthreads();
+        if (tid == 0) *A.n_matches = s_nm[0] + s_nm[1];
+    } else {
+        const bool bFactor = A.th != 1.0f;
+        uint8_t* occ_r = s_occ + nl;
+        int nm = 0;
+        for (int i = 0; i < A.n_pts; i++) {
+            const int inL = A.valid[i], inR = A.valid_r[i];
+            if (!inL && !inR) continue;                                // :52
+            if (A.far_points && A.depth[i] > A.th_far) continue;       // :55
+            if (A.bad[i]) continue;                                    // :58
+            const int lvlR = A.level_r[i];
+            const bool doR = inR && lvlR != -1;                        // :144-146
+            unsigned long long d[4], kb = kNoKey, ks = kNoKey;
+            rig_load_desc(A.desc, i, d);
+            float xr = 0.f, yr = 0.f, rr = 0.f;
+            if (wave == 0) {
+                if (inL) {
+                    const int lvl = A.level[i];
+                    float r = ((double)A.view_cos[i] > 0.998) ? 2.5f : 4.0f;       // RadiusByViewingCos (:215-221)
+                    if (bFactor) r *= A.th;
+                    r = r * s_scale[lvl];
+                    search_window<true>(L, s_occ, A.u[i], A.v[i], r, lvl - 1, lvl, 0.f, d, lane, s_col[0], kb, ks);
+                }
+                if (lane == 0) { s_res[0] = kb; s_res[1] = ks; }
+            } else if (doR) {
+                rr = ((double)A.view_cos_r[i] > 0.998) ? 2.5f : 4.0f;              // :147: th is not applied
+                rr = rr * s_scale[lvlR];
+                xr = A.u_r[i]; yr = A.v_r[i];
+                search_window<true>(R, occ_r, xr, yr, rr, lvlR - 1, lvlR, 0.f, d, lane, s_col[1], kb, ks);
+            }
+            __syncthreads();
+            if (wave == 1) {
+                const unsigned long long lb = s_res[0], ls = s_res[1];
+                const uint8_t ho = A.has_obs[i];
+                bool cancel = false, dirty = false;
+                if (lb != kNoKey && key_dist(lb) <= TH_HIGH) {         // :123
+                    const int bi = key_idx(lb);
+                    const int bd2 = (ls == kNoKey) ? 256 : key_dist(ls);
+                    const int lev = L.octave[bi], lev2 = (ls == kNoKey) ? -1 : L.octave[key_idx(ls)];
+                    if (lev == lev2 && (float)key_dist(lb) > A.nnratio * (float)bd2) cancel = true;     // :125-126: `continue` takes the right pass with it
+                    else {
+                        const int p = A.l2r[bi];
+                        const bool was = (p != -1) ? occ_r[p] != 0 : ho != 0;
+                        if (lane == 0) {
+                            A.assign[bi] = i; s_occ[bi] = ho;                          // :129
+                            if (p != -1) { A.assign[nl + p] = i; occ_r[p] = ho; }      // :131-135, unconditional
+                        }
+                        nm += (p != -1) ? 2 : 1;
+                        if (doR && p != -1 && was != (ho != 0))
+                            dirty = !ho || (kb != kNoKey && key_idx(kb) == p) || (ks != kNoKey && key_idx(ks) == p);
+                    }
+                }
+                if (!cancel && doR) {
+                    if (dirty) {
+                        wave_lds_sync();
+                        search_window<true>(R, occ_r, xr, yr, rr, lvlR - 1, lvlR, 0.f, d, lane, s_col[1], kb, ks);
+                    }
+                    if (kb != kNoKey && key_dist(kb) <= TH_HIGH) {     // :193
+                        const int bi = key_idx(kb);
+                        const int bd2 = (ks == kNoKey) ? 256 : key_dist(ks);
+                        const int lev = R.octave[bi], lev2 = (ks == kNoKey) ? -1 : R.octave[key_idx(ks)];
+                        if (!(lev == lev2 && (float)key_dist(kb) > A.nnratio * (float)bd2)) {          // :195
+                            const int q = A.r2l[bi];
+                            if (lane == 0) {
+                                if (q != -1) { A.assign[q] = i; s_occ[q] = ho; }       // :198-202
+                                A.assign[nl + bi] = i; occ_r[bi] = ho;                 // :205
+                            }
+                            nm += (q != -1) ? 2 : 1;
+                        }
+                    }
+                }
+            }
+            __syncthreads();        // the occupancy updates must be seen by the next point's two windows
+        }
+        if (tid == 64) *A.n_matches = nm;
+    }
+    __syncthreads();
+    for (int i = tid; i < nl + nr; i += kRigThreads) A.occupied[i] = s_occ[i];
+}
+
+}  // namespace orbm
+
+// one rig search problem; host pointers
+struct RigJob {
+    const OrbmRigFrame* rig;
+    const OrbmRigMapPoints* mp;         // exactly one of mp / last
+    const OrbmRigLastPoints* last;
+    int level_window;
+    int32_t* assign; uint8_t* occupied;
+    int n_matches;                      // out
+};
+
+static int rig_check_side(const OrbmFrame* f, const char* name)
+{
+    if (f->n < 0) return fail(ORBX_ERR_ARG, "rig %s: negative n", name);
+    if (f->n >= (1 << 21)) return fail(ORBX_ERR_ARG, "rig %s: too many features", name);
+    if (f->n > 0 && (!f->x || !f->y || !f->octave || !f->desc)) return fail(ORBX_ERR_ARG, "rig %s: NULL frame arrays", name);
+    if (f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20)) return fail(ORBX_ERR_ARG, "rig %s: bad frame grid", name);
+    if (!f->scale_factors || f->n_levels < 1 || f->n_levels > 32) return fail(ORBX_ERR_ARG, "rig %s: NULL scale factors or n_levels outside [1, 32]", name);
+    return ORBX_OK;
+}
+
+static int rig_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const OrbmRigLastPoints* last, const int32_t* assign, const uint8_t* occupied)
+{
+    if (!rig) return fail(ORBX_ERR_ARG, "NULL rig frame");
+    if ((mp != nullptr) == (last != nullptr)) return fail(ORBX_ERR_ARG, "exactly one of the map points and the last-frame points is given");
+    if (!assign || !occupied) return fail(ORBX_ERR_ARG, "NULL assign/occupied");
+    const OrbmFrame& l = rig->left; const OrbmFrame& r = rig->right;
+    if (int e = rig_check_side(&l, "left")) return e;
+    if (int e = rig_check_side(&r, "right")) return e;
+    if (l.u_right) return fail(ORBX_ERR_ARG, "a rig frame has no u_right (left.u_right must be NULL)");
+    if (!(l.min_x == r.min_x && l.min_y == r.min_y && l.max_x == r.max_x && l.max_y == r.max_y)) return fail(ORBX_ERR_ARG, "the two sides disagree in the image bounds");
+    if (l.grid_cols != r.grid_cols || l.grid_rows != r.grid_rows) return fail(ORBX_ERR_ARG, "the two sides disagree in the grid");
+    if (l.n_levels != r.n_levels) return fail(ORBX_ERR_ARG, "the two sides disagree in n_levels");
+    for (int k = 0; k < l.n_levels; k++)
+        if (!(l.scale_factors[k] == r.scale_factors[k])) return fail(ORBX_ERR_ARG, "the two sides disagree in scale factor %d", k);
+    if ((l.n > 0 && !rig->left_to_right) || (r.n > 0 && !rig->right_to_left)) return fail(ORBX_ERR_ARG, "NULL left_to_right / right_to_left");
+    for (int i = 0; i < l.n; i++)
+        if (rig->left_to_right[i] < -1 || rig->left_to_right[i] >= r.n) return fail(ORBX_ERR_ARG, "left_to_right[%d] = %d outside [-1, %d)", i, rig->left_to_right[i], r.n);
+    for (int i = 0; i < r.n; i++)
+        if (rig->right_to_left[i] < -1 || rig->right_to_left[i] >= l.n) return fail(ORBX_ERR_ARG, "right_to_left[%d] = %d outside [-1, %d)", i, rig->right_to_left[i], l.n);
+    const int nlv = l.n_levels;
+    if (mp) {
+        if (mp->n < 0) return fail(ORBX_ERR_ARG, "negative point count");
+        if (mp->n > 0 && (!mp->in_view || !mp->proj_u || !mp->proj_v || !mp->pred_level || !mp->view_cos || !mp->in_view_r || !mp->proj_u_r || !mp->proj_v_r ||
+                          !mp->pred_level_r || !mp->view_cos_r || !mp->track_depth || !mp->bad || !mp->has_obs || !mp->desc))
+            return fail(ORBX_ERR_ARG, "NULL map point arrays");
+        for (int i = 0; i < mp->n; i++) {
+            if (mp->in_view[i] && (mp->pred_level[i] < 0 || mp->pred_level[i] >= nlv)) return fail(ORBX_ERR_ARG, "point %d: level %d out of range", i, mp->pred_level[i]);
+            if (mp->in_view_r[i] && (mp->pred_level_r[i] < -1 || mp->pred_level_r[i] >= nlv)) return fail(ORBX_ERR_ARG, "point %d: right level %d out of range", i, mp->pred_level_r[i]);
+        }
+    } else {
+        if (last->n < 0) return fail(ORBX_ERR_ARG, "negative point count");
+        if (last->n > 0 && (!last->valid || !last->proj_u || !last->proj_v || !last->proj_u_r || !last->proj_v_r || !last->octave || !last->has_obs || !last->desc))
+            return fail(ORBX_ERR_ARG, "NULL last-frame point arrays");
+        for (int i = 0; i < last->n; i++)
+            if (last->valid[i] && (last->octave[i] < 0 || last->octave[i] >= nlv)) return fail(ORBX_ERR_ARG, "entry %d: octave %d out of range", i, last->octave[i]);
+    }
+    return ORBX_OK;
+}
+
+// dynamic LDS k_rig may ask for: the CU's 160 KB minus the kernel's own static LDS and a margin (as proj_dynamic_lds_budget)
+static size_t rig_dynamic_lds_budget()
+{
+    static size_t budget = 0;
+    if (budget == 0) {
+        size_t st = 0;
+        const void* ks[2] = {(const void*)orbm::k_rig<true>, (const void*)orbm::k_rig<false>};
+        for (const void* k : ks) {
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, k) == hipSuccess) st = std::max(st, (size_t)fa.sharedSizeBytes);
+        }
+        (void)hipGetLastError();
+        budget = 160 * 1024 - std::max(st, (size_t)4096) - 1024;
+    }
+    return budget;
+}
+
+// Packs all jobs into one blob; ONE k_grid launch over the 2 x n_jobs sides, ONE k_rig launch with a workgroup per rig frame;
+// one copy brings assign / occupied / counts back.
+static int run_rig_jobs(orbm_matcher* m, RigJob* jobs, int n_jobs, int last_mode, float th, int far_points, float th_far, float nnratio, int check_ori)
+{
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    if (!jobs || n_jobs < 1) return fail(ORBX_ERR_ARG, "no jobs");
+    for (int j = 0; j < n_jobs; j++) {
+        const RigJob& q = jobs[j];
+        if (int e = rig_check(q.rig, last_mode ? nullptr : q.mp, last_mode ? q.last : nullptr, q.assign, q.occupied)) return e;
+        if (last_mode) {
+            if (q.level_window < ORBM_LEVELS_AROUND || q.level_window > ORBM_LEVELS_BACKWARD) return fail(ORBX_ERR_ARG, "job %d: bad level_window %d", j, q.level_window);
+            if (check_ori && q.last->n > 0 && (!q.last->angle || (q.rig->left.n > 0 && !q.rig->left.angle) || (q.rig->right.n > 0 && !q.rig->right.angle)))
+                return fail(ORBX_ERR_ARG, "job %d: NULL angle arrays", j);
+        }
+    }
+    ORBX_HIP(hipSetDevice(m->device));
+    (void)hipGetLastError();
+    const size_t lds_budget = rig_dynamic_lds_budget();
+    Blob blob(m->h_blob);
+    const size_t oargs = blob.reserve(sizeof(orbm::RigArgs) * (size_t)n_jobs);
+    const size_t ogrid = blob.reserve(sizeof(orbm::ProjArgs) * (size_t)n_jobs * 2);
+    struct SideOff { size_t x, y, oct, ang, desc, coff, cfeat; float winv, hinv; };
+    struct Off { SideOff s[2]; size_t sf, l2r, r2l, valid, u, v, level, vc, valid_r, u_r, v_r, level_r, vc_r, dep, bad, angl, dmp, obs, logs, logb, assign, occ, nm; };
+    std::vector<Off> offs(n_jobs);
+    std::vector<int32_t> cell_off, cell_feat;
+    size_t max_n = 0, lds_full = 0, lds_occ = 64;
+    bool device_grid = true;            // Frame::AssignFeaturesToGrid of both sides on the device (k_grid) when every side fits its LDS sort
+    for (int j = 0; j < n_jobs; j++) device_grid = device_grid && jobs[j].rig->left.n <= 8192 && jobs[j].rig->right.n <= 8192;
+    for (int j = 0; j < n_jobs; j++) {
+        const RigJob& q = jobs[j];
+        Off& o = offs[j];
+        const OrbmFrame* side[2] = {&q.rig->left, &q.rig->right};
+        for (int s = 0; s < 2; s++) {
+            const OrbmFrame* f = side[s];
+            SideOff& so = o.s[s];
+            if (device_grid) {
+                so.winv = (float)f->grid_cols / (f->max_x - f->min_x);         // mfGridElementWidthInv (src/Frame.cc:338)
+                so.hinv = (float)f->grid_rows / (f->max_y - f->min_y);
+                cell_off.assign((size_t)f->grid_cols * f->grid_rows + 1, 0);
+                cell_feat.assign(std::max(f->n, 1), 0);
+            } else if (int e = build_grid(f, cell_off, cell_feat, so.winv, so.hinv)) return e;
+            const int n = f->n;
+            max_n = std::max(max_n, (size_t)n);
+            so.x = blob.put(f->x, sizeof(float) * n); so.y = blob.put(f->y, sizeof(float) * n);
+            so.oct = blob.put(f->octave, sizeof(int32_t) * n);
+            so.ang = blob.put(f->angle, f->angle ? sizeof(float) * n : 0);
+            so.desc = blob.put(f->desc, (size_t)n * 32);
+            so.coff = blob.put(cell_off.data(), sizeof(int32_t) * cell_off.size());
+            so.cfeat = blob.put(cell_feat.data(), sizeof(int32_t) * cell_feat.size());
+        }
+        const int nl = side[0]->n, nr = side[1]->n, ncell = side[0]->grid_cols * side[0]->grid_rows;
+        const size_t slots = (size_t)nl + nr;
+        if (slots + 256 > lds_budget) return fail(ORBX_ERR_ARG, "rig frame with %d + %d features exceeds the LDS occupancy table", nl, nr);
+        lds_occ = std::max(lds_occ, (slots + 63) & ~(size_t)63);
+        lds_full = std::max(lds_full, ((slots + 15) & ~(size_t)15) + orbm::rig_side_bytes(nl, ncell) + orbm::rig_side_bytes(nr, ncell));
+        o.sf = blob.put(side[0]->scale_factors, sizeof(float) * side[0]->n_levels);
+        o.l2r = blob.put(q.rig->left_to_right, sizeof(int32_t) * nl); o.r2l = blob.put(q.rig->right_to_left, sizeof(int32_t) * nr);
+        if (!last_mode) {
+            const OrbmRigMapPoints* p = q.mp;
+            const size_t n = p->n;
+            o.valid = blob.put(p->in_view, n); o.u = blob.put(p->proj_u, 4 * n); o.v = blob.put(p->proj_v, 4 * n);
+            o.level = blob.put(p->pred_level, 4 * n); o.vc = blob.put(p->view_cos, 4 * n);
+            o.valid_r = blob.put(p->in_view_r, n); o.u_r = blob.put(p->proj_u_r, 4 * n); o.v_r = blob.put(p->proj_v_r, 4 * n);
+            o.level_r = blob.put(p->pred_level_r, 4 * n); o.vc_r = blob.put(p->view_cos_r, 4 * n);
+            o.dep = blob.put(p->track_depth, 4 * n); o.bad = blob.put(p->bad, n);
+            o.dmp = blob.put(p->desc, 32 * n); o.obs = blob.put(p->has_obs, n);
+            o.angl = o.logs = o.logb = 0;
+        } else {
+            const OrbmRigLastPoints* p = q.last;
+            const size_t n = p->n;
+            o.valid = blob.put(p->valid, n); o.u = blob.put(p->proj_u, 4 * n); o.v = blob.put(p->proj_v, 4 * n);
+            o.u_r = blob.put(p->proj_u_r, 4 * n); o.v_r = blob.put(p->proj_v_r, 4 * n);
+            o.level = blob.put(p->octave, 4 * n); o.angl = blob.put(p->angle, p->angle ? 4 * n : 0);
+            o.dmp = blob.put(p->desc, 32 * n); o.obs = blob.put(p->has_obs, n);
+            o.logs = blob.reserve(sizeof(int32_t) * 2 * std::max(n, (size_t)1)); o.logb = blob.reserve(sizeof(int32_t) * 2 * std::max(n, (size_t)1));
+            o.vc = o.valid_r = o.level_r = o.vc_r = o.dep = o.bad = 0;
+        }
+    }
+    // in/out and output arrays of all jobs sit together at the end: one copy brings every result back
+    const size_t out_begin = (m->h_blob.size() + 15) & ~(size_t)15;
+    for (int j = 0; j < n_jobs; j++) {
+        const RigJob& q = jobs[j];
+        const size_t slots = (size_t)q.rig->left.n + q.rig->right.n;
+        offs[j].assign = blob.put(q.assign, sizeof(int32_t) * slots); offs[j].occ = blob.put(q.occupied, slots);
+        offs[j].nm = blob.reserve(sizeof(int32_t));
+    }
+    if (int e = m->ensure(m->h_blob.size())) return e;
+    uint8_t* base = m->d_blob;
+    orbm::RigArgs* args = (orbm::RigArgs*)(m->h_blob.data() + oargs);
+    orbm::ProjArgs* grids = (orbm::ProjArgs*)(m->h_blob.data() + ogrid);
+    for (int j = 0; j < n_jobs; j++) {
+        const RigJob& q = jobs[j];
+        const Off& o = offs[j];
+        const OrbmFrame* side[2] = {&q.rig->left, &q.rig->right};
+        orbm::RigArgs A{};
+        for (int s = 0; s < 2; s++) {
+            const OrbmFrame* f = side[s];
+            const SideOff& so = o.s[s];
+            orbm::ProjFrameDev& F = s ? A.R : A.L;
+            F.x = (const float*)(base + so.x); F.y = (const float*)(base + so.y); F.octave = (const int32_t*)(base + so.oct);
+            F.angle = (const float*)(base + so.ang); F.desc = base + so.desc;
+            F.cell_off = (const int32_t*)(base + so.coff); F.cell_feat = (const int32_t*)(base + so.cfeat);
+            F.scale_factors = (const float*)(base + o.sf);
+            F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y; F.winv = so.winv; F.hinv = so.hinv;
+            F.n = f->n; F.cols = f->grid_cols; F.rows = f->grid_rows; F.n_levels = f->n_levels;
+            F.u_right = nullptr;
+            orbm::ProjArgs G{};
+            G.F = F;
+            grids[2 * j + s] = G;
+        }
+        A.l2r = (const int32_t*)(base + o.l2r); A.r2l = (const int32_t*)(base + o.r2l);
+        A.n_pts = last_mode ? q.last->n : q.mp->n;
+        A.valid = base + o.valid; A.u = (const float*)(base + o.u); A.v = (const float*)(base + o.v);
+        A.level = (const int32_t*)(base + o.level); A.view_cos = (const float*)(base + o.vc);
+        A.valid_r = base + o.valid_r; A.u_r = (const float*)(base + o.u_r); A.v_r = (const float*)(base + o.v_r);
+        A.level_r = (const int32_t*)(base + o.level_r); A.view_cos_r = (const float*)(base + o.vc_r);
+        A.depth = (const float*)(base + o.dep); A.bad = base + o.bad; A.angle = (const float*)(base + o.angl);
+        A.desc = base + o.dmp; A.has_obs = base + o.obs;
+        A.th = th; A.th_far = th_far; A.nnratio = nnratio; A.far_points = far_points; A.check_ori = check_ori;
+        A.level_window = q.level_window; A.last_mode = last_mode;
+        A.assign = (int32_t*)(base + o.assign); A.occupied = base + o.occ;
+        A.log_slot = (int32_t*)(base + o.logs); A.log_bin = (int32_t*)(base + o.logb); A.n_matches = (int32_t*)(base + o.nm);
+        args[j] = A;
+    }
+    const bool stage = lds_full <= lds_budget;      // selected per launch: every frame of the batch fits, or none is staged
+    const size_t lds = stage ? lds_full : lds_occ;
+    for (hipEvent_t& e : m->rig_ev)
+        if (!e) ORBX_HIP(hipEventCreate(&e));
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipEventRecord(m->rig_ev[0], m->stream));
+    if (device_grid) {
+        int n_pow2 = 2;
+        while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
+        hipLaunchKernelGGL(orbm::k_grid, dim3(2 * n_jobs), dim3(256), (size_t)n_pow2 * 8, m->stream, (const orbm::ProjArgs*)(base + ogrid), n_pow2);
+    }
+    if (stage) {
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_rig<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(orbm::k_rig<true>, dim3(n_jobs), dim3(orbm::kRigThreads), lds, m->stream, (const orbm::RigArgs*)(base + oargs));
+    } else {
+        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_rig<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(orbm::k_rig<false>, dim3(n_jobs), dim3(orbm::kRigThreads), lds, m->stream, (const orbm::RigArgs*)(base + oargs));
+    }
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(m->rig_ev[1], m->stream));
+    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, m->h_blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipStreamSynchronize(m->stream));
+    ORBX_HIP(hipEventElapsedTime(&m->rig_kernel_ms, m->rig_ev[0], m->rig_ev[1]));
+    for (int j = 0; j < n_jobs; j++) {
+        const Off& o = offs[j];
+        const size_t slots = (size_t)jobs[j].rig->left.n + jobs[j].rig->right.n;
+        if (slots > 0) {
+            std::memcpy(jobs[j].assign, m->h_blob.data() + o.assign, sizeof(int32_t) * slots);
+            std::memcpy(jobs[j].occupied, m->h_blob.data() + o.occ, slots);
+        }
+        std::memcpy(&jobs[j].n_matches, m->h_blob.data() + o.nm, sizeof(int32_t));
+    }
+    return ORBX_OK;
+}
+
+extern "C" {
+
+int orbm_rig_search_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const OrbmRigLastPoints* last, const int32_t* assign, const uint8_t* occupied)
+{
+    return rig_check(rig, mp, last, assign, occupied);
+}
+
+int orbm_search_by_projection_rig(orbm_matcher* m, const OrbmRigFrame* rig, const OrbmRigMapPoints* pts, float th, int far_points, float th_far, float nnratio,
+                                  int32_t* assign, uint8_t* occupied)
+{
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    if (!pts) return fail(ORBX_ERR_ARG, "NULL map points");
+    RigJob q{rig, pts, nullptr, 0, assign, occupied, 0};
+    const int r = run_rig_jobs(m, &q, 1, 0, th, far_points, th_far, nnratio, 0);
+    return r ? r : q.n_matches;
+}
+
+int orbm_search_by_projection_last_rig(orbm_matcher* m, const OrbmRigFrame* rig, const OrbmRigLastPoints* pts, float th, int level_window, int check_orientation,
+                                       int32_t* assign, uint8_t* occupied)
+{
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    if (!pts) return fail(ORBX_ERR_ARG, "NULL last-frame points");
+    RigJob q{rig, nullptr, pts, level_window, assign, occupied, 0};
+    const int r = run_rig_jobs(m, &q, 1, 1, th, 0, 0.f, 0.f, check_orientation ? 1 : 0);
+    return r ? r : q.n_matches;
+}
+
+int orbm_search_by_projection_rig_batch(orbm_matcher* m, OrbmRigMapQuery* queries, int n_frames, float th, int far_points, float th_far, float nnratio)
+{
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    if (!queries || n_frames < 1) return fail(ORBX_ERR_ARG, "no queries");
+    std::vector<RigJob> jobs(n_frames);
+    for (int j = 0; j < n_frames; j++) {
+        if (!queries[j].pts) return fail(ORBX_ERR_ARG, "query %d: NULL map points", j);
+        jobs[j] = RigJob{queries[j].rig, queries[j].pts, nullptr, 0, queries[j].assign, queries[j].occupied, 0};
+    }
+    if (int r = run_rig_jobs(m, jobs.data(), n_frames, 0, th, far_points, th_far, nnratio, 0)) return r;
+    for (int j = 0; j < n_frames; j++) queries[j].n_matches = jobs[j].n_matches;
+    return ORBX_OK;
+}
+
+int orbm_search_by_projection_last_rig_batch(orbm_matcher* m, OrbmRigLastQuery* queries, int n_frames, float th, int check_orientation)
+{
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    if (!queries || n_frames < 1) return fail(ORBX_ERR_ARG, "no queries");
+    std::vector<RigJob> jobs(n_frames);
+    for (int j = 0; j < n_frames; j++) {
+        if (!queries[j].pts) return fail(ORBX_ERR_ARG, "query %d: NULL last-frame points", j);
+        jobs[j] = RigJob{queries[j].rig, nullptr, queries[j].pts, queries[j].level_window, queries[j].assign, queries[j].occupied, 0};
+    }
+    if (int r = run_rig_jobs(m, jobs.data(), n_frames, 1, th, 0, 0.f, 0.f, check_orientation ? 1 : 0)) return r;
+    for (int j = 0; j < n_frames; j++) queries[j].n_matches = jobs[j].n_matches;
+    return ORBX_OK;
+}
+
+float orbm_rig_search_last_kernel_ms(const orbm_matcher* m) { return m ? m->rig_kernel_ms : 0.f; }
+
+}  // extern "C"

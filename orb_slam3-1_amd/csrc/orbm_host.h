@@ -1,5 +1,5 @@
-// Host-side state of the orbm_matcher handle and the blob packer its entry points share (orbm_matcher.hip and
-// orbm_new_points.hip): every host-buffer entry packs its arrays into one pinned blob and moves them with one copy.
+// Host-side state of the orbm_matcher handle and the blob packer its entry points share (orbm_matcher.hip, orbm_new_points.hip
+// and stereo_fisheye.hip): every host-buffer entry packs its arrays into one pinned blob and moves them with one copy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
@@ -51,22 +52,40 @@ struct PinnedBytes {
     }
 };
 
+// two events around the kernels of an entry, created on first use; ms is the kernel time of the entry's last call
+struct KernelTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms = 0.f;
+    ~KernelTimer()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create()                        // (before the upload: nothing may fail between the copies and the launch)
+    {
+        for (hipEvent_t& e : ev)
+            if (!e) ORBX_HIP(hipEventCreate(&e));
+        return ORBX_OK;
+    }
+    int start(hipStream_t s) { ORBX_HIP(hipEventRecord(ev[0], s)); return ORBX_OK; }
+    int stop(hipStream_t s) { ORBX_HIP(hipEventRecord(ev[1], s)); return ORBX_OK; }
+    int read() { ORBX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); return ORBX_OK; }      // after the stream was synchronised
+};
+
 struct orbm_matcher {
     int device = 0;
     hipStream_t stream = nullptr;
     uint8_t* d_blob = nullptr;
     size_t blob_cap = 0;
     PinnedBytes h_blob;
+    std::vector<void*> h_fields;        // Blob's record of the pointer fields it has to bind
     uint8_t* d_ws = nullptr;            // workspace of the device-resident batch entries (SoA key points, grids, logs, job table)
     size_t ws_cap = 0;
     float* d_scale = nullptr;           // scale factors of the last device-resident call
     float h_scale[32] = {};             // ... staged here: the asynchronous copy must not read the caller's array after the call returned
-    hipEvent_t nmp_ev[2] = {nullptr, nullptr};      // orbm_create_new_map_points: events around its one kernel (created on first use)
-    float nmp_kernel_ms = 0.f;
-    hipEvent_t sfe_ev[2] = {nullptr, nullptr};      // orbm_stereo_fisheye: events around its two kernels (created on first use)
-    float sfe_kernel_ms = 0.f;
-    hipEvent_t rig_ev[2] = {nullptr, nullptr};      // the rig-frame tracking searches: events around k_grid + k_rig (created on first use)
-    float rig_kernel_ms = 0.f;
+    KernelTimer nmp_timer;              // orbm_create_new_map_points: its one kernel
+    KernelTimer sfe_timer;              // orbm_stereo_fisheye: its two kernels
+    KernelTimer rig_timer;              // the rig-frame tracking searches: k_grid + k_rig
 
     int ensure(size_t bytes)
     {
@@ -80,17 +99,72 @@ struct orbm_matcher {
     }
 };
 
-struct Blob {                   // host-side packer: every array is appended 16-byte aligned, device address = base + offset
+// Host-side packer.  Every array is appended 16-byte aligned and its place goes straight into the pointer field of the kernel's
+// argument struct: the field first holds the offset, bind(base) -- once, after the device blob is known -- turns every such field
+// into base + offset.  Counts are in elements of the field's type.
+// RULE: an argument struct lives in storage that does not move between its first in() and bind() -- the stack, or a std::vector
+// sized before packing -- because the packer remembers the fields' addresses.  A struct the kernel reads from the blob gets a
+// slot<T>() and is copied there with store() after bind().
+// Inputs go first, outputs last: begin_out() / size() mark the split, so that upload and download are one copy each.
+struct Blob {
     PinnedBytes& buf;
-    explicit Blob(PinnedBytes& b) : buf(b) { buf.clear(); }
-    size_t put(const void* src, size_t bytes)
+    std::vector<void*>& fields;         // the fields to bind (the caller's vector: reused across calls, no allocation in steady state)
+    uint8_t* base = nullptr;
+    Blob(PinnedBytes& b, std::vector<void*>& f) : buf(b), fields(f) { buf.clear(); fields.clear(); }
+    explicit Blob(orbm_matcher* m) : Blob(m->h_blob, m->h_fields) {}
+    size_t size() const { return buf.size(); }
+    size_t begin_out() const { return (buf.size() + 15) & ~(size_t)15; }
+
+    // a required array (src == NULL with count > 0: zeros); returns its offset, like out() and inout()
+    template <class P> size_t in(P& field, const void* src, size_t count)
+    {
+        const size_t off = append(src, count * sizeof(*field));
+        note(field, off);
+        return off;
+    }
+    // an optional array: absent (src == NULL) it is a NON-NULL pointer to zero bytes, which no kernel reads
+    template <class P> void in_opt(P& field, const void* src, size_t count) { in(field, src, src ? count : 0); }
+    // fields the kernel does not read in this mode: non-null pointers to zero bytes as well
+    template <class... P> void none(P&... field) { (in(field, nullptr, 0), ...); }
+    // an optional array whose absence the kernel branches on: absent it is a real nullptr and takes no place
+    template <class P> void in_or_null(P& field, const void* src, size_t count) { if (src) in(field, src, count); else field = nullptr; }
+    // an array the kernel writes (zeros), and one it reads and writes
+    template <class P> size_t out(P& field, size_t count) { return in(field, nullptr, count); }
+    template <class P> size_t inout(P& field, const void* src, size_t count) { return in(field, src, count); }
+    // a field that shares the array of another, already packed, field
+    template <class P, class Q> void alias(P& field, const Q& packed) { note(field, (size_t)reinterpret_cast<uintptr_t>(packed)); }
+    // room for n structs T that the kernel reads from the blob
+    template <class T> size_t slot(size_t n) { return append(nullptr, sizeof(T) * n); }
+
+    void bind(uint8_t* device_base)
+    {
+        base = device_base;
+        for (void* f : fields) {
+            uintptr_t v;
+            std::memcpy(&v, f, sizeof(v));
+            v += reinterpret_cast<uintptr_t>(base);
+            std::memcpy(f, &v, sizeof(v));
+        }
+        fields.clear();
+    }
+    template <class T> void store(size_t slot_off, const T* structs, size_t n) { std::memcpy(buf.data() + slot_off, structs, sizeof(T) * n); }
+    template <class T> const T* device(size_t slot_off) const { return (const T*)(base + slot_off); }
+    template <class T> T* host(const T* bound) { return (T*)(buf.data() + ((const uint8_t*)bound - base)); }   // host copy of a bound field's array
+
+private:
+    size_t append(const void* src, size_t bytes)
     {
         const size_t off = (buf.size() + 15) & ~(size_t)15;
         buf.resize(off + bytes);
         if (src && bytes) std::memcpy(buf.data() + off, src, bytes);
         return off;
     }
-    size_t reserve(size_t bytes) { return put(nullptr, bytes); }
+    template <class P> void note(P& field, size_t off)
+    {
+        static_assert(std::is_pointer<P>::value && sizeof(P) == sizeof(uintptr_t), "a pointer field");
+        field = reinterpret_cast<P>((uintptr_t)off);
+        fields.push_back(&field);
+    }
 };
 
 inline bool features_unique(const OrbmFeatVec* fv, int n)

@@ -1601,70 +1601,142 @@ __global__ __launch_bounds__(256) void k_normal_depth(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
+namespace orbm {
+
+// What the two search kernels carve out of s_dyn, for a launch whose largest frame has n features and ncell grid cells (u_right is
+// counted whether or not a frame has it).  k_proj: occupancy [| descriptors, x, y, octave, CSR entries, u_right: 52 B a feature |
+// cell table].  k_proj_par: two int tables a feature | occupancy [| descriptors, octave, u_right: 40 B | cell table | the 16-byte
+// records in grid order].  The bracketed part only when the frame is staged.
+__host__ __device__ inline size_t proj_par_table_bytes(size_t n) { return 8 * ((n + 15) & ~(size_t)15); }
+__host__ __device__ inline size_t proj_unstaged_bytes(size_t n, bool par)
+{
+    const size_t occ = (n + 63) & ~(size_t)63;
+    return (occ > 64 ? occ : 64) + (par ? proj_par_table_bytes(n) : 0);
+}
+__host__ __device__ inline size_t proj_staged_bytes(size_t n, size_t ncell, bool par)
+{
+    return ((n + 15) & ~(size_t)15) + n * (par ? 40 : 52) + (ncell + 1) * 4 + 64 + (par ? proj_par_table_bytes(n) + n * 16 + 32 : 0);
+}
+
+}  // namespace orbm
+
 namespace {
 
-struct PairOffsets {
-    size_t d1, v1, a1, node1, off1, feat1, d2, v2, a2, node2, off2, feat2, match, matched2, nmatch;
-    int n1, n2, nn1, nn2, serial, n_out;
-};
+// ---- launch helpers ----
 
-}  // namespace
+// Dynamic LDS a kernel of the set may ask for: the CU's 160 KB minus the largest static LDS of the set (block tables, histogram ...)
+// and a margin.  (A fixed 150 KB ignored the static part: frames of about 1 700 .. 1 900 features -- staged size between the true
+// budget and 150 KB -- made hipFuncSetAttribute fail; found by probing the feature counts around the limit.)
+template <auto... Kernels>
+size_t dynamic_lds_budget()
+{
+    static const size_t budget = [] {
+        size_t st = 0;
+        for (const void* k : {(const void*)Kernels...}) {
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, k) == hipSuccess) st = std::max(st, (size_t)fa.sharedSizeBytes);
+        }
+        (void)hipGetLastError();
+        return 160 * 1024 - std::max(st, (size_t)4096) - 1024;
+    }();
+    return budget;
+}
+
+// the <true> (frame staged in LDS) or <false> instance of a STAGE kernel template, a workgroup per job
+template <class Args>
+int launch_staged(void (*staged)(const Args*), void (*unstaged)(const Args*), bool stage, int n_jobs, int threads, size_t lds, hipStream_t st, const Args* jobs)
+{
+    void (*const k)(const Args*) = stage ? staged : unstaged;
+    ORBX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(n_jobs), dim3(threads), lds, st, jobs);
+    return ORBX_OK;
+}
+
+// Frame::AssignFeaturesToGrid on the device: a workgroup per frame (jobs[b].F), frames of at most 8192 features (the LDS sort)
+int launch_grid(hipStream_t st, const orbm::ProjArgs* jobs, int n_blocks, size_t max_n)
+{
+    int n_pow2 = 2;
+    while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
+    ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
+    hipLaunchKernelGGL(orbm::k_grid, dim3(n_blocks), dim3(256), (size_t)n_pow2 * 8, st, jobs, n_pow2);
+    return ORBX_OK;
+}
+
+// Which projection-search kernel a launch takes and its dynamic LDS.  k_proj_par (64 points at a time) keeps two int tables per
+// feature in LDS; frames too large for them keep the sequential k_proj -- where the entry has it (allow_sequential), else par comes
+// back false.  The frame is staged when all of it fits as well.
+struct ProjLdsPlan { bool par, stage; size_t bytes; };
+ProjLdsPlan proj_lds_plan(size_t max_n, size_t max_cells, bool allow_sequential)
+{
+    static const bool force_seq = std::getenv("ORBM_PROJ_SEQUENTIAL") != nullptr;      // measurement knob (tools/proj_timing.py)
+    const size_t budget = dynamic_lds_budget<orbm::k_proj_par<true>, orbm::k_proj_par<false>, orbm::k_proj<true>, orbm::k_proj<false>>();
+    ProjLdsPlan p;
+    p.par = !(allow_sequential && force_seq) && orbm::proj_par_table_bytes(max_n) + ((max_n + 63) & ~(size_t)63) + 1024 <= budget;
+    p.stage = orbm::proj_staged_bytes(max_n, max_cells, p.par) <= budget;
+    p.bytes = p.stage ? orbm::proj_staged_bytes(max_n, max_cells, p.par) : orbm::proj_unstaged_bytes(max_n, p.par);
+    return p;
+}
+
+int launch_proj(const ProjLdsPlan& p, hipStream_t st, const orbm::ProjArgs* jobs, int n_jobs)
+{
+    if (p.par) return launch_staged(orbm::k_proj_par<true>, orbm::k_proj_par<false>, p.stage, n_jobs, orbm::kProjThreads, p.bytes, st, jobs);
+    return launch_staged(orbm::k_proj<true>, orbm::k_proj<false>, p.stage, n_jobs, 64, p.bytes, st, jobs);
+}
+
+// ---- SearchByBoW ----
+
+struct PairOffsets { size_t match, nmatch; int n_out; };       // what orbm_bow_plan_fetch reads of a packed pair
+
+// one side of a SearchByBoW pair; host pointers
+struct BowSide { const uint8_t* desc; int n; const uint8_t* valid; const float* angle; const OrbmFeatVec* fv; };
+
+// Appends one pair, checked by the caller, and fills its descriptor.  kfkf: the KF-KF variant (valid2, matched2, a match per feature
+// of side 1); otherwise s2.valid is not read.
+void pack_bow_pair(Blob& blob, bool kfkf, const BowSide& s1, const BowSide& s2, orbm::BowPairDev& D, PairOffsets& o)
+{
+    static const int32_t zero_off[1] = {0};
+    auto side = [&](const BowSide& s, const uint8_t* valid, const uint8_t*& d, const uint8_t*& v, const float*& a, const uint32_t*& node,
+                    const int32_t*& off, const uint32_t*& feat, int32_t& n, int32_t& nn) {
+        n = s.n; nn = s.fv->n_nodes;
+        blob.in(d, s.desc, (size_t)n * 32); blob.in_opt(v, valid, n); blob.in_opt(a, s.angle, n);
+        blob.in(node, s.fv->node_id, nn); blob.in(off, nn ? s.fv->offset : zero_off, nn + 1);
+        blob.in(feat, s.fv->feat, nn ? s.fv->offset[nn] : 0);
+    };
+    side(s1, s1.valid, D.d1, D.v1, D.a1, D.node1, D.off1, D.feat1, D.n1, D.nn1);
+    side(s2, kfkf ? s2.valid : nullptr, D.d2, D.v2, D.a2, D.node2, D.off2, D.feat2, D.n2, D.nn2);
+    D.serial = !features_unique(s2.fv, s2.n) || (kfkf && !features_unique(s1.fv, s1.n));
+    o.n_out = kfkf ? s1.n : s2.n;
+    o.match = blob.out(D.match, std::max(o.n_out, 1));
+    blob.out(D.matched2, kfkf ? std::max(s2.n, 1) : 0);
+    o.nmatch = blob.out(D.n_matches, 1);
+}
 
 template <bool KFKF>
-static int bow_batch(orbm_matcher* m, int n_pairs,
-                     const uint8_t* const* d1, const int* n1, const uint8_t* const* v1, const float* const* a1, const OrbmFeatVec* const* fv1,
-                     const uint8_t* const* d2, const int* n2, const uint8_t* const* v2, const float* const* a2, const OrbmFeatVec* const* fv2,
-                     float nnratio, int check_ori, int32_t* const* match_out, int32_t* nmatches_out)
+int bow_batch(orbm_matcher* m, int n_pairs, const BowSide* s1, const BowSide* s2, float nnratio, int check_ori, int32_t* const* match_out, int32_t* nmatches_out)
 {
     if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
+    Blob blob(m);
+    std::vector<orbm::BowPairDev> descs(n_pairs);
     std::vector<PairOffsets> po(n_pairs);
-    const size_t desc_off = blob.reserve(sizeof(orbm::BowPairDev) * n_pairs);
-    static const int32_t zero_off[1] = {0};
+    const size_t desc_off = blob.slot<orbm::BowPairDev>(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
+        const BowSide& a = s1[p]; const BowSide& b = s2[p];
         int r;
-        if (n1[p] < 0 || n2[p] < 0) return fail(ORBX_ERR_ARG, "negative feature count");
-        if ((n1[p] > 0 && (!d1[p] || !v1[p])) || (n2[p] > 0 && !d2[p])) return fail(ORBX_ERR_ARG, "NULL descriptor/valid array");
-        if (KFKF && n2[p] > 0 && !v2[p]) return fail(ORBX_ERR_ARG, "NULL valid2");
-        if (check_ori && ((n1[p] > 0 && !a1[p]) || (n2[p] > 0 && !a2[p]))) return fail(ORBX_ERR_ARG, "NULL angle array");
-        if ((r = check_fv(fv1[p], n1[p], "fv1")) || (r = check_fv(fv2[p], n2[p], "fv2"))) return r;
-        PairOffsets& o = po[p];
-        o.n1 = n1[p]; o.n2 = n2[p]; o.nn1 = fv1[p]->n_nodes; o.nn2 = fv2[p]->n_nodes;
-        o.serial = !features_unique(fv2[p], n2[p]) || (KFKF && !features_unique(fv1[p], n1[p]));
-        o.d1 = blob.put(d1[p], (size_t)o.n1 * 32); o.v1 = blob.put(v1[p], o.n1);
-        o.a1 = blob.put(a1[p], a1[p] ? sizeof(float) * o.n1 : 0);
-        o.node1 = blob.put(fv1[p]->node_id, sizeof(uint32_t) * o.nn1);
-        o.off1 = blob.put(o.nn1 ? fv1[p]->offset : zero_off, sizeof(int32_t) * (o.nn1 + 1));
-        o.feat1 = blob.put(fv1[p]->feat, sizeof(uint32_t) * (o.nn1 ? fv1[p]->offset[o.nn1] : 0));
-        o.d2 = blob.put(d2[p], (size_t)o.n2 * 32); o.v2 = blob.put(KFKF ? v2[p] : nullptr, KFKF ? o.n2 : 0);
-        o.a2 = blob.put(a2[p], a2[p] ? sizeof(float) * o.n2 : 0);
-        o.node2 = blob.put(fv2[p]->node_id, sizeof(uint32_t) * o.nn2);
-        o.off2 = blob.put(o.nn2 ? fv2[p]->offset : zero_off, sizeof(int32_t) * (o.nn2 + 1));
-        o.feat2 = blob.put(fv2[p]->feat, sizeof(uint32_t) * (o.nn2 ? fv2[p]->offset[o.nn2] : 0));
-        o.n_out = KFKF ? o.n1 : o.n2;
-        o.match = blob.reserve(sizeof(int32_t) * std::max(o.n_out, 1));
-        o.matched2 = blob.reserve(KFKF ? std::max(o.n2, 1) : 0);
-        o.nmatch = blob.reserve(sizeof(int32_t));
+        if (a.n < 0 || b.n < 0) return fail(ORBX_ERR_ARG, "negative feature count");
+        if ((a.n > 0 && (!a.desc || !a.valid)) || (b.n > 0 && !b.desc)) return fail(ORBX_ERR_ARG, "NULL descriptor/valid array");
+        if (KFKF && b.n > 0 && !b.valid) return fail(ORBX_ERR_ARG, "NULL valid2");
+        if (check_ori && ((a.n > 0 && !a.angle) || (b.n > 0 && !b.angle))) return fail(ORBX_ERR_ARG, "NULL angle array");
+        if ((r = check_fv(a.fv, a.n, "fv1")) || (r = check_fv(b.fv, b.n, "fv2"))) return r;
+        pack_bow_pair(blob, KFKF, a, b, descs[p], po[p]);
     }
-    int r = m->ensure(m->h_blob.size());
+    int r = m->ensure(blob.size());
     if (r) return r;
+    blob.bind(m->d_blob);
+    blob.store(desc_off, descs.data(), n_pairs);
     uint8_t* base = m->d_blob;
-    orbm::BowPairDev* descs = (orbm::BowPairDev*)(m->h_blob.data() + desc_off);
-    for (int p = 0; p < n_pairs; p++) {
-        const PairOffsets& o = po[p];
-        orbm::BowPairDev D;
-        D.d1 = base + o.d1; D.v1 = base + o.v1; D.a1 = (const float*)(base + o.a1);
-        D.node1 = (const uint32_t*)(base + o.node1); D.off1 = (const int32_t*)(base + o.off1); D.feat1 = (const uint32_t*)(base + o.feat1);
-        D.d2 = base + o.d2; D.v2 = base + o.v2; D.a2 = (const float*)(base + o.a2);
-        D.node2 = (const uint32_t*)(base + o.node2); D.off2 = (const int32_t*)(base + o.off2); D.feat2 = (const uint32_t*)(base + o.feat2);
-        D.n1 = o.n1; D.n2 = o.n2; D.nn1 = o.nn1; D.nn2 = o.nn2;
-        D.match = (int32_t*)(base + o.match); D.matched2 = base + o.matched2; D.n_matches = (int32_t*)(base + o.nmatch);
-        D.serial = o.serial;
-        descs[p] = D;
-    }
-    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(orbm::k_bow<KFKF>, dim3(n_pairs), dim3(orbm::kBowThreads), 0, m->stream, (const orbm::BowPairDev*)(base + desc_off), nnratio, check_ori);
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), blob.size(), hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(orbm::k_bow<KFKF>, dim3(n_pairs), dim3(orbm::kBowThreads), 0, m->stream, blob.device<orbm::BowPairDev>(desc_off), nnratio, check_ori);
     ORBX_HIP(hipGetLastError());
     for (int p = 0; p < n_pairs; p++) {
         const PairOffsets& o = po[p];
@@ -1675,16 +1747,23 @@ static int bow_batch(orbm_matcher* m, int n_pairs,
     return ORBX_OK;
 }
 
-// Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:472-503, 812-822): host-side flattening of mGrid into CSR.
-static int build_grid(const OrbmFrame* f, std::vector<int32_t>& cell_off, std::vector<int32_t>& cell_feat, float& winv, float& hinv)
+// ---- frames ----
+
+// The checks every entry makes of a host frame; `who` prefixes the messages (the rig names the side).  n < 2^21: the search keys hold
+// the feature index in 21 bits.  (A launch builds its grids on the device only when none of its frames has more than 8192 features:
+// neither this limit nor build_grid's limit on a cell can bite there.)
+int check_frame(const OrbmFrame* f, const char* who = "", int max_levels = 1 << 30)
 {
-    if (!f || f->n < 0 || f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20))
-        return fail(ORBX_ERR_ARG, "bad frame grid");
-    if (f->n > 0 && (!f->x || !f->y || !f->octave || !f->desc)) return fail(ORBX_ERR_ARG, "NULL frame arrays");
-    if (!f->scale_factors || f->n_levels < 1) return fail(ORBX_ERR_ARG, "NULL scale factors");
-    if (f->n >= (1 << 21)) return fail(ORBX_ERR_ARG, "too many features");
-    winv = (float)f->grid_cols / (f->max_x - f->min_x);         // mfGridElementWidthInv (src/Frame.cc:338)
-    hinv = (float)f->grid_rows / (f->max_y - f->min_y);
+    if (!f || f->n < 0 || f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20)) return fail(ORBX_ERR_ARG, "%sbad frame grid", who);
+    if (f->n > 0 && (!f->x || !f->y || !f->octave || !f->desc)) return fail(ORBX_ERR_ARG, "%sNULL frame arrays", who);
+    if (!f->scale_factors || f->n_levels < 1 || f->n_levels > max_levels) return fail(ORBX_ERR_ARG, "%sNULL scale factors or bad n_levels", who);
+    if (f->n >= (1 << 21)) return fail(ORBX_ERR_ARG, "%stoo many features", who);
+    return ORBX_OK;
+}
+
+// Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:472-503, 812-822): host-side flattening of mGrid into CSR.
+int build_grid(const OrbmFrame* f, float winv, float hinv, std::vector<int32_t>& cell_off, std::vector<int32_t>& cell_feat, const char* who)
+{
     const int ncell = f->grid_cols * f->grid_rows;
     std::vector<int32_t> cell_of(f->n);
     cell_off.assign(ncell + 1, 0);
@@ -1696,7 +1775,7 @@ static int build_grid(const OrbmFrame* f, std::vector<int32_t>& cell_off, std::v
         cell_off[cell_of[i] + 1]++;
     }
     for (int c = 0; c < ncell; c++) {
-        if (cell_off[c + 1] >= (1 << 14)) return fail(ORBX_ERR_ARG, "grid cell %d holds %d features (limit 16383)", c, cell_off[c + 1]);
+        if (cell_off[c + 1] >= (1 << 14)) return fail(ORBX_ERR_ARG, "%sgrid cell %d holds %d features (limit 16383)", who, c, cell_off[c + 1]);
         cell_off[c + 1] += cell_off[c];
     }
     cell_feat.assign(std::max(cell_off[ncell], 1), 0);
@@ -1705,196 +1784,132 @@ static int build_grid(const OrbmFrame* f, std::vector<int32_t>& cell_off, std::v
     return ORBX_OK;
 }
 
+// Checks a host frame and appends it: key points, descriptors and the grid as CSR -- built here, or with device_grid only reserved
+// for k_grid (launch_grid) to fill.  with_angle / with_scale: the arrays the entry's kernel reads besides (its checks ask for the
+// scale factors either way).  u_right stays nullptr: a tracking search adds it.
+int stage_frame(Blob& blob, const OrbmFrame* f, bool device_grid, orbm::ProjFrameDev& F, bool with_angle = true, bool with_scale = true, const char* who = "",
+                int max_levels = 1 << 30)
+{
+    if (int e = check_frame(f, who, max_levels)) return e;
+    const int n = f->n;
+    F = orbm::ProjFrameDev{};
+    F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y;
+    F.winv = (float)f->grid_cols / (f->max_x - f->min_x);         // mfGridElementWidthInv (src/Frame.cc:338)
+    F.hinv = (float)f->grid_rows / (f->max_y - f->min_y);
+    F.n = n; F.cols = f->grid_cols; F.rows = f->grid_rows;
+    blob.in(F.x, f->x, n); blob.in(F.y, f->y, n); blob.in(F.octave, f->octave, n);
+    if (with_angle) blob.in_opt(F.angle, f->angle, n);
+    blob.in(F.desc, f->desc, (size_t)n * 32);
+    if (device_grid) {
+        blob.out(F.cell_off, (size_t)f->grid_cols * f->grid_rows + 1); blob.out(F.cell_feat, std::max(n, 1));
+    } else {
+        std::vector<int32_t> cell_off, cell_feat;
+        if (int e = build_grid(f, F.winv, F.hinv, cell_off, cell_feat, who)) return e;
+        blob.in(F.cell_off, cell_off.data(), cell_off.size()); blob.in(F.cell_feat, cell_feat.data(), cell_feat.size());
+    }
+    if (with_scale) { blob.in(F.scale_factors, f->scale_factors, f->n_levels); F.n_levels = f->n_levels; }
+    return ORBX_OK;
+}
+
 // one projection-search problem (a frame and the points projected into it); host pointers
 struct ProjJob {
-    const OrbmFrame* f;
-    int n_pts;
-    const uint8_t* valid; const float* u; const float* v; const int32_t* level;
+    const OrbmFrame* f = nullptr;
+    int n_pts = 0;
+    const uint8_t* valid = nullptr; const float* u = nullptr; const float* v = nullptr; const int32_t* level = nullptr;
     const float* ur = nullptr;      // M4 / M5 with a rectified-stereo frame (f->u_right != NULL); other searches never gate on it
     int level_window = 0;           // M5: ORBM_LEVELS_*
     bool stereo_gate = false;       // the entry point is one of the two tracking searches (:92-98, :1751-1757)
-    const float* view_cos; const float* depth; const uint8_t* bad;     // mode 0
-    const float* angle;                                                  // mode 1
-    const uint8_t* desc; const uint8_t* has_obs;
-    int32_t* assign; uint8_t* occupied;
-    int n_matches;      // out
+    const float* view_cos = nullptr; const float* depth = nullptr; const uint8_t* bad = nullptr;       // mode 0
+    const float* angle = nullptr;                                                                       // mode 1
+    const uint8_t* desc = nullptr; const uint8_t* has_obs = nullptr;
+    int32_t* assign = nullptr; uint8_t* occupied = nullptr;
+    int n_matches = 0;  // out
 };
 
-// Packs all jobs into one blob, ONE k_proj launch with a wave per job, copies assign / occupied / counts back.
-// Dynamic LDS a search kernel may ask for: the CU's 160 KB minus the kernel's own static LDS (block tables, histogram ...) and a
-// margin.  (A fixed 150 KB ignored the static part: frames of about 1 700 .. 1 900 features -- staged size between the true budget and
-// 150 KB -- made hipFuncSetAttribute fail; found by probing the feature counts around the limit.)
-static size_t proj_dynamic_lds_budget()
-{
-    static size_t budget = 0;
-    if (budget == 0) {
-        size_t st = 0;
-        const void* ks[4] = {(const void*)orbm::k_proj_par<true>, (const void*)orbm::k_proj_par<false>, (const void*)orbm::k_proj<true>, (const void*)orbm::k_proj<false>};
-        for (const void* k : ks) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, k) == hipSuccess) st = std::max(st, (size_t)fa.sharedSizeBytes);
-        }
-        (void)hipGetLastError();
-        budget = 160 * 1024 - std::max(st, (size_t)4096) - 1024;
-    }
-    return budget;
-}
+// what of a launch is the same for all its jobs
+struct ProjLaunch { int last_mode; float th; int far_points; float th_far, nnratio; int check_ori; float dist_th; };
 
-static int run_projection_jobs(orbm_matcher* m, ProjJob* jobs, int n_jobs, int last_mode,
-                               float th, int far_points, float th_far, float nnratio, int check_ori, float dist_th)
+// Packs all jobs into one blob, ONE search launch with a workgroup per job, copies assign / occupied / counts back.
+int run_projection_jobs(orbm_matcher* m, ProjJob* jobs, int n_jobs, const ProjLaunch& P)
 {
     if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
     if (!jobs || n_jobs < 1) return fail(ORBX_ERR_ARG, "no jobs");
     ORBX_HIP(hipSetDevice(m->device));
     (void)hipGetLastError();            // (an error an earlier, failed call left behind must not fail this one)
-    Blob blob(m->h_blob);
-    const size_t oargs = blob.reserve(sizeof(orbm::ProjArgs) * (size_t)n_jobs);
-    struct Off { size_t x, y, oct, ang, desc, coff, cfeat, sf, uright, ur, valid, u, v, level, vc, dep, bad, angl, dmp, obs, assign, occ, logf, logb, nm; float winv, hinv; };
-    std::vector<Off> offs(n_jobs);
-    std::vector<int32_t> cell_off, cell_feat;
-    size_t max_n = 0;
+    Blob blob(m);
+    std::vector<orbm::ProjArgs> args(n_jobs);
+    const size_t oargs = blob.slot<orbm::ProjArgs>(n_jobs);
+    size_t max_n = 0, max_cells = 0;
     bool device_grid = true;        // Frame::AssignFeaturesToGrid on the device (k_grid) when every frame fits its LDS sort
     for (int j = 0; j < n_jobs; j++) device_grid = device_grid && jobs[j].f && jobs[j].f->n <= 8192;
     for (int j = 0; j < n_jobs; j++) {
         const ProjJob& q = jobs[j];
         const OrbmFrame* f = q.f;
         const int n_pts = q.n_pts;
+        orbm::ProjArgs& A = args[j];
         if (n_pts < 0 || (n_pts > 0 && (!q.valid || !q.u || !q.v || !q.level || !q.desc))) return fail(ORBX_ERR_ARG, "job %d: NULL point arrays", j);
-        if (last_mode == 0 && n_pts > 0 && (!q.has_obs || !q.view_cos || !q.depth || !q.bad)) return fail(ORBX_ERR_ARG, "job %d: NULL map point arrays", j);
+        if (P.last_mode == 0 && n_pts > 0 && (!q.has_obs || !q.view_cos || !q.depth || !q.bad)) return fail(ORBX_ERR_ARG, "job %d: NULL map point arrays", j);
         if (!q.assign || !q.occupied) return fail(ORBX_ERR_ARG, "job %d: NULL assign/occupied", j);
-        Off& o = offs[j];
-        int r;
-        if (device_grid) {      // validation and the two reciprocals only: the CSR itself is built by k_grid
-            if (!f || f->n < 0 || f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20)) return fail(ORBX_ERR_ARG, "bad frame grid");
-            if (f->n > 0 && (!f->x || !f->y || !f->octave || !f->desc)) return fail(ORBX_ERR_ARG, "NULL frame arrays");
-            if (!f->scale_factors || f->n_levels < 1) return fail(ORBX_ERR_ARG, "NULL scale factors");
-            o.winv = (float)f->grid_cols / (f->max_x - f->min_x);
-            o.hinv = (float)f->grid_rows / (f->max_y - f->min_y);
-            cell_off.assign((size_t)f->grid_cols * f->grid_rows + 1, 0);
-            cell_feat.assign(std::max(f->n, 1), 0);
-        } else if ((r = build_grid(f, cell_off, cell_feat, o.winv, o.hinv))) return r;
-        if (last_mode == 1 && check_ori && n_pts > 0 && (!q.angle || !f->angle)) return fail(ORBX_ERR_ARG, "job %d: NULL angle arrays", j);
+        if (int r = stage_frame(blob, f, device_grid, A.F)) return r;
+        if (P.last_mode == 1 && P.check_ori && n_pts > 0 && (!q.angle || !f->angle)) return fail(ORBX_ERR_ARG, "job %d: NULL angle arrays", j);
         const bool gate = q.stereo_gate && f->u_right != nullptr && f->n > 0;
         if (gate && n_pts > 0 && !q.ur) return fail(ORBX_ERR_ARG, "job %d: the frame has u_right but the points have no proj_ur", j);
         if (q.level_window < ORBM_LEVELS_AROUND || q.level_window > ORBM_LEVELS_BACKWARD) return fail(ORBX_ERR_ARG, "job %d: bad level_window %d", j, q.level_window);
         for (int i = 0; i < n_pts; i++)
             if (q.valid[i] && (q.level[i] < 0 || q.level[i] >= f->n_levels)) return fail(ORBX_ERR_ARG, "job %d point %d: level %d out of range", j, i, q.level[i]);
         if ((size_t)f->n + 256 > 150 * 1024) return fail(ORBX_ERR_ARG, "frame with %d features exceeds the LDS occupancy table", f->n);
-        const int n = f->n;
-        max_n = std::max(max_n, (size_t)n);
-        o.x = blob.put(f->x, sizeof(float) * n); o.y = blob.put(f->y, sizeof(float) * n);
-        o.oct = blob.put(f->octave, sizeof(int32_t) * n);
-        o.ang = blob.put(f->angle, f->angle ? sizeof(float) * n : 0);
-        o.desc = blob.put(f->desc, (size_t)n * 32);
-        o.coff = blob.put(cell_off.data(), sizeof(int32_t) * cell_off.size());
-        o.cfeat = blob.put(cell_feat.data(), sizeof(int32_t) * cell_feat.size());
-        o.sf = blob.put(f->scale_factors, sizeof(float) * f->n_levels);
-        o.uright = blob.put(gate ? f->u_right : nullptr, gate ? sizeof(float) * n : 0);
-        o.ur = blob.put(gate ? q.ur : nullptr, gate ? sizeof(float) * n_pts : 0);
-        o.valid = blob.put(q.valid, n_pts); o.u = blob.put(q.u, sizeof(float) * n_pts); o.v = blob.put(q.v, sizeof(float) * n_pts);
-        o.level = blob.put(q.level, sizeof(int32_t) * n_pts);
-        o.vc = blob.put(q.view_cos, q.view_cos ? sizeof(float) * n_pts : 0); o.dep = blob.put(q.depth, q.depth ? sizeof(float) * n_pts : 0);
-        o.bad = blob.put(q.bad, q.bad ? n_pts : 0); o.angl = blob.put(q.angle, q.angle ? sizeof(float) * n_pts : 0);
-        o.dmp = blob.put(q.desc, (size_t)n_pts * 32); o.obs = blob.put(q.has_obs, q.has_obs ? n_pts : 0);
-        o.logf = blob.reserve(sizeof(int32_t) * std::max(n_pts, 1)); o.logb = blob.reserve(sizeof(int32_t) * std::max(n_pts, 1));
+        max_n = std::max(max_n, (size_t)f->n);
+        max_cells = std::max(max_cells, (size_t)f->grid_cols * f->grid_rows);
+        blob.in_or_null(A.F.u_right, gate ? f->u_right : nullptr, f->n);
+        blob.in_opt(A.ur, gate ? q.ur : nullptr, n_pts);
+        blob.in(A.valid, q.valid, n_pts); blob.in(A.u, q.u, n_pts); blob.in(A.v, q.v, n_pts); blob.in(A.level, q.level, n_pts);
+        blob.in_opt(A.view_cos, q.view_cos, n_pts); blob.in_opt(A.depth, q.depth, n_pts); blob.in_opt(A.bad, q.bad, n_pts);
+        blob.in_opt(A.angle, q.angle, n_pts);
+        blob.in(A.desc, q.desc, (size_t)n_pts * 32);
+        blob.in_or_null(A.has_obs, q.has_obs, n_pts);
+        blob.out(A.log_feat, std::max(n_pts, 1)); blob.out(A.log_bin, std::max(n_pts, 1));
+        A.n_pts = n_pts; A.level_window = q.level_window; A.dist_th = P.dist_th;
+        A.th = P.th; A.th_far = P.th_far; A.nnratio = P.nnratio; A.far_points = P.far_points; A.check_ori = P.check_ori; A.last_frame_mode = P.last_mode;
     }
     // in/out and output arrays of all jobs sit together at the end: one copy brings every result back
-    const size_t out_begin = (m->h_blob.size() + 15) & ~(size_t)15;
+    const size_t out_begin = blob.begin_out();
     for (int j = 0; j < n_jobs; j++) {
-        const ProjJob& q = jobs[j];
-        const int n = q.f->n;
-        Off& o = offs[j];
-        o.assign = blob.put(q.assign, sizeof(int32_t) * n); o.occ = blob.put(q.occupied, n);
-        o.nm = blob.reserve(sizeof(int32_t));
+        const int n = jobs[j].f->n;
+        blob.inout(args[j].assign, jobs[j].assign, n); blob.inout(args[j].occupied, jobs[j].occupied, n);
+        blob.out(args[j].n_matches, 1);
     }
-    int r = m->ensure(m->h_blob.size());
-    if (r) return r;
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
+    const ProjLdsPlan plan = proj_lds_plan(max_n, max_cells, true);
+    for (int j = 0; j < n_jobs; j++) args[j].lds_frame = plan.stage ? 1 : 0;
+    blob.store(oargs, args.data(), n_jobs);
     uint8_t* base = m->d_blob;
-    orbm::ProjArgs* args = (orbm::ProjArgs*)(m->h_blob.data() + oargs);
-    for (int j = 0; j < n_jobs; j++) {
-        const ProjJob& q = jobs[j];
-        const OrbmFrame* f = q.f;
-        const Off& o = offs[j];
-        orbm::ProjArgs A;
-        A.F.x = (const float*)(base + o.x); A.F.y = (const float*)(base + o.y); A.F.octave = (const int32_t*)(base + o.oct);
-        A.F.angle = (const float*)(base + o.ang); A.F.desc = base + o.desc;
-        A.F.cell_off = (const int32_t*)(base + o.coff); A.F.cell_feat = (const int32_t*)(base + o.cfeat);
-        A.F.scale_factors = (const float*)(base + o.sf);
-        A.F.min_x = f->min_x; A.F.min_y = f->min_y; A.F.max_x = f->max_x; A.F.max_y = f->max_y; A.F.winv = o.winv; A.F.hinv = o.hinv;
-        A.F.n = f->n; A.F.cols = f->grid_cols; A.F.rows = f->grid_rows; A.F.n_levels = f->n_levels;
-        const bool gate = q.stereo_gate && f->u_right != nullptr && f->n > 0;
-        A.F.u_right = gate ? (const float*)(base + o.uright) : nullptr;
-        A.ur = (const float*)(base + o.ur); A.level_window = q.level_window;
-        A.n_pts = q.n_pts; A.valid = base + o.valid; A.u = (const float*)(base + o.u); A.v = (const float*)(base + o.v);
-        A.level = (const int32_t*)(base + o.level); A.view_cos = (const float*)(base + o.vc); A.depth = (const float*)(base + o.dep);
-        A.bad = base + o.bad; A.angle = (const float*)(base + o.angl); A.desc = base + o.dmp; A.has_obs = q.has_obs ? base + o.obs : nullptr;
-        A.dist_th = dist_th;
-        A.th = th; A.th_far = th_far; A.nnratio = nnratio; A.far_points = far_points; A.check_ori = check_ori; A.last_frame_mode = last_mode;
-        A.assign = (int32_t*)(base + o.assign); A.occupied = base + o.occ;
-        A.log_feat = (int32_t*)(base + o.logf); A.log_bin = (int32_t*)(base + o.logb); A.n_matches = (int32_t*)(base + o.nm);
-        args[j] = A;
-    }
-    size_t max_cells = 0;
-    for (int j = 0; j < n_jobs; j++) max_cells = std::max(max_cells, (size_t)jobs[j].f->grid_cols * jobs[j].f->grid_rows);
-    // k_proj_par (64 points at a time) keeps two int tables per feature in LDS; frames too large for them keep the sequential k_proj
-    static const bool force_seq = std::getenv("ORBM_PROJ_SEQUENTIAL") != nullptr;      // measurement knob (tools/proj_timing.py)
-    const size_t tabs = 8 * ((max_n + 15) & ~(size_t)15);
-    const size_t lds_budget = proj_dynamic_lds_budget();
-    const bool par = !force_seq && tabs + ((max_n + 63) & ~(size_t)63) + 1024 <= lds_budget;
-    const size_t lds_occ = std::max((max_n + 63) & ~(size_t)63, (size_t)64) + (par ? tabs : 0);
-    const size_t lds_full = ((max_n + 15) & ~(size_t)15) + max_n * (par ? 40 : 52) + (max_cells + 1) * 4 + 64 + (par ? tabs + max_n * 16 + 32 : 0);     // k_proj: descriptor, x, y, octave, CSR entry, u_right; k_proj_par: descriptor, octave, u_right + the 16-byte records in grid order
-    const bool stage = lds_full <= lds_budget;
-    const size_t lds = stage ? lds_full : lds_occ;
-    for (int j = 0; j < n_jobs; j++) args[j].lds_frame = stage ? 1 : 0;
-    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
-    if (device_grid) {
-        int n_pow2 = 2;
-        while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
-        hipLaunchKernelGGL(orbm::k_grid, dim3(n_jobs), dim3(256), (size_t)n_pow2 * 8, m->stream, (const orbm::ProjArgs*)(base + oargs), n_pow2);
-    }
-    if (par && stage) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj_par<true>, dim3(n_jobs), dim3(orbm::kProjThreads), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
-    } else if (par) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj_par<false>, dim3(n_jobs), dim3(orbm::kProjThreads), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
-    } else if (stage) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj<true>, dim3(n_jobs), dim3(64), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
-    } else {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj<false>, dim3(n_jobs), dim3(64), lds, m->stream, (const orbm::ProjArgs*)(base + oargs));
-    }
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), blob.size(), hipMemcpyHostToDevice, m->stream));
+    if (device_grid)
+        if (int r = launch_grid(m->stream, blob.device<orbm::ProjArgs>(oargs), n_jobs, max_n)) return r;
+    if (int r = launch_proj(plan, m->stream, blob.device<orbm::ProjArgs>(oargs), n_jobs)) return r;
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, m->h_blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     for (int j = 0; j < n_jobs; j++) {
-        const Off& o = offs[j];
         const int n = jobs[j].f->n;
         if (n > 0) {
-            std::memcpy(jobs[j].assign, m->h_blob.data() + o.assign, sizeof(int32_t) * n);
-            std::memcpy(jobs[j].occupied, m->h_blob.data() + o.occ, n);
+            std::memcpy(jobs[j].assign, blob.host(args[j].assign), sizeof(int32_t) * n);
+            std::memcpy(jobs[j].occupied, blob.host(args[j].occupied), n);
         }
-        std::memcpy(&jobs[j].n_matches, m->h_blob.data() + o.nm, sizeof(int32_t));
+        std::memcpy(&jobs[j].n_matches, blob.host(args[j].n_matches), sizeof(int32_t));
     }
     return ORBX_OK;
 }
 
-static int run_projection(orbm_matcher* m, const OrbmFrame* f, int last_mode, int n_pts, const uint8_t* valid,
-                          const float* u, const float* v, const int32_t* level, const float* view_cos, const float* depth,
-                          const uint8_t* bad, const float* angle, const uint8_t* desc, const uint8_t* has_obs,
-                          float th, int far_points, float th_far, float nnratio, int check_ori,
-                          int32_t* assign, uint8_t* occupied, float dist_th = (float)orbm::TH_HIGH,
-                          const float* ur = nullptr, int level_window = 0, bool stereo_gate = false)
+// a single job: its match count, or the error
+int run_projection_job(orbm_matcher* m, ProjJob& q, const ProjLaunch& P)
 {
-    ProjJob q;
-    q.ur = ur; q.level_window = level_window; q.stereo_gate = stereo_gate;
-    q.f = f; q.n_pts = n_pts; q.valid = valid; q.u = u; q.v = v; q.level = level; q.view_cos = view_cos; q.depth = depth; q.bad = bad;
-    q.angle = angle; q.desc = desc; q.has_obs = has_obs; q.assign = assign; q.occupied = occupied; q.n_matches = 0;
-    const int r = run_projection_jobs(m, &q, 1, last_mode, th, far_points, th_far, nnratio, check_ori, dist_th);
+    const int r = run_projection_jobs(m, &q, 1, P);
     return r ? r : q.n_matches;
 }
+
+}  // namespace
 
 #include "orbm_rig_search.inc"      // the same two searches for a two-camera fisheye rig frame (include/orbslam3_hip_rig_match.h)
 
@@ -1929,12 +1944,6 @@ void orbm_destroy(orbm_matcher* m)
     if (m->d_blob) (void)hipFree(m->d_blob);
     if (m->d_ws) (void)hipFree(m->d_ws);
     if (m->d_scale) (void)hipFree(m->d_scale);
-    for (hipEvent_t e : m->nmp_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : m->sfe_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : m->rig_ev)
-        if (e) (void)hipEventDestroy(e);
     delete m;
 }
 
@@ -1944,30 +1953,25 @@ int orbm_search_by_bow(orbm_matcher* m,
                        float nnratio, int check_orientation, int32_t* match_f2kf)
 {
     if (!match_f2kf && n_f > 0) return fail(ORBX_ERR_ARG, "match_f2kf is NULL");
-    const uint8_t* v2 = nullptr;
+    const BowSide kf{desc_kf, n_kf, valid_kf, angle_kf, fv_kf}, f{desc_f, n_f, nullptr, angle_f, fv_f};
     int32_t nm = 0;
-    int r = bow_batch<false>(m, 1, &desc_kf, &n_kf, &valid_kf, &angle_kf, &fv_kf, &desc_f, &n_f, &v2, &angle_f, &fv_f,
-                             nnratio, check_orientation, &match_f2kf, &nm);
+    int r = bow_batch<false>(m, 1, &kf, &f, nnratio, check_orientation, &match_f2kf, &nm);
     return r < 0 ? r : nm;
 }
 
 int orbm_search_by_bow_batch(orbm_matcher* m, OrbmBowPair* pairs, int n_pairs, float nnratio, int check_orientation)
 {
     if (!pairs || n_pairs < 1) return fail(ORBX_ERR_ARG, "no pairs");
-    std::vector<const uint8_t*> d1(n_pairs), v1(n_pairs), d2(n_pairs), v2(n_pairs, nullptr);
-    std::vector<const float*> a1(n_pairs), a2(n_pairs);
-    std::vector<const OrbmFeatVec*> f1(n_pairs), f2(n_pairs);
-    std::vector<int> n1(n_pairs), n2(n_pairs);
+    std::vector<BowSide> kf(n_pairs), f(n_pairs);
     std::vector<int32_t*> mo(n_pairs);
     std::vector<int32_t> nm(n_pairs, 0);
     for (int p = 0; p < n_pairs; p++) {
-        d1[p] = pairs[p].desc_kf; v1[p] = pairs[p].valid_kf; a1[p] = pairs[p].angle_kf; f1[p] = &pairs[p].fv_kf; n1[p] = pairs[p].n_kf;
-        d2[p] = pairs[p].desc_f; a2[p] = pairs[p].angle_f; f2[p] = &pairs[p].fv_f; n2[p] = pairs[p].n_f;
+        kf[p] = BowSide{pairs[p].desc_kf, pairs[p].n_kf, pairs[p].valid_kf, pairs[p].angle_kf, &pairs[p].fv_kf};
+        f[p] = BowSide{pairs[p].desc_f, pairs[p].n_f, nullptr, pairs[p].angle_f, &pairs[p].fv_f};
         mo[p] = pairs[p].match_f2kf;
-        if (!mo[p] && n2[p] > 0) return fail(ORBX_ERR_ARG, "pair %d: match_f2kf is NULL", p);
+        if (!mo[p] && f[p].n > 0) return fail(ORBX_ERR_ARG, "pair %d: match_f2kf is NULL", p);
     }
-    int r = bow_batch<false>(m, n_pairs, d1.data(), n1.data(), v1.data(), a1.data(), f1.data(), d2.data(), n2.data(), v2.data(), a2.data(), f2.data(),
-                             nnratio, check_orientation, mo.data(), nm.data());
+    int r = bow_batch<false>(m, n_pairs, kf.data(), f.data(), nnratio, check_orientation, mo.data(), nm.data());
     if (r < 0) return r;
     for (int p = 0; p < n_pairs; p++) pairs[p].n_matches = nm[p];
     return ORBX_OK;
@@ -1988,11 +1992,12 @@ int orbm_bow_plan_create(orbm_matcher* m, const OrbmBowPair* pairs, int n_pairs,
     *out = nullptr;
     ORBX_HIP(hipSetDevice(m->device));
     PinnedBytes host;            // (a plan is created once: its staging buffer lives for this call only)
-    Blob blob(host);
+    std::vector<void*> fields;
+    Blob blob(host, fields);
+    std::vector<orbm::BowPairDev> descs(n_pairs);
     orbm_bow_plan* pl = new orbm_bow_plan();
     pl->m = m; pl->n_pairs = n_pairs; pl->po.resize(n_pairs);
-    pl->desc_off = blob.reserve(sizeof(orbm::BowPairDev) * n_pairs);
-    static const int32_t zero_off[1] = {0};
+    pl->desc_off = blob.slot<orbm::BowPairDev>(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
         const OrbmBowPair& q = pairs[p];
         int r;
@@ -2000,38 +2005,12 @@ int orbm_bow_plan_create(orbm_matcher* m, const OrbmBowPair* pairs, int n_pairs,
             delete pl; return fail(ORBX_ERR_ARG, "pair %d: NULL arrays", p);
         }
         if ((r = check_fv(&q.fv_kf, q.n_kf, "fv_kf")) || (r = check_fv(&q.fv_f, q.n_f, "fv_f"))) { delete pl; return r; }
-        PairOffsets& o = pl->po[p];
-        o.n1 = q.n_kf; o.n2 = q.n_f; o.nn1 = q.fv_kf.n_nodes; o.nn2 = q.fv_f.n_nodes;
-        o.serial = !features_unique(&q.fv_f, q.n_f);
-        o.d1 = blob.put(q.desc_kf, (size_t)o.n1 * 32); o.v1 = blob.put(q.valid_kf, o.n1); o.a1 = blob.put(q.angle_kf, sizeof(float) * o.n1);
-        o.node1 = blob.put(q.fv_kf.node_id, sizeof(uint32_t) * o.nn1);
-        o.off1 = blob.put(o.nn1 ? q.fv_kf.offset : zero_off, sizeof(int32_t) * (o.nn1 + 1));
-        o.feat1 = blob.put(q.fv_kf.feat, sizeof(uint32_t) * (o.nn1 ? q.fv_kf.offset[o.nn1] : 0));
-        o.d2 = blob.put(q.desc_f, (size_t)o.n2 * 32); o.v2 = blob.reserve(0); o.a2 = blob.put(q.angle_f, sizeof(float) * o.n2);
-        o.node2 = blob.put(q.fv_f.node_id, sizeof(uint32_t) * o.nn2);
-        o.off2 = blob.put(o.nn2 ? q.fv_f.offset : zero_off, sizeof(int32_t) * (o.nn2 + 1));
-        o.feat2 = blob.put(q.fv_f.feat, sizeof(uint32_t) * (o.nn2 ? q.fv_f.offset[o.nn2] : 0));
-        o.n_out = o.n2;
-        o.match = blob.reserve(sizeof(int32_t) * std::max(o.n_out, 1));
-        o.matched2 = blob.reserve(0);
-        o.nmatch = blob.reserve(sizeof(int32_t));
+        pack_bow_pair(blob, false, BowSide{q.desc_kf, q.n_kf, q.valid_kf, q.angle_kf, &q.fv_kf}, BowSide{q.desc_f, q.n_f, nullptr, q.angle_f, &q.fv_f}, descs[p], pl->po[p]);
     }
     if (hipMalloc((void**)&pl->d_blob, host.size()) != hipSuccess) { delete pl; return fail(ORBX_ERR_HIP, "hipMalloc(%zu) failed", host.size()); }
-    uint8_t* base = pl->d_blob;
-    orbm::BowPairDev* descs = (orbm::BowPairDev*)(host.data() + pl->desc_off);
-    for (int p = 0; p < n_pairs; p++) {
-        const PairOffsets& o = pl->po[p];
-        orbm::BowPairDev D;
-        D.d1 = base + o.d1; D.v1 = base + o.v1; D.a1 = (const float*)(base + o.a1);
-        D.node1 = (const uint32_t*)(base + o.node1); D.off1 = (const int32_t*)(base + o.off1); D.feat1 = (const uint32_t*)(base + o.feat1);
-        D.d2 = base + o.d2; D.v2 = base + o.v2; D.a2 = (const float*)(base + o.a2);
-        D.node2 = (const uint32_t*)(base + o.node2); D.off2 = (const int32_t*)(base + o.off2); D.feat2 = (const uint32_t*)(base + o.feat2);
-        D.n1 = o.n1; D.n2 = o.n2; D.nn1 = o.nn1; D.nn2 = o.nn2;
-        D.match = (int32_t*)(base + o.match); D.matched2 = base + o.matched2; D.n_matches = (int32_t*)(base + o.nmatch);
-        D.serial = o.serial;
-        descs[p] = D;
-    }
-    if (hipMemcpy(base, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(pl->d_blob); delete pl; return fail(ORBX_ERR_HIP, "upload failed"); }
+    blob.bind(pl->d_blob);
+    blob.store(pl->desc_off, descs.data(), n_pairs);
+    if (hipMemcpy(pl->d_blob, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(pl->d_blob); delete pl; return fail(ORBX_ERR_HIP, "upload failed"); }
     *out = pl;
     return ORBX_OK;
 }
@@ -2112,9 +2091,9 @@ int orbm_search_by_bow_kfkf(orbm_matcher* m,
                             float nnratio, int check_orientation, int32_t* match12)
 {
     if (!match12 && n1 > 0) return fail(ORBX_ERR_ARG, "match12 is NULL");
+    const BowSide k1{desc1, n1, valid1, angle1, fv1}, k2{desc2, n2, valid2, angle2, fv2};
     int32_t nm = 0;
-    int r = bow_batch<true>(m, 1, &desc1, &n1, &valid1, &angle1, &fv1, &desc2, &n2, &valid2, &angle2, &fv2,
-                            nnratio, check_orientation, &match12, &nm);
+    int r = bow_batch<true>(m, 1, &k1, &k2, nnratio, check_orientation, &match12, &nm);
     return r < 0 ? r : nm;
 }
 
@@ -2125,9 +2104,11 @@ int orbm_search_by_projection(orbm_matcher* m, const OrbmFrame* f,
                               float th, int far_points, float th_far, float nnratio,
                               int32_t* assign, uint8_t* occupied)
 {
-    return run_projection(m, f, 0, n_mp, in_view, proj_u, proj_v, pred_level, view_cos, track_depth, mp_bad, nullptr,
-                          desc_mp, mp_has_obs, th, far_points, th_far, nnratio, 0, assign, occupied, (float)orbm::TH_HIGH,
-                          proj_ur, 0, true);
+    ProjJob q;
+    q.f = f; q.n_pts = n_mp; q.valid = in_view; q.u = proj_u; q.v = proj_v; q.ur = proj_ur; q.stereo_gate = true; q.level = pred_level;
+    q.view_cos = view_cos; q.depth = track_depth; q.bad = mp_bad; q.desc = desc_mp; q.has_obs = mp_has_obs;
+    q.assign = assign; q.occupied = occupied;
+    return run_projection_job(m, q, ProjLaunch{0, th, far_points, th_far, nnratio, 0, (float)orbm::TH_HIGH});
 }
 
 int orbm_search_by_projection_last(orbm_matcher* m, const OrbmFrame* cur,
@@ -2138,27 +2119,28 @@ int orbm_search_by_projection_last(orbm_matcher* m, const OrbmFrame* cur,
                                    int32_t* assign, uint8_t* occupied)
 {
     if (n_last > 0 && !mp_has_obs) return fail(ORBX_ERR_ARG, "NULL mp_has_obs");
-    return run_projection(m, cur, 1, n_last, last_valid, proj_u, proj_v, last_octave, nullptr, nullptr, nullptr, last_angle,
-                          desc_mp, mp_has_obs, th, 0, 0.f, 0.f, check_orientation, assign, occupied, (float)orbm::TH_HIGH,
-                          proj_ur, level_window, true);
+    ProjJob q;
+    q.f = cur; q.n_pts = n_last; q.valid = last_valid; q.u = proj_u; q.v = proj_v; q.ur = proj_ur; q.stereo_gate = true; q.level = last_octave;
+    q.level_window = level_window; q.angle = last_angle; q.desc = desc_mp; q.has_obs = mp_has_obs;
+    q.assign = assign; q.occupied = occupied;
+    return run_projection_job(m, q, ProjLaunch{1, th, 0, 0.f, 0.f, check_orientation, (float)orbm::TH_HIGH});
 }
 
-// Batched forms: n_frames independent (frame, points) problems in ONE launch, a wave per frame.
-static int run_projection_batch(orbm_matcher* m, OrbmProjQuery* q, int n_frames, int mode, float th, int far_points, float th_far,
-                                float nnratio, int check_ori, float dist_th)
+// Batched forms: n_frames independent (frame, points) problems in ONE launch, a workgroup per frame.
+static int run_projection_batch(orbm_matcher* m, OrbmProjQuery* q, int n_frames, const ProjLaunch& P)
 {
     if (!q || n_frames < 1) return fail(ORBX_ERR_ARG, "no queries");
     std::vector<ProjJob> jobs(n_frames);
     for (int j = 0; j < n_frames; j++) {
         ProjJob& p = jobs[j];
         p.f = q[j].frame; p.n_pts = q[j].n_pts; p.valid = q[j].valid; p.u = q[j].proj_u; p.v = q[j].proj_v; p.level = q[j].level;
-        p.ur = q[j].proj_ur; p.level_window = mode == 1 ? q[j].level_window : 0; p.stereo_gate = true;
+        p.ur = q[j].proj_ur; p.level_window = P.last_mode == 1 ? q[j].level_window : 0; p.stereo_gate = true;
         p.view_cos = q[j].view_cos; p.depth = q[j].track_depth; p.bad = q[j].mp_bad; p.angle = q[j].angle; p.desc = q[j].desc_mp;
-        p.has_obs = q[j].mp_has_obs; p.assign = q[j].assign; p.occupied = q[j].occupied; p.n_matches = 0;
+        p.has_obs = q[j].mp_has_obs; p.assign = q[j].assign; p.occupied = q[j].occupied;
         if (!p.f) return fail(ORBX_ERR_ARG, "query %d: NULL frame", j);
-        if (mode == 1 && p.n_pts > 0 && !p.has_obs) return fail(ORBX_ERR_ARG, "query %d: NULL mp_has_obs", j);
+        if (P.last_mode == 1 && p.n_pts > 0 && !p.has_obs) return fail(ORBX_ERR_ARG, "query %d: NULL mp_has_obs", j);
     }
-    const int r = run_projection_jobs(m, jobs.data(), n_frames, mode, th, far_points, th_far, nnratio, check_ori, dist_th);
+    const int r = run_projection_jobs(m, jobs.data(), n_frames, P);
     if (r) return r;
     for (int j = 0; j < n_frames; j++) q[j].n_matches = jobs[j].n_matches;
     return ORBX_OK;
@@ -2166,12 +2148,12 @@ static int run_projection_batch(orbm_matcher* m, OrbmProjQuery* q, int n_frames,
 
 int orbm_search_by_projection_last_batch(orbm_matcher* m, OrbmProjQuery* queries, int n_frames, float th, int check_orientation)
 {
-    return run_projection_batch(m, queries, n_frames, 1, th, 0, 0.f, 0.f, check_orientation, (float)orbm::TH_HIGH);
+    return run_projection_batch(m, queries, n_frames, ProjLaunch{1, th, 0, 0.f, 0.f, check_orientation, (float)orbm::TH_HIGH});
 }
 
 int orbm_search_by_projection_batch(orbm_matcher* m, OrbmProjQuery* queries, int n_frames, float th, int far_points, float th_far, float nnratio)
 {
-    return run_projection_batch(m, queries, n_frames, 0, th, far_points, th_far, nnratio, 0, (float)orbm::TH_HIGH);
+    return run_projection_batch(m, queries, n_frames, ProjLaunch{0, th, far_points, th_far, nnratio, 0, (float)orbm::TH_HIGH});
 }
 
 // shared body of the two device-resident tracking searches (mode 1: last frame, mode 0: Frame x map points)
@@ -2211,15 +2193,8 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
         std::memcpy(m->h_scale, cur->scale_factors, sizeof(float) * cur->n_levels);
         ORBX_HIP(hipMemcpyAsync(m->d_scale, m->h_scale, sizeof(float) * cur->n_levels, hipMemcpyHostToDevice, st));
     }
-    // LDS of the search kernel, as in run_projection_jobs
-    const size_t max_n = cap;
-    const size_t tabs = 8 * ((max_n + 15) & ~(size_t)15);
-    const size_t lds_budget = proj_dynamic_lds_budget();
-    if (tabs + ((max_n + 63) & ~(size_t)63) + 1024 > lds_budget) return fail(ORBX_ERR_CAPACITY, "frames of %zu features exceed the search kernel's LDS tables", max_n);
-    const size_t lds_occ = std::max((max_n + 63) & ~(size_t)63, (size_t)64) + tabs;
-    const size_t lds_full = ((max_n + 15) & ~(size_t)15) + max_n * 40 + (cells + 1) * 4 + 64 + tabs + max_n * 16 + 32;
-    const bool stage = lds_full <= lds_budget;
-    const size_t lds = stage ? lds_full : lds_occ;
+    const ProjLdsPlan plan = proj_lds_plan(cap, cells, false);         // (this entry has the block-parallel search only)
+    if (!plan.par) return fail(ORBX_ERR_CAPACITY, "frames of %zu features exceed the search kernel's LDS tables", cap);
     orbm::ProjDevSetup P;
     P.kps = cur->d_kps; P.desc = cur->d_desc; P.n = cur->d_n; P.cap = cur->cap;
     P.p_valid = last->d_valid; P.p_u = last->d_u; P.p_v = last->d_v; P.p_oct = last->d_octave; P.p_angle = last->d_angle; P.p_desc = last->d_desc; P.p_n = last->d_n; P.p_cap = last->cap; P.p_obs = last->d_has_obs;
@@ -2228,24 +2203,15 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
     P.cell_off = (int32_t*)(w + o_coff); P.cell_feat = (int32_t*)(w + o_cfeat); P.log_feat = (int32_t*)(w + o_lf); P.log_bin = (int32_t*)(w + o_lb);
     P.scale = m->d_scale; P.n_levels = cur->n_levels; P.cols = cur->grid_cols; P.rows = cur->grid_rows;
     P.min_x = cur->min_x; P.min_y = cur->min_y; P.max_x = cur->max_x; P.max_y = cur->max_y; P.th = th; P.dist_th = (float)orbm::TH_HIGH;
-    P.check_ori = mode == 1 ? check_orientation : 0; P.lds_frame = stage ? 1 : 0;
+    P.check_ori = mode == 1 ? check_orientation : 0; P.lds_frame = plan.stage ? 1 : 0;
     P.mode = mode;
     P.p_vcos = mp ? mp->d_view_cos : nullptr; P.p_depth = mp ? mp->d_track_depth : nullptr; P.p_bad = mp ? mp->d_bad : nullptr;
     P.th_far = mp ? mp->th_far : 0.f; P.nnratio = mp ? mp->nnratio : 0.f; P.far_points = mp ? mp->far_points : 0;
     P.assign = d_assign; P.occupied = d_occupied; P.n_matches = d_n_matches;
     P.jobs = (orbm::ProjArgs*)(w + o_jobs);
     hipLaunchKernelGGL(orbm::k_proj_dev_setup, dim3(batch), dim3(256), 0, st, P);
-    int n_pow2 = 2;
-    while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
-    ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
-    hipLaunchKernelGGL(orbm::k_grid, dim3(batch), dim3(256), (size_t)n_pow2 * 8, st, (const orbm::ProjArgs*)P.jobs, n_pow2);
-    if (stage) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj_par<true>, dim3(batch), dim3(orbm::kProjThreads), lds, st, (const orbm::ProjArgs*)P.jobs);
-    } else {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_proj_par<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_proj_par<false>, dim3(batch), dim3(orbm::kProjThreads), lds, st, (const orbm::ProjArgs*)P.jobs);
-    }
+    if (int r = launch_grid(st, P.jobs, batch, cap)) return r;
+    if (int r = launch_proj(plan, st, P.jobs, batch)) return r;
     ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
@@ -2277,8 +2243,10 @@ int orbm_search_by_projection_kf(orbm_matcher* m, const OrbmFrame* cur,
                                  const int32_t* pred_level, const float* kf_angle, const uint8_t* desc_mp,
                                  float th, int orb_dist, int check_orientation, int32_t* assign, uint8_t* occupied)
 {
-    return run_projection(m, cur, 1, n_pts, valid, proj_u, proj_v, pred_level, nullptr, nullptr, nullptr, kf_angle,
-                          desc_mp, nullptr, th, 0, 0.f, 0.f, check_orientation, assign, occupied, (float)orb_dist);
+    ProjJob q;
+    q.f = cur; q.n_pts = n_pts; q.valid = valid; q.u = proj_u; q.v = proj_v; q.level = pred_level; q.angle = kf_angle; q.desc = desc_mp;
+    q.assign = assign; q.occupied = occupied;
+    return run_projection_job(m, q, ProjLaunch{1, th, 0, 0.f, 0.f, check_orientation, (float)orb_dist});
 }
 
 int orbm_search_by_projection_sim3(orbm_matcher* m, const OrbmFrame* kf,
@@ -2286,8 +2254,10 @@ int orbm_search_by_projection_sim3(orbm_matcher* m, const OrbmFrame* kf,
                                    const int32_t* pred_level, const uint8_t* desc_mp, int th, float ratio_hamming,
                                    int32_t* assign, uint8_t* occupied)
 {
-    return run_projection(m, kf, 2, n_pts, valid, proj_u, proj_v, pred_level, nullptr, nullptr, nullptr, nullptr,
-                          desc_mp, nullptr, (float)th, 0, 0.f, 0.f, 0, assign, occupied, (float)orbm::TH_LOW * ratio_hamming);
+    ProjJob q;
+    q.f = kf; q.n_pts = n_pts; q.valid = valid; q.u = proj_u; q.v = proj_v; q.level = pred_level; q.desc = desc_mp;
+    q.assign = assign; q.occupied = occupied;
+    return run_projection_job(m, q, ProjLaunch{2, (float)th, 0, 0.f, 0.f, 0, (float)orbm::TH_LOW * ratio_hamming});
 }
 
 int orbm_search_for_triangulation(orbm_matcher* m, const OrbmTriSide* k1, const OrbmTriSide* k2, float ep_x, float ep_y, const float* F12,
@@ -2309,40 +2279,32 @@ int orbm_search_for_triangulation(orbm_matcher* m, const OrbmTriSide* k1, const 
     if (k1->n > 0 && !match12) return fail(ORBX_ERR_ARG, "NULL match12");
     if (k1->n == 0) return 0;
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
-    size_t o[2][10];
-    for (int q = 0; q < 2; q++) {
-        const OrbmTriSide* k = side[q];
-        const int n = k->n, nn = k->fv.n_nodes, tot = nn > 0 ? k->fv.offset[nn] : 0;
-        o[q][0] = blob.put(k->desc, (size_t)n * 32); o[q][1] = blob.put(k->has_mp, n); o[q][2] = blob.put(k->stereo, n);
-        o[q][3] = blob.put(k->x, sizeof(float) * n); o[q][4] = blob.put(k->y, sizeof(float) * n);
-        o[q][5] = blob.put(k->octave, sizeof(int32_t) * n); o[q][6] = blob.put(k->angle, k->angle ? sizeof(float) * n : 0);
-        o[q][7] = blob.put(k->fv.node_id, sizeof(uint32_t) * nn); o[q][8] = blob.put(k->fv.offset, sizeof(int32_t) * (nn + 1));
-        o[q][9] = blob.put(k->fv.feat, sizeof(uint32_t) * tot);
-    }
-    const size_t osig = blob.put(level_sigma2_2, sizeof(float) * n_levels_2), osc = blob.put(scale_factors_2, sizeof(float) * n_levels_2);
-    const size_t in_bytes = m->h_blob.size();
-    const size_t omatch = blob.reserve(sizeof(int32_t) * k1->n), onm = blob.reserve(sizeof(int32_t));
-    int r = m->ensure(m->h_blob.size());
-    if (r) return r;
-    uint8_t* b = m->d_blob;
+    Blob blob(m);
     orbm::TriArgs A;
-    A.d1 = b + o[0][0]; A.mp1 = b + o[0][1]; A.st1 = b + o[0][2]; A.x1 = (const float*)(b + o[0][3]); A.y1 = (const float*)(b + o[0][4]);
-    A.a1 = (const float*)(b + o[0][6]); A.node1 = (const uint32_t*)(b + o[0][7]); A.off1 = (const int32_t*)(b + o[0][8]); A.feat1 = (const uint32_t*)(b + o[0][9]);
-    A.d2 = b + o[1][0]; A.mp2 = b + o[1][1]; A.st2 = b + o[1][2]; A.x2 = (const float*)(b + o[1][3]); A.y2 = (const float*)(b + o[1][4]);
-    A.oct2 = (const int32_t*)(b + o[1][5]); A.a2 = (const float*)(b + o[1][6]);
-    A.node2 = (const uint32_t*)(b + o[1][7]); A.off2 = (const int32_t*)(b + o[1][8]); A.feat2 = (const uint32_t*)(b + o[1][9]);
-    A.sigma2_2 = (const float*)(b + osig); A.scale2 = (const float*)(b + osc);
+    auto pack_side = [&](const OrbmTriSide* k, const uint8_t*& d, const uint8_t*& mp, const uint8_t*& st, const float*& x, const float*& y, const int32_t*& oct,
+                         const float*& a, const uint32_t*& node, const int32_t*& off, const uint32_t*& feat) {
+        const int n = k->n, nn = k->fv.n_nodes;
+        blob.in(d, k->desc, (size_t)n * 32); blob.in(mp, k->has_mp, n); blob.in(st, k->stereo, n);
+        blob.in(x, k->x, n); blob.in(y, k->y, n); blob.in(oct, k->octave, n); blob.in_opt(a, k->angle, n);
+        blob.in(node, k->fv.node_id, nn); blob.in(off, k->fv.offset, nn + 1); blob.in(feat, k->fv.feat, nn > 0 ? k->fv.offset[nn] : 0);
+    };
+    const int32_t* oct1;            // (the octaves of side 1 travel with the rest; the kernel does not read them)
+    pack_side(k1, A.d1, A.mp1, A.st1, A.x1, A.y1, oct1, A.a1, A.node1, A.off1, A.feat1);
+    pack_side(k2, A.d2, A.mp2, A.st2, A.x2, A.y2, A.oct2, A.a2, A.node2, A.off2, A.feat2);
+    blob.in(A.sigma2_2, level_sigma2_2, n_levels_2); blob.in(A.scale2, scale_factors_2, n_levels_2);
+    const size_t in_bytes = blob.size();
+    blob.out(A.match12, k1->n); blob.out(A.n_matches, 1);
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
     for (int i = 0; i < 9; i++) A.F12[i] = F12[i];
     A.ep_x = ep_x; A.ep_y = ep_y;
     A.n1 = k1->n; A.nn1 = k1->fv.n_nodes; A.nn2 = k2->fv.n_nodes; A.only_stereo = only_stereo; A.coarse = coarse; A.check_ori = check_orientation;
-    A.match12 = (int32_t*)(b + omatch); A.n_matches = (int32_t*)(b + onm);
-    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(m->d_blob, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_triangulation, dim3(1), dim3(256), 0, m->stream, A);
     ORBX_HIP(hipGetLastError());
     int nm = 0;
-    ORBX_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * k1->n, hipMemcpyDeviceToHost, m->stream));
-    ORBX_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(match12, A.match12, sizeof(int32_t) * k1->n, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(&nm, A.n_matches, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     return nm;
 }
@@ -2354,41 +2316,28 @@ int orbm_search_for_initialization(orbm_matcher* m, const uint8_t* desc1, int n1
     if (!m || !f2) return fail(ORBX_ERR_ARG, "NULL argument");
     if (n1 < 0 || (n1 > 0 && (!desc1 || !octave1 || !prev_x || !prev_y || !match12))) return fail(ORBX_ERR_ARG, "NULL F1 arrays");
     if (check_orientation && ((n1 > 0 && !angle1) || (f2->n > 0 && !f2->angle))) return fail(ORBX_ERR_ARG, "NULL angles");
-    std::vector<int32_t> cell_off, cell_feat;
-    float winv, hinv;
-    int r = build_grid(f2, cell_off, cell_feat, winv, hinv);
-    if (r) return r;
+    ORBX_HIP(hipSetDevice(m->device));
+    Blob blob(m);
+    orbm::InitArgs A;
+    if (int r = stage_frame(blob, f2, false, A.F2, true, false)) return r;       // (the kernel reads no scale factors)
     if (n1 == 0) return 0;
     const int n = f2->n;
     if ((size_t)n * 8 + 256 > 150 * 1024) return fail(ORBX_ERR_ARG, "F2 with %d features exceeds the LDS state", n);
-    ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
-    const size_t ox = blob.put(f2->x, sizeof(float) * n), oy = blob.put(f2->y, sizeof(float) * n);
-    const size_t ooct = blob.put(f2->octave, sizeof(int32_t) * n), oang = blob.put(f2->angle, f2->angle ? sizeof(float) * n : 0);
-    const size_t odesc = blob.put(f2->desc, (size_t)n * 32);
-    const size_t ocoff = blob.put(cell_off.data(), sizeof(int32_t) * cell_off.size()), ocfeat = blob.put(cell_feat.data(), sizeof(int32_t) * cell_feat.size());
-    const size_t od1 = blob.put(desc1, (size_t)n1 * 32), oo1 = blob.put(octave1, sizeof(int32_t) * n1), oa1 = blob.put(angle1, angle1 ? sizeof(float) * n1 : 0);
-    const size_t opx = blob.put(prev_x, sizeof(float) * n1), opy = blob.put(prev_y, sizeof(float) * n1);
-    const size_t in_bytes = m->h_blob.size();
-    const size_t omatch = blob.reserve(sizeof(int32_t) * n1), onm = blob.reserve(sizeof(int32_t));
-    if ((r = m->ensure(m->h_blob.size()))) return r;
-    uint8_t* b = m->d_blob;
-    orbm::InitArgs A;
-    A.F2.x = (const float*)(b + ox); A.F2.y = (const float*)(b + oy); A.F2.octave = (const int32_t*)(b + ooct); A.F2.angle = (const float*)(b + oang);
-    A.F2.desc = b + odesc; A.F2.cell_off = (const int32_t*)(b + ocoff); A.F2.cell_feat = (const int32_t*)(b + ocfeat); A.F2.scale_factors = nullptr;
-    A.F2.min_x = f2->min_x; A.F2.min_y = f2->min_y; A.F2.max_x = f2->max_x; A.F2.max_y = f2->max_y; A.F2.winv = winv; A.F2.hinv = hinv;
-    A.F2.n = n; A.F2.cols = f2->grid_cols; A.F2.rows = f2->grid_rows;
-    A.d1 = b + od1; A.oct1 = (const int32_t*)(b + oo1); A.a1 = (const float*)(b + oa1); A.prev_x = (const float*)(b + opx); A.prev_y = (const float*)(b + opy);
+    blob.in(A.d1, desc1, (size_t)n1 * 32); blob.in(A.oct1, octave1, n1); blob.in_opt(A.a1, angle1, n1);
+    blob.in(A.prev_x, prev_x, n1); blob.in(A.prev_y, prev_y, n1);
+    const size_t in_bytes = blob.size();
+    blob.out(A.match12, n1); blob.out(A.n_matches, 1);
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
     A.n1 = n1; A.window = window_size; A.check_ori = check_orientation; A.nnratio = nnratio;
-    A.match12 = (int32_t*)(b + omatch); A.n_matches = (int32_t*)(b + onm);
     const size_t lds = std::max((size_t)n * 8, (size_t)64);
     ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_initialization, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    ORBX_HIP(hipMemcpyAsync(m->d_blob, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_initialization, dim3(1), dim3(64), lds, m->stream, A);
     ORBX_HIP(hipGetLastError());
     int nm = 0;
-    ORBX_HIP(hipMemcpyAsync(match12, b + omatch, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, m->stream));
-    ORBX_HIP(hipMemcpyAsync(&nm, b + onm, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(match12, A.match12, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(&nm, A.n_matches, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     return nm;
 }
@@ -2402,48 +2351,31 @@ int orbm_fuse_search(orbm_matcher* m, const OrbmFrame* kf, const float* u_right,
     if (n_pts < 0 || (n_pts > 0 && (!valid || !proj_u || !proj_v || !pred_level || !desc_mp || !best_idx || !best_dist)))
         return fail(ORBX_ERR_ARG, "NULL point arrays");
     if (chi2_check && (!u_right || !inv_level_sigma2 || (n_pts > 0 && !proj_ur))) return fail(ORBX_ERR_ARG, "NULL stereo / sigma arrays");
-    std::vector<int32_t> cell_off, cell_feat;
-    float winv, hinv;
-    int r = build_grid(kf, cell_off, cell_feat, winv, hinv);
-    if (r) return r;
+    ORBX_HIP(hipSetDevice(m->device));
+    Blob blob(m);
+    orbm::FuseArgs A;
+    if (int r = stage_frame(blob, kf, false, A.F, false)) return r;              // (the kernel reads no angles)
     for (int i = 0; i < n_pts; i++)
         if (valid[i] && (pred_level[i] < 0 || pred_level[i] >= kf->n_levels)) return fail(ORBX_ERR_ARG, "point %d: level %d out of range", i, pred_level[i]);
     if (chi2_check)
         for (int i = 0; i < kf->n; i++)
             if (kf->octave[i] < 0 || kf->octave[i] >= kf->n_levels) return fail(ORBX_ERR_ARG, "key point %d: octave %d out of range", i, kf->octave[i]);
     if (n_pts == 0) return ORBX_OK;
-    ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
-    const int n = kf->n;
-    const size_t ox = blob.put(kf->x, sizeof(float) * n), oy = blob.put(kf->y, sizeof(float) * n);
-    const size_t ooct = blob.put(kf->octave, sizeof(int32_t) * n), odesc = blob.put(kf->desc, (size_t)n * 32);
-    const size_t ocoff = blob.put(cell_off.data(), sizeof(int32_t) * cell_off.size());
-    const size_t ocfeat = blob.put(cell_feat.data(), sizeof(int32_t) * cell_feat.size());
-    const size_t osf = blob.put(kf->scale_factors, sizeof(float) * kf->n_levels);
-    const size_t our = blob.put(u_right, chi2_check ? sizeof(float) * n : 0);
-    const size_t osig = blob.put(inv_level_sigma2, chi2_check ? sizeof(float) * kf->n_levels : 0);
-    const size_t ovalid = blob.put(valid, n_pts), ou = blob.put(proj_u, sizeof(float) * n_pts), ov = blob.put(proj_v, sizeof(float) * n_pts);
-    const size_t opr = blob.put(proj_ur, (chi2_check && proj_ur) ? sizeof(float) * n_pts : 0);
-    const size_t olevel = blob.put(pred_level, sizeof(int32_t) * n_pts), odmp = blob.put(desc_mp, (size_t)n_pts * 32);
-    const size_t obi = blob.reserve(sizeof(int32_t) * n_pts), obd = blob.reserve(sizeof(int32_t) * n_pts);
-    if ((r = m->ensure(m->h_blob.size()))) return r;
-    uint8_t* base = m->d_blob;
-    orbm::FuseArgs A;
-    A.F.x = (const float*)(base + ox); A.F.y = (const float*)(base + oy); A.F.octave = (const int32_t*)(base + ooct);
-    A.F.angle = nullptr; A.F.desc = base + odesc;
-    A.F.cell_off = (const int32_t*)(base + ocoff); A.F.cell_feat = (const int32_t*)(base + ocfeat);
-    A.F.scale_factors = (const float*)(base + osf);
-    A.F.min_x = kf->min_x; A.F.min_y = kf->min_y; A.F.max_x = kf->max_x; A.F.max_y = kf->max_y; A.F.winv = winv; A.F.hinv = hinv;
-    A.F.n = n; A.F.cols = kf->grid_cols; A.F.rows = kf->grid_rows;
-    A.u_right = (const float*)(base + our); A.inv_sigma2 = (const float*)(base + osig);
-    A.n_pts = n_pts; A.valid = base + ovalid; A.u = (const float*)(base + ou); A.v = (const float*)(base + ov); A.ur = (const float*)(base + opr);
-    A.level = (const int32_t*)(base + olevel); A.desc = base + odmp; A.th = th; A.chi2_check = chi2_check;
-    A.best_idx = (int32_t*)(base + obi); A.best_dist = (int32_t*)(base + obd);
-    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), obi, hipMemcpyHostToDevice, m->stream));
+    blob.in_opt(A.u_right, chi2_check ? u_right : nullptr, kf->n);
+    blob.in_opt(A.inv_sigma2, chi2_check ? inv_level_sigma2 : nullptr, kf->n_levels);
+    blob.in(A.valid, valid, n_pts); blob.in(A.u, proj_u, n_pts); blob.in(A.v, proj_v, n_pts);
+    blob.in_opt(A.ur, chi2_check ? proj_ur : nullptr, n_pts);
+    blob.in(A.level, pred_level, n_pts); blob.in(A.desc, desc_mp, (size_t)n_pts * 32);
+    const size_t in_bytes = blob.begin_out();
+    blob.out(A.best_idx, n_pts); blob.out(A.best_dist, n_pts);
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
+    A.n_pts = n_pts; A.th = th; A.chi2_check = chi2_check;
+    ORBX_HIP(hipMemcpyAsync(m->d_blob, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(orbm::k_fuse, dim3((n_pts + 3) / 4), dim3(256), 0, m->stream, A);
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipMemcpyAsync(best_idx, base + obi, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
-    ORBX_HIP(hipMemcpyAsync(best_dist, base + obd, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(best_idx, A.best_idx, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(best_dist, A.best_dist, sizeof(int32_t) * n_pts, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
@@ -2463,21 +2395,20 @@ int orbm_distinctive_descriptors(orbm_matcher* m, const uint8_t* desc, const int
     if (total > 0 && !desc) return fail(ORBX_ERR_ARG, "NULL descriptors");
     if (max_n > 4096) return fail(ORBX_ERR_CAPACITY, "a map point with %d observations exceeds the LDS staging (4096)", max_n);
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
-    const size_t od = blob.put(desc, (size_t)total * 32), oo = blob.put(off, sizeof(int32_t) * (n_points + 1));
-    const size_t in_bytes = m->h_blob.size();
-    const size_t ob = blob.reserve(sizeof(int32_t) * n_points), om = blob.reserve(sizeof(int32_t) * n_points);
-    int r = m->ensure(m->h_blob.size());
-    if (r) return r;
-    uint8_t* b = m->d_blob;
+    Blob blob(m);
+    const uint8_t* d_desc; const int32_t* d_off; int32_t* d_best; int32_t* d_median;       // the kernel's arguments
+    blob.in(d_desc, desc, (size_t)total * 32); blob.in(d_off, off, n_points + 1);
+    const size_t in_bytes = blob.size();
+    blob.out(d_best, n_points); blob.out(d_median, n_points);
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
     const size_t lds = std::max((size_t)max_n * 32, (size_t)64);
     ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_distinctive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(orbm::k_distinctive, dim3(n_points), dim3(64), lds, m->stream, b + od, (const int32_t*)(b + oo), n_points,
-                       (int32_t*)(b + ob), (int32_t*)(b + om));
+    ORBX_HIP(hipMemcpyAsync(m->d_blob, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(orbm::k_distinctive, dim3(n_points), dim3(64), lds, m->stream, d_desc, d_off, n_points, d_best, d_median);
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipMemcpyAsync(best_idx, b + ob, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
-    if (best_median) ORBX_HIP(hipMemcpyAsync(best_median, b + om, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(best_idx, d_best, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
+    if (best_median) ORBX_HIP(hipMemcpyAsync(best_median, d_median, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
@@ -2495,25 +2426,25 @@ int orbm_update_normal_and_depth(orbm_matcher* m, const float* pos, const float*
     const int total = off[n_points];
     if (!centers) return fail(ORBX_ERR_ARG, "NULL camera centres");
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
-    const size_t op = blob.put(pos, sizeof(float) * 3 * n_points), oc = blob.put(centers, sizeof(float) * 3 * total);
-    const size_t oo = blob.put(off, sizeof(int32_t) * (n_points + 1)), orc = blob.put(ref_center, sizeof(float) * 3 * n_points);
-    const size_t ol = blob.put(level_scale, sizeof(float) * n_points);
-    const size_t in_bytes = m->h_blob.size();
-    const size_t on = blob.reserve(sizeof(float) * 3 * n_points), omx = blob.reserve(sizeof(float) * n_points), omn = blob.reserve(sizeof(float) * n_points);
-    int r = m->ensure(m->h_blob.size());
-    if (r) return r;
-    uint8_t* b = m->d_blob;
-    ORBX_HIP(hipMemcpyAsync(b, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(orbm::k_normal_depth, dim3((n_points + 255) / 256), dim3(256), 0, m->stream, (const float*)(b + op), (const float*)(b + oc),
-                       (const int32_t*)(b + oo), (const float*)(b + orc), (const float*)(b + ol), last_level_scale, n_points,
-                       (float*)(b + on), (float*)(b + omx), (float*)(b + omn));
+    Blob blob(m);
+    const float* d_pos; const float* d_centers; const int32_t* d_off; const float* d_ref; const float* d_scale;        // the kernel's arguments
+    float* d_normal; float* d_max; float* d_min;
+    blob.in(d_pos, pos, (size_t)3 * n_points); blob.in(d_centers, centers, (size_t)3 * total); blob.in(d_off, off, n_points + 1);
+    blob.in(d_ref, ref_center, (size_t)3 * n_points); blob.in(d_scale, level_scale, n_points);
+    const size_t in_bytes = blob.size();
+    blob.out(d_normal, (size_t)3 * n_points); blob.out(d_max, n_points); blob.out(d_min, n_points);
+    if (int r = m->ensure(blob.size())) return r;
+    blob.bind(m->d_blob);
+    ORBX_HIP(hipMemcpyAsync(m->d_blob, m->h_blob.data(), in_bytes, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(orbm::k_normal_depth, dim3((n_points + 255) / 256), dim3(256), 0, m->stream, d_pos, d_centers, d_off, d_ref, d_scale, last_level_scale, n_points,
+                       d_normal, d_max, d_min);
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipMemcpyAsync(normal, b + on, sizeof(float) * 3 * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBX_HIP(hipMemcpyAsync(max_dist, b + omx, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
-    ORBX_HIP(hipMemcpyAsync(min_dist, b + omn, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(normal, d_normal, sizeof(float) * 3 * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(max_dist, d_max, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
+    ORBX_HIP(hipMemcpyAsync(min_dist, d_min, sizeof(float) * n_points, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
     return ORBX_OK;
 }
 
 }  // extern "C"
+

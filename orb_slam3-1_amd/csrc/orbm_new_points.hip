@@ -148,8 +148,6 @@ int check_key_frame(const OrbmMapKeyFrame* k, const char* name)
     return ORBX_OK;
 }
 
-struct KeyFrameOffsets { size_t desc, has_mp, stereo, x, y, octave, u_right, depth, key_x, key_y, off, feat, sigma2, scale, node_of; };
-
 }  // namespace
 
 extern "C" {
@@ -185,63 +183,31 @@ int orbm_create_new_map_points(orbm_matcher* m, const OrbmMapKeyFrame* kf1, cons
     if (n1 == 0 || n_neighbours == 0 || total1 == 0) return 0;
 
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
+    Blob blob(m);
     const int nkf = 1 + n_neighbours;
-    std::vector<KeyFrameOffsets> o(nkf);
+    std::vector<orbm::NmpKeyFrameDev> kfs(nkf);
+    std::memset((void*)kfs.data(), 0, sizeof(orbm::NmpKeyFrameDev) * nkf);
     std::vector<int32_t> node_of(nn1);
     for (int q = 0; q < nkf; q++) {
         const OrbmMapKeyFrame* k = q ? &neighbours[q - 1] : kf1;
         const OrbmTriSide& s = k->side;
         const int n = s.n, nn = s.fv.n_nodes, tot = nn > 0 ? s.fv.offset[nn] : 0;
-        KeyFrameOffsets& f = o[q];
-        f.desc = blob.put(s.desc, (size_t)n * 32); f.has_mp = blob.put(s.has_mp, n); f.stereo = blob.put(s.stereo, n);
-        f.x = blob.put(s.x, sizeof(float) * n); f.y = blob.put(s.y, sizeof(float) * n); f.octave = blob.put(s.octave, sizeof(int32_t) * n);
-        f.u_right = blob.put(k->u_right, sizeof(float) * n); f.depth = blob.put(k->depth, sizeof(float) * n);
-        f.key_x = k->key_x ? blob.put(k->key_x, sizeof(float) * n) : f.x;
-        f.key_y = k->key_y ? blob.put(k->key_y, sizeof(float) * n) : f.y;
-        f.off = blob.put(s.fv.offset, sizeof(int32_t) * (nn > 0 ? nn + 1 : 0)); f.feat = blob.put(s.fv.feat, sizeof(uint32_t) * tot);
-        f.sigma2 = blob.put(k->level_sigma2, sizeof(float) * k->n_levels); f.scale = blob.put(k->scale_factors, sizeof(float) * k->n_levels);
-        f.node_of = 0;
+        orbm::NmpKeyFrameDev& d = kfs[q];
+        blob.in(d.desc, s.desc, (size_t)n * 32); blob.in(d.has_mp, s.has_mp, n); blob.in(d.stereo, s.stereo, n);
+        blob.in(d.x, s.x, n); blob.in(d.y, s.y, n); blob.in(d.octave, s.octave, n);
+        blob.in(d.u_right, k->u_right, n); blob.in(d.depth, k->depth, n);
+        if (k->key_x) { blob.in(d.key_x, k->key_x, n); blob.in(d.key_y, k->key_y, n); }
+        else { blob.alias(d.key_x, d.x); blob.alias(d.key_y, d.y); }
+        blob.in(d.off, s.fv.offset, nn > 0 ? nn + 1 : 0); blob.in(d.feat, s.fv.feat, tot);
+        blob.in(d.sigma2, k->level_sigma2, k->n_levels); blob.in(d.scale, k->scale_factors, k->n_levels);
         if (q) {                                                // both node lists ascend (check_fv): one merge pass per neighbour
             int b = 0;
             for (int a = 0; a < nn1; a++) {
                 while (b < nn && s.fv.node_id[b] < fv1.node_id[a]) b++;
                 node_of[a] = (b < nn && s.fv.node_id[b] == fv1.node_id[a]) ? b : -1;
             }
-            f.node_of = blob.put(node_of.data(), sizeof(int32_t) * nn1);
-        }
-    }
-    std::vector<int32_t> entry_node(total1);
-    for (int a = 0; a < nn1; a++)
-        for (int e = fv1.offset[a]; e < fv1.offset[a + 1]; e++) entry_node[e] = a;
-    const size_t o_entry = blob.put(entry_node.data(), sizeof(int32_t) * total1);
-    const size_t o_kf = blob.reserve(sizeof(orbm::NmpKeyFrameDev) * nkf);
-    // outputs: `neighbour` (-1) and the two counters (0) travel with the inputs, the rest is written where neighbour >= 0
-    const size_t o_out = blob.reserve(0);
-    const size_t o_nb = blob.reserve(sizeof(int32_t) * n1);
-    const size_t o_nm = blob.reserve(sizeof(int32_t) * n_neighbours), o_nc = blob.reserve(sizeof(int32_t) * n_neighbours);
-    const size_t in_bytes = m->h_blob.size();
-    const size_t o_idx2 = blob.reserve(sizeof(int32_t) * n1), o_x3d = blob.reserve(sizeof(float) * 3 * n1), o_ps = blob.reserve(n1);
-    const size_t o_nrm = blob.reserve(sizeof(float) * 3 * n1), o_mx = blob.reserve(sizeof(float) * n1), o_mn = blob.reserve(sizeof(float) * n1);
-    const size_t o_m12 = out->match12 ? blob.reserve(sizeof(int32_t) * n1 * n_neighbours) : 0;
-    const size_t all_bytes = m->h_blob.size();
-    r = m->ensure(all_bytes);
-    if (r) return r;
-    uint8_t* b = m->d_blob;
-    uint8_t* h = m->h_blob.data();
-    std::memset(h + o_nb, 0xFF, sizeof(int32_t) * n1);
-    for (int q = 0; q < nkf; q++) {
-        const OrbmMapKeyFrame* k = q ? &neighbours[q - 1] : kf1;
-        const KeyFrameOffsets& f = o[q];
-        orbm::NmpKeyFrameDev d;
-        std::memset(&d, 0, sizeof(d));
-        d.desc = b + f.desc; d.has_mp = b + f.has_mp; d.stereo = b + f.stereo;
-        d.x = (const float*)(b + f.x); d.y = (const float*)(b + f.y); d.octave = (const int32_t*)(b + f.octave);
-        d.u_right = (const float*)(b + f.u_right); d.depth = (const float*)(b + f.depth);
-        d.key_x = (const float*)(b + f.key_x); d.key_y = (const float*)(b + f.key_y);
-        d.off = (const int32_t*)(b + f.off); d.feat = (const uint32_t*)(b + f.feat);
-        d.sigma2 = (const float*)(b + f.sigma2); d.scale = (const float*)(b + f.scale);
-        d.node_of = (const int32_t*)(b + f.node_of);
+            blob.in(d.node_of, node_of.data(), nn1);
+        } else blob.none(d.node_of);
         std::memcpy(d.cam.Rcw, k->Rcw, sizeof(d.cam.Rcw)); std::memcpy(d.cam.tcw, k->tcw, sizeof(d.cam.tcw)); std::memcpy(d.cam.Ow, k->Ow, sizeof(d.cam.Ow));
         d.cam.fx = k->fx; d.cam.fy = k->fy; d.cam.cx = k->cx; d.cam.cy = k->cy; d.cam.invfx = k->invfx; d.cam.invfy = k->invfy;
         d.cam.mb = k->mb; d.cam.mbf = k->mbf;
@@ -249,51 +215,66 @@ int orbm_create_new_map_points(orbm_matcher* m, const OrbmMapKeyFrame* kf1, cons
             const OrbmMapPair& p = pairs[q - 1];
             std::memcpy(d.F12, p.F12, sizeof(d.F12)); d.ep_x = p.ep_x; d.ep_y = p.ep_y; d.coarse = p.coarse;
         }
-        std::memcpy(h + o_kf + sizeof(d) * q, &d, sizeof(d));
     }
+    std::vector<int32_t> entry_node(total1);
+    for (int a = 0; a < nn1; a++)
+        for (int e = fv1.offset[a]; e < fv1.offset[a + 1]; e++) entry_node[e] = a;
     orbm::NmpArgs A;
-    A.kf = (const orbm::NmpKeyFrameDev*)(b + o_kf); A.entry_node = (const int32_t*)(b + o_entry);
+    blob.in(A.entry_node, entry_node.data(), total1);
+    const size_t o_kf = blob.slot<orbm::NmpKeyFrameDev>(nkf);
+    // outputs: `neighbour` (-1) and the two counters (0) travel with the inputs, the rest is written where neighbour >= 0
+    const size_t o_out = blob.begin_out();
+    blob.out(A.neighbour, n1); blob.out(A.n_matched, n_neighbours); blob.out(A.n_created, n_neighbours);
+    const size_t in_bytes = blob.size();
+    blob.out(A.idx2, n1); blob.out(A.x3d, (size_t)3 * n1); blob.out(A.point_stereo, n1);
+    blob.out(A.normal, (size_t)3 * n1); blob.out(A.max_dist, n1); blob.out(A.min_dist, n1);
+    if (out->match12) blob.out(A.match12, (size_t)n1 * n_neighbours); else A.match12 = nullptr;
+    const size_t all_bytes = blob.size();
+    r = m->ensure(all_bytes);
+    if (r) return r;
+    blob.bind(m->d_blob);
+    blob.store(o_kf, kfs.data(), nkf);
+    uint8_t* b = m->d_blob;
+    uint8_t* h = m->h_blob.data();
+    std::memset(blob.host(A.neighbour), 0xFF, sizeof(int32_t) * n1);
+    A.kf = blob.device<orbm::NmpKeyFrameDev>(o_kf);
     A.total1 = total1; A.n_nb = n_neighbours; A.n1 = n1;
-    A.match12 = out->match12 ? (int32_t*)(b + o_m12) : nullptr;
     A.rule.inertial = params->inertial; A.rule.far_points = params->far_points; A.rule.th_far = params->th_far;
     A.rule.ratio_factor = 1.5f * params->scale_factor_1;
     A.last_scale = kf1->scale_factors[kf1->n_levels - 1];
-    A.neighbour = (int32_t*)(b + o_nb); A.idx2 = (int32_t*)(b + o_idx2); A.x3d = (float*)(b + o_x3d); A.point_stereo = b + o_ps;
-    A.normal = (float*)(b + o_nrm); A.max_dist = (float*)(b + o_mx); A.min_dist = (float*)(b + o_mn);
-    A.n_matched = (int32_t*)(b + o_nm); A.n_created = (int32_t*)(b + o_nc);
-    for (hipEvent_t& e : m->nmp_ev)
-        if (!e) ORBX_HIP(hipEventCreate(&e));
+    if ((r = m->nmp_timer.create())) return r;
     ORBX_HIP(hipMemcpyAsync(b, h, in_bytes, hipMemcpyHostToDevice, m->stream));
-    if (out->match12) ORBX_HIP(hipMemsetAsync(b + o_m12, 0xFF, sizeof(int32_t) * n1 * n_neighbours, m->stream));
+    if (out->match12) ORBX_HIP(hipMemsetAsync(A.match12, 0xFF, sizeof(int32_t) * n1 * n_neighbours, m->stream));
     const int groups_per_block = orbm::kNmpThreads / orbm::kNmpGroup;
-    ORBX_HIP(hipEventRecord(m->nmp_ev[0], m->stream));
+    if ((r = m->nmp_timer.start(m->stream))) return r;
     hipLaunchKernelGGL(orbm::k_new_map_points, dim3((total1 + groups_per_block - 1) / groups_per_block), dim3(orbm::kNmpThreads), 0, m->stream, A);
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(m->nmp_ev[1], m->stream));
+    if ((r = m->nmp_timer.stop(m->stream))) return r;
     ORBX_HIP(hipMemcpyAsync(h + o_out, b + o_out, all_bytes - o_out, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
-    ORBX_HIP(hipEventElapsedTime(&m->nmp_kernel_ms, m->nmp_ev[0], m->nmp_ev[1]));
+    if ((r = m->nmp_timer.read())) return r;
 
-    const int32_t* h_nb = (const int32_t*)(h + o_nb); const int32_t* h_idx2 = (const int32_t*)(h + o_idx2);
-    const float* h_x3d = (const float*)(h + o_x3d); const float* h_nrm = (const float*)(h + o_nrm);
-    const float* h_mx = (const float*)(h + o_mx); const float* h_mn = (const float*)(h + o_mn);
+    const int32_t* h_nb = blob.host(A.neighbour); const int32_t* h_idx2 = blob.host(A.idx2);
+    const float* h_x3d = blob.host(A.x3d); const float* h_nrm = blob.host(A.normal);
+    const float* h_mx = blob.host(A.max_dist); const float* h_mn = blob.host(A.min_dist);
+    const uint8_t* h_ps = blob.host(A.point_stereo);
     int created = 0;
     for (int i = 0; i < n1; i++) {
         if (h_nb[i] < 0) continue;
         created++;
-        out->neighbour[i] = h_nb[i]; out->idx2[i] = h_idx2[i]; out->point_stereo[i] = h[o_ps + i];
+        out->neighbour[i] = h_nb[i]; out->idx2[i] = h_idx2[i]; out->point_stereo[i] = h_ps[i];
         for (int c = 0; c < 3; c++) out->x3d[3 * i + c] = h_x3d[3 * i + c];
         if (want_normal) {
             for (int c = 0; c < 3; c++) out->normal[3 * i + c] = h_nrm[3 * i + c];
             out->max_dist[i] = h_mx[i]; out->min_dist[i] = h_mn[i];
         }
     }
-    if (out->match12) std::memcpy(out->match12, h + o_m12, sizeof(int32_t) * n1 * n_neighbours);
-    std::memcpy(out->n_matched, h + o_nm, sizeof(int32_t) * n_neighbours);
-    std::memcpy(out->n_created, h + o_nc, sizeof(int32_t) * n_neighbours);
+    if (out->match12) std::memcpy(out->match12, blob.host(A.match12), sizeof(int32_t) * n1 * n_neighbours);
+    std::memcpy(out->n_matched, blob.host(A.n_matched), sizeof(int32_t) * n_neighbours);
+    std::memcpy(out->n_created, blob.host(A.n_created), sizeof(int32_t) * n_neighbours);
     return created;
 }
 
-float orbm_create_new_map_points_last_kernel_ms(const orbm_matcher* m) { return m ? m->nmp_kernel_ms : 0.0f; }
+float orbm_create_new_map_points_last_kernel_ms(const orbm_matcher* m) { return m ? m->nmp_timer.ms : 0.0f; }
 
 }  // extern "C"

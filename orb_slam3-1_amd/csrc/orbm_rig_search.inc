@@ -1,6 +1,6 @@
 // orbm_rig_search.inc -- the two tracking searches for a two-camera fisheye rig frame (F.Nleft != -1): kernel, host driver and
-// the C ABI of include/orbslam3_hip_rig_match.h.  Included by orbm_matcher.hip (once, after run_projection), whose
-// search_window, key helpers, rot_bin, three_maxima, ProjFrameDev, k_grid and build_grid it uses as they are.
+// the C ABI of include/orbslam3_hip_rig_match.h.  Included by orbm_matcher.hip (once, after its host helpers), whose
+// search_window, key helpers, rot_bin, three_maxima, ProjFrameDev, k_grid, check_frame, stage_frame and launch helpers it uses as they are.
 // Reference: src/ORBmatcher.cc:43-213 (Frame x map points) and :1676-1887 (last frame).  DESIGN.md 4k.
 namespace orbm {
 
@@ -283,15 +283,7 @@ struct RigJob {
     int n_matches;                      // out
 };
 
-static int rig_check_side(const OrbmFrame* f, const char* name)
-{
-    if (f->n < 0) return fail(ORBX_ERR_ARG, "rig %s: negative n", name);
-    if (f->n >= (1 << 21)) return fail(ORBX_ERR_ARG, "rig %s: too many features", name);
-    if (f->n > 0 && (!f->x || !f->y || !f->octave || !f->desc)) return fail(ORBX_ERR_ARG, "rig %s: NULL frame arrays", name);
-    if (f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20)) return fail(ORBX_ERR_ARG, "rig %s: bad frame grid", name);
-    if (!f->scale_factors || f->n_levels < 1 || f->n_levels > 32) return fail(ORBX_ERR_ARG, "rig %s: NULL scale factors or n_levels outside [1, 32]", name);
-    return ORBX_OK;
-}
+static const char* const kRigSide[2] = {"rig left: ", "rig right: "};      // check_frame's and stage_frame's `who`
 
 static int rig_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const OrbmRigLastPoints* last, const int32_t* assign, const uint8_t* occupied)
 {
@@ -299,8 +291,8 @@ static int rig_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const 
     if ((mp != nullptr) == (last != nullptr)) return fail(ORBX_ERR_ARG, "exactly one of the map points and the last-frame points is given");
     if (!assign || !occupied) return fail(ORBX_ERR_ARG, "NULL assign/occupied");
     const OrbmFrame& l = rig->left; const OrbmFrame& r = rig->right;
-    if (int e = rig_check_side(&l, "left")) return e;
-    if (int e = rig_check_side(&r, "right")) return e;
+    if (int e = check_frame(&l, kRigSide[0], 32)) return e;           // (k_rig keeps the one scale table in 32 floats of LDS)
+    if (int e = check_frame(&r, kRigSide[1], 32)) return e;
     if (l.u_right) return fail(ORBX_ERR_ARG, "a rig frame has no u_right (left.u_right must be NULL)");
     if (!(l.min_x == r.min_x && l.min_y == r.min_y && l.max_x == r.max_x && l.max_y == r.max_y)) return fail(ORBX_ERR_ARG, "the two sides disagree in the image bounds");
     if (l.grid_cols != r.grid_cols || l.grid_rows != r.grid_rows) return fail(ORBX_ERR_ARG, "the two sides disagree in the grid");
@@ -331,24 +323,6 @@ static int rig_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const 
     }
     return ORBX_OK;
 }
-
-// dynamic LDS k_rig may ask for: the CU's 160 KB minus the kernel's own static LDS and a margin (as proj_dynamic_lds_budget)
-static size_t rig_dynamic_lds_budget()
-{
-    static size_t budget = 0;
-    if (budget == 0) {
-        size_t st = 0;
-        const void* ks[2] = {(const void*)orbm::k_rig<true>, (const void*)orbm::k_rig<false>};
-        for (const void* k : ks) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, k) == hipSuccess) st = std::max(st, (size_t)fa.sharedSizeBytes);
-        }
-        (void)hipGetLastError();
-        budget = 160 * 1024 - std::max(st, (size_t)4096) - 1024;
-    }
-    return budget;
-}
-
 // Packs all jobs into one blob; ONE k_grid launch over the 2 x n_jobs sides, ONE k_rig launch with a workgroup per rig frame;
 // one copy brings assign / occupied / counts back.
 static int run_rig_jobs(orbm_matcher* m, RigJob* jobs, int n_jobs, int last_mode, float th, int far_points, float th_far, float nnratio, int check_ori)
@@ -366,148 +340,94 @@ static int run_rig_jobs(orbm_matcher* m, RigJob* jobs, int n_jobs, int last_mode
     }
     ORBX_HIP(hipSetDevice(m->device));
     (void)hipGetLastError();
-    const size_t lds_budget = rig_dynamic_lds_budget();
-    Blob blob(m->h_blob);
-    const size_t oargs = blob.reserve(sizeof(orbm::RigArgs) * (size_t)n_jobs);
-    const size_t ogrid = blob.reserve(sizeof(orbm::ProjArgs) * (size_t)n_jobs * 2);
-    struct SideOff { size_t x, y, oct, ang, desc, coff, cfeat; float winv, hinv; };
-    struct Off { SideOff s[2]; size_t sf, l2r, r2l, valid, u, v, level, vc, valid_r, u_r, v_r, level_r, vc_r, dep, bad, angl, dmp, obs, logs, logb, assign, occ, nm; };
-    std::vector<Off> offs(n_jobs);
-    std::vector<int32_t> cell_off, cell_feat;
+    const size_t lds_budget = dynamic_lds_budget<orbm::k_rig<true>, orbm::k_rig<false>>();
+    Blob blob(m);
+    std::vector<orbm::RigArgs> args(n_jobs);
+    const size_t oargs = blob.slot<orbm::RigArgs>(n_jobs);
+    const size_t ogrid = blob.slot<orbm::ProjArgs>((size_t)n_jobs * 2);        // k_grid's jobs: the sides as frames
     size_t max_n = 0, lds_full = 0, lds_occ = 64;
     bool device_grid = true;            // Frame::AssignFeaturesToGrid of both sides on the device (k_grid) when every side fits its LDS sort
     for (int j = 0; j < n_jobs; j++) device_grid = device_grid && jobs[j].rig->left.n <= 8192 && jobs[j].rig->right.n <= 8192;
     for (int j = 0; j < n_jobs; j++) {
         const RigJob& q = jobs[j];
-        Off& o = offs[j];
+        orbm::RigArgs& A = args[j];
         const OrbmFrame* side[2] = {&q.rig->left, &q.rig->right};
-        for (int s = 0; s < 2; s++) {
-            const OrbmFrame* f = side[s];
-            SideOff& so = o.s[s];
-            if (device_grid) {
-                so.winv = (float)f->grid_cols / (f->max_x - f->min_x);         // mfGridElementWidthInv (src/Frame.cc:338)
-                so.hinv = (float)f->grid_rows / (f->max_y - f->min_y);
-                cell_off.assign((size_t)f->grid_cols * f->grid_rows + 1, 0);
-                cell_feat.assign(std::max(f->n, 1), 0);
-            } else if (int e = build_grid(f, cell_off, cell_feat, so.winv, so.hinv)) return e;
-            const int n = f->n;
-            max_n = std::max(max_n, (size_t)n);
-            so.x = blob.put(f->x, sizeof(float) * n); so.y = blob.put(f->y, sizeof(float) * n);
-            so.oct = blob.put(f->octave, sizeof(int32_t) * n);
-            so.ang = blob.put(f->angle, f->angle ? sizeof(float) * n : 0);
-            so.desc = blob.put(f->desc, (size_t)n * 32);
-            so.coff = blob.put(cell_off.data(), sizeof(int32_t) * cell_off.size());
-            so.cfeat = blob.put(cell_feat.data(), sizeof(int32_t) * cell_feat.size());
-        }
+        for (int s = 0; s < 2; s++)     // (the one scale table of the frame follows the sides)
+            if (int e = stage_frame(blob, side[s], device_grid, s ? A.R : A.L, true, false, kRigSide[s], 32)) return e;
         const int nl = side[0]->n, nr = side[1]->n, ncell = side[0]->grid_cols * side[0]->grid_rows;
         const size_t slots = (size_t)nl + nr;
+        max_n = std::max(max_n, (size_t)std::max(nl, nr));
         if (slots + 256 > lds_budget) return fail(ORBX_ERR_ARG, "rig frame with %d + %d features exceeds the LDS occupancy table", nl, nr);
         lds_occ = std::max(lds_occ, (slots + 63) & ~(size_t)63);
         lds_full = std::max(lds_full, ((slots + 15) & ~(size_t)15) + orbm::rig_side_bytes(nl, ncell) + orbm::rig_side_bytes(nr, ncell));
-        o.sf = blob.put(side[0]->scale_factors, sizeof(float) * side[0]->n_levels);
-        o.l2r = blob.put(q.rig->left_to_right, sizeof(int32_t) * nl); o.r2l = blob.put(q.rig->right_to_left, sizeof(int32_t) * nr);
+        blob.in(A.L.scale_factors, side[0]->scale_factors, side[0]->n_levels); blob.alias(A.R.scale_factors, A.L.scale_factors);
+        A.L.n_levels = A.R.n_levels = side[0]->n_levels;
+        blob.in(A.l2r, q.rig->left_to_right, nl); blob.in(A.r2l, q.rig->right_to_left, nr);
         if (!last_mode) {
             const OrbmRigMapPoints* p = q.mp;
             const size_t n = p->n;
-            o.valid = blob.put(p->in_view, n); o.u = blob.put(p->proj_u, 4 * n); o.v = blob.put(p->proj_v, 4 * n);
-            o.level = blob.put(p->pred_level, 4 * n); o.vc = blob.put(p->view_cos, 4 * n);
-            o.valid_r = blob.put(p->in_view_r, n); o.u_r = blob.put(p->proj_u_r, 4 * n); o.v_r = blob.put(p->proj_v_r, 4 * n);
-            o.level_r = blob.put(p->pred_level_r, 4 * n); o.vc_r = blob.put(p->view_cos_r, 4 * n);
-            o.dep = blob.put(p->track_depth, 4 * n); o.bad = blob.put(p->bad, n);
-            o.dmp = blob.put(p->desc, 32 * n); o.obs = blob.put(p->has_obs, n);
-            o.angl = o.logs = o.logb = 0;
+            A.n_pts = p->n;
+            blob.in(A.valid, p->in_view, n); blob.in(A.u, p->proj_u, n); blob.in(A.v, p->proj_v, n);
+            blob.in(A.level, p->pred_level, n); blob.in(A.view_cos, p->view_cos, n);
+            blob.in(A.valid_r, p->in_view_r, n); blob.in(A.u_r, p->proj_u_r, n); blob.in(A.v_r, p->proj_v_r, n);
+            blob.in(A.level_r, p->pred_level_r, n); blob.in(A.view_cos_r, p->view_cos_r, n);
+            blob.in(A.depth, p->track_depth, n); blob.in(A.bad, p->bad, n);
+            blob.in(A.desc, p->desc, 32 * n); blob.in(A.has_obs, p->has_obs, n);
+            blob.none(A.angle, A.log_slot, A.log_bin);
         } else {
             const OrbmRigLastPoints* p = q.last;
             const size_t n = p->n;
-            o.valid = blob.put(p->valid, n); o.u = blob.put(p->proj_u, 4 * n); o.v = blob.put(p->proj_v, 4 * n);
-            o.u_r = blob.put(p->proj_u_r, 4 * n); o.v_r = blob.put(p->proj_v_r, 4 * n);
-            o.level = blob.put(p->octave, 4 * n); o.angl = blob.put(p->angle, p->angle ? 4 * n : 0);
-            o.dmp = blob.put(p->desc, 32 * n); o.obs = blob.put(p->has_obs, n);
-            o.logs = blob.reserve(sizeof(int32_t) * 2 * std::max(n, (size_t)1)); o.logb = blob.reserve(sizeof(int32_t) * 2 * std::max(n, (size_t)1));
-            o.vc = o.valid_r = o.level_r = o.vc_r = o.dep = o.bad = 0;
+            A.n_pts = p->n;
+            blob.in(A.valid, p->valid, n); blob.in(A.u, p->proj_u, n); blob.in(A.v, p->proj_v, n);
+            blob.in(A.u_r, p->proj_u_r, n); blob.in(A.v_r, p->proj_v_r, n);
+            blob.in(A.level, p->octave, n); blob.in_opt(A.angle, p->angle, n);
+            blob.in(A.desc, p->desc, 32 * n); blob.in(A.has_obs, p->has_obs, n);
+            blob.out(A.log_slot, 2 * std::max(n, (size_t)1)); blob.out(A.log_bin, 2 * std::max(n, (size_t)1));
+            blob.none(A.view_cos, A.valid_r, A.level_r, A.view_cos_r, A.depth, A.bad);
         }
-    }
-    // in/out and output arrays of all jobs sit together at the end: one copy brings every result back
-    const size_t out_begin = (m->h_blob.size() + 15) & ~(size_t)15;
-    for (int j = 0; j < n_jobs; j++) {
-        const RigJob& q = jobs[j];
-        const size_t slots = (size_t)q.rig->left.n + q.rig->right.n;
-        offs[j].assign = blob.put(q.assign, sizeof(int32_t) * slots); offs[j].occ = blob.put(q.occupied, slots);
-        offs[j].nm = blob.reserve(sizeof(int32_t));
-    }
-    if (int e = m->ensure(m->h_blob.size())) return e;
-    uint8_t* base = m->d_blob;
-    orbm::RigArgs* args = (orbm::RigArgs*)(m->h_blob.data() + oargs);
-    orbm::ProjArgs* grids = (orbm::ProjArgs*)(m->h_blob.data() + ogrid);
-    for (int j = 0; j < n_jobs; j++) {
-        const RigJob& q = jobs[j];
-        const Off& o = offs[j];
-        const OrbmFrame* side[2] = {&q.rig->left, &q.rig->right};
-        orbm::RigArgs A{};
-        for (int s = 0; s < 2; s++) {
-            const OrbmFrame* f = side[s];
-            const SideOff& so = o.s[s];
-            orbm::ProjFrameDev& F = s ? A.R : A.L;
-            F.x = (const float*)(base + so.x); F.y = (const float*)(base + so.y); F.octave = (const int32_t*)(base + so.oct);
-            F.angle = (const float*)(base + so.ang); F.desc = base + so.desc;
-            F.cell_off = (const int32_t*)(base + so.coff); F.cell_feat = (const int32_t*)(base + so.cfeat);
-            F.scale_factors = (const float*)(base + o.sf);
-            F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y; F.winv = so.winv; F.hinv = so.hinv;
-            F.n = f->n; F.cols = f->grid_cols; F.rows = f->grid_rows; F.n_levels = f->n_levels;
-            F.u_right = nullptr;
-            orbm::ProjArgs G{};
-            G.F = F;
-            grids[2 * j + s] = G;
-        }
-        A.l2r = (const int32_t*)(base + o.l2r); A.r2l = (const int32_t*)(base + o.r2l);
-        A.n_pts = last_mode ? q.last->n : q.mp->n;
-        A.valid = base + o.valid; A.u = (const float*)(base + o.u); A.v = (const float*)(base + o.v);
-        A.level = (const int32_t*)(base + o.level); A.view_cos = (const float*)(base + o.vc);
-        A.valid_r = base + o.valid_r; A.u_r = (const float*)(base + o.u_r); A.v_r = (const float*)(base + o.v_r);
-        A.level_r = (const int32_t*)(base + o.level_r); A.view_cos_r = (const float*)(base + o.vc_r);
-        A.depth = (const float*)(base + o.dep); A.bad = base + o.bad; A.angle = (const float*)(base + o.angl);
-        A.desc = base + o.dmp; A.has_obs = base + o.obs;
         A.th = th; A.th_far = th_far; A.nnratio = nnratio; A.far_points = far_points; A.check_ori = check_ori;
         A.level_window = q.level_window; A.last_mode = last_mode;
-        A.assign = (int32_t*)(base + o.assign); A.occupied = base + o.occ;
-        A.log_slot = (int32_t*)(base + o.logs); A.log_bin = (int32_t*)(base + o.logb); A.n_matches = (int32_t*)(base + o.nm);
-        args[j] = A;
+    }
+    // in/out and output arrays of all jobs sit together at the end: one copy brings every result back
+    const size_t out_begin = blob.begin_out();
+    for (int j = 0; j < n_jobs; j++) {
+        const size_t slots = (size_t)jobs[j].rig->left.n + jobs[j].rig->right.n;
+        blob.inout(args[j].assign, jobs[j].assign, slots); blob.inout(args[j].occupied, jobs[j].occupied, slots);
+        blob.out(args[j].n_matches, 1);
+    }
+    if (int e = m->ensure(blob.size())) return e;
+    blob.bind(m->d_blob);
+    blob.store(oargs, args.data(), n_jobs);
+    orbm::ProjArgs* grids = (orbm::ProjArgs*)(m->h_blob.data() + ogrid);
+    for (int j = 0; j < n_jobs; j++) {
+        grids[2 * j] = orbm::ProjArgs{}; grids[2 * j].F = args[j].L;
+        grids[2 * j + 1] = orbm::ProjArgs{}; grids[2 * j + 1].F = args[j].R;
     }
     const bool stage = lds_full <= lds_budget;      // selected per launch: every frame of the batch fits, or none is staged
     const size_t lds = stage ? lds_full : lds_occ;
-    for (hipEvent_t& e : m->rig_ev)
-        if (!e) ORBX_HIP(hipEventCreate(&e));
-    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), m->h_blob.size(), hipMemcpyHostToDevice, m->stream));
-    ORBX_HIP(hipEventRecord(m->rig_ev[0], m->stream));
-    if (device_grid) {
-        int n_pow2 = 2;
-        while ((size_t)n_pow2 < max_n) n_pow2 <<= 1;
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_grid, hipFuncAttributeMaxDynamicSharedMemorySize, n_pow2 * 8));
-        hipLaunchKernelGGL(orbm::k_grid, dim3(2 * n_jobs), dim3(256), (size_t)n_pow2 * 8, m->stream, (const orbm::ProjArgs*)(base + ogrid), n_pow2);
-    }
-    if (stage) {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_rig<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_rig<true>, dim3(n_jobs), dim3(orbm::kRigThreads), lds, m->stream, (const orbm::RigArgs*)(base + oargs));
-    } else {
-        ORBX_HIP(hipFuncSetAttribute((const void*)orbm::k_rig<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(orbm::k_rig<false>, dim3(n_jobs), dim3(orbm::kRigThreads), lds, m->stream, (const orbm::RigArgs*)(base + oargs));
-    }
+    uint8_t* base = m->d_blob;
+    if (int e = m->rig_timer.create()) return e;
+    ORBX_HIP(hipMemcpyAsync(base, m->h_blob.data(), blob.size(), hipMemcpyHostToDevice, m->stream));
+    if (int e = m->rig_timer.start(m->stream)) return e;
+    if (device_grid)
+        if (int e = launch_grid(m->stream, blob.device<orbm::ProjArgs>(ogrid), 2 * n_jobs, max_n)) return e;
+    if (int e = launch_staged(orbm::k_rig<true>, orbm::k_rig<false>, stage, n_jobs, orbm::kRigThreads, lds, m->stream, blob.device<orbm::RigArgs>(oargs))) return e;
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(m->rig_ev[1], m->stream));
-    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, m->h_blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
+    if (int e = m->rig_timer.stop(m->stream)) return e;
+    ORBX_HIP(hipMemcpyAsync(m->h_blob.data() + out_begin, base + out_begin, blob.size() - out_begin, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
-    ORBX_HIP(hipEventElapsedTime(&m->rig_kernel_ms, m->rig_ev[0], m->rig_ev[1]));
+    if (int e = m->rig_timer.read()) return e;
     for (int j = 0; j < n_jobs; j++) {
-        const Off& o = offs[j];
         const size_t slots = (size_t)jobs[j].rig->left.n + jobs[j].rig->right.n;
         if (slots > 0) {
-            std::memcpy(jobs[j].assign, m->h_blob.data() + o.assign, sizeof(int32_t) * slots);
-            std::memcpy(jobs[j].occupied, m->h_blob.data() + o.occ, slots);
+            std::memcpy(jobs[j].assign, blob.host(args[j].assign), sizeof(int32_t) * slots);
+            std::memcpy(jobs[j].occupied, blob.host(args[j].occupied), slots);
         }
-        std::memcpy(&jobs[j].n_matches, m->h_blob.data() + o.nm, sizeof(int32_t));
+        std::memcpy(&jobs[j].n_matches, blob.host(args[j].n_matches), sizeof(int32_t));
     }
     return ORBX_OK;
 }
+
 
 extern "C" {
 
@@ -564,6 +484,6 @@ int orbm_search_by_projection_last_rig_batch(orbm_matcher* m, OrbmRigLastQuery* 
     return ORBX_OK;
 }
 
-float orbm_rig_search_last_kernel_ms(const orbm_matcher* m) { return m ? m->rig_kernel_ms : 0.f; }
+float orbm_rig_search_last_kernel_ms(const orbm_matcher* m) { return m ? m->rig_timer.ms : 0.f; }
 
 }  // extern "C"

@@ -230,56 +230,49 @@ int orbm_stereo_fisheye(orbm_matcher* m,
     if (n_l == 0 && n_r == 0) return 0;
 
     ORBX_HIP(hipSetDevice(m->device));
-    Blob blob(m->h_blob);
+    Blob blob(m);
     const size_t L = (size_t)n_l, R = (size_t)n_r;
     const int32_t counts[4] = {n_l, mono_l, n_r, mono_r};
-    const size_t o_kl = blob.put(kps_l, sizeof(OrbxKeyPoint) * L), o_dl = blob.put(desc_l, 32 * L);
-    const size_t o_kr = blob.put(kps_r, sizeof(OrbxKeyPoint) * R), o_dr = blob.put(desc_r, 32 * R);
-    const size_t o_cnt = blob.put(counts, sizeof(counts));
-    const size_t in_bytes = m->h_blob.size();
-    const size_t o_out = blob.reserve(0);
-    const size_t o_ltr = blob.reserve(sizeof(int32_t) * L), o_rtl = blob.reserve(sizeof(int32_t) * R);
-    const size_t o_dep = blob.reserve(sizeof(float) * L), o_p3d = blob.reserve(sizeof(float) * 3 * L);
-    const size_t o_kn = blob.reserve(sizeof(int32_t) * L), o_k0 = blob.reserve(sizeof(int32_t) * L), o_k1 = blob.reserve(sizeof(int32_t) * L);
-    const size_t all_bytes = m->h_blob.size();
-    if (int r = m->ensure(all_bytes)) return r;
-    uint8_t* b = m->d_blob;
-    uint8_t* h = m->h_blob.data();
-
     sfe::Args A;
     std::memset(&A, 0, sizeof(A));
-    const int32_t* d_cnt = (const int32_t*)(b + o_cnt);
-    A.kps_l = (const OrbxKeyPoint*)(b + o_kl); A.desc_l = b + o_dl; A.n_l = d_cnt; A.mono_l = d_cnt + 1;
-    A.kps_r = (const OrbxKeyPoint*)(b + o_kr); A.desc_r = b + o_dr; A.n_r = d_cnt + 2; A.mono_r = d_cnt + 3;
+    blob.in(A.kps_l, kps_l, L); blob.in(A.desc_l, desc_l, 32 * L);
+    blob.in(A.kps_r, kps_r, R); blob.in(A.desc_r, desc_r, 32 * R);
+    blob.in(A.n_l, counts, 4);
+    const size_t in_bytes = blob.size(), o_out = blob.begin_out();
+    blob.out(A.left_to_right, L); blob.out(A.right_to_left, R); blob.out(A.depth, L); blob.out(A.p3d, 3 * L);
+    blob.out(A.knn_right, L); blob.out(A.knn_d0, L); blob.out(A.knn_d1, L);
+    const size_t all_bytes = blob.size();
+    if (int r = m->ensure(all_bytes)) return r;
+    blob.bind(m->d_blob);
+    uint8_t* b = m->d_blob;
+    uint8_t* h = m->h_blob.data();
+    A.mono_l = A.n_l + 1; A.n_r = A.n_l + 2; A.mono_r = A.n_l + 3;          // the four counts are one array
     A.cap_l = n_l; A.cap_r = n_r;
-    A.left_to_right = (int32_t*)(b + o_ltr); A.right_to_left = (int32_t*)(b + o_rtl); A.depth = (float*)(b + o_dep); A.p3d = (float*)(b + o_p3d);
-    A.knn_right = (int32_t*)(b + o_kn); A.knn_d0 = (int32_t*)(b + o_k0); A.knn_d1 = (int32_t*)(b + o_k1);
     A.rig = rig_of(rig);
     std::memcpy(A.sigma2, level_sigma2, sizeof(float) * n_levels);
     A.n_levels = n_levels;
 
-    for (hipEvent_t& e : m->sfe_ev)
-        if (!e) ORBX_HIP(hipEventCreate(&e));
+    if (int r = m->sfe_timer.create()) return r;
     ORBX_HIP(hipMemcpyAsync(b, h, in_bytes, hipMemcpyHostToDevice, m->stream));
-    if (int r = launch(A, 1, m->stream, m->sfe_ev)) return r;
+    if (int r = launch(A, 1, m->stream, m->sfe_timer.ev)) return r;
     if (all_bytes > o_out) ORBX_HIP(hipMemcpyAsync(h + o_out, b + o_out, all_bytes - o_out, hipMemcpyDeviceToHost, m->stream));
     ORBX_HIP(hipStreamSynchronize(m->stream));
-    ORBX_HIP(hipEventElapsedTime(&m->sfe_kernel_ms, m->sfe_ev[0], m->sfe_ev[1]));
+    if (int r = m->sfe_timer.read()) return r;
 
-    const int32_t* h_ltr = (const int32_t*)(h + o_ltr);
+    const int32_t* h_ltr = blob.host(A.left_to_right);
     int matches = 0;
     for (int i = 0; i < n_l; i++) matches += h_ltr[i] >= 0;
-    if (left_to_right) std::memcpy(left_to_right, h + o_ltr, sizeof(int32_t) * L);
-    if (right_to_left) std::memcpy(right_to_left, h + o_rtl, sizeof(int32_t) * R);
-    if (depth) std::memcpy(depth, h + o_dep, sizeof(float) * L);
-    if (p3d) std::memcpy(p3d, h + o_p3d, sizeof(float) * 3 * L);
-    if (knn_right) std::memcpy(knn_right, h + o_kn, sizeof(int32_t) * L);
-    if (knn_d0) std::memcpy(knn_d0, h + o_k0, sizeof(int32_t) * L);
-    if (knn_d1) std::memcpy(knn_d1, h + o_k1, sizeof(int32_t) * L);
+    if (left_to_right) std::memcpy(left_to_right, h_ltr, sizeof(int32_t) * L);
+    if (right_to_left) std::memcpy(right_to_left, blob.host(A.right_to_left), sizeof(int32_t) * R);
+    if (depth) std::memcpy(depth, blob.host(A.depth), sizeof(float) * L);
+    if (p3d) std::memcpy(p3d, blob.host(A.p3d), sizeof(float) * 3 * L);
+    if (knn_right) std::memcpy(knn_right, blob.host(A.knn_right), sizeof(int32_t) * L);
+    if (knn_d0) std::memcpy(knn_d0, blob.host(A.knn_d0), sizeof(int32_t) * L);
+    if (knn_d1) std::memcpy(knn_d1, blob.host(A.knn_d1), sizeof(int32_t) * L);
     return matches;
 }
 
-float orbm_stereo_fisheye_last_kernel_ms(const orbm_matcher* m) { return m ? m->sfe_kernel_ms : 0.0f; }
+float orbm_stereo_fisheye_last_kernel_ms(const orbm_matcher* m) { return m ? m->sfe_timer.ms : 0.0f; }
 
 int orbm_stereo_fisheye_batch_device(orbm_matcher* m, int batch, int cap,
                                      const OrbxKeyPoint* d_kps_l, const uint8_t* d_desc_l, const int32_t* d_n_l, const int32_t* d_mono_l,

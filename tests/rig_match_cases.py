@@ -381,6 +381,9 @@ def random_calls():
 # 160 KB - max(static LDS of the kernel, 4 KB) - 1 KB.  With 2000 features a side the frame alone needs 48 * 4000 = 192 000 B, more
 # than the whole 160 KB = 163 840 B whatever the static part is: the launch takes the unstaged path.  (1000 a side, 122.6 KB, is staged.)
 UNSTAGED_N = 2000
+# A side of 8193 features is one more than the device's grid sort takes: the grids of the whole launch are built on the host.  By the
+# same sum 8193 + 300 features need 48 * 8493 = 407 664 B: unstaged as well.
+HOST_GRID_N = (8193, 300)
 
 
 def _crowded_rig(seed):
@@ -406,6 +409,7 @@ def shape_calls():
         c[kind + "_65_points"] = make(14, nl=80, nr=70, n_pts=65)
         c[kind + "_129_points"] = make(15, nl=120, nr=100, n_pts=129)
         c[kind + "_unstaged_%d_a_side" % UNSTAGED_N] = make(16, nl=UNSTAGED_N, nr=UNSTAGED_N, n_pts=60)
+        c[kind + "_host_grid_%d_and_%d" % HOST_GRID_N] = make(20, nl=HOST_GRID_N[0], nr=HOST_GRID_N[1], n_pts=60)
         c[kind + "_batch_of_3"] = [make(17, nl=90, nr=60, n_pts=70), make(18, nl=0, nr=0, n_pts=10, partner_frac=0.0), make(19, nl=150, nr=170, n_pts=40)]
     rig, D = _crowded_rig(5)
     rng = np.random.default_rng(6)

@@ -145,8 +145,11 @@ def test_search_by_projection_last_frame_stereo(pkg, oracle, sm, seed, th, ori, 
     np.testing.assert_array_equal(o1, o0)
 
 
-def test_projection_stereo_argument_errors(pkg, sm):
-    """a stereo frame without the points' right columns is refused, never searched as if it were monocular"""
+def test_projection_stereo_argument_errors(pkg, oracle, sm):
+    """a stereo frame without the points' right columns is refused, never searched as if it were monocular; and a refused call leaves
+    the handle usable: the next good call of every entry that shares the frame staging equals its oracle"""
+    import rig_match_cases
+    from test_rig_match_reference import run_reference
     g, dF, angF, scale, last, assign, occ = sm.make_last_frame_case(2, n=200, n_last=100, stereo_frac=0.5)
     bad = {k: v for k, v in last.items() if k != "ur"}
     m = pkg.Matcher(0.9, True)
@@ -156,6 +159,29 @@ def test_projection_stereo_argument_errors(pkg, sm):
         bad = dict(last); bad["level_window"] = 3
         with pytest.raises(pkg.OrbxError):
             m.SearchByProjection_last(g, dF, angF, scale, bad, 15.0, assign.copy(), occ.copy())
+        bad = dict(last); bad["octave"] = last["octave"].copy(); bad["octave"][np.flatnonzero(last["valid"])[0]] = len(scale)
+        with pytest.raises(pkg.OrbxError, match="out of range"):
+            m.SearchByProjection_last(g, dF, angF, scale, bad, 15.0, assign.copy(), occ.copy())
+        a0, o0 = assign.copy(), occ.copy()
+        n0 = oracle.search_by_projection_last(g, dF, angF, scale, last, 15.0, True, a0, o0)
+        a1, o1 = assign.copy(), occ.copy()
+        assert m.SearchByProjection_last(g, dF, angF, scale, last, 15.0, a1, o1) == n0 and n0 > 20
+        np.testing.assert_array_equal(a1, a0); np.testing.assert_array_equal(o1, o0)
+        for c in (rig_match_cases.random_mp_call(1), rig_match_cases.random_last_call(1)):
+            want = run_reference(c)
+            ra, ro = c["assign"].copy(), c["occupied"].copy()
+            m.nnratio, m.check_ori = c["nnratio"], c["check_ori"]
+            if c["kind"] == "mp":
+                rn = m.search_by_projection_rig(c["rig"], c["pts"], c["th"], ra, ro, c["far_points"], c["th_far"])
+            else:
+                rn = m.search_by_projection_last_rig(c["rig"], c["pts"], c["th"], ra, ro)
+            assert rn == want[0] and rn > 20
+            np.testing.assert_array_equal(ra, want[1]); np.testing.assert_array_equal(ro, want[2])
+        fg, fd, fscale, fur, fs2, fpts = sm.make_fuse_case(5, n_pts=300)
+        bi0, bd0 = oracle.fuse_search(fg, fd, fscale, fur, fs2, fpts, 3.0, True)
+        bi1, bd1 = m.FuseSearch(fg, fd, fscale, fur, fs2, fpts, 3.0, True)
+        np.testing.assert_array_equal(bi1, bi0); np.testing.assert_array_equal(bd1, bd0)
+        assert (bi0 >= 0).sum() > 20
     finally:
         m.close()
 
@@ -435,6 +461,42 @@ def test_projection_searches_around_the_lds_staging_limit(pkg, oracle, sm, n):
     np.testing.assert_array_equal(b1, b0); np.testing.assert_array_equal(p1, p0)
     assert int(d_nm.item()) == n0
     np.testing.assert_array_equal(a3, a0); np.testing.assert_array_equal(o3, o0)
+
+
+@pytest.mark.parametrize("n", [8193, 20000])
+def test_projection_searches_on_large_frames(pkg, oracle, sm, n):
+    """the two branches of the host driver that frames of ordinary size never take.  8193 features: one more than the device's grid sort
+    takes, so Frame::AssignFeaturesToGrid runs on the host -- for the whole batch when one of its frames is that large (the second half:
+    the same frame in one launch with a 500-feature frame).  20000 features: the block-parallel search's two tables alone would need more
+    than 9 bytes a feature, over 160 KB of LDS whatever the static part is, so the sequential kernel runs, unstaged.  (Its staged
+    instance is reachable only through the ORBM_PROJ_SEQUENTIAL knob, read once per process: tools/proj_timing.py covers it.)"""
+    big = sm.make_last_frame_case(21, n=n, n_last=130)
+    g, dF, aF, sc, last, a, oc = big
+    a0, o0 = a.copy(), oc.copy()
+    n0 = oracle.search_by_projection_last(g, dF, aF, sc, last, 15.0, True, a0, o0)
+    g2, dF2, aF2, sc2, mp, a2, oc2 = sm.make_projection_case(21, n=n, n_mp=130)
+    b0, p0 = a2.copy(), oc2.copy()
+    k0 = oracle.search_by_projection(g2, dF2, sc2, mp, 3.0, 0.8, b0, p0)
+    assert n0 > 40 and k0 > 40
+    m = pkg.Matcher(0.8, True)
+    try:
+        a1, o1 = a.copy(), oc.copy()
+        n1 = m.SearchByProjection_last(g, dF, aF, sc, last, 15.0, a1, o1)
+        b1, p1 = a2.copy(), oc2.copy()
+        k1 = m.SearchByProjection(g2, dF2, sc2, mp, 3.0, b1, p1)
+        assert (n1, k1) == (n0, k0)
+        np.testing.assert_array_equal(a1, a0); np.testing.assert_array_equal(o1, o0)
+        np.testing.assert_array_equal(b1, b0); np.testing.assert_array_equal(p1, p0)
+        if n == 8193:
+            small = sm.make_last_frame_case(22, n=500, n_last=130)
+            sa, so = small[5].copy(), small[6].copy()
+            sn = oracle.search_by_projection_last(small[0], small[1], small[2], small[3], small[4], 15.0, True, sa, so)
+            cases = [big[:5] + (a.copy(), oc.copy()), small[:5] + (small[5].copy(), small[6].copy())]
+            assert m.run_last_batch(m.prepare_last_batch(cases), 15.0) == [n0, sn] and sn > 40
+            np.testing.assert_array_equal(cases[0][5], a0); np.testing.assert_array_equal(cases[0][6], o0)
+            np.testing.assert_array_equal(cases[1][5], sa); np.testing.assert_array_equal(cases[1][6], so)
+    finally:
+        m.close()
 
 
 def _crowd(rs, g, desc, targets, followers=7):

@@ -75,7 +75,7 @@ def test_hand_built_calls_in_one_launch(matcher):
 
 
 SHAPES = sorted(k + s for k in ("mp", "last") for s in ("_no_left_features", "_no_right_features", "_no_points", "_65_points", "_129_points",
-                                                         "_unstaged_%d_a_side" % cases.UNSTAGED_N, "_batch_of_3", "_70_features_in_one_cell",
+                                                         "_unstaged_%d_a_side" % cases.UNSTAGED_N, "_host_grid_%d_and_%d" % cases.HOST_GRID_N, "_batch_of_3", "_70_features_in_one_cell",
                                                          "_window_wider_than_16_columns"))
 
 

@@ -135,6 +135,17 @@ int orbx_debug_last_schedule(orbx_extractor* h);
  * lower levels (or all levels, when there is one launch), 2 the upper levels; 0 when the call had no such launch.  ORBX_OCT_WAVES =
  * 1 | 2 | 4 (read at construction) forces the value for every launch. */
 int orbx_debug_octree_waves(orbx_extractor* h, int launch);
+/* Test hook: 1 when the LAST extract call resized a pyramid level with k_resize (bands of rows, frames across the lanes: batches of 64
+ * frames and more, or of ORBX_RESIZE_BAND_MIN, read at construction), 0 when every level took k_resize_tiles / k_resize_generic. */
+int orbx_debug_resize_bands(orbx_extractor* h);
+/* Test hook (host only, no device needed): the per-row table of the table-driven pyramid resize from `src_h` to `dst_h` rows as the
+ * kernels read it -- four words per destination row into rows[4 * dst_h]: the two source rows clamped to the image
+ * (sy0 | sy1 << 16), the two vertical coefficients (0 .. 2048) shifted left by 12, and the reuse plan of a row walked after its
+ * predecessor: bits 0-1 the top source row is fresh (0), the previous row's bottom (1) or top (2) source row; bit 2 the bottom
+ * source row is the top one.  The kernels reuse the previous bottom row (plan 1) and load every other row; the first row of a band
+ * of *band_rows destination rows (bands start at multiples of it) loads both.  Returns 1 when the coefficient sums of every row
+ * are at most 2048 (the kernels then drop the clamp to 255, provided the columns pass too), 0 when not, negative on error. */
+int orbx_debug_resize_rows(int src_h, int dst_h, uint32_t* rows, int* band_rows);
 /* Test hook: the FAST score tree of the extractor's corner kernel alone.  `patches` holds n row-major 7 x 7 patches (49 bytes each,
  * host memory); out[i] = M of patch i's centre = max(0, max over the 16 arcs of nine of min(d), of min(-d)), d = centre - ring
  * pixel: OpenCV's corner score + 1.  `pitch` (8..1024) is the row pitch at which the kernel lays the patches out in LDS. */

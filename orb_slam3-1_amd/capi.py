@@ -85,6 +85,8 @@ lib.orbx_debug_level_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_voi
 lib.orbx_debug_set_tail_delay.argtypes = [C.c_void_p, C.c_int]
 lib.orbx_debug_last_schedule.argtypes = [C.c_void_p]
 lib.orbx_debug_octree_waves.argtypes = [C.c_void_p, C.c_int]
+lib.orbx_debug_resize_bands.argtypes = [C.c_void_p]
+lib.orbx_debug_resize_rows.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
 lib.orbx_debug_introsort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.orbx_debug_wave_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.orbx_debug_fast_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -251,6 +253,10 @@ class Extractor:
 
     def debug_set_tail_delay(self, microseconds):
         _check(lib.orbx_debug_set_tail_delay(self._h, int(microseconds)))
+
+    def debug_resize_bands(self):
+        """test hook: did the last extract call resize a level with k_resize (bands of rows, frames across the lanes)?"""
+        return bool(lib.orbx_debug_resize_bands(self._h))
 
     def debug_last_schedule(self):
         """bits: 0-1 octree instantiation (0 node pool in HBM, 1 keys + nodes in LDS, 2 keys in the scratch), 4 two octree launches,

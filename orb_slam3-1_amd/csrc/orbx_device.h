@@ -41,8 +41,15 @@ struct TileDesc {
 // One destination row of the table-driven resize (k_resize, k_resize_tail): the two source rows clamped to the source image
 // (sy0 | sy1 << 16) and the two vertical coefficients (0 .. 2048) shifted left by 12.  The host pads the table to whole tiles of
 // 64 rows with copies of the last row, so that a thread reads its rows without a bound test.
+// `plan` says which of the row's two source rows the previous destination row has filtered already, for a kernel that walks the
+// rows in order and keeps the previous row's two horizontal results (resize_band): bits 0-1 the top row -- kResizeTopFresh, or
+// the previous row's bottom / top source row; bit 2 (kResizeBottomIsTop) the bottom row is the top row, otherwise it is fresh.
+// Computed on the clamped source rows.  resize_band reuses the previous BOTTOM row (five rows out of six at scale 1.2); the other
+// two plans only arise where source rows are clamped, and it filters such a row again.
+constexpr uint32_t kResizeTopFresh = 0, kResizeTopPrevBottom = 1, kResizeTopPrevTop = 2, kResizeBottomIsTop = 4;
+constexpr int kResizeBand = 16;      // output rows a wave walks with the horizontal results in registers
 struct __attribute__((aligned(16))) ResizeRow {
-    uint32_t sy, b0, b1, pad;
+    uint32_t sy, b0, b1, plan;
 };
 
 // Workgroups are dispatched round-robin over the 8 XCDs, so workgroups b and b+8 share an L2 (MI355X_MICROARCH.md,

@@ -35,6 +35,43 @@ int fail(int code, const char* fmt, ...)
 static inline int cv_round_host(double v) { return (int)std::nearbyint(v); }
 static inline int cv_floor_host(double v) { int i = (int)v; return i - (i > v); }
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
+constexpr int kResizeFrames = 4;       // frames across the lanes of a wave of the table-driven resize (resize_band's F)
+// a lane reaches its frame of the group with a 32-bit byte offset
+static inline bool resize_frames_fit(size_t frame_stride) { return (uint64_t)kResizeFrames * frame_stride < ((uint64_t)1 << 31); }
+static inline short sat_short(float v) { int iv = (int)std::nearbyintf(v); return (short)std::min(std::max(iv, -32768), 32767); }
+
+// The per-row tables of cv::resize INTER_LINEAR 8UC1 from src_h to dst_h rows: yofs / ib as OpenCV builds
+// them, and `rows`, what the table-driven kernels read -- the source rows clamped to the image, the coefficients as the kernels
+// multiply them (b << 12) and the reuse plan of resize_band (ResizeRow::plan, on the clamped rows), padded to whole tiles of
+// kResizeRows rows with copies of the last row.  *sums_ok: b0 + b1 <= 2048 in every row (the unclamped form is exact).
+static int build_resize_rows(int src_h, int dst_h, std::vector<int>& yofs, std::vector<short>& ib, std::vector<ResizeRow>& rows, bool* sums_ok)
+{
+    const double scale_y = 1. / ((double)dst_h / src_h);
+    yofs.assign(dst_h, 0); ib.assign((size_t)dst_h * 2, 0);
+    for (int dy = 0; dy < dst_h; dy++) {
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        int sy = cv_floor_host(fy);
+        fy -= sy;
+        yofs[dy] = sy;
+        ib[2 * dy] = sat_short((1.f - fy) * 2048);
+        ib[2 * dy + 1] = sat_short(fy * 2048);
+    }
+    rows.assign((size_t)round_up(dst_h, kResizeRows), ResizeRow());
+    *sums_ok = true;
+    int p0 = -1, p1 = -1;               // the previous row's clamped source rows
+    for (size_t dy = 0; dy < rows.size(); dy++) {
+        const int y = std::min((int)dy, dst_h - 1);
+        const int sy0 = std::min(std::max(yofs[y], 0), src_h - 1), sy1 = std::min(std::max(yofs[y] + 1, 0), src_h - 1);
+        if (ib[2 * y] < 0 || ib[2 * y] > 2048 || ib[2 * y + 1] < 0 || ib[2 * y + 1] > 2048)
+            return fail(ORBX_ERR_INTERNAL, "resize table: row coefficients %d %d", ib[2 * y], ib[2 * y + 1]);
+        if (ib[2 * y] + ib[2 * y + 1] > 2048) *sums_ok = false;
+        rows[dy].sy = (uint32_t)sy0 | ((uint32_t)sy1 << 16);
+        rows[dy].b0 = (uint32_t)ib[2 * y] << 12; rows[dy].b1 = (uint32_t)ib[2 * y + 1] << 12;
+        rows[dy].plan = (sy0 == p1 ? kResizeTopPrevBottom : (sy0 == p0 ? kResizeTopPrevTop : kResizeTopFresh)) | (sy1 == sy0 ? kResizeBottomIsTop : 0u);
+        p0 = sy0; p1 = sy1;
+    }
+    return ORBX_OK;
+}
 
 // getGaussianKernelFixedPoint_ED (OpenCV 4.x): Q8.8 taps, error diffusion, centre = 256 - 2*sum(others)
 static void gauss_taps_q8(int n, double sigma, int* taps)
@@ -124,6 +161,7 @@ struct orbx_extractor {
     std::vector<DevBuf<int> > d_xofs, d_yofs;    // per-column / per-row tables of the levels that take k_resize_generic (resize_generic[l])
     std::vector<DevBuf<short> > d_ialpha, d_ibeta;
     std::vector<uint8_t> resize_generic;
+    std::vector<uint8_t> resize_sat;     // levels whose coefficient sums do not prove the clamp to 255 dead: the saturating kernels
 
     // per-batch scratch
     int batch_cap = 0, last_batch = 0;
@@ -160,6 +198,8 @@ struct orbx_extractor {
     // streams for the ranges a large batch is cut into (enqueue)
     int split_parts = 1;                 // ORBX_SPLIT (measurement knob, see enqueue)
     bool serial_schedule = false;        // ORBX_SERIAL=1: every kernel of a batch on the launch stream, one launch per stage (per-kernel profiles)
+    bool last_resize_bands = false;      // the last enqueue resized a level with k_resize (orbx_debug_resize_bands)
+    int resize_band_min = 64;            // batches from this size on take k_resize (bands of rows, frames across the lanes), smaller ones k_resize_tiles (ORBX_RESIZE_BAND_MIN)
     int resize_tail_first = 4;           // first pyramid level of the fused resize tail (ORBX_RESIZE_TAIL; 0: a launch per level)
     bool oct_dyn_off = false;            // ORBX_OCT_DYN=0: small batches keep the scratch instantiation (measurement / tests)
     int oct_dyn_max_batch = 64;          // largest batch that takes k_octree_dyn (ORBX_OCT_DYN_MAXB; measured: one frame 0.163 -> 0.136 ms,
@@ -232,7 +272,7 @@ int orbx_extractor::setup_geometry(int w, int h)
     int cand_off = 0, sel_off = 0, max_tw = 0, max_th = 0, max_nfeat = 0;
     std::vector<int> node_need(nlevels, 0);
     d_qsx0.resize(nlevels); d_yofs.resize(nlevels); d_qsel.resize(nlevels); d_qalpha.resize(nlevels); d_ibeta.resize(nlevels); d_rows.resize(nlevels);
-    d_xofs.resize(nlevels); d_ialpha.resize(nlevels); resize_generic.assign(nlevels, 0);
+    d_xofs.resize(nlevels); d_ialpha.resize(nlevels); resize_generic.assign(nlevels, 0); resize_sat.assign(nlevels, 0);
     for (int l = 0; l < nlevels; l++) {
         LevelDesc& L = levels[l];
         L.w = (int)std::nearbyintf((float)w * inv_scale[l]);      // ComputePyramid :1175
@@ -318,11 +358,12 @@ int orbx_extractor::setup_geometry(int w, int h)
         // resize tables (cv::resize INTER_LINEAR 8UC1); level l is made from level l-1
         if (l > 0) {
             const LevelDesc& P = levels[l - 1];
-            const double scale_x = 1. / ((double)L.w / P.w), scale_y = 1. / ((double)L.h / P.h);
+            const double scale_x = 1. / ((double)L.w / P.w);
             const int wpad = round_up(L.w, 4);          // k_resize reads 4 entries per 16-B load
-            std::vector<int> xofs(wpad, 0), yofs(L.h);
-            std::vector<short> ia((size_t)wpad * 2, 0), ib((size_t)L.h * 2);
-            auto sat = [](float v) { int iv = (int)std::nearbyintf(v); return (short)std::min(std::max(iv, -32768), 32767); };
+            std::vector<int> xofs(wpad, 0), yofs;
+            std::vector<short> ia((size_t)wpad * 2, 0), ib;
+            auto sat = sat_short;
+            bool sums_ok = true;                        // a0 + a1 <= 2048 in every column and b0 + b1 <= 2048 in every row
             for (int dx = 0; dx < L.w; dx++) {
                 float fx = (float)((dx + 0.5) * scale_x - 0.5);
                 int sx = cv_floor_host(fx);
@@ -332,14 +373,7 @@ int orbx_extractor::setup_geometry(int w, int h)
                 xofs[dx] = sx;
                 ia[2 * dx] = sat((1.f - fx) * 2048);
                 ia[2 * dx + 1] = sat(fx * 2048);
-            }
-            for (int dy = 0; dy < L.h; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = cv_floor_host(fy);
-                fy -= sy;
-                yofs[dy] = sy;
-                ib[2 * dy] = sat((1.f - fy) * 2048);
-                ib[2 * dy + 1] = sat(fy * 2048);
+                if (ia[2 * dx] < 0 || ia[2 * dx + 1] < 0 || ia[2 * dx] + ia[2 * dx + 1] > 2048) sums_ok = false;
             }
             // per quad of destination columns (k_resize): sx0, selectors of (S[sx], S[sx+1]) inside the 8 bytes from sx0 on,
             // coefficient pairs; columns past the level's width get coefficient 0 (they land in the row padding as 0)
@@ -362,16 +396,12 @@ int orbx_extractor::setup_geometry(int w, int h)
                 qsel[q] = make_uint4(se[0], se[1], se[2], se[3]);
                 qal[q] = make_uint4(al[0], al[1], al[2], al[3]);
             }
-            // per destination row: the source rows clamped to the image and the coefficients as k_resize multiplies them (b << 12)
-            std::vector<ResizeRow> rows((size_t)round_up(L.h, kResizeRows));
-            for (size_t dy = 0; dy < rows.size(); dy++) {
-                const int y = std::min((int)dy, L.h - 1);
-                const int sy0 = std::min(std::max(yofs[y], 0), P.h - 1), sy1 = std::min(std::max(yofs[y] + 1, 0), P.h - 1);
-                if (ib[2 * y] < 0 || ib[2 * y] > 2048 || ib[2 * y + 1] < 0 || ib[2 * y + 1] > 2048)
-                    return fail(ORBX_ERR_INTERNAL, "resize table: row coefficients %d %d", ib[2 * y], ib[2 * y + 1]);
-                rows[dy].sy = (uint32_t)sy0 | ((uint32_t)sy1 << 16);
-                rows[dy].b0 = (uint32_t)ib[2 * y] << 12; rows[dy].b1 = (uint32_t)ib[2 * y + 1] << 12; rows[dy].pad = 0;
-            }
+            // per destination row: the clamped source rows, the shifted coefficients and the reuse plan (build_resize_rows)
+            std::vector<ResizeRow> rows;
+            bool rows_ok = true;
+            if (int rr = build_resize_rows(P.h, L.h, yofs, ib, rows, &rows_ok)) return rr;
+            // the kernels drop the clamp to 255 where both coefficient sums prove it dead; a level that fails keeps the saturating form
+            resize_sat[l] = !(sums_ok && rows_ok);
             int r;
             if (resize_generic[l] && ((r = d_xofs[l].upload(xofs)) || (r = d_ialpha[l].upload(ia)) || (r = d_yofs[l].upload(yofs)) || (r = d_ibeta[l].upload(ib)))) return r;
             if ((r = d_qsx0[l].upload(qsx0)) || (r = d_qsel[l].upload(qsel)) || (r = d_qalpha[l].upload(qal)) || (r = d_rows[l].upload(rows))) return r;
@@ -595,19 +625,33 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
                                   !strips.empty() && strips[0].level == 0;
         hipStream_t rs = chain_beside ? oct_stream : s;
         if (chain_beside) { ORBX_HIP(hipEventRecord(ev_fork, s)); ORBX_HIP(hipStreamWaitEvent(rs, ev_fork, 0)); }
+        bool resize_bands = false;          // a level went through k_resize (orbx_debug_resize_bands)
         for (int l = 1; l < l_tail; l++) {
             const LevelDesc& D = levels[l];
-            dim3 g(xcd_grid(((D.w + kResizeTW - 1) / kResizeTW) * ((D.h + kResizeRows - 1) / kResizeRows)), nB);
             const LevelDesc& P = levels[l - 1];
             SrcImage src;
             src.base = pyr + P.off; src.frame_stride = pyr_frame_bytes; src.stride = P.stride; src.w = P.w; src.h = P.h;
             if (l == 1 && in_place) src = lvl0;
-            if (resize_generic[l])
+            if (resize_generic[l]) {
                 hipLaunchKernelGGL(k_resize_generic, dim3((D.w + 255) / 256, D.h, nB), dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
                                    d_xofs[l].p, d_ialpha[l].p, d_yofs[l].p, d_ibeta[l].p);
-            else
-            hipLaunchKernelGGL(k_resize, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
-                               d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
+                ORBX_LAUNCHED("k_resize_generic");
+                continue;
+            }
+            if (nB < resize_band_min) {          // few frames: short waves, a workgroup per tile and frame
+                dim3 g(xcd_grid(((D.w + kResizeTileW - 1) / kResizeTileW) * ((D.h + kResizeRows - 1) / kResizeRows)), nB);
+                hipLaunchKernelGGL(resize_sat[l] ? k_resize_tiles<true> : k_resize_tiles<false>, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
+                                   d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
+                ORBX_LAUNCHED("k_resize_tiles");
+                continue;
+            }
+            // four frames across the lanes of a wave where a lane reaches all four with a 32-bit offset, in the source (level 1 read
+            // in place: the caller's frame stride) and in the pyramid; batches below four frames and larger frames: one frame per wave
+            const int F = (nB >= 4 && resize_frames_fit(src.frame_stride) && resize_frames_fit(pyr_frame_bytes)) ? kResizeFrames : 1;
+            dim3 g(xcd_grid(((D.w + resize_strip_w(F) - 1) / resize_strip_w(F)) * ((D.h + kResizeRows - 1) / kResizeRows)), (nB + F - 1) / F);
+            auto kern = F == 1 ? (resize_sat[l] ? k_resize<1, true> : k_resize<1, false>) : (resize_sat[l] ? k_resize<kResizeFrames, true> : k_resize<kResizeFrames, false>);
+            hipLaunchKernelGGL(kern, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D, nB, d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
+            resize_bands = true;
             ORBX_LAUNCHED("k_resize");
         }
         if (chain_beside) ORBX_HIP(hipEventRecord(ev_resize, rs));
@@ -666,7 +710,9 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             hipStream_t ts = beside ? oct_stream : s;
             if (beside && !chain_beside) { ORBX_HIP(hipEventRecord(ev_fork, s)); ORBX_HIP(hipStreamWaitEvent(ts, ev_fork, 0)); }
             if (dbg_tail_delay_us > 0) hipLaunchKernelGGL(k_debug_spin, dim3(1), dim3(64), 0, ts, (long long)dbg_tail_delay_us * 100);
-            hipLaunchKernelGGL(k_resize_tail, dim3(nB), dim3(1024), 0, ts, pyr, pyr_frame_bytes, d_levels.p, T, l_tail, nlevels);
+            bool tail_sat = false;
+            for (int l = l_tail; l < nlevels; l++) tail_sat = tail_sat || resize_sat[l];
+            hipLaunchKernelGGL(tail_sat ? k_resize_tail<true> : k_resize_tail<false>, dim3(nB), dim3(1024), 0, ts, pyr, pyr_frame_bytes, d_levels.p, T, l_tail, nlevels);
             ORBX_LAUNCHED("k_resize_tail");
             if (beside) {
                 // the blur runs on `s` and reads EVERY level: it has to wait for the tail's levels (FAST on them may still run)
@@ -728,6 +774,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             launch_blur(s);
         }
         last_octree_variant = (oct_nodes_hbm ? 0 : (dyn_keys ? 3 : (o_keys > 0 ? 1 : 2))) | (two_launches ? 4 : 0) | (oct0_early ? 8 : 0) | (in_place ? 16 : 0) | (tail_beside ? 32 : 0) | (chain_beside ? 64 : 0);
+        last_resize_bands = resize_bands;
         if (two_launches) ORBX_HIP(hipStreamWaitEvent(os, ev_oct_join, 0));
         ORBX_LAUNCHED("k_octree / k_blur");
         if (marks) mark();
@@ -836,6 +883,7 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
     if (const char* env = getenv("ORBX_SERIAL")) e->serial_schedule = atoi(env) != 0;
     if (const char* env = getenv("ORBX_SPLIT")) e->split_parts = std::max(1, std::min(atoi(env), 4));
     if (const char* env = getenv("ORBX_RESIZE_TAIL")) e->resize_tail_first = atoi(env);
+    if (const char* env = getenv("ORBX_RESIZE_BAND_MIN")) e->resize_band_min = std::max(atoi(env), 1);
     if (const char* env = getenv("ORBX_RESIZE_BESIDE")) e->resize_beside = atoi(env) != 0;
     if (const char* env = getenv("ORBX_OCT_DYN")) e->oct_dyn_off = atoi(env) == 0;
     if (const char* env = getenv("ORBX_OCT_DYN_MAXB")) e->oct_dyn_max_batch = atoi(env);
@@ -1082,6 +1130,25 @@ int orbx_debug_set_tail_delay(orbx_extractor* e, int microseconds)
     if (!e || microseconds < 0 || microseconds > 20000) return fail(ORBX_ERR_ARG, "bad tail delay");
     e->dbg_tail_delay_us = microseconds;
     return ORBX_OK;
+}
+
+int orbx_debug_resize_bands(orbx_extractor* e)
+{
+    if (!e) return fail(ORBX_ERR_ARG, "NULL handle");
+    return e->last_resize_bands ? 1 : 0;
+}
+
+int orbx_debug_resize_rows(int src_h, int dst_h, uint32_t* rows, int* band_rows)
+{
+    if (src_h < 1 || dst_h < 1 || !rows || !band_rows) return fail(ORBX_ERR_ARG, "bad row table request");
+    std::vector<int> yofs;
+    std::vector<short> ib;
+    std::vector<ResizeRow> t;
+    bool sums_ok = true;
+    if (int r = build_resize_rows(src_h, dst_h, yofs, ib, t, &sums_ok)) return r;
+    for (int y = 0; y < dst_h; y++) { rows[4 * y] = t[y].sy; rows[4 * y + 1] = t[y].b0; rows[4 * y + 2] = t[y].b1; rows[4 * y + 3] = t[y].plan; }
+    *band_rows = kResizeBand;
+    return sums_ok ? 1 : 0;
 }
 
 int orbx_debug_octree_waves(orbx_extractor* e, int launch)

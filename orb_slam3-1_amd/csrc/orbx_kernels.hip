@@ -33,7 +33,8 @@ __device__ __forceinline__ uint32_t as_u32(us2 v) { return __builtin_bit_cast(ui
 
 // ------------------------------------------------------------------------------------------------
 // E1: bilinear resize, OpenCV fixed-point scheme (cv::resize INTER_LINEAR 8UC1).  One thread -> 4 horizontally
-// adjacent output pixels (one aligned dword store); a wave = 256 pixels of one output row, a workgroup = 4 rows.
+// adjacent output pixels (one aligned dword store) of a BAND of 16 consecutive output rows; the lanes of a wave are the quads
+// of one column strip in F frames of the batch (resize_band), so every lane of a wave is on the same output row.
 // Everything that depends on the output column only is a host-built table per QUAD of columns: the first source column
 // sx0, and per pixel a v_perm selector that pulls (S[sx], S[sx + 1]) out of the 8 source bytes starting at sx0 as a u16 pair,
 // and the coefficient pair (ialpha0, ialpha1) -- so the horizontal pass of a pixel and source row is v_perm + v_dot2.
@@ -50,22 +51,182 @@ struct SrcImage {
 __device__ __forceinline__ uint32_t mul_hi_u24(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu)) >> 32); }
 
 struct __attribute__((aligned(4))) Dwords3 { uint32_t x, y, z; };     // 12 bytes at dword alignment: one global_load_dwordx3
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+typedef __attribute__((address_space(1))) uint32_t global_u32;
+typedef __attribute__((address_space(1))) u32x3 global_u32x3 __attribute__((aligned(4)));     // ... as a vector in global memory: the load stays one instruction
 struct __attribute__((aligned(4))) Dwords4 { uint32_t x, y, z, w; };  // 16 bytes at dword alignment: one global_load_dwordx4
-constexpr int kResizeRows = 64, kResizeTW = 64;      // output tile of a workgroup: 64 x 64 (16 rows per wave, 64-pixel segments of four rows per wave step)
+// a wave-uniform pointer, opaque to the compiler at this point: what is added to it afterwards is not folded into it
+// (returned as a pointer into global memory: a pointer out of a register has no address space the compiler could infer)
+typedef __attribute__((address_space(1))) uint8_t global_u8;
+__device__ __forceinline__ global_u8* scalar_base(const uint8_t* p) { uint64_t v = (uint64_t)p; asm("" : "+s"(v)); return (global_u8*)v; }
 
-// one tile of 64 x 64 outputs of level `dst` of one frame by 4 waves (`wave` 0..3, 16 rows each).  A wave covers 16 quads
-// (64 pixels) of FOUR rows at a time: levels are 179..533 pixels wide, and whole waves per row (256 pixels) left a third of the
-// lanes idle on average (533 px = 2.08 waves); with 64-pixel segments the idle share is a few percent.
+// Four vertical sums t = b0 h0 + b1 h1 + 2 (each term after its shift) -> the four result bytes (t >> 2) of a quad as one dword.
+// SAT = false: the host has checked a0 + a1 <= 2048 for every column and b0 + b1 <= 2048 for every row of the level, so each
+// product term is at most b * 255 / 512, t at most 1022 and t >> 2 at most 255 -- no clamp: pixels 0 | 2 and 1 | 3 as u16 pairs
+// (one v_perm each), one packed 16-bit shift each (nothing crosses the halves), one v_lshl_or: 5 instructions against 11.
+template <bool SAT>
+__device__ __forceinline__ uint32_t resize_pack(const uint32_t (&t)[4])
+{
+    if (SAT) return min(t[0] >> 2, 255u) | (min(t[1] >> 2, 255u) << 8) | (min(t[2] >> 2, 255u) << 16) | (min(t[3] >> 2, 255u) << 24);
+    const us2 sh2 = {2, 2};
+    const uint32_t e = as_u32(as_us2(__builtin_amdgcn_perm(t[2], t[0], 0x05040100u)) >> sh2);
+    const uint32_t o = as_u32(as_us2(__builtin_amdgcn_perm(t[3], t[1], 0x05040100u)) >> sh2);
+    return e | (o << 8);
+}
+
+constexpr int kResizeRows = 64;        // output rows of a workgroup of k_resize: four bands of kResizeBand rows, one per wave
+constexpr int kResizeGroup = 4;        // rows of a band whose fresh source rows are loaded together
+constexpr int resize_strip_w(int F) { return 256 / F; }      // pixels of a column strip: 64 quads shared by F frames
+
+// One work item of the table-driven resize: the band of kResizeBand output rows from row band * kResizeBand on, of the column
+// strip `strip`, in F frames.  Lane (lane / (64 / F), lane % (64 / F)) = (frame of the group, quad of the strip): F = 4 is 16 quads
+// (64 pixels) x 4 frames -- the levels are 179..533 pixels wide, a few percent of the lanes idle in the last strip -- and F = 1 is
+// 64 quads of one frame (batches below 4 frames).  All frames of a batch share one geometry, so the output row, its ResizeRow
+// entry (scalar loads), the source and destination row addresses and both vertical coefficients are wave-uniform; a lane adds its
+// frame's and its column's byte offset as ONE 32-bit value (the host checks F x frame stride < 2 GiB for source and destination and
+// takes F = 1 otherwise).  `S` / `D`: source image / destination level of the group's first frame, `n_frames` how many of the
+// group's frames exist (lanes of frames past the batch do nothing).
+// The band is walked top to bottom.  A lane keeps the masked horizontal sums (v_perm + v_dot2 + v_and per pixel) of the previous
+// output row's two source rows; where ResizeRow::plan says that the row's top source row is the previous row's bottom one, its
+// sums are taken as they are -- a scalar branch, not a select.  Consecutive rows share a source row five times out of six at scale
+// 1.2 (1.2 fresh source rows per output row against 2), and a fresh row is one 12-byte load per lane and one horizontal pass.  The
+// first row of a band computes both: 1/16 of a row per row.
+// The fresh rows of kResizeGroup output rows are loaded together, and those of the next group are issued before the current
+// group's stores.  SAT: resize_pack.
+template <int F, bool SAT>
+__device__ __forceinline__ void resize_band(const uint8_t* S, uint32_t s_frame_stride, int s_stride, uint8_t* D, uint32_t d_frame_stride,
+                                            const LevelDesc& dst, const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel,
+                                            const uint4* __restrict__ q_alpha, const ResizeRow* __restrict__ rows, int strip, int band,
+                                            int n_frames, int lane)
+{
+    constexpr int QL = 64 / F, G = kResizeGroup;
+    static_assert(kResizeBand == 4 * G, "a band is four row groups");
+    const int fsel = F == 1 ? 0 : lane / QL, q = strip * QL + (F == 1 ? lane : lane % QL);
+    const int y0 = band * kResizeBand, nrows = min(kResizeBand, dst.h - y0);        // (both wave-uniform)
+    if (fsel >= n_frames || 4 * q >= dst.w || nrows <= 0) return;
+    const int sx0 = q_sx0[q];
+    const uint4 sel = q_sel[q], al = q_alpha[q];
+    const uint32_t sels[4] = {sel.x, sel.y, sel.z, sel.w}, als[4] = {al.x, al.y, al.z, al.w};
+    const uint32_t a = (uint32_t)(sx0 & ~3);
+    const uint32_t sh = (uint32_t)(sx0 & 3);
+    const uint32_t last = (uint32_t)(s_stride - 4);             // last dword of a row: bytes past the row's pixels only meet coefficient 0
+    const bool wide = a + 8 <= last;                            // one 12-byte load per row: the address unit handles 4 lanes per clock whatever the width
+    const uint32_t s_off = (uint32_t)fsel * s_frame_stride + a, d_off = (uint32_t)fsel * d_frame_stride + 4u * (uint32_t)q;
+    // the last quads of a row: never read past the row's last dword
+    const uint32_t s_off0 = s_off + (min(a, last) - a), s_off1 = s_off + (min(a + 4, last) - a), s_off2 = s_off + (min(a + 8, last) - a);
+    // (the row address is a scalar pair and stays one -- scalar_base() -- so that a lane's 32-bit offset is the instruction's
+    // vector operand: no 64-bit vector addition per load or store)
+    auto load_row = [&](uint32_t sy) __attribute__((always_inline)) -> u32x3 {
+        const global_u8* row = scalar_base(S + (size_t)sy * (uint32_t)s_stride);
+        if (wide) return *(const global_u32x3*)(row + s_off);
+        u32x3 t;
+        t.x = *(const global_u32*)(row + s_off0); t.y = *(const global_u32*)(row + s_off1); t.z = *(const global_u32*)(row + s_off2);
+        return t;
+    };
+    // masked horizontal sums of the 4 pixels on one source row: S[sx] a0 + S[sx+1] a1 out of the 8 source bytes from column sx0 on
+    auto hpass = [&](u32x3 raw, uint32_t (&h)[4]) __attribute__((always_inline)) {
+        const uint32_t lo = __builtin_amdgcn_alignbyte(raw.y, raw.x, sh), hi = __builtin_amdgcn_alignbyte(raw.z, raw.y, sh);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            h[k] = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(hi, lo, sels[k])), as_us2(als[k]), 0u, false) & 0xFFFFF0u;    // (h < 2^24)
+    };
+    // the table entry (scalar loads; the table is padded to whole 64-row tiles); row i of the band reuses the previous row's bottom
+    // row as its top row where the plan says so -- the band's first row has no previous row.  The two rare plans of clamped
+    // rows (top = previous top, bottom = top) are not reused: such a row is loaded and filtered again.
+    auto reuse_top = [&](const ResizeRow& rw, int i) __attribute__((always_inline)) { return i > 0 && (rw.plan & 3u) == kResizeTopPrevBottom; };
+    auto issue = [&](int i, u32x3& top, u32x3& bot) __attribute__((always_inline)) {
+        if (i >= nrows) return;
+        const ResizeRow rw = rows[y0 + i];
+        if (!reuse_top(rw, i)) top = load_row(rw.sy & 0xFFFFu);
+        bot = load_row(rw.sy >> 16);
+    };
+    // The two sets of horizontal sums swap roles with every row: the bottom row's sums of row i are the top row's of row i + 1
+    // where they are reused, so the reuse moves nothing.
+    uint32_t hx[4], hy[4];
+    auto finish = [&](int i, const u32x3& top, const u32x3& bot) __attribute__((always_inline)) {
+        if (i >= nrows) return;
+        uint32_t (&ht)[4] = (i & 1) ? hx : hy;
+        uint32_t (&hb)[4] = (i & 1) ? hy : hx;
+        const ResizeRow rw = rows[y0 + i];
+        if (!reuse_top(rw, i)) hpass(top, ht);
+        hpass(bot, hb);
+        // (b * (h >> 4)) >> 16 is the high dword of (b << 12) * (h & ~15): b <= 2048 and h <= 255 * 2048 keep both factors inside
+        // 24 bits (v_mul_hi_u32_u24); the table holds b << 12
+        uint32_t t[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) t[k] = mul_hi_u24(rw.b0, ht[k]) + mul_hi_u24(rw.b1, hb[k]) + 2u;
+        // columns past dst.w: coefficients 0 -> 0; the row padding absorbs the tail of the last dword
+        *(global_u32*)(scalar_base(D + (size_t)(uint32_t)(y0 + i) * (uint32_t)dst.stride) + d_off) = resize_pack<SAT>(t);
+    };
+    // (the staged rows are variables of their own: as arrays the compiler keeps them as one wide register tuple and copies it)
+    u32x3 ta0, ta1, ta2, ta3, ba0, ba1, ba2, ba3, tb0, tb1, tb2, tb3, bb0, bb1, bb2, bb3;
+#define ORBX_RESIZE_GROUP(f, g, t, b) do { f(G * (g), t##0, b##0); f(G * (g) + 1, t##1, b##1); f(G * (g) + 2, t##2, b##2); f(G * (g) + 3, t##3, b##3); } while (0)
+    ORBX_RESIZE_GROUP(issue, 0, ta, ba);
+    ORBX_RESIZE_GROUP(issue, 1, tb, bb); ORBX_RESIZE_GROUP(finish, 0, ta, ba);
+    ORBX_RESIZE_GROUP(issue, 2, ta, ba); ORBX_RESIZE_GROUP(finish, 1, tb, bb);
+    ORBX_RESIZE_GROUP(issue, 3, tb, bb); ORBX_RESIZE_GROUP(finish, 2, ta, ba);
+    ORBX_RESIZE_GROUP(finish, 3, tb, bb);
+#undef ORBX_RESIZE_GROUP
+}
+
+template <int F, bool SAT>
+__global__ __launch_bounds__(256) void k_resize(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst, int n_frames,
+                                                const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
+                                                const ResizeRow* __restrict__ rows)
+{
+    // a workgroup is 64 rows (a band per wave) of one column strip in F frames (blockIdx.y = group of F frames).  These tiles are
+    // numbered row-major and handed to the XCDs in contiguous bands (xcd_remap), so the source rows a band of destination rows
+    // needs are fetched by one L2 only
+    const int strips_x = (dst.w + resize_strip_w(F) - 1) / resize_strip_w(F), tiles_y = (dst.h + kResizeRows - 1) / kResizeRows;
+    const int tile = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);
+    if (tile >= strips_x * tiles_y) return;
+    const int ty = tile / strips_x, tx = tile - ty * strips_x;
+    const int f0 = blockIdx.y * F, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    resize_band<F, SAT>(src.base + (size_t)f0 * src.frame_stride, (uint32_t)src.frame_stride, src.stride, pyr + (size_t)f0 * frame_stride + dst.off,
+                        (uint32_t)frame_stride, dst, q_sx0, q_sel, q_alpha, rows, tx, ty * (kResizeRows / kResizeBand) + wave, n_frames - f0,
+                        threadIdx.x & 63);
+}
+
+// Fallback for levels whose four-column source span exceeds the 8-byte window of the table-driven kernel above (scale factors of
+// 2 and more: 3 x scale_x >= 6 source columns between the first and the last pixel of a quad, plus its right neighbour): one thread
+// per output pixel straight from the per-column / per-row tables of cv::resize -- the same fixed-point arithmetic, no window.
+__global__ __launch_bounds__(256) void k_resize_generic(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst,
+                                                        const int* __restrict__ xofs, const short* __restrict__ ialpha,
+                                                        const int* __restrict__ yofs, const short* __restrict__ ibeta)
+{
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, frame = blockIdx.z;
+    if (dx >= dst.w) return;
+    const uint8_t* S = src.base + (size_t)frame * src.frame_stride;
+    const int sx = xofs[dx], sy = yofs[dy];
+    const uint32_t a0 = (uint16_t)ialpha[2 * dx], a1 = (uint16_t)ialpha[2 * dx + 1];
+    const uint32_t b0 = (uint16_t)ibeta[2 * dy], b1 = (uint16_t)ibeta[2 * dy + 1];
+    const int sy0 = min(max(sy, 0), src.h - 1), sy1 = min(max(sy + 1, 0), src.h - 1);
+    const int sx1 = min(sx + 1, src.w - 1);                     // (its coefficient is 0 where sx is the last column)
+    const uint8_t* r0 = S + (size_t)sy0 * src.stride;
+    const uint8_t* r1 = S + (size_t)sy1 * src.stride;
+    const uint32_t h0 = r0[sx] * a0 + r0[sx1] * a1, h1 = r1[sx] * a0 + r1[sx1] * a1;
+    const uint32_t val = ((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2u) >> 2;
+    pyr[(size_t)frame * frame_stride + dst.off + (size_t)dy * dst.stride + dx] = (uint8_t)min(val, 255u);
+}
+
+// The work split of k_resize_tiles and k_resize_tail (below): one tile of 64 x 64 outputs of level `dst` of ONE frame by 4 waves
+// (`wave` 0..3, 16 rows each), the rows across the lanes: a wave covers 16 quads (64 pixels) of FOUR rows at a time, and a
+// thread's four rows are dy0 + 4 r, so both source rows of every output row are loaded and filtered (nothing is shared inside a
+// thread) -- but a wave is short: one round of loads, four rows.  That is what the latency-bound users need.  The tail is one
+// workgroup per frame: with resize_band's four frames per wave it is a quarter of the workgroups with four times the work each
+// and took 181 us against 55.
 // `S` and `D` are the frame's source image and destination level (wave-uniform: scalar registers); a thread addresses both with
 // 32-bit byte offsets (the host refuses frames of 2 GiB and more).  Everything that depends on the output row only is the
 // host-built `rows` table (ResizeRow, padded to whole tiles): the two source rows, already clamped, and the two coefficients.
+constexpr int kResizeTileW = 64;
+template <bool SAT>
 __device__ __forceinline__ void resize_tile(const uint8_t* __restrict__ S, int s_stride, uint8_t* __restrict__ D, const LevelDesc& dst,
                                             const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
                                             const ResizeRow* __restrict__ rows, int tile, int lane, int wave)
 {
-    const int tiles_x = (dst.w + kResizeTW - 1) / kResizeTW;
+    const int tiles_x = (dst.w + kResizeTileW - 1) / kResizeTileW;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int q = tx * (kResizeTW / 4) + (lane & 15), rsel = lane >> 4;
+    const int q = tx * (kResizeTileW / 4) + (lane & 15), rsel = lane >> 4;
     if (4 * q >= dst.w) return;
     constexpr int NR = kResizeRows / 16;                        // row groups of 4 per wave
     const int dy0 = ty * kResizeRows + wave * (kResizeRows / 4) + rsel;
@@ -114,59 +275,41 @@ __device__ __forceinline__ void resize_tile(const uint8_t* __restrict__ S, int s
             const us2 ak = as_us2(als[k]);
             const uint32_t h0 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(uhi, ulo, sels[k])), ak, 0u, false);    // S0[sx] a0 + S0[sx+1] a1
             const uint32_t h1 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(vhi, vlo, sels[k])), ak, 0u, false);
-            out[k] = min((mul_hi_u24(b0, h0 & ~15u) + mul_hi_u24(b1, h1 & ~15u) + 2u) >> 2, 255u);
+            out[k] = mul_hi_u24(b0, h0 & ~15u) + mul_hi_u24(b1, h1 & ~15u) + 2u;
         }
         // (gfx950's v_ashr_pk_u8_i32 does shift, saturation and packing of two pixels in one instruction, but issues every 8.2
-        // cycles against 4.2-4.3 for each of these: not used)
+        // cycles against 4.2-4.3 for each of resize_pack's: not used)
         // columns past dst.w: coefficients 0 -> 0; the row padding absorbs the tail of the last dword
-        *(uint32_t*)(D + (off0 + (uint32_t)(4 * r) * (uint32_t)dst.stride)) = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+        *(uint32_t*)(D + (off0 + (uint32_t)(4 * r) * (uint32_t)dst.stride)) = resize_pack<SAT>(out);
     }
 }
 
-__global__ __launch_bounds__(256) void k_resize(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst,
-                                                const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
-                                                const ResizeRow* __restrict__ rows)
+// One level of a SMALL batch: a workgroup per 64 x 64 tile and frame (resize_tile).  With few frames the chip is empty and a launch
+// lasts as long as its longest wave: four rows per thread behind one round of loads, against resize_band's sixteen rows behind
+// four (B = 1 .. 16: 0.112 / 0.120 / 0.152 ms per call with this kernel, 0.139 / 0.145 / 0.175 with k_resize).
+template <bool SAT>
+__global__ __launch_bounds__(256) void k_resize_tiles(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst,
+                                                      const int* __restrict__ q_sx0, const uint4* __restrict__ q_sel, const uint4* __restrict__ q_alpha,
+                                                      const ResizeRow* __restrict__ rows)
 {
-    // tiles of 64 x 64 outputs are numbered row-major and handed to the XCDs in contiguous bands (xcd_remap), so the source
-    // rows a band of destination rows needs are fetched by one L2 only
-    const int tiles_x = (dst.w + kResizeTW - 1) / kResizeTW, tiles_y = (dst.h + kResizeRows - 1) / kResizeRows;
+    const int tiles_x = (dst.w + kResizeTileW - 1) / kResizeTileW, tiles_y = (dst.h + kResizeRows - 1) / kResizeRows;
     const int tile = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);
     if (tile >= tiles_x * tiles_y) return;
-    resize_tile(src.base + (size_t)blockIdx.y * src.frame_stride, src.stride, pyr + (size_t)blockIdx.y * frame_stride + dst.off, dst,
-                q_sx0, q_sel, q_alpha, rows, tile, threadIdx.x & 63, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-}
-
-// Fallback for levels whose four-column source span exceeds the 8-byte window of the table-driven kernel above (scale factors of
-// 2 and more: 3 x scale_x >= 6 source columns between the first and the last pixel of a quad, plus its right neighbour): one thread
-// per output pixel straight from the per-column / per-row tables of cv::resize -- the same fixed-point arithmetic, no window.
-__global__ __launch_bounds__(256) void k_resize_generic(SrcImage src, uint8_t* __restrict__ pyr, size_t frame_stride, LevelDesc dst,
-                                                        const int* __restrict__ xofs, const short* __restrict__ ialpha,
-                                                        const int* __restrict__ yofs, const short* __restrict__ ibeta)
-{
-    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, frame = blockIdx.z;
-    if (dx >= dst.w) return;
-    const uint8_t* S = src.base + (size_t)frame * src.frame_stride;
-    const int sx = xofs[dx], sy = yofs[dy];
-    const uint32_t a0 = (uint16_t)ialpha[2 * dx], a1 = (uint16_t)ialpha[2 * dx + 1];
-    const uint32_t b0 = (uint16_t)ibeta[2 * dy], b1 = (uint16_t)ibeta[2 * dy + 1];
-    const int sy0 = min(max(sy, 0), src.h - 1), sy1 = min(max(sy + 1, 0), src.h - 1);
-    const int sx1 = min(sx + 1, src.w - 1);                     // (its coefficient is 0 where sx is the last column)
-    const uint8_t* r0 = S + (size_t)sy0 * src.stride;
-    const uint8_t* r1 = S + (size_t)sy1 * src.stride;
-    const uint32_t h0 = r0[sx] * a0 + r0[sx1] * a1, h1 = r1[sx] * a0 + r1[sx1] * a1;
-    const uint32_t val = ((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2u) >> 2;
-    pyr[(size_t)frame * frame_stride + dst.off + (size_t)dy * dst.stride + dx] = (uint8_t)min(val, 255u);
+    resize_tile<SAT>(src.base + (size_t)blockIdx.y * src.frame_stride, src.stride, pyr + (size_t)blockIdx.y * frame_stride + dst.off, dst,
+                     q_sx0, q_sel, q_alpha, rows, tile, threadIdx.x & 63, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
 // The upper pyramid levels are small and each depends on the one below: as launches of their own they are a chain of short,
 // launch-latency-bound kernels.  Here ONE 1024-thread workgroup per frame walks the levels l_first .. n_levels-1 in turn (four
-// tiles at a time, a workgroup barrier between levels: the level just written is read back by the same CU).
+// tiles at a time -- resize_tile --, a workgroup barrier between levels: the level just written is read back by the same CU).
+// SAT: one flag for the whole tail (any of its levels fails the host's coefficient-sum check -> the saturating form).
 struct ResizeTables {
     const int* q_sx0[kMaxLevels]; const uint4* q_sel[kMaxLevels]; const uint4* q_alpha[kMaxLevels];
     const ResizeRow* rows[kMaxLevels];
 };
+template <bool SAT>
 __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr, size_t frame_stride, const LevelDesc* __restrict__ levels,
-                                                      ResizeTables T, int l_first, int n_levels)
+                                                            ResizeTables T, int l_first, int n_levels)
 {
     const int frame = blockIdx.x;
     const int sub = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3);
@@ -174,9 +317,9 @@ __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr,
     for (int l = l_first; l < n_levels; l++) {
         const LevelDesc D = levels[l], P = levels[l - 1];
         uint8_t* fp = pyr + (size_t)frame * frame_stride;
-        const int tiles = ((D.w + kResizeTW - 1) / kResizeTW) * ((D.h + kResizeRows - 1) / kResizeRows);
+        const int tiles = ((D.w + kResizeTileW - 1) / kResizeTileW) * ((D.h + kResizeRows - 1) / kResizeRows);
         for (int t = sub; t < tiles; t += 4)
-            resize_tile(fp + P.off, P.stride, fp + D.off, D, T.q_sx0[l], T.q_sel[l], T.q_alpha[l], T.rows[l], t, lane, wave);
+            resize_tile<SAT>(fp + P.off, P.stride, fp + D.off, D, T.q_sx0[l], T.q_sel[l], T.q_alpha[l], T.rows[l], t, lane, wave);
         __syncthreads();            // the level is complete (and visible to this CU) before it becomes the next one's source
     }
 }

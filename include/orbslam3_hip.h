@@ -135,6 +135,11 @@ int orbx_debug_last_schedule(orbx_extractor* h);
  * lower levels (or all levels, when there is one launch), 2 the upper levels; 0 when the call had no such launch.  ORBX_OCT_WAVES =
  * 1 | 2 | 4 (read at construction) forces the value for every launch. */
 int orbx_debug_octree_waves(orbx_extractor* h, int launch);
+/* Test hook: the octree's bucket table of `level` for the image size of the LAST extract call, read back from the device: the table's
+ * depth D, the number of roots and their boundaries -- (2^D + 1) x boundaries per root, root after root, then the (2^D + 1) y boundaries
+ * (coordinates relative to the level's border, as DistributeOctTree sees them).  Returns the number of boundaries written (0 for a
+ * level without roots), ORBX_ERR_CAPACITY when `cap` is smaller.  ORBX_OCT_TAB_DEPTH = 0 .. 6 (read at construction) caps D. */
+int orbx_debug_octree_table(orbx_extractor* h, int level, int* depth, int* n_ini, int16_t* bounds, int cap);
 /* Test hook: 1 when the LAST extract call resized a pyramid level with k_resize (bands of rows, frames across the lanes: batches of 64
  * frames and more, or of ORBX_RESIZE_BAND_MIN, read at construction), 0 when every level took k_resize_tiles / k_resize_generic. */
 int orbx_debug_resize_bands(orbx_extractor* h);

@@ -85,6 +85,7 @@ lib.orbx_debug_level_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_voi
 lib.orbx_debug_set_tail_delay.argtypes = [C.c_void_p, C.c_int]
 lib.orbx_debug_last_schedule.argtypes = [C.c_void_p]
 lib.orbx_debug_octree_waves.argtypes = [C.c_void_p, C.c_int]
+lib.orbx_debug_octree_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int]
 lib.orbx_debug_resize_bands.argtypes = [C.c_void_p]
 lib.orbx_debug_resize_rows.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
 lib.orbx_debug_introsort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -267,6 +268,16 @@ class Extractor:
         """waves per workgroup of the last call's octree launch: 0 level 0 started early, 1 the lower (or all) levels, 2 the upper
         levels; 0 when there was no such launch"""
         return int(lib.orbx_debug_octree_waves(self._h, launch))
+
+    def debug_octree_table(self, level):
+        """the octree's bucket table of `level` as the device holds it (image size of the last call): (D, n_ini, x boundaries as an
+        array of n_ini rows of 2^D + 1, y boundaries)"""
+        depth, n_ini = C.c_int(), C.c_int()
+        out = np.zeros(2 * 65537, np.int16)      # (roots + 1) * (2^D + 1) with roots * 4^D <= 65536: largest at D = 0
+        n = _check(lib.orbx_debug_octree_table(self._h, level, C.byref(depth), C.byref(n_ini), _p(out), out.size))
+        nb = (1 << depth.value) + 1
+        assert n == (n_ini.value + 1) * nb or n == 0
+        return depth.value, n_ini.value, out[:n_ini.value * nb].reshape(n_ini.value, nb).copy(), out[n_ini.value * nb:n].copy()
 
     def candidates(self, level, frame=0, cap=200000):
         out = np.zeros(cap, KP_DTYPE)

@@ -33,6 +33,24 @@ struct CellDesc {
     int32_t slot_off, slot_cap;    // where this cell's keypoints go in the per-frame candidate buffer
 };
 
+// One level's quadtree bucket table (k_octree).  DistributeOctTree's splits are fixed before any key is looked at: a node's box
+// depends only on its path from its root (halfX = ceil(w / 2)), so the cell a key reaches after `depth` divides is a function of
+// its coordinates and these boundaries alone.  x boundaries: (2^depth + 1) per root, root after root; the y boundaries
+// (2^depth + 1, every root spans the level's height) follow them.  Boundaries repeat where a box is narrower than 2^depth:
+// such cells are empty, as the reference's empty children are.  Cell code of a key: its root, then per depth
+// (x >= midx) + 2 * (y >= midy), most significant depth first.
+constexpr int kOctTabMaxDepth = 6;   // (a node's depth takes three bits of its flags; 7 marks a node below the table)
+struct OctTabDesc {
+    int32_t depth, n_ini;
+    int32_t bounds_off;            // first boundary of the level in the int16 boundary array
+    int32_t prefix_off;            // the level's (n_ini << 2 depth) + 1 prefix sums inside the per-frame prefix buffer
+    int32_t w_cell_inv, h_cell_inv;    // ceil(2^20 / FAST cell pitch): candidate order is (cell row, cell column, y, x), cell = (coordinate - 3) / pitch
+    // The same table as two maps, so that a key finds its cell with two loads: per x (0 .. width) the root and the x bits of the cell
+    // code in place, per y (0 .. height) the y bits; cell code = xmap[x] | ymap[y].  uint16 entries, x map first.
+    int32_t map_off;
+    int32_t maps_lds;              // the maps fit the node pool beside the counters: the kernel stages them in LDS
+};
+
 struct TileDesc {
     int16_t level, x0, y0;     // x0: a multiple of the tile width
     int16_t edge;              // bit 0: a stored output reads columns left of column 0, bit 1: right of the last column

@@ -153,6 +153,15 @@ struct orbx_extractor {
     DevBuf<CellDesc> d_cells;
     DevBuf<TileDesc> d_tiles;
     DevBuf<StripRec> d_strips;
+    // the octree's bucket tables (OctTabDesc): per level the depth, and the boundaries of its cells
+    std::vector<OctTabDesc> oct_tabs;
+    std::vector<int16_t> oct_bounds;
+    std::vector<uint16_t> oct_maps;
+    DevBuf<OctTabDesc> d_oct_tabs;
+    DevBuf<int16_t> d_oct_bounds;        // (the kernel reads the maps; the boundaries they are made from are kept for orbx_debug_octree_table)
+    DevBuf<uint16_t> d_oct_maps;
+    size_t oct_prefix_frame = 0;         // prefix sums per frame, all levels
+    int oct_tab_depth_max = kOctTabMaxDepth;     // ORBX_OCT_TAB_DEPTH (tests: a shallow table sends the divides below it through the partition code)
     // resize tables per destination level: per quad of columns the first source column, 4 v_perm selectors, 4 coefficient pairs
     // and per destination row the two source rows and the two coefficients (ResizeRow)
     std::vector<DevBuf<int> > d_qsx0;
@@ -168,6 +177,7 @@ struct orbx_extractor {
     DevBuf<uint8_t> d_pyr, d_blur;
     DevBuf<uint32_t> d_cand, d_scratch, d_sel;
     DevBuf<uint8_t> d_oct_nodes;
+    DevBuf<int> d_oct_prefix;
     DevBuf<int> d_cell_count, d_sel_count, d_kp_dst;
     DevBuf<OrbxKeyPoint> d_lvl_kps;
     // staging for the host-pointer API
@@ -260,10 +270,26 @@ static void build_tables(orbx_extractor* e)
     gauss_taps_q8(7, 2.0, e->taps);
 }
 
+// The boundaries of the 2^depth cells that DivideNode's ceil-halving (src/ORBextractor.cc:480-486; oct_node_box on the device) cuts
+// [lo, hi) into when it is applied `depth` times: out[0 .. 2^depth].  A box narrower than 2^depth repeats boundaries (empty cells).
+static void oct_cell_bounds(int lo, int hi, int depth, int16_t* out)
+{
+    out[0] = (int16_t)lo; out[1 << depth] = (int16_t)hi;
+    for (int step = 1 << depth; step > 1; step >>= 1)
+        for (int i = 0; i < (1 << depth); i += step) {
+            const int a = out[i], b = out[i + step];
+            out[i + step / 2] = (int16_t)(a + ((b - a + 1) >> 1));
+        }
+}
+
 int orbx_extractor::setup_geometry(int w, int h)
 {
     if (w == geo_w && h == geo_h) return ORBX_OK;
+    geo_w = geo_h = 0;          // (a failure below leaves no geometry: the tables are rebuilt by the next call, whatever its size)
     levels.assign(nlevels, LevelDesc());
+    oct_tabs.assign(nlevels, OctTabDesc());
+    oct_bounds.clear();
+    oct_maps.clear();
     cells.clear();
     tiles.clear();
     strips.clear();
@@ -300,8 +326,10 @@ int orbx_extractor::setup_geometry(int w, int h)
         const int minBX = kEdge - 3, minBY = minBX, maxBX = L.w - kEdge + 3, maxBY = L.h - kEdge + 3;
         const float width = (float)(maxBX - minBX), height = (float)(maxBY - minBY);
         const int nCols = (int)(width / 35.f), nRows = (int)(height / 35.f);
+        int cell_pitch_x = 4096, cell_pitch_y = 4096;           // (a level without FAST cells has no key to rank)
         if (nCols > 0 && nRows > 0) {
             const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
+            cell_pitch_x = std::max(wCell, 2); cell_pitch_y = std::max(hCell, 2);
             for (int i = 0; i < nRows; i++) {
                 const float iniY = (float)(minBY + i * hCell);
                 float maxY = iniY + hCell + 6;
@@ -328,6 +356,15 @@ int orbx_extractor::setup_geometry(int w, int h)
         }
         L.cell_count = (int)cells.size() - L.cell_begin;
         L.cand_cap = cand_off - L.cand_off;
+        {   // the pitch's reciprocal for oct_cand_rank, exact for every coordinate of the level.  ceil(2^20 / pitch) is exact for
+            // v * (pitch - 1) < 2^20, i.e. up to about 15 000 px at pitches of 35-70; levels are at most 4 128 px (keys are 12-bit,
+            // checked above), so the loop below is a guard that cannot trip today.
+            auto inv = [](int pitch) { return (int)(((1u << 20) + (uint32_t)pitch - 1u) / (uint32_t)pitch); };
+            oct_tabs[l].w_cell_inv = inv(cell_pitch_x); oct_tabs[l].h_cell_inv = inv(cell_pitch_y);
+            for (int v = 0; v < std::max(L.w, L.h); v++)
+                if ((int)(((uint32_t)v * (uint32_t)oct_tabs[l].w_cell_inv) >> 20) != v / cell_pitch_x || (int)(((uint32_t)v * (uint32_t)oct_tabs[l].h_cell_inv) >> 20) != v / cell_pitch_y)
+                    return fail(ORBX_ERR_INTERNAL, "level %d: FAST cell of coordinate %d is not exact as a multiplication", l, v);
+        }
         // strips: the cells of a cell row are adjacent (interiors tile the row); cut every row into runs of at most
         // kStripMaxCells cells and about kStripWidth columns, evenly
         for (int c0 = L.cell_begin; c0 < (int)cells.size();) {
@@ -500,6 +537,43 @@ int orbx_extractor::setup_geometry(int w, int h)
     }
     // the node pool of a level lives in LDS (about 2500 nodes); a level with more features takes the instantiation whose pool
     // lives in an HBM scratch (ensure_batch allocates it)
+    // the bucket tables: the deepest table that the level's feature budget can use (about four cells per feature: the list ends at N
+    // nodes) and whose counters and boundaries fit the level's own node pool, which lends them its bytes while the keys are placed
+    oct_prefix_frame = 0;
+    for (int l = 0; l < nlevels; l++) {
+        const LevelDesc& L = levels[l];
+        OctTabDesc& T = oct_tabs[l];
+        const int bw = (L.w - kEdge + 3) - (kEdge - 3), bh = (L.h - kEdge + 3) - (kEdge - 3);
+        T.n_ini = bh > 0 ? std::max((int)std::roundf((float)bw / (float)bh), 0) : 0;
+        T.depth = 0; T.bounds_off = (int)oct_bounds.size(); T.prefix_off = (int)oct_prefix_frame;
+        if (T.n_ini < 1) continue;                      // (the kernel returns no key point for such a level)
+        if (bw < 1) return fail(ORBX_ERR_INTERNAL, "level %d: %d roots in a tree %d wide", l, T.n_ini, bw);
+        const size_t pool_b = pool_bytes(node_need[l] + 16), map_bytes = 2 * (size_t)(bw + bh);
+        auto counter_bytes = [&](int d) { return 4 * (((size_t)T.n_ini << (2 * d)) + 1); };
+        while (T.depth < oct_tab_depth_max && ((long long)T.n_ini << (2 * T.depth)) < 4LL * L.nfeat &&
+               ((size_t)T.n_ini << (2 * (T.depth + 1))) <= 65536 && counter_bytes(T.depth + 1) <= pool_b) T.depth++;
+        if (counter_bytes(T.depth) > pool_b) return fail(ORBX_ERR_ARG, "level %d: %d roots do not fit the octree's node pool", l, T.n_ini);
+        T.maps_lds = counter_bytes(T.depth) + map_bytes <= pool_b;      // (not with a tiny budget on a large image: the maps stay in global memory)
+        const int nb = (1 << T.depth) + 1;
+        const float hX = (float)bw / (float)T.n_ini;
+        oct_bounds.resize(oct_bounds.size() + (size_t)(T.n_ini + 1) * nb);
+        int16_t* xb = oct_bounds.data() + T.bounds_off;
+        for (int s = 0; s <= T.n_ini; s++, xb += nb)       // roots (:564-577), then the rows
+            if (s < T.n_ini) oct_cell_bounds((int)(hX * (float)s), (int)(hX * (float)(s + 1)), T.depth, xb);
+            else oct_cell_bounds(0, bh, T.depth, xb);
+        oct_prefix_frame += ((size_t)T.n_ini << (2 * T.depth)) + 1;
+        // the maps: a key's root is (int)(x / hX) (:585); inside the root, the quadrant at every depth (x >= midx, y >= midy)
+        auto spread = [](int v) { int s = 0; for (int b = 0; b < kOctTabMaxDepth; b++) s |= ((v >> b) & 1) << (2 * b); return s; };
+        auto cell_index = [&](const int16_t* b, int v) { int i = 0; for (int d = T.depth - 1; d >= 0; d--) i = 2 * i + (v >= b[(2 * i + 1) << d] ? 1 : 0); return i; };
+        T.map_off = (int)oct_maps.size();
+        const int16_t* b0 = oct_bounds.data() + T.bounds_off;
+        for (int x = 0; x < bw; x++) {
+            const int root = std::min(std::max((int)((float)x / hX), 0), T.n_ini - 1);
+            oct_maps.push_back((uint16_t)((root << (2 * T.depth)) | spread(cell_index(b0 + root * nb, x))));
+        }
+        for (int y = 0; y < bh; y++) oct_maps.push_back((uint16_t)(2 * spread(cell_index(b0 + T.n_ini * nb, y))));
+    }
+    oct_prefix_frame = std::max<size_t>(oct_prefix_frame, 1);
     oct_nodes_hbm = node_bytes > 150 * 1024;
     oct_node_stride = (node_bytes + 255) & ~(size_t)255;
     if (oct_nodes_hbm) oct_lds_keys = 0;
@@ -530,6 +604,7 @@ int orbx_extractor::setup_geometry(int w, int h)
     }
     ORBX_HIP(hipFuncSetAttribute((const void*)k_fast_strips, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds));
     int r;
+    if ((r = d_oct_tabs.upload(oct_tabs)) || (r = d_oct_bounds.upload(oct_bounds)) || (r = d_oct_maps.upload(oct_maps))) return r;
     if ((r = d_levels.upload(levels)) || (r = d_cells.upload(cells)) || (r = d_tiles.upload(tiles)) || (r = d_strips.upload(strip_recs))) return r;
     geo_w = w; geo_h = h;
     batch_cap = 0;      // scratch must be re-sized for the new geometry
@@ -549,6 +624,7 @@ int orbx_extractor::ensure_batch(int batch)
         (r = d_lvl_kps.ensure(B * sel_frame_entries)) || (r = d_n.ensure(B)) || (r = d_mono.ensure(B)) || (r = d_status.ensure(B)))
         return r;
     if (oct_nodes_hbm && (r = d_oct_nodes.ensure(B * nlevels * oct_node_stride))) return r;
+    if ((r = d_oct_prefix.ensure(B * oct_prefix_frame))) return r;
     // the pyramid row padding is read by dword loads at row ends; keep it defined
     ORBX_HIP(hipMemset(d_pyr.p, 0, B * pyr_frame_bytes + 64));
     ORBX_HIP(hipMemset(d_blur.p, 0, B * pyr_frame_bytes + 64));
@@ -682,7 +758,8 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
                 hipLaunchKernelGGL(oct_kernel, dim3(lv1 - lv0, nB), dim3(64 * W), lds, qs, d_levels.p, d_cells.p, d_cand.p + (size_t)f0 * cand_frame_entries, (size_t)cand_frame_entries,
                                    d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1), n_cells, d_scratch.p + (size_t)f0 * 2 * cand_frame_entries, (size_t)2 * cand_frame_entries, pool, keys,
                                    sel, sel_frame_entries, sel_cnt, nlevels, o_status + f0,
-                                   d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0, W > 1 ? oct_small_max_waves : 32);
+                                   d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0, W > 1 ? oct_small_max_waves : 32,
+                                   d_oct_tabs.p, d_oct_maps.p, d_oct_prefix.p + (size_t)f0 * oct_prefix_frame, oct_prefix_frame);
         };
         auto launch_blur = [&](hipStream_t bs) {
             hipLaunchKernelGGL(k_blur, dim3(xcd_grid((int)tiles.size()), nB), dim3(256), 0, bs, lvl0, pyr, in_place ? pyr : nullptr, blr, pyr_frame_bytes,
@@ -888,6 +965,7 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
     if (const char* env = getenv("ORBX_OCT_DYN")) e->oct_dyn_off = atoi(env) == 0;
     if (const char* env = getenv("ORBX_OCT_DYN_MAXB")) e->oct_dyn_max_batch = atoi(env);
     if (const char* env = getenv("ORBX_OCT_WAVES")) { const int wv = atoi(env); if (wv == 1 || wv == 2 || wv == 4) e->oct_waves_env = wv; }
+    if (const char* env = getenv("ORBX_OCT_TAB_DEPTH")) e->oct_tab_depth_max = std::max(0, std::min(kOctTabMaxDepth, atoi(env)));
     if (const char* env = getenv("ORBX_OCT_SMALL_MAX")) e->oct_small_max_waves = std::max(0, std::min(64, atoi(env)));
     if (const char* env = getenv("ORBX_OCT_WAVES_BESIDE")) {       // A/B runs: three digits, e.g. 412 (early level 0, lower, upper levels)
         for (int i = 0; i < 3 && env[i]; i++) { const int wv = env[i] - '0'; if (wv == 1 || wv == 2 || wv == 4) e->oct_waves_beside[i] = wv; }
@@ -930,7 +1008,7 @@ void orbx_destroy(orbx_extractor* e)
     for (auto& b : e->d_rows) b.release();
     for (auto& b : e->d_xofs) b.release();
     for (auto& b : e->d_ialpha) b.release();
-    e->d_pyr.release(); e->d_blur.release(); e->d_cand.release(); e->d_scratch.release(); e->d_sel.release(); e->d_oct_nodes.release();
+    e->d_pyr.release(); e->d_blur.release(); e->d_cand.release(); e->d_scratch.release(); e->d_sel.release(); e->d_oct_nodes.release(); e->d_oct_prefix.release(); e->d_oct_tabs.release(); e->d_oct_bounds.release(); e->d_oct_maps.release();
     e->d_cell_count.release(); e->d_sel_count.release(); e->d_kp_dst.release(); e->d_lvl_kps.release();
     e->d_kps.release(); e->d_desc.release(); e->d_n.release(); e->d_mono.release(); e->d_status.release();
     e->d_sad.release(); e->d_stereo_io.release();
@@ -1155,6 +1233,19 @@ int orbx_debug_octree_waves(orbx_extractor* e, int launch)
 {
     if (!e || launch < 0 || launch > 2) return fail(ORBX_ERR_ARG, "NULL handle or launch outside 0..2");
     return e->last_oct_waves[launch];
+}
+
+int orbx_debug_octree_table(orbx_extractor* e, int level, int* depth, int* n_ini, int16_t* bounds, int cap)
+{
+    if (!e || !depth || !n_ini || !bounds || level < 0 || level >= (int)e->oct_tabs.size()) return fail(ORBX_ERR_ARG, "NULL argument, no geometry yet or level outside the pyramid");
+    ORBX_HIP(hipSetDevice(e->device));
+    OctTabDesc t;
+    ORBX_HIP(hipMemcpy(&t, e->d_oct_tabs.p + level, sizeof(t), hipMemcpyDeviceToHost));
+    const int n = t.n_ini > 0 ? (t.n_ini + 1) * ((1 << t.depth) + 1) : 0;
+    if (n > cap) return fail(ORBX_ERR_CAPACITY, "%d boundaries, room for %d", n, cap);
+    if (n > 0) ORBX_HIP(hipMemcpy(bounds, e->d_oct_bounds.p + t.bounds_off, sizeof(int16_t) * n, hipMemcpyDeviceToHost));
+    *depth = t.depth; *n_ini = t.n_ini;
+    return n;
 }
 
 int orbx_debug_last_schedule(orbx_extractor* e)

@@ -279,6 +279,9 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
                 const int rk = (int)pre[j * WPC + (q >> 5)] + __popc(wd & ((1u << (q & 31)) - 1u));
                 const int m = mmap[(y + 1) * MP + mc];
                 // coordinates relative to minBorder (= level coordinates - 16), as vToDistributeKeys holds them (:865-866)
+                // k_octree depends on this order: its tie-break between keys of equal response (oct_cand_rank, orbx_kernels.hip)
+                // recomputes a key's place in it from the coordinates alone -- cells in table order (row-major, pitch wCell x hCell,
+                // interiors from 3 px inside the cell), rank rk row-major inside the cell's interior.  Change one, change the other.
                 if (rk < s_tab.slot_cap[j])
                     cand[(size_t)frame * cand_frame_stride + s_tab.slot_off[j] + rk] =
                         pack_key((uint32_t)(4 * g0 + mc - 4 - 16), (uint32_t)(sy0 + 3 + y - 16), (uint32_t)(m - 1));

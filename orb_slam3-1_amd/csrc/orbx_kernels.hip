@@ -5,7 +5,7 @@
 //   k_fast_strips   FAST-9/16 score + per-cell NMS / threshold fallback / ordered compaction, a workgroup per strip of cells
 //                                                                    (E2, ComputeKeyPointsOctTree :787-872)
 //   k_octree        quadtree keypoint selection, a workgroup of 1 / 2 / 4 waves per (frame, level): one control wave, a lane per node
-//                   within a pass; the helper waves share the key partition of large nodes, the gather and the final selection
+//                   within a pass; the helper waves share the key partition of large nodes, the placement of the keys and the final selection
 //                                                                    (E3, DistributeOctTree :555-779)
 //   k_index         output slot of every keypoint (lapping-area split) (E8, operator() :1140-1167)
 //   k_blur          7x7 sigma-2 Gaussian, Q8.8 fixed point             (E6, :1132-1133)
@@ -331,8 +331,10 @@ __global__ __launch_bounds__(1024) void k_resize_tail(uint8_t* __restrict__ pyr,
 
 // ------------------------------------------------------------------------------------------------
 // E3: DistributeOctTree.  One control wave per (frame, level), plus up to three helper waves (see OctJob).  The std::list of nodes is an index-linked list
-// in LDS; a node's keys are a contiguous, order-preserving segment of a ping-pong key array (LDS when
-// the level's candidates fit, HBM scratch otherwise).  A pass of the reference's loops is a batch of up to 64
+// in LDS; a node's keys are a contiguous segment of a ping-pong key array (LDS when the level's candidates fit, HBM scratch
+// otherwise).  The keys are placed ONCE, ordered by the cell of the level's bucket table they fall into (OctTabDesc, oct_place):
+// down to the table's depth a node is a run of cells and divides by arithmetic on the cells' prefix sums (OctTab); only below it
+// are keys partitioned, order-preserving, into the other buffer.  A pass of the reference's loops is a batch of up to 64
 // DivideNode calls, a lane per node (see k_octree); std::sort is wave-parallel (orbx_introsort.h).
 // ------------------------------------------------------------------------------------------------
 #ifdef ORBX_OCT_TIMING      // cycle split of the (level 0, frame 0) wave (tools/oct_timing.py); never defined in the product build
@@ -340,17 +342,17 @@ __device__ unsigned long long d_oct_prof[11];
 #endif
 // A workgroup is W = 1, 2 or 4 waves (the host chooses per launch).  Wave 0 is the CONTROL wave: it runs octree_body and owns all the
 // sequential state.  The other waves are helpers that run oct_helper_loop and nothing else.  Wave 0 hands them the parts of a pass
-// whose items are independent -- the key partition of the nodes the whole wave takes one by one, the initial gather, the final
+// whose items are independent -- the key partition of the nodes the whole wave takes one by one, the initial placement of the keys, the final
 // selection -- as JOBS through this LDS record.  Workgroup barriers stand at exactly two points:
 //   A  wave 0 has written the job (oct_post_job)    | the helpers wait here between jobs
 //   B  every wave, wave 0 included, has done its share of the job
 // The record is written by wave 0 only between B and the next A and read by the helpers only between A and B.  Everything else that
 // was a barrier when the workgroup was one wave is a fence of the control wave alone (wave_mem_fence).
-enum { kOctJobExit = 0, kOctJobPartition = 1, kOctJobGather = 2, kOctJobSelect = 3 };
+enum { kOctJobExit = 0, kOctJobPartition = 1, kOctJobPlace = 2, kOctJobSelect = 3 };
 constexpr int kOctMaxJobs = 1 << 24;    // the helpers' loop bound; wave 0 stops posting one short of it, so that the EXIT job always fits
 struct OctJob {
     int op, n, lds_keys, pad;
-    int list[64];           // PARTITION: (batch lane << 16) | node id;  GATHER: the first key slot of every block of 64 cells
+    int list[64];           // PARTITION: (batch lane << 16) | node id
     int cnt[4 * 64];        // PARTITION: the four child sizes of the node of batch lane l at cnt[4 l ..]
 };
 struct OctArgs {
@@ -363,13 +365,31 @@ struct OctArgs {
     int* sel_count; int n_levels; int* status;
     uint8_t* node_scratch; size_t node_stride; int level_first;
     int small_max;          // a node of at most this many keys is partitioned by its lane, a larger one by the whole wave(s)
+    const OctTabDesc* tabs; const uint16_t* maps;           // the levels' bucket tables (setup_geometry)
+    int* prefix; size_t prefix_frame_stride;                // per frame and level: the prefix sums over the table's cells
 };
 struct OctLds {
     short* ulx; short* uly; short* brx; short* bry;
     int* beg; int* cnt;
     int* pidx; short* freelist; short* order;       // pidx indexes the push log (6 x pool entries: beyond 16 bits for large pools)
     short* plog;            // push log: the std::list order is the REVERSE of this array without its tombstones (-1)
-    uint8_t* flg;           // bit0: bNoMore, bit1: keys live in buffer 1
+    uint8_t* flg;           // bit0: bNoMore, bit1: keys live in buffer 1, bits 2-4: depth of a node of the bucket table, kOctDeep below it
+};
+// A node of depth d <= D (the level's table depth) is a run of 4^(D-d) cells of the bucket table: its `beg` field holds its FIRST CELL,
+// its keys are kb[P[cell] .. P[cell + 4^(D-d)]), and its four children are four quarters of that run -- dividing it moves no key.
+// A node of depth D is one cell; dividing it partitions its keys as before the table (ping-pong into the other buffer), and its
+// children and theirs are DEEP nodes whose `beg` is a key offset.
+constexpr int kOctDeep = 7;
+struct OctTab {
+    int D, n_ini, ncell, w_cell_inv, h_cell_inv;
+    float hx;
+    int* P;                 // prefix sums over the cells (global, L2-resident): ncell + 1 entries
+    int* C;                 // placement only, overlaid on the node pool (which is empty then): counters / cursors per cell ...
+    uint16_t* lmap;         // ... and, where they fit too (maps_lds), the level's two maps, staged from gmap
+    const uint16_t* gmap;
+    int bw, bh;             // entries of the x map and of the y map: the tree's width and height
+    bool maps_lds;
+    bool fits;              // the overlay fits the pool (the host chose D so; checked by the control wave)
 };
 
 // LDS_KEYS: both ping-pong key buffers live in LDS (the host sizes them for the largest level, so the choice is static and
@@ -390,6 +410,7 @@ struct OctMem {
     SortNode* ex_sorted;    // the sorted previous one (and the sort's scratch)
     uint32_t* kb;           // the two key buffers: kb[0 .. cap) and kb[cap .. 2 cap)
     int cap;
+    OctTab T;
 };
 
 // carve the node pool and the key buffers of this (frame, level); every wave of the workgroup computes the same pointers
@@ -412,19 +433,35 @@ __device__ __forceinline__ OctMem oct_carve(const OctArgs& A, const LevelDesc& L
     S.freelist = (short*)p; p += 2 * pool; S.order = (short*)p; p += 2 * pool;
     S.plog = (short*)p; p += 2 * kOctLogFactor * pool;
     S.flg = p; p += (pool + 15) & ~15;
+    {
+        const OctTabDesc td = A.tabs[A.level_first + blockIdx.x];
+        OctTab& T = M.T;
+        T.D = td.depth; T.n_ini = td.n_ini; T.ncell = td.n_ini << (2 * td.depth); T.w_cell_inv = td.w_cell_inv; T.h_cell_inv = td.h_cell_inv;
+        T.bw = (L.w - kEdge + 3) - (kEdge - 3); T.bh = (L.h - kEdge + 3) - (kEdge - 3);
+        T.hx = (float)T.bw / (float)td.n_ini;
+        T.P = A.prefix + (size_t)blockIdx.y * A.prefix_frame_stride + td.prefix_off;
+        T.C = (int*)M.ex_new;
+        T.lmap = (uint16_t*)(T.C + T.ncell + 1);
+        T.gmap = A.maps + td.map_off;
+        T.maps_lds = td.maps_lds != 0;
+        T.fits = td.depth >= 0 && td.depth <= kOctTabMaxDepth && td.n_ini >= 1 && T.bw >= 1 && T.bh >= 1 &&
+                 (uint8_t*)(T.lmap + (T.maps_lds ? T.bw + T.bh : 0)) <= p;
+    }
     if constexpr (LDS_KEYS) { M.kb = (uint32_t*)p; M.cap = A.lds_keys_cap; }
     else { M.kb = A.scratch + (size_t)blockIdx.y * A.scratch_frame_stride + 2 * (size_t)L.cand_off; M.cap = L.cand_cap; }
     return M;
 }
 
 // what DivideNode needs of the node of this lane
-struct OctNodeBox { int ulx, uly, brx, bry, beg, cnt, src, midx, midy, in_off, out_off; };
-__device__ __forceinline__ OctNodeBox oct_node_box(const OctLds& S, int cap, int id)
+struct OctNodeBox { int ulx, uly, brx, bry, beg, cnt, src, midx, midy, in_off, out_off, dep, cell; };
+__device__ __forceinline__ OctNodeBox oct_node_box(const OctLds& S, const OctTab& T, int cap, int id)
 {
-    OctNodeBox b = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    OctNodeBox b = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, kOctDeep, 0};
     if (id >= 0) {
         b.ulx = S.ulx[id]; b.uly = S.uly[id]; b.brx = S.brx[id]; b.bry = S.bry[id];
-        b.beg = S.beg[id]; b.cnt = S.cnt[id]; b.src = (S.flg[id] >> 1) & 1;
+        const int f = S.flg[id];
+        b.beg = S.beg[id]; b.cnt = S.cnt[id]; b.src = (f >> 1) & 1; b.dep = (f >> 2) & 7;
+        if (b.dep <= T.D) { b.cell = b.beg; b.beg = T.P[b.cell]; }         // a node of the table: its keys begin where its first cell does
     }
     const int halfX = (b.brx - b.ulx + 1) >> 1;     // ceil(float(w)/2), w >= 0
     const int halfY = (b.bry - b.uly + 1) >> 1;
@@ -510,7 +547,7 @@ __device__ __forceinline__ void oct_job_partition(const OctMem& M, OctJob* __res
     const int n = min(__builtin_amdgcn_readfirstlane(J->n), 64);
     int id = -1, bl = 0;
     if (lane < n) { const int v = J->list[lane]; id = v & 0xFFFF; bl = v >> 16; }
-    const OctNodeBox nb = oct_node_box(M.S, M.cap, id);
+    const OctNodeBox nb = oct_node_box(M.S, M.T, M.cap, id);
     const unsigned long long all = (n >= 64) ? ~0ull : (1ull << n) - 1ull;
     const unsigned long long stripe = ((W == 4) ? 0x1111111111111111ull : (W == 2) ? 0x5555555555555555ull : ~0ull) << w;
     const unsigned long long mine = all & stripe;
@@ -519,51 +556,99 @@ __device__ __forceinline__ void oct_job_partition(const OctMem& M, OctJob* __res
     if ((mine >> lane) & 1ull) { int* o = J->cnt + 4 * (bl & 63); o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3; }
 }
 
-// GATHER: blocks of 64 cells w, w + W, ...; J->list[block] is the block's first key slot
-__device__ __forceinline__ void oct_gather_block(const LevelDesc& L, const CellDesc* __restrict__ cells, const uint32_t* __restrict__ fc, const int* __restrict__ cc,
-                                                 uint32_t* __restrict__ kb, const int cap, const int c0, const int first, const int lane, int& block_total)
+// the cell of the bucket table a key falls into: its root, then the quadrant at every depth, all in the level's two maps
+template <class Map>
+__device__ __forceinline__ int oct_cell_of(const OctTab& T, const Map xm, const Map ym, const uint32_t e)
 {
-    const int ci = c0 + lane;
-    int n = 0, slot_off = 0;
-    if (ci < L.cell_count) { n = cc[L.cell_begin + ci]; slot_off = cells[L.cell_begin + ci].slot_off; }
-    const int incl = wave_incl_scan(n);
-    const int base = first + incl - n;
-    if (base < 0 || base + n > cap) n = 0;          // cannot happen (the buffers hold a whole level); reported by the control wave
-    for (int k = 0; __ballot(k < n) != 0ull; k += 8) {
-        uint32_t e[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) e[u] = (k + u < n) ? fc[slot_off + k + u] : 0u;
-#pragma unroll
-        for (int u = 0; u < 8; u++) if (k + u < n) kb[base + k + u] = e[u];
-    }
-    block_total = __builtin_amdgcn_readlane(incl, 63);
-}
-__device__ __forceinline__ void oct_job_gather(const OctArgs& A, const LevelDesc& L, const OctMem& M, const OctJob* __restrict__ J, const int w, const int W, const int lane)
-{
-    const uint32_t* fc = A.cand + (size_t)blockIdx.y * A.cand_frame_stride;
-    const int* cc = A.cell_count + (size_t)blockIdx.y * A.n_cells;
-    const int nblk = min(__builtin_amdgcn_readfirstlane(J->n), 64);
-    for (int blk = w; blk < nblk; blk += W) {
-        int unused;
-        oct_gather_block(L, A.cells, fc, cc, M.kb, M.cap, 64 * blk, __builtin_amdgcn_readfirstlane(J->list[blk]), lane, unused);
-    }
+    return (int)xm[min((int)key_x(e), T.bw - 1)] | (int)ym[min((int)key_y(e), T.bh - 1)];
 }
 
-// SELECT: the best-response key of every node, first wins ties (:758-776); blocks of 64 nodes w, w + W, ..., a lane per node
+// where a key stands in vToDistributeKeys order (FAST cell row-major, row-major inside a cell): the order that decides between
+// keys of equal response
+__device__ __forceinline__ unsigned long long oct_cand_rank(const OctTab& T, const uint32_t e)
+{
+    const uint32_t x = key_x(e), y = key_y(e);
+    // FAST cell = (coordinate - 3) / pitch, the division as a multiplication (the host checked it for every coordinate of the level)
+    const uint32_t cj = ((x >= 3u ? x - 3u : 0u) * (uint32_t)T.w_cell_inv) >> 20, ci = ((y >= 3u ? y - 3u : 0u) * (uint32_t)T.h_cell_inv) >> 20;
+    return ((unsigned long long)((ci << 12) | cj) << 24) | (unsigned long long)((y << 12) | x);
+}
+// one number to maximise: the response first, then the EARLIER candidate (rank below 2^48)
+__device__ __forceinline__ unsigned long long oct_select_score(const OctTab& T, const uint32_t e)
+{
+    return ((unsigned long long)key_resp(e) << 48) | (0xFFFFFFFFFFFFull - oct_cand_rank(T, e));
+}
+
+// PLACE: every candidate of the level goes ONCE to its cell's run of key buffer 0 (counting sort by cell code, not stable), read
+// straight from the FAST cells' slots; waves take blocks of 64 FAST cells w, w + W, ..., a lane per FAST cell.  `step` separates
+// the phases: a workgroup barrier when the helpers share the job, the control wave's own fence when it works alone.
+template <class Step>
+__device__ __forceinline__ void oct_place(const OctArgs& A, const LevelDesc& L, const OctMem& M, const int w, const int W, const int lane, Step step)
+{
+    const OctTab& T = M.T;
+    const uint32_t* fc = A.cand + (size_t)blockIdx.y * A.cand_frame_stride;
+    const int* cc = A.cell_count + (size_t)blockIdx.y * A.n_cells;
+    for (int i = 64 * w + lane; i <= T.ncell; i += 64 * W) T.C[i] = 0;
+    if (T.maps_lds) for (int i = 64 * w + lane; i < T.bw + T.bh; i += 64 * W) T.lmap[i] = T.gmap[i];
+    step();
+    const int nblk = (L.cell_count + 63) >> 6;
+    auto pass = [&](const auto xm, const auto ym, const bool scatter) {
+        for (int blk = w; blk < nblk; blk += W) {
+            const int ci = 64 * blk + lane;
+            int n = 0, slot_off = 0;
+            if (ci < L.cell_count) { n = cc[L.cell_begin + ci]; slot_off = A.cells[L.cell_begin + ci].slot_off; }
+            for (int k = 0; __ballot(k < n) != 0ull; k += 8) {
+                uint32_t e[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) e[u] = (k + u < n) ? fc[slot_off + k + u] : 0u;
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    if (k + u < n) {
+                        const int cell = min(oct_cell_of(T, xm, ym, e[u]), T.ncell - 1);
+                        if (!scatter) atomicAdd(&T.C[cell], 1);
+                        else { const int pos = atomicAdd(&T.C[cell], 1); if ((unsigned)pos < (unsigned)M.cap) M.kb[pos] = e[u]; }
+                    }
+                }
+            }
+        }
+    };
+    // (one call per home of the maps: each is compiled with its own addressing)
+    if (T.maps_lds) pass((const uint16_t*)T.lmap, (const uint16_t*)T.lmap + T.bw, false); else pass(T.gmap, T.gmap + T.bw, false);
+    step();
+    if (w == 0) {       // exclusive prefix over the cells: P for the divides, C as the scatter's cursors; entry ncell is the total
+        int run = 0;
+        for (int i0 = 0; i0 <= T.ncell; i0 += 64) {
+            const int i = i0 + lane;
+            const int v = (i < T.ncell) ? T.C[i] : 0;
+            const int incl = wave_incl_scan(v);
+            if (i <= T.ncell) { T.P[i] = run + incl - v; T.C[i] = run + incl - v; }
+            run += __builtin_amdgcn_readlane(incl, 63);
+        }
+    }
+    step();
+    if (T.maps_lds) pass((const uint16_t*)T.lmap, (const uint16_t*)T.lmap + T.bw, true); else pass(T.gmap, T.gmap + T.bw, true);
+}
+
+// SELECT: the best-response key of every node (:758-776); blocks of 64 nodes w, w + W, ..., a lane per node.  The reference keeps the
+// FIRST key of maximal response in vKeys order; a node's keys no longer stand in that order, so ties go to the key that comes first
+// in candidate order (oct_cand_rank).
 __device__ __forceinline__ void oct_select_blocks(const OctMem& M, uint32_t* __restrict__ out, const int n_out, const int w, const int W, const int lane)
 {
     const OctLds& S = M.S;
     for (int k0 = 64 * w; k0 < n_out; k0 += 64 * W) {
         const int k = k0 + lane;
         int off = 0, cnt = 0;
-        if (k < n_out) { const int id = S.order[k]; off = (((S.flg[id] >> 1) & 1) ? M.cap : 0) + S.beg[id]; cnt = S.cnt[id]; }
+        if (k < n_out) { const OctNodeBox nb = oct_node_box(S, M.T, M.cap, S.order[k]); off = nb.in_off; cnt = nb.cnt; }
         uint32_t best = 0;
+        unsigned long long best_score = 0ull;
         for (int i = 0; __ballot(i < cnt) != 0ull; i += 4) {
             uint32_t e[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) e[u] = (i + u < cnt) ? M.kb[off + i + u] : 0u;
 #pragma unroll
-            for (int u = 0; u < 4; u++) if (i + u < cnt && (i + u == 0 || key_resp(e[u]) > key_resp(best))) best = e[u];
+            for (int u = 0; u < 4; u++) {
+                const unsigned long long s = oct_select_score(M.T, e[u]);
+                if (i + u < cnt && (i + u == 0 || s > best_score)) { best = e[u]; best_score = s; }
+            }
         }
         if (k < n_out) out[k] = best;
     }
@@ -575,7 +660,7 @@ __device__ __forceinline__ void oct_do_job(const int op, const OctArgs& A, const
 {
     const OctMem M = oct_carve<LDS_KEYS, LDS_NODES>(A, L, smem);
     if (op == kOctJobPartition) oct_job_partition(M, J, w, W, lane, lt);
-    else if (op == kOctJobGather) oct_job_gather(A, L, M, J, w, W, lane);
+    else if (op == kOctJobPlace) oct_place(A, L, M, w, W, lane, [] { __syncthreads(); });
     else if (op == kOctJobSelect)
         oct_select_blocks(M, A.sel + (size_t)blockIdx.y * A.sel_frame_stride + L.sel_off, min(__builtin_amdgcn_readfirstlane(J->n), L.sel_cap), w, W, lane);
 }
@@ -615,7 +700,7 @@ template <bool LDS_KEYS, bool LDS_NODES>
 __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restrict__ smem, int* __restrict__ s_sort_stack, OctJob* __restrict__ J, const int W, int& jobs)
 {
     static_assert(LDS_NODES || !LDS_KEYS, "a pool too large for LDS leaves no room for LDS keys");
-    const LevelDesc* __restrict__ levels = A.levels; const CellDesc* __restrict__ cells = A.cells;
+    const LevelDesc* __restrict__ levels = A.levels;
     const int pool = A.pool, n_levels = A.n_levels;
     int* __restrict__ status = A.status;
     const int level = A.level_first + blockIdx.x, frame = blockIdx.y;     // (a launch covers the levels level_first ..: see enqueue())
@@ -647,49 +732,41 @@ __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restric
     int* out_count = A.sel_count + (size_t)frame * n_levels + level;
     uint32_t* out = A.sel + (size_t)frame * A.sel_frame_stride + L.sel_off;
 
-    // ---- gather the level's candidates in vToDistributeKeys order (cell row-major, row-major inside a cell): one lane per
-    // cell, the in-wave prefix of the cell counts gives each cell its place in the ordered list
-    const uint32_t* fc = A.cand + (size_t)frame * A.cand_frame_stride;
-    const int* cc = A.cell_count + (size_t)frame * A.n_cells;
-    int total = 0;
-    const int n_blocks = (L.cell_count + 63) >> 6;
-    if (can_post() && n_blocks > 1 && n_blocks <= 64) {
-        // the running total per block of 64 cells first, so that every wave knows where its blocks begin
-        for (int blk = 0; blk < n_blocks; blk++) {
-            const int ci = 64 * blk + lane;
-            int n = (ci < L.cell_count) ? cc[L.cell_begin + ci] : 0;
-            for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-            if (lane == 0) J->list[blk] = total;
-            total += __builtin_amdgcn_readfirstlane(n);
-        }
-        oct_post_job(J, kOctJobGather, n_blocks, LDS_KEYS ? 1 : 0, lane, jobs);
-        oct_job_gather(A, L, M, J, 0, W, lane);
+    const int width = (L.w - kEdge + 3) - (kEdge - 3), height = (L.h - kEdge + 3) - (kEdge - 3);
+    const int nIni = (height > 0) ? (int)roundf((float)width / (float)height) : 0;      // :559
+    if (nIni <= 0) {
+        if (lane == 0) *out_count = 0;
+        return;
+    }
+    const OctTab& T = M.T;
+    if (nIni > pool / 2 || nIni != T.n_ini || !T.fits) {        // (the host builds the table for these very roots, inside the pool's bytes)
+        if (lane == 0) { atomicExch(status + frame, ORBX_ERR_INTERNAL); *out_count = 0; }
+        return;
+    }
+
+    // ---- place the level's candidates: every key goes once to its cell of the bucket table (oct_place); the node pool is still
+    // empty and lends the placement its counters
+    if (can_post()) {
+        oct_post_job(J, kOctJobPlace, 0, LDS_KEYS ? 1 : 0, lane, jobs);
+        oct_place(A, L, M, 0, W, lane, [] { __syncthreads(); });
         ORBX_OTICK(0)
         __syncthreads();                                    // B
         ORBX_OTICK(7)
     } else {
-        for (int c0 = 0; c0 < L.cell_count; c0 += 64) {
-            int block_total;
-            oct_gather_block(L, cells, fc, cc, kb, cap, c0, total, lane, block_total);
-            total += block_total;
-        }
+        oct_place(A, L, M, 0, 1, lane, fence);
+        wave_mem_fence<true>();         // (the prefix sums are in global memory whatever the home of the keys)
     }
+    const int total = T.C[T.ncell];
     if (total > cap) {
         if (lane == 0) { atomicExch(status + frame, ORBX_ERR_INTERNAL); *out_count = 0; }
         return;
     }
-    fence();
     ORBX_OTICK(0)
-
-    const int width = (L.w - kEdge + 3) - (kEdge - 3), height = (L.h - kEdge + 3) - (kEdge - 3);
-    const int nIni = (height > 0) ? (int)roundf((float)width / (float)height) : 0;      // :559
-    if (total == 0 || nIni <= 0 || nIni > pool / 2) {
-        if (lane == 0) {
-            *out_count = 0;
-            if (total != 0 && nIni > pool / 2) atomicExch(status + frame, ORBX_ERR_INTERNAL);
-        }
+    if (total == 0) {
+        if (lane == 0) *out_count = 0;
         return;
     }
+    fence();        // (the counters are read: the pool may be written)
 
     // ---- the list.  std::list<ExtractorNode> with push_front / erase only needs an append-only push log: iterating the
     // list from begin() is walking the log backwards, erase() leaves a tombstone, and nodes pushed while a pass is running
@@ -712,53 +789,30 @@ __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restric
         fence();
     };
 
-    // ---- root nodes (:564-586): nIni vertical strips of width hX
-    const float hX = (float)width / (float)nIni;
-    if (nIni == 1) {
-        // one root that owns every key: they already stand in order in buffer 0 ((int)(x / hX) is 0 for every x < width)
-        if (lane == 0) {
-            const int id = S.freelist[nfree - 1];
-            S.ulx[id] = 0; S.uly[id] = 0; S.brx[id] = (short)(int)hX; S.bry[id] = (short)height;
-            S.beg[id] = 0; S.cnt[id] = total; S.flg[id] = (uint8_t)(total == 1 ? 1 : 0);
-            S.plog[0] = (short)id; S.pidx[id] = 0;
-        }
-        nfree--; np = 1; size = 1;
-        fence();
-    } else {
-        // stable partition of the keys by strip into buffer 1
-        int strip_beg = 0;
-        for (int s = 0; s < nIni; s++) {
-            int cnt = 0;
-            for (int k0 = 0; k0 < total; k0 += 64) {
-                const int k = k0 + lane;
-                bool in = false;
-                uint32_t e = 0;
-                if (k < total) { e = kb[k]; in = ((int)((float)key_x(e) / hX) == s); }
-                const unsigned long long m = __ballot(in);
-                if (in) kb[cap + strip_beg + cnt + __popcll(m & lt)] = e;
-                cnt += __popcll(m);
+    // ---- root nodes (:564-586): nIni vertical strips of width hX; root s is the cells [s << 2D, (s + 1) << 2D) of the table
+    const float hX = T.hx;
+    for (int s = 0; s < nIni; s++) {
+        const int cell = s << (2 * T.D);
+        const int cnt = __builtin_amdgcn_readfirstlane(T.P[cell + (1 << (2 * T.D))] - T.P[cell]);
+        int id = -1;
+        if (cnt > 0) {      // empty roots are erased (:595-596)
+            id = S.freelist[--nfree];
+            if (lane == 0) {
+                S.ulx[id] = (short)(int)(hX * (float)s);       S.uly[id] = 0;
+                S.brx[id] = (short)(int)(hX * (float)(s + 1)); S.bry[id] = (short)height;
+                S.beg[id] = cell; S.cnt[id] = cnt;
+                S.flg[id] = (uint8_t)(cnt == 1 ? 1 : 0);        // depth 0, keys in buffer 0
             }
-            int id = -1;
-            if (cnt > 0) {      // empty roots are erased (:595-596)
-                id = S.freelist[--nfree];
-                if (lane == 0) {
-                    S.ulx[id] = (short)(int)(hX * (float)s);       S.uly[id] = 0;
-                    S.brx[id] = (short)(int)(hX * (float)(s + 1)); S.bry[id] = (short)height;
-                    S.beg[id] = strip_beg; S.cnt[id] = cnt;
-                    S.flg[id] = (uint8_t)(2 | (cnt == 1 ? 1 : 0));
-                }
-            }
-            if (lane == 0) S.order[s] = (short)id;
-            strip_beg += cnt;
         }
-        fence();
-        // the reference push_back()s the roots in strip order; in push-log terms the first strip is pushed last
-        for (int s = nIni - 1; s >= 0; s--) {
-            const int id = S.order[s];
-            if (id >= 0) { if (lane == 0) { S.plog[np] = (short)id; S.pidx[id] = np; } np++; size++; }
-        }
-        fence();
+        if (lane == 0) S.order[s] = (short)id;
     }
+    fence();
+    // the reference push_back()s the roots in strip order; in push-log terms the first strip is pushed last
+    for (int s = nIni - 1; s >= 0; s--) {
+        const int id = S.order[s];
+        if (id >= 0) { if (lane == 0) { S.plog[np] = (short)id; S.pidx[id] = np; } np++; size++; }
+    }
+    fence();
     ORBX_OTICK(1)
 
     // One batch of DivideNode calls (:480-536 and the loop bodies :610-676 / :706-750): lane l divides node `id` (or none: -1);
@@ -766,22 +820,32 @@ __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restric
     // whether that happened.
     auto divide_batch = [&](const int id, const bool sorted_phase, int& n_to_expand) -> bool {
         const bool act = id >= 0;
-        const OctNodeBox nb = oct_node_box(S, cap, id);
+        const OctNodeBox nb = oct_node_box(S, T, cap, id);
         const int ulx = nb.ulx, uly = nb.uly, brx = nb.brx, bry = nb.bry, beg = nb.beg, cnt = nb.cnt, src = nb.src;
         const int midx = nb.midx, midy = nb.midy, in_off = nb.in_off, out_off = nb.out_off;
-        // Scattering a node's keys into the other buffer is harmless when the node ends up not being divided (its range of
-        // the other buffer is dead space of its own), so counting and scattering do not wait for the cut.
-        const unsigned long long m_act = __ballot(act);
-        const int small_max = (__popcll(m_act) <= 6) ? 0 : A.small_max;       // a handful of nodes: the whole wave takes them one by one
-        const bool small = act && cnt <= small_max;
+        // A node above the table's depth divides by lookup: its children are the four quarters of its run of cells, their sizes
+        // differences of the prefix sums; no key is read or moved.
+        const bool tab = act && nb.dep < T.D;
+        const int quarter = tab ? 1 << (2 * (T.D - nb.dep - 1)) : 0;
+        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        if (tab) {
+            const int p1 = T.P[nb.cell + quarter], p2 = T.P[nb.cell + 2 * quarter], p3 = T.P[nb.cell + 3 * quarter], p4 = T.P[nb.cell + 4 * quarter];
+            c0 = p1 - beg; c1 = p2 - p1; c2 = p3 - p2; c3 = p4 - p3;
+        }
+        // The others (a cell of the table, or a node below it) partition their keys.  Scattering a node's keys into the other
+        // buffer is harmless when the node ends up not being divided (its range of the other buffer is dead space of its own),
+        // so counting and scattering do not wait for the cut.
+        const bool part = act && !tab;
+        const unsigned long long m_part = __ballot(part);
+        const int small_max = (__popcll(m_part) <= 6) ? 0 : A.small_max;      // a handful of nodes: the whole wave takes them one by one
+        const bool small = part && cnt <= small_max;
         // the nodes the whole wave takes one by one: with helpers, and more than one such node, they are a PARTITION job
-        const unsigned long long m_big = __ballot(act && !small);
+        const unsigned long long m_big = __ballot(part && !small);
         const bool job = __popcll(m_big) > 1 && can_post();
         if (job) {
-            if (act && !small) J->list[__popcll(m_big & lt)] = (lane << 16) | id;
+            if (part && !small) J->list[__popcll(m_big & lt)] = (lane << 16) | id;
             oct_post_job(J, kOctJobPartition, __popcll(m_big), LDS_KEYS ? 1 : 0, lane, jobs);
         }
-        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
         if (__ballot(small) != 0ull) {
             // a lane per node: count, then stable scatter
             for (int k = 0; __ballot(small && k < cnt) != 0ull; k += 4) {
@@ -816,7 +880,7 @@ __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restric
             ORBX_OTICK(2)
             __syncthreads();                                // B
             ORBX_OTICK(7)
-            if (act && !small) { const int* o = J->cnt + 4 * lane; c0 = o[0]; c1 = o[1]; c2 = o[2]; c3 = o[3]; }
+            if (part && !small) { const int* o = J->cnt + 4 * lane; c0 = o[0]; c1 = o[1]; c2 = o[2]; c3 = o[3]; }
         } else {
             oct_partition_nodes(kb, m_big, lane, lt, in_off, out_off, cnt, midx, midy, c0, c1, c2, c3);
         }
@@ -854,8 +918,9 @@ __device__ __forceinline__ void octree_body(const OctArgs& A, uint8_t* __restric
                         const int ux = (c & 1) ? midx : ulx, uy = (c & 2) ? midy : uly;
                         S.ulx[ch] = (short)ux; S.uly[ch] = (short)uy;
                         S.brx[ch] = (short)((c & 1) ? brx : midx); S.bry[ch] = (short)((c & 2) ? bry : midy);
-                        S.beg[ch] = cb; S.cnt[ch] = cn;
-                        S.flg[ch] = (uint8_t)(((src ^ 1) << 1) | (cn == 1 ? 1 : 0));
+                        // a child by lookup is a quarter of its parent's cells, in the same buffer; a partitioned one is a key range of the other
+                        S.beg[ch] = tab ? nb.cell + c * quarter : cb; S.cnt[ch] = cn;
+                        S.flg[ch] = (uint8_t)((tab ? ((nb.dep + 1) << 2) | (src << 1) : (kOctDeep << 2) | ((src ^ 1) << 1)) | (cn == 1 ? 1 : 0));
                         S.plog[slot] = (short)ch; S.pidx[ch] = slot; slot++;            // push_front, children n1..n4 in order
                         if (cn > 1) { SortNode sn; sn.count = cn; sn.ulx = ux; sn.node = ch; ex_new[xs++] = sn; }
                         cb += cn;
@@ -956,13 +1021,15 @@ __global__ __launch_bounds__(256) void k_octree(const LevelDesc* __restrict__ le
     const uint32_t* __restrict__ cand, size_t cand_frame_stride, const int* __restrict__ cell_count, int n_cells,
     uint32_t* __restrict__ scratch, size_t scratch_frame_stride, int pool, int lds_keys_cap,
     uint32_t* __restrict__ sel, int sel_frame_stride, int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
-    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max)
+    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max,
+    const OctTabDesc* __restrict__ tabs, const uint16_t* __restrict__ maps, int* __restrict__ prefix, size_t prefix_frame_stride)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_sort_stack[3 * kIntrosortStack];       // the sort's explicit stack (in LDS, not in private scratch)
     __shared__ OctJob s_job;
     const OctArgs A = {levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
-                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max};
+                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max,
+                       tabs, maps, prefix, prefix_frame_stride};
     const int W = (int)(blockDim.x >> 6);                                   // 1, 2 or 4 waves (the host's choice per launch)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (wave != 0) { oct_helper_loop<LDS_KEYS ? 1 : 0, LDS_NODES>(A, smem, &s_job, wave, W); return; }
@@ -981,13 +1048,15 @@ __global__ __launch_bounds__(256) void k_octree_dyn(const LevelDesc* __restrict_
     const uint32_t* __restrict__ cand, size_t cand_frame_stride, const int* __restrict__ cell_count, int n_cells,
     uint32_t* __restrict__ scratch, size_t scratch_frame_stride, int pool, int lds_keys_cap,
     uint32_t* __restrict__ sel, int sel_frame_stride, int* __restrict__ sel_count, int n_levels, int* __restrict__ status,
-    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max)
+    uint8_t* __restrict__ node_scratch, size_t node_stride, int level_first, int small_max,
+    const OctTabDesc* __restrict__ tabs, const uint16_t* __restrict__ maps, int* __restrict__ prefix, size_t prefix_frame_stride)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_sort_stack[3 * kIntrosortStack];
     __shared__ OctJob s_job;
     const OctArgs A = {levels, cells, cand, cand_frame_stride, cell_count, n_cells, scratch, scratch_frame_stride, pool, lds_keys_cap,
-                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max};
+                       sel, sel_frame_stride, sel_count, n_levels, status, node_scratch, node_stride, level_first, small_max,
+                       tabs, maps, prefix, prefix_frame_stride};
     const int W = (int)(blockDim.x >> 6);                                   // 1, 2 or 4 waves (the host's choice per launch)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (wave != 0) { oct_helper_loop<2, true>(A, smem, &s_job, wave, W); return; }

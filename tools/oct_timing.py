@@ -17,7 +17,9 @@ ex(img); ex(img)
 out = (C.c_ulonglong * 11)()
 pkg.lib.orbx_debug_oct_prof(out)
 v = list(out)
-names = ["gather", "roots", "count+scatter", "bookkeeping", "compact/other", "sort", "final selection"]
+# "placement": every key once to its cell of the bucket table (counting sort); "partition below the table": the count + scatter of the
+# nodes deeper than the table (all the divides' key movement before the table existed: the bucket then read "count+scatter")
+names = ["placement", "roots", "child sizes (lookup / partition below the table)", "bookkeeping", "compact/other", "sort", "final selection"]
 print("level-0 wave: %d cycles, %d candidates, %d divides" % (v[7], v[8], v[9]))
 print("  " + ", ".join("%s %d" % (n, c) for n, c in zip(names, v[:7])))
 print("  waiting at the job barriers %d (control wave, %d waves per workgroup)" % (v[10], ex.debug_octree_waves(1)))

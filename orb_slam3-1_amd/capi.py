@@ -669,6 +669,53 @@ class Matcher:
         return float(lib.orbm_rig_search_last_kernel_ms(self._h))
 
 
+    # ---- SearchByBoW and SearchForTriangulation for two-camera fisheye rigs (include/orbslam3_hip_rig_bow.h) ----
+    def search_by_bow_rig(self, s):
+        """SearchByBoW(KeyFrame*, Frame&, ...) with F.Nleft != -1.  s: dict(dKF, validKF, angKF, fvKF, dF, n_left, angF, fvF), all over
+        the concatenated (left, then right) arrays.  Returns (nmatches, match_f2kf[nF])."""
+        _rig_bow_argtypes()
+        p, keep = bow_rig_pair(s)
+        a, b = p.fv_kf, p.fv_f
+        n = _check(lib.orbm_search_by_bow_rig(self._h, p.desc_kf, p.n_kf, p.valid_kf, p.angle_kf, C.byref(a), p.desc_f, p.n_f, p.n_left_f, p.angle_f, C.byref(b),
+                                              self.nnratio, int(self.check_ori), p.match_f2kf))
+        return n, keep["match"][:p.n_f]
+
+    def search_by_bow_rig_batch(self, sets):
+        """sets: list of dicts as search_by_bow_rig takes -> list of (nmatches, match_f2kf); ONE launch"""
+        _rig_bow_argtypes()
+        arr = (OrbmBowRigPair * len(sets))()
+        keep = []
+        for i, s in enumerate(sets):
+            arr[i], k = bow_rig_pair(s)
+            keep.append(k)
+        _check(lib.orbm_search_by_bow_rig_batch(self._h, arr, len(sets), self.nnratio, int(self.check_ori)))
+        return [(int(arr[i].n_matches), keep[i]["match"][:arr[i].n_f]) for i in range(len(sets))]
+
+    def search_for_triangulation_rig(self, s, only_stereo=False, coarse=False):
+        """SearchForTriangulation(pKF1, pKF2, ...) of two rig key frames.  s: dict(kf1, kf2 (dicts of desc, has_mp, x, y, octave, angle, fv,
+        n_left over the concatenated lists), geom=dict(cam [4][9], R12 [4][9], t12 [4][3]), sigma2_1, sigma2_2).  Returns (nmatches, match12)."""
+        _rig_bow_argtypes()
+        p, keep = rig_tri_pair(s)
+        n = _check(lib.orbm_search_for_triangulation_rig(self._h, p.kf1, p.n_left_1, p.kf2, p.n_left_2, p.geom, p.level_sigma2_1, p.level_sigma2_2, p.n_levels,
+                                                         int(only_stereo), int(coarse), int(self.check_ori), p.match12))
+        return n, keep["match"][:p.kf1.contents.n]
+
+    def search_for_triangulation_rig_batch(self, sets, only_stereo=False, coarse=False):
+        """sets: list of dicts as search_for_triangulation_rig takes -> list of (nmatches, match12); ONE search launch"""
+        _rig_bow_argtypes()
+        arr = (OrbmRigTriPair * len(sets))()
+        keep = []
+        for i, s in enumerate(sets):
+            arr[i], k = rig_tri_pair(s)
+            keep.append(k)
+        _check(lib.orbm_search_for_triangulation_rig_batch(self._h, arr, len(sets), int(only_stereo), int(coarse), int(self.check_ori)))
+        return [(int(arr[i].n_matches), keep[i]["match"][:arr[i].kf1.contents.n]) for i in range(len(sets))]
+
+    def rig_bow_last_kernel_ms(self):
+        _rig_bow_argtypes()
+        return float(lib.orbm_rig_bow_last_kernel_ms(self._h))
+
+
 class OrbmRigFrame(C.Structure):
     """OrbmRigFrame of include/orbslam3_hip_rig_match.h"""
     _fields_ = [("left", Frame), ("right", Frame), ("left_to_right", C.c_void_p), ("right_to_left", C.c_void_p)]
@@ -740,6 +787,108 @@ def rig_search_check(rig, mp=None, last=None, assign=None, occupied=None):
     a = None if mp is None else C.byref(rig_map_points(mp))
     b = None if last is None else C.byref(rig_last_points(last))
     return int(lib.orbm_rig_search_check(r, a, b, _p(assign), _p(occupied)))
+
+
+class OrbmBowRigPair(C.Structure):
+    """OrbmBowRigPair of include/orbslam3_hip_rig_bow.h"""
+    _fields_ = [("desc_kf", C.c_void_p), ("n_kf", C.c_int32), ("valid_kf", C.c_void_p), ("angle_kf", C.c_void_p), ("fv_kf", FeatVec),
+                ("desc_f", C.c_void_p), ("n_f", C.c_int32), ("n_left_f", C.c_int32), ("angle_f", C.c_void_p), ("fv_f", FeatVec),
+                ("match_f2kf", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+class OrbmRigTriGeometry(C.Structure):
+    _fields_ = [("cam", (C.c_float * 9) * 4), ("R12", (C.c_float * 9) * 4), ("t12", (C.c_float * 3) * 4)]
+
+
+class OrbmRigTriPair(C.Structure):
+    _fields_ = [("kf1", C.POINTER(Matcher._TriSide)), ("n_left_1", C.c_int32), ("kf2", C.POINTER(Matcher._TriSide)), ("n_left_2", C.c_int32),
+                ("geom", C.POINTER(OrbmRigTriGeometry)), ("level_sigma2_1", C.c_void_p), ("level_sigma2_2", C.c_void_p), ("n_levels", C.c_int32),
+                ("match12", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+def _rig_bow_argtypes():
+    lib.orbm_rig_bow_check.argtypes = [C.POINTER(OrbmBowRigPair), C.POINTER(OrbmRigTriPair), C.c_int]
+    lib.orbm_search_by_bow_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(FeatVec),
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(FeatVec), C.c_float, C.c_int, C.c_void_p]
+    lib.orbm_search_by_bow_rig_batch.argtypes = [C.c_void_p, C.POINTER(OrbmBowRigPair), C.c_int, C.c_float, C.c_int]
+    lib.orbm_search_for_triangulation_rig.argtypes = [C.c_void_p, C.POINTER(Matcher._TriSide), C.c_int, C.POINTER(Matcher._TriSide), C.c_int,
+                                                      C.POINTER(OrbmRigTriGeometry), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.orbm_search_for_triangulation_rig_batch.argtypes = [C.c_void_p, C.POINTER(OrbmRigTriPair), C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.orbm_rig_bow_last_kernel_ms.restype = C.c_float
+    lib.orbm_rig_bow_last_kernel_ms.argtypes = [C.c_void_p]
+
+
+def _fv_opt(fv):
+    """_fv for a (node ids, offsets, features) triple whose arrays may be None; a 4-tuple gives n_nodes itself"""
+    if fv is None:
+        return FeatVec(0, None, None, None), ()
+    arrs = [None if a is None else np.ascontiguousarray(a) for a in fv[:3]]
+    n = int(fv[3]) if len(fv) > 3 else (0 if arrs[0] is None else len(arrs[0]))
+    return FeatVec(n, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2])), arrs
+
+
+def _len(a):
+    return 0 if a is None else len(a)
+
+
+def bow_rig_pair(s):
+    """dict(dKF, validKF, angKF, fvKF, dF, n_left, angF, fvF [, n_kf, n_f, match]) -> (OrbmBowRigPair, what it points to).  Arrays may be
+    None and the counts may be given, for the argument checks."""
+    dKF = None if s.get("dKF") is None else np.ascontiguousarray(s["dKF"])
+    dF = None if s.get("dF") is None else np.ascontiguousarray(s["dF"])
+    n_kf, n_f = int(s.get("n_kf", _len(dKF))), int(s.get("n_f", _len(dF)))
+    a, ka = _fv_opt(s.get("fvKF"))
+    b, kb = _fv_opt(s.get("fvF"))
+    match = s["match"] if "match" in s else np.full(max(n_f, 1), -1, np.int32)
+    keep = dict(arrays=(dKF, dF, ka, kb, s), match=match)
+    return OrbmBowRigPair(_ptr(dKF), n_kf, _ptr(s.get("validKF")), _ptr(s.get("angKF")), a, _ptr(dF), n_f, int(s.get("n_left", n_f)), _ptr(s.get("angF")), b,
+                          _ptr(match), 0), keep
+
+
+def _rig_tri_side(k):
+    fv, kf = _fv_opt(k.get("fv"))
+    n = int(k["n"]) if "n" in k else next((len(k[q]) for q in ("x", "y", "octave", "desc") if k.get(q) is not None), 0)
+    return Matcher._TriSide(n, _ptr(k.get("desc")), _ptr(k.get("has_mp")), _ptr(k.get("stereo")), _ptr(k.get("x")), _ptr(k.get("y")), _ptr(k.get("octave")),
+                            _ptr(k.get("angle")), fv), kf
+
+
+def rig_tri_geometry(g):
+    geo = OrbmRigTriGeometry()
+    for name, w in (("cam", 9), ("R12", 9), ("t12", 3)):
+        a = np.ascontiguousarray(g[name], np.float32).reshape(4, w)
+        for c in range(4):
+            for i in range(w):
+                getattr(geo, name)[c][i] = float(a[c, i])
+    return geo
+
+
+def rig_tri_pair(s):
+    """dict(kf1, kf2, geom, sigma2_1, sigma2_2 [, n_levels, match]) -> (OrbmRigTriPair, what it points to); kf1 / kf2 / geom / the sigmas
+    may be None, for the argument checks"""
+    sides, keep = [], dict(arrays=[s])
+    for q in ("kf1", "kf2"):
+        if s.get(q) is None:
+            sides.append((None, 0))
+        else:
+            t, kf = _rig_tri_side(s[q])
+            keep["arrays"] += [t, kf]
+            sides.append((C.pointer(t), int(s[q].get("n_left", t.n))))
+    geo = None if s.get("geom") is None else rig_tri_geometry(s["geom"])
+    n1 = sides[0][0].contents.n if sides[0][0] else 0
+    match = s["match"] if "match" in s else np.full(max(n1, 1), -1, np.int32)
+    keep["match"] = match
+    keep["arrays"].append(geo)
+    n_levels = int(s.get("n_levels", _len(s.get("sigma2_1"))))
+    return OrbmRigTriPair(sides[0][0], sides[0][1], sides[1][0], sides[1][1], None if geo is None else C.pointer(geo), _ptr(s.get("sigma2_1")), _ptr(s.get("sigma2_2")),
+                          n_levels, _ptr(match), 0), keep
+
+
+def rig_bow_check(bow=None, tri=None, check_orientation=0):
+    """orbm_rig_bow_check with the arguments as given (dicts or None): the code"""
+    _rig_bow_argtypes()
+    a = None if bow is None else bow_rig_pair(bow)
+    b = None if tri is None else rig_tri_pair(tri)
+    return int(lib.orbm_rig_bow_check(None if a is None else C.byref(a[0]), None if b is None else C.byref(b[0]), int(check_orientation)))
 
 
 ORBM_MAX_NEIGHBOURS = 64

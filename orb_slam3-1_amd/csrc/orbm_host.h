@@ -86,6 +86,7 @@ struct orbm_matcher {
     KernelTimer nmp_timer;              // orbm_create_new_map_points: its one kernel
     KernelTimer sfe_timer;              // orbm_stereo_fisheye: its two kernels
     KernelTimer rig_timer;              // the rig-frame tracking searches: k_grid + k_rig
+    KernelTimer rig_bow_timer;          // the rig SearchByBoW / SearchForTriangulation: k_bow_rig, or k_tri_rig + k_tri_rig_finish
 
     int ensure(size_t bytes)
     {

@@ -1912,6 +1912,7 @@ int run_projection_job(orbm_matcher* m, ProjJob& q, const ProjLaunch& P)
 }  // namespace
 
 #include "orbm_rig_search.inc"      // the same two searches for a two-camera fisheye rig frame (include/orbslam3_hip_rig_match.h)
+#include "orbm_rig_bow.inc"         // SearchByBoW and SearchForTriangulation for rigs (include/orbslam3_hip_rig_bow.h)
 
 extern "C" {
 

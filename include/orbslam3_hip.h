@@ -997,6 +997,7 @@ double essg_last_device_ms(const essg_solver* s, double* stage_ms);
 #include "orbslam3_hip_fisheye.h"
 #include "orbslam3_hip_rig_match.h"
 #include "orbslam3_hip_rig_bow.h"
+#include "orbslam3_hip_rig_newpoints.h"
 
 #ifdef __cplusplus
 }

@@ -949,6 +949,128 @@ def _fill_map_key_frame(s, k, keep, name):
     s.level_sigma2, s.scale_factors, s.n_levels = sig.ctypes.data, sc.ctypes.data, len(sc)
 
 
+class OrbmRigMapKeyFrame(C.Structure):
+    """OrbmRigMapKeyFrame of include/orbslam3_hip_rig_newpoints.h"""
+    _fields_ = [("side", Matcher._TriSide), ("n_left", C.c_int32), ("Rcw", (C.c_float * 9) * 2), ("tcw", (C.c_float * 3) * 2),
+                ("Ow", (C.c_float * 3) * 2), ("cam", (C.c_float * 9) * 2), ("mb", C.c_float),
+                ("level_sigma2", C.c_void_p), ("scale_factors", C.c_void_p), ("n_levels", C.c_int32)]
+
+
+class OrbmRigMapPair(C.Structure):
+    _fields_ = [("geom", C.POINTER(OrbmRigTriGeometry)), ("coarse", C.c_int32)]
+
+
+def _rig_newpoints_argtypes():
+    lib.orbm_create_new_map_points_rig_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orbm_create_new_map_points_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orbm_create_new_map_points_rig_last_kernel_ms.restype = C.c_float
+    lib.orbm_create_new_map_points_rig_last_kernel_ms.argtypes = [C.c_void_p]
+    lib.orbm_create_new_map_points_rig_last_launches.argtypes = [C.c_void_p]
+
+
+def _fill_rig_map_key_frame(s, k, keep):
+    """one OrbmRigMapKeyFrame from dict(desc, has_mp, x, y, octave, fv, n_left, Rcw [2][9], tcw [2][3], Ow [2][3], cam [2][9], mb,
+    level_sigma2, scale_factors [, n, n_levels]); arrays may be None and the counts may be given, for the argument checks"""
+    typed = dict(desc=np.uint8, has_mp=np.uint8, x=np.float32, y=np.float32, octave=np.int32)
+    a = {f: None if k.get(f) is None else np.ascontiguousarray(k[f], t) for f, t in typed.items()}
+    n = int(k["n"]) if "n" in k else next((len(a[f]) for f in ("x", "y", "octave", "desc") if a[f] is not None), 0)
+    if "n" not in k:
+        for f, v in a.items():
+            if v is not None and len(v) != n:
+                raise ValueError("%s does not hold %d features" % (f, n))
+    sig = None if k.get("level_sigma2") is None else np.ascontiguousarray(k["level_sigma2"], np.float32)
+    sc = None if k.get("scale_factors") is None else np.ascontiguousarray(k["scale_factors"], np.float32)
+    fv, kfv = _fv_opt(k.get("fv"))
+    keep.append((a, sig, sc, kfv))
+    s.side = Matcher._TriSide(n, _ptr(a["desc"]), _ptr(a["has_mp"]), None, _ptr(a["x"]), _ptr(a["y"]), _ptr(a["octave"]), None, fv)
+    s.n_left = int(k.get("n_left", n))
+    for f, w in (("Rcw", 9), ("tcw", 3), ("Ow", 3), ("cam", 9)):
+        v = np.asarray(k[f], np.float32).reshape(2, w)
+        for c in range(2):
+            getattr(s, f)[c][:] = [float(t) for t in v[c]]
+    s.mb = float(k["mb"])
+    s.level_sigma2, s.scale_factors, s.n_levels = _ptr(sig), _ptr(sc), int(k.get("n_levels", _len(sc)))
+
+
+def rig_new_points_args(kf1, neighbours, pairs, params, n_neighbours=None, null=()):
+    """the arguments of orbm_create_new_map_points_rig flattened once (no device needed).  kf1 / neighbours[j]: dicts as
+    _fill_rig_map_key_frame takes (kf1 may be None); pairs[j]: dict(geom, coarse) (geom may be None); params: dict(inertial,
+    far_points, th_far, scale_factor_1).  n_neighbours overrides the count, `null` names output arrays to pass as NULL."""
+    if len(pairs) != len(neighbours):
+        raise ValueError("%d pairs for %d neighbours" % (len(pairs), len(neighbours)))
+    keep = []
+    kfs = (OrbmRigMapKeyFrame * (1 + max(len(neighbours), 1)))()
+    for q, k in enumerate([kf1] + list(neighbours)):
+        if k is not None:
+            _fill_rig_map_key_frame(kfs[q], k, keep)
+    prs = (OrbmRigMapPair * max(len(pairs), 1))()
+    for j, w in enumerate(pairs):
+        if w.get("geom") is not None:
+            g = rig_tri_geometry(w["geom"])
+            keep.append(g)
+            prs[j].geom = C.pointer(g)
+        prs[j].coarse = int(bool(w.get("coarse", False)))
+    par = OrbmMapParams(int(bool(params["inertial"])), int(bool(params["far_points"])), float(params["th_far"]), float(params["scale_factor_1"]))
+    n1 = kfs[0].side.n if kf1 is not None else 0
+    nb = len(neighbours) if n_neighbours is None else int(n_neighbours)
+    m1, mb = max(n1, 1), max(len(neighbours), 1)
+    o = dict(neighbour=np.full(m1, -1, np.int32), idx2=np.full(m1, -1, np.int32), x3d=np.zeros((m1, 3), np.float32),
+             point_stereo=np.zeros(m1, np.uint8), normal=np.zeros((m1, 3), np.float32), max_dist=np.zeros(m1, np.float32),
+             min_dist=np.zeros(m1, np.float32), n_matched=np.zeros(mb, np.int32), n_created=np.zeros(mb, np.int32),
+             match12=np.full((mb, m1), -1, np.int32))
+    out = OrbmNewPoints(*[None if f in null else o[f].ctypes.data for f, _ in OrbmNewPoints._fields_])
+    skipped = np.zeros(mb, np.uint8)
+    return dict(kfs=kfs, pairs=prs, params=par, out=out, arrays=o, skipped=skipped, n1=n1, n_neighbours=nb, keep=keep, has_kf1=kf1 is not None)
+
+
+def create_new_map_points_rig_check(kf1, neighbours, pairs, params, n_neighbours=None, null=(), null_args=()):
+    """orbm_create_new_map_points_rig_check with the arguments as given: the code.  null_args names whole arguments to pass as
+    NULL: "neighbours", "pairs", "params", "out"."""
+    _rig_newpoints_argtypes()
+    p = rig_new_points_args(kf1, neighbours, pairs, params, n_neighbours, null)
+    nbs = None if "neighbours" in null_args else C.byref(p["kfs"], C.sizeof(OrbmRigMapKeyFrame))
+    return int(lib.orbm_create_new_map_points_rig_check(C.byref(p["kfs"]) if p["has_kf1"] else None, nbs, p["n_neighbours"],
+                                                        None if "pairs" in null_args else C.byref(p["pairs"]),
+                                                        None if "params" in null_args else C.byref(p["params"]),
+                                                        None if "out" in null_args else C.byref(p["out"])))
+
+
+def create_new_map_points_rig_launch(handle, prep):
+    """the C call alone on a matcher handle (None: no handle)"""
+    _rig_newpoints_argtypes()
+    nbs = C.byref(prep["kfs"], C.sizeof(OrbmRigMapKeyFrame))
+    return _check(lib.orbm_create_new_map_points_rig(handle, C.byref(prep["kfs"]), nbs, prep["n_neighbours"], C.byref(prep["pairs"]),
+                                                     C.byref(prep["params"]), C.byref(prep["out"]), prep["skipped"].ctypes.data))
+
+
+def rig_new_points_result(prep, created):
+    a, n1, nb = prep["arrays"], prep["n1"], prep["n_neighbours"]
+    r = {k: (a[k][:nb] if k in ("n_matched", "n_created") else a[k][:nb, :n1] if k == "match12" else a[k][:n1]).copy() for k in a}
+    r["created"] = created
+    r["skipped"] = prep["skipped"][:nb].copy()
+    return r
+
+
+def _matcher_create_new_map_points_rig(self, kf1, neighbours, pairs, params):
+    """LocalMapping::CreateNewMapPoints for rig key frames: dict(created, neighbour, idx2, x3d, point_stereo, normal, max_dist,
+    min_dist [n1], n_matched, n_created, skipped [n_neighbours], match12 [n_neighbours][n1]); (neighbour, idx1) ascending over
+    neighbour >= 0 is the reference's creation order"""
+    prep = rig_new_points_args(kf1, neighbours, pairs, params)
+    return rig_new_points_result(prep, create_new_map_points_rig_launch(self._h, prep))
+
+
+def _matcher_rig_new_points_last(self):
+    """(device milliseconds, launches) of the last create_new_map_points_rig on this handle"""
+    _rig_newpoints_argtypes()
+    return float(lib.orbm_create_new_map_points_rig_last_kernel_ms(self._h)), int(lib.orbm_create_new_map_points_rig_last_launches(self._h))
+
+
+Matcher.create_new_map_points_rig_prepare = staticmethod(rig_new_points_args)
+Matcher.create_new_map_points_rig_launch = lambda self, prep: create_new_map_points_rig_launch(self._h, prep)
+Matcher.create_new_map_points_rig = _matcher_create_new_map_points_rig
+Matcher.create_new_map_points_rig_last = _matcher_rig_new_points_last
+
+
 class _BowSideDevice(C.Structure):
     _fields_ = [("desc", C.c_void_p), ("kps", C.c_void_p), ("n", C.c_void_p), ("cap", C.c_int32), ("valid", C.c_void_p),
                 ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p), ("n_fv_nodes", C.c_void_p)]

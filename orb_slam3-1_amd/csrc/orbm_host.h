@@ -87,6 +87,9 @@ struct orbm_matcher {
     KernelTimer sfe_timer;              // orbm_stereo_fisheye: its two kernels
     KernelTimer rig_timer;              // the rig-frame tracking searches: k_grid + k_rig
     KernelTimer rig_bow_timer;          // the rig SearchByBoW / SearchForTriangulation: k_bow_rig, or k_tri_rig + k_tri_rig_finish
+    KernelTimer rig_nmp_timer;          // orbm_create_new_map_points_rig: k_new_map_points_rig, once per segment
+    float rig_nmp_ms = 0.f;             // ... summed over the segments of the last call
+    int rig_nmp_launches = 0;
 
     int ensure(size_t bytes)
     {

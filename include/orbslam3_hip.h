@@ -155,6 +155,24 @@ int orbx_debug_resize_rows(int src_h, int dst_h, uint32_t* rows, int* band_rows)
  * host memory); out[i] = M of patch i's centre = max(0, max over the 16 arcs of nine of min(d), of min(-d)), d = centre - ring
  * pixel: OpenCV's corner score + 1.  `pitch` (8..1024) is the row pitch at which the kernel lays the patches out in LDS. */
 int orbx_debug_fast_scores(const uint8_t* patches, int n, int pitch, int* out);
+/* Test hook: the orientation + descriptor kernel alone, through the launch the pipeline itself uses, on hand-built stage outputs for
+ * `batch` (1..64) frames of a width x height image (the handle's geometry is set for that size).
+ *   raw, blurred   per frame the unblurred and the blurred level images, level after level, each w_l x h_l tightly packed
+ *                  (orbx_pyramid_level_size); the two are independent of each other.  Row padding, the gaps between levels and the
+ *                  tail of the device buffers are filled with pad_byte (0..255).
+ *   counts         [batch][nlevels] keys per frame and level, at most the level's selection slots (returned in sel_caps[nlevels])
+ *   keys           (x, y, response, row) per key, frames in order, levels in order: level coordinates, response 0..255, `row` the
+ *                  key's output row (any value; rows outside [0, cap) are not written, as in the pipeline)
+ *   kps, desc      in / out, guard_rows + batch * cap + guard_rows rows: uploaded as they are, written by the kernel at row
+ *                  guard_rows + frame * cap + row, read back whole -- what the kernel did not write keeps the caller's bytes
+ *   lvl_kps        out, [batch][nlevels][lvl_cap]: every selection slot of every level (slots at and beyond a level's count hold
+ *                  0xFF bytes unless the kernel wrote them)
+ * Keys outside [19, w_l - 20] x [19, h_l - 20] (where FAST cannot report a corner and the kernel's loads could leave the level),
+ * counts above the slots and responses outside a byte are ORBX_ERR_ARG before anything is launched.  Afterwards the handle holds
+ * these levels as its LAST call's pyramid (orbx_pyramid_level, orbx_debug_blurred_level). */
+int orbx_debug_orient_desc(orbx_extractor* h, int width, int height, int batch, const uint8_t* raw, const uint8_t* blurred, int pad_byte,
+                           const int32_t* counts, const int32_t* keys, int cap, int guard_rows,
+                           OrbxKeyPoint* kps, uint8_t* desc, OrbxKeyPoint* lvl_kps, int lvl_cap, int32_t* sel_caps);
 
 /* ------------------------------------------------------------------------------------------------
  * Matcher -- replaces ORB_SLAM3::ORBmatcher (include/ORBmatcher.h:40-106)

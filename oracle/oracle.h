@@ -63,6 +63,10 @@ void  orb_oracle_gauss_taps(int ksize, double sigma, int* taps_q8);
 float orb_oracle_fast_atan2(float y, float x);
 void  orb_oracle_sincos(float angle_rad, float* c, float* s);
 int   orb_oracle_cvround(double v);
+/* IC_Angle (:76-103) of the key point (x, y) of an unblurred image and computeOrbDescriptor (:107-146) on a blurred one: what the
+ * extractor computes per key point, on the caller's images (the 31 x 31 patch / the rotated pattern must lie inside them) */
+float orb_oracle_ic_angle(const uint8_t* img, int stride, float x, float y);
+void  orb_oracle_descriptor(const uint8_t* blur, int stride, float x, float y, float angle, uint8_t* out32);
 /* std::sort with the reference's compareNodes ordering on (count, ULx) pairs; used to pin the device introsort */
 void  orb_oracle_sort_nodes(int* count, int* ulx, int* tag, int n);
 

@@ -782,6 +782,19 @@ void orb_oracle_gauss_taps(int ksize, double sigma, int* taps_q8) { gauss_taps_q
 float orb_oracle_fast_atan2(float y, float x) { return fast_atan2(y, x); }
 void orb_oracle_sincos(float angle_rad, float* c, float* s) { sincos_f(angle_rad, c, s); }
 int orb_oracle_cvround(double v) { return cv_round(v); }
+// IC_Angle and computeOrbDescriptor as the extractor applies them, on a caller's image (umax does not depend on the parameters)
+float orb_oracle_ic_angle(const uint8_t* img, int stride, float x, float y)
+{
+    static const Extractor e(100, 1.2f, 1, 20, 7);
+    return e.ic_angle(img, stride, x, y);
+}
+void orb_oracle_descriptor(const uint8_t* blur, int stride, float x, float y, float angle, uint8_t* out32)
+{
+    static const Extractor e(100, 1.2f, 1, 20, 7);
+    KP k = KP();
+    k.x = x; k.y = y; k.angle = angle;
+    e.descriptor(k, blur, stride, out32);
+}
 
 void orb_oracle_sort_nodes(int* count, int* ulx, int* tag, int n)
 {

@@ -91,6 +91,8 @@ lib.orbx_debug_resize_rows.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C
 lib.orbx_debug_introsort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.orbx_debug_wave_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.orbx_debug_fast_scores.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+lib.orbx_debug_orient_desc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
 lib.orbx_debug_fast_atan2.restype = C.c_float
 lib.orbx_debug_fast_atan2.argtypes = [C.c_float, C.c_float]
 lib.orbx_debug_sincos.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -290,6 +292,33 @@ class Extractor:
         n = C.c_int()
         _check(lib.orbx_debug_level_keypoints(self._h, frame, level, _p(out), cap, C.byref(n)))
         return out[:min(n.value, cap)].copy()
+
+    def debug_orient_desc(self, width, height, raw, blurred, keys, cap, guard_rows=0, canary=0xC3, pad_byte=0xA5):
+        """orbx_debug_orient_desc: the orientation + descriptor kernel alone, through the pipeline's own launch.
+        raw, blurred: [frame][level] uint8 images of the level sizes of a width x height image; keys: [frame][level] integer arrays
+        [n, 4] of (x, y, response, row).  Returns (kps, desc, lvl) with kps / desc the whole output buffers, guard_rows + B * cap +
+        guard_rows rows that held `canary` bytes before the launch, and lvl[frame][level] every selection slot of the level (0xFF
+        bytes where the kernel wrote nothing)."""
+        B, nl = len(raw), self.nlevels
+        assert len(blurred) == B and len(keys) == B and all(len(a) == nl for a in list(raw) + list(blurred) + list(keys))
+        inv = self.GetInverseScaleFactors()         # the level sizes of ComputePyramid: what the library will read of each image
+        for l in range(nl):
+            shape = (int(np.rint(np.float32(height) * inv[l])), int(np.rint(np.float32(width) * inv[l])))
+            assert all(tuple(raw[b][l].shape) == shape == tuple(blurred[b][l].shape) for b in range(B)), (l, shape)
+        pack = lambda fr: np.concatenate([np.ascontiguousarray(im, np.uint8).ravel() for f in fr for im in f])
+        raw_b, blur_b = pack(raw), pack(blurred)
+        ks = [np.asarray(k, np.int32).reshape(-1, 4) for f in keys for k in f]
+        counts = np.array([len(k) for k in ks], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(ks)) if ks else np.zeros((0, 4), np.int32)
+        rows = 2 * guard_rows + B * cap
+        kps = np.full(rows * KP_DTYPE.itemsize, canary, np.uint8).view(KP_DTYPE)
+        desc = np.full((rows, 32), canary, np.uint8)
+        lvl_cap = max(64, self.max_keypoints)
+        lvl = np.zeros((B, nl, lvl_cap), KP_DTYPE)
+        caps = np.zeros(nl, np.int32)
+        _check(lib.orbx_debug_orient_desc(self._h, int(width), int(height), B, _p(raw_b), _p(blur_b), int(pad_byte), _p(counts), _p(flat),
+                                          int(cap), int(guard_rows), _p(kps), _p(desc), _p(lvl), lvl_cap, _p(caps)))
+        return kps, desc, [[lvl[b, l, :caps[l]].copy() for l in range(nl)] for b in range(B)]
 
 
 def hamming(a, b):

@@ -237,6 +237,7 @@ struct orbx_extractor {
     int enqueue(const uint8_t* d_imgs, bool level0_ready, int batch, int row_stride, size_t frame_stride,
                 int lap0, int lap1, OrbxKeyPoint* o_kps, uint8_t* o_desc, int cap, int* o_n, int* o_mono, int* o_status,
                 hipStream_t st);
+    int launch_orient_desc(int f0, int n_frames, hipStream_t s, OrbxKeyPoint* o_kps, uint8_t* o_desc, int cap);
 };
 
 // E0: constructor tables (reference src/ORBextractor.cc:409-445)
@@ -654,6 +655,22 @@ __global__ __launch_bounds__(256) void k_copy_level0(const uint8_t* __restrict__
 }
 }  // namespace orbx
 
+// The one launch of k_orient_desc, for frames [f0, f0 + n_frames) of the batch scratch: the pipeline (enqueue) and the test entry
+// orbx_debug_orient_desc both come through here, so the grid expression and the argument list cannot drift apart.  o_kps / o_desc
+// are the [batch][cap] outputs of the whole batch.
+int orbx_extractor::launch_orient_desc(int f0, int n_frames, hipStream_t s, OrbxKeyPoint* o_kps, uint8_t* o_desc, int cap)
+{
+    const int quads = (sel_frame_entries + 7) / 8;       // workgroups per frame: 8 key points each (two per wave)
+    hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)(((long long)quads * n_frames + 7) / 8 * 8)), dim3(256), 0, s,
+                       d_pyr.p + (size_t)f0 * pyr_frame_bytes, d_blur.p + (size_t)f0 * pyr_frame_bytes, pyr_frame_bytes,
+                       d_levels.p, nlevels, d_sel.p + (size_t)f0 * sel_frame_entries, sel_frame_entries, d_sel_count.p + (size_t)f0 * nlevels,
+                       d_kp_dst.p + (size_t)f0 * sel_frame_entries, sel_frame_entries,
+                       o_kps + (size_t)f0 * cap, o_desc + (size_t)f0 * cap * 32, cap, d_lvl_kps.p + (size_t)f0 * sel_frame_entries, quads, n_frames);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(ORBX_ERR_HIP, "launch of k_orient_desc: %s", hipGetErrorString(le));
+    return ORBX_OK;
+}
+
 int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch, int row_stride, size_t frame_stride,
                             int lap0, int lap1, OrbxKeyPoint* o_kps, uint8_t* o_desc, int cap, int* o_n, int* o_mono, int* o_status,
                             hipStream_t st)
@@ -671,7 +688,6 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
     // (... and when a tile's rows are within 32-bit offsets of its first one, as k_fast_strips addresses them)
     const bool in_place = !level0_ready && ((uintptr_t)d_imgs % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) && row_stride < (1 << 23);
     const int n_cells = (int)cells.size();
-    const int quads = (sel_frame_entries + 7) / 8;       // workgroups of k_orient_desc per frame: 8 key points each (two per wave)
 
     // One range of frames [f0, f0 + nB) through the whole pipeline on stream `s`; the blur either on `blur_s` beside the octree
     // (a single range: the octree is one wave per frame and level and leaves most of the chip idle) or on `s` itself.
@@ -862,10 +878,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
         if (blur_s) { ORBX_HIP(hipEventRecord(ev_join, blur_s)); ORBX_HIP(hipStreamWaitEvent(s, ev_join, 0)); }
         else launch_blur(s);
         if (marks) mark();
-        hipLaunchKernelGGL(k_orient_desc, dim3((unsigned)(((long long)quads * nB + 7) / 8 * 8)), dim3(256), 0, s, pyr, blr, pyr_frame_bytes,
-                           d_levels.p, nlevels, sel, sel_frame_entries, sel_cnt, kp_dst, sel_frame_entries,
-                           o_kps + (size_t)f0 * cap, o_desc + (size_t)f0 * cap * 32, cap, d_lvl_kps.p + (size_t)f0 * sel_frame_entries, quads, nB);
-        ORBX_LAUNCHED("k_orient_desc");
+        if (const int lr = launch_orient_desc(f0, nB, s, o_kps, o_desc, cap)) return lr;
         if (marks) mark();
         return ORBX_OK;
     };
@@ -1323,6 +1336,88 @@ int orbx_debug_fast_scores(const uint8_t* patches, int n, int pitch, int* out)
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     if (r) return fail(r, "device score tree failed");
+    return ORBX_OK;
+}
+
+// k_orient_desc alone, through the pipeline's own launch (launch_orient_desc), on hand-built stage outputs: level images, blurred
+// levels, selection records, counts and output rows are written where the pipeline stages would have left them.  See the header.
+int orbx_debug_orient_desc(orbx_extractor* e, int width, int height, int batch, const uint8_t* raw, const uint8_t* blurred, int pad_byte,
+                           const int32_t* counts, const int32_t* keys, int cap, int guard_rows,
+                           OrbxKeyPoint* kps, uint8_t* desc, OrbxKeyPoint* lvl_kps, int lvl_cap, int32_t* sel_caps)
+{
+    if (!e || !raw || !blurred || !counts || !kps || !desc || !lvl_kps) return fail(ORBX_ERR_ARG, "NULL argument");
+    if (width < 1 || height < 1 || batch < 1 || batch > 64 || cap < 1 || cap > (1 << 20) || guard_rows < 0 || guard_rows > (1 << 20) || pad_byte < 0 || pad_byte > 255)
+        return fail(ORBX_ERR_ARG, "bad batch/geometry/capacity");
+    ORBX_HIP(hipSetDevice(e->device));
+    int r;
+    if ((r = e->setup_geometry(width, height)) || (r = e->ensure_batch(batch))) return r;
+    const int nl = e->nlevels, B = batch, S = e->sel_frame_entries;
+    // every key inside the area FAST can report (EDGE_THRESHOLD = 19: the kernel's loads then stay inside the level), every count
+    // within the level's slots -- checked before anything is uploaded
+    size_t n_keys = 0, level_bytes = 0;
+    for (int l = 0; l < nl; l++) level_bytes += (size_t)e->levels[l].w * e->levels[l].h;
+    for (int b = 0; b < B; b++)
+        for (int l = 0; l < nl; l++) {
+            const LevelDesc& L = e->levels[l];
+            const int c = counts[(size_t)b * nl + l];
+            if (c < 0 || c > L.sel_cap || c > lvl_cap) return fail(ORBX_ERR_ARG, "frame %d level %d: %d keys, the level has %d slots (lvl_cap %d)", b, l, c, L.sel_cap, lvl_cap);
+            if (c > 0 && !keys) return fail(ORBX_ERR_ARG, "keys is NULL");
+            for (int k = 0; k < c; k++, n_keys++) {
+                const int32_t* q = keys + 4 * n_keys;
+                if (q[0] < kEdge || q[0] > L.w - kEdge - 1 || q[1] < kEdge || q[1] > L.h - kEdge - 1 || q[2] < 0 || q[2] > 255)
+                    return fail(ORBX_ERR_ARG, "frame %d level %d key %d: (%d, %d, %d) outside [%d, %d] x [%d, %d] x [0, 255]", b, l, k, q[0], q[1], q[2],
+                                kEdge, L.w - kEdge - 1, kEdge, L.h - kEdge - 1);
+            }
+        }
+    for (int l = 0; l < nl; l++) {
+        if (e->levels[l].sel_cap > lvl_cap) return fail(ORBX_ERR_ARG, "lvl_cap %d below the %d slots of level %d", lvl_cap, e->levels[l].sel_cap, l);
+        if (sel_caps) sel_caps[l] = e->levels[l].sel_cap;
+    }
+    // slots beyond a level's count hold a key the kernel could read safely: a lane that took one for live would show in lvl_kps
+    // (cleared to 0xFF below, written by every live lane whatever its row), not as a fault
+    std::vector<uint32_t> sel((size_t)B * S, pack_key((uint32_t)(kEdge - 16), (uint32_t)(kEdge - 16), 0xEEu));
+    std::vector<int> dst((size_t)B * S, -1), cnt((size_t)B * nl);
+    n_keys = 0;
+    for (int b = 0; b < B; b++)
+        for (int l = 0; l < nl; l++) {
+            const LevelDesc& L = e->levels[l];
+            cnt[(size_t)b * nl + l] = counts[(size_t)b * nl + l];
+            for (int k = 0; k < counts[(size_t)b * nl + l]; k++, n_keys++) {
+                const int32_t* q = keys + 4 * n_keys;
+                sel[(size_t)b * S + L.sel_off + k] = pack_key((uint32_t)(q[0] - 16), (uint32_t)(q[1] - 16), (uint32_t)q[2]);
+                dst[(size_t)b * S + L.sel_off + k] = q[3];
+            }
+        }
+    const size_t out_rows = (size_t)B * cap + 2 * (size_t)guard_rows;
+    if ((r = e->d_kps.ensure(out_rows)) || (r = e->d_desc.ensure(out_rows * 32))) return r;
+    hipStream_t st = e->stream;
+    ORBX_HIP(hipMemsetAsync(e->d_pyr.p, pad_byte, (size_t)B * e->pyr_frame_bytes + 64, st));
+    ORBX_HIP(hipMemsetAsync(e->d_blur.p, pad_byte, (size_t)B * e->pyr_frame_bytes + 64, st));
+    e->batch_cap = 0;           // the next extract call clears the padding again (ensure_batch)
+    for (int b = 0; b < B; b++) {
+        size_t o = (size_t)b * level_bytes;
+        for (int l = 0; l < nl; l++) {
+            const LevelDesc& L = e->levels[l];
+            ORBX_HIP(hipMemcpy2DAsync(e->d_pyr.p + (size_t)b * e->pyr_frame_bytes + L.off, L.stride, raw + o, L.w, L.w, L.h, hipMemcpyHostToDevice, st));
+            ORBX_HIP(hipMemcpy2DAsync(e->d_blur.p + (size_t)b * e->pyr_frame_bytes + L.off, L.stride, blurred + o, L.w, L.w, L.h, hipMemcpyHostToDevice, st));
+            o += (size_t)L.w * L.h;
+        }
+    }
+    ORBX_HIP(hipMemcpyAsync(e->d_sel.p, sel.data(), sizeof(uint32_t) * sel.size(), hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync(e->d_kp_dst.p, dst.data(), sizeof(int) * dst.size(), hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync(e->d_sel_count.p, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemsetAsync(e->d_lvl_kps.p, 0xFF, sizeof(OrbxKeyPoint) * (size_t)B * S, st));
+    ORBX_HIP(hipMemcpyAsync(e->d_kps.p, kps, sizeof(OrbxKeyPoint) * out_rows, hipMemcpyHostToDevice, st));
+    ORBX_HIP(hipMemcpyAsync(e->d_desc.p, desc, 32 * out_rows, hipMemcpyHostToDevice, st));
+    if ((r = e->launch_orient_desc(0, B, st, e->d_kps.p + guard_rows, e->d_desc.p + (size_t)guard_rows * 32, cap))) return r;
+    e->last_batch = B;
+    ORBX_HIP(hipMemcpyAsync(kps, e->d_kps.p, sizeof(OrbxKeyPoint) * out_rows, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipMemcpyAsync(desc, e->d_desc.p, 32 * out_rows, hipMemcpyDeviceToHost, st));
+    for (int b = 0; b < B; b++)
+        for (int l = 0; l < nl; l++)
+            ORBX_HIP(hipMemcpyAsync(lvl_kps + ((size_t)b * nl + l) * lvl_cap, e->d_lvl_kps.p + (size_t)b * S + e->levels[l].sel_off,
+                                    sizeof(OrbxKeyPoint) * e->levels[l].sel_cap, hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipStreamSynchronize(st));
     return ORBX_OK;
 }
 

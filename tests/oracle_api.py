@@ -77,6 +77,10 @@ class Oracle:
         L.orb_oracle_fast_atan2.argtypes = [C.c_float, C.c_float]
         L.orb_oracle_sincos.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.orb_oracle_cvround.argtypes = [C.c_double]
+        L.orb_oracle_ic_angle.restype = C.c_float
+        L.orb_oracle_ic_angle.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        L.orb_oracle_descriptor.restype = None
+        L.orb_oracle_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]
         L.orb_oracle_sort_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.orbm_oracle_hamming.argtypes = [C.c_void_p, C.c_void_p]
         L.orbm_oracle_three_maxima.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 3
@@ -99,6 +103,18 @@ class Oracle:
     # ---- extractor
     def extractor(self, nfeatures=1000, scale=1.2, nlevels=8, ini=20, mn=7):
         return OracleExtractor(self, nfeatures, scale, nlevels, ini, mn)
+
+    def ic_angle(self, img, x, y):
+        """IC_Angle of key point (x, y) of an unblurred uint8 image, as a float32"""
+        assert img.dtype == np.uint8 and img.strides[1] == 1
+        return np.float32(self.lib.orb_oracle_ic_angle(_p(img), img.strides[0], float(x), float(y)))
+
+    def descriptor(self, blur, x, y, angle):
+        """computeOrbDescriptor at key point (x, y, angle) of a blurred uint8 image: 32 bytes"""
+        assert blur.dtype == np.uint8 and blur.strides[1] == 1
+        out = np.zeros(32, np.uint8)
+        self.lib.orb_oracle_descriptor(_p(blur), blur.strides[0], float(x), float(y), C.c_float(float(angle)), _p(out))
+        return out
 
     # ---- matcher
     def hamming(self, a, b):

@@ -14,15 +14,10 @@ goes through restatements written from the DEFINITIONS, sharing no code and no e
   * computeOrbDescriptor (:107-146): 256 comparisons of the blurred level at cvRound-ed rotated pattern points, float32
     products and sums without FMA, (float)cos / sin of the float angle.
 """
-import math
-import os
-import re
-
 import numpy as np
 import pytest
 
 RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-UMAX = [15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3]          # SURVEY.md 8 table (src/ORBextractor.cc:452-468)
 
 
 def fast_definitional(img, t, want_map=False):
@@ -84,68 +79,9 @@ def test_fast_on_a_sub_image_with_stride(oracle, synth):
     assert got == fast_definitional(img[y0:y0 + ch, x0:x0 + cw], 7) and len(got) > 3
 
 
-# ---- float32 restatements (numpy float32 scalars: every operation rounds to float32, nothing is contracted) ----
-F = np.float32
-
-
-def fast_atan2_f32(y, x):
-    """cv::fastAtan2 (SURVEY.md appendix A.4), degrees"""
-    s = F(57.29577951308232)            # (float)(180 / pi)
-    p1, p3, p5, p7 = F(0.9997878412794807) * s, F(-0.3258083974640975) * s, F(0.1555786518463281) * s, F(-0.04432655554792128) * s
-    eps = F(2.220446049250313e-16)      # (float)DBL_EPSILON
-    ax, ay = F(abs(x)), F(abs(y))
-    if ax >= ay:
-        c = ay / (ax + eps)
-        c2 = c * c
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c
-    else:
-        c = ax / (ay + eps)
-        c2 = c * c
-        a = F(90.0) - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c
-    if x < 0:
-        a = F(180.0) - a
-    if y < 0:
-        a = F(360.0) - a
-    return F(a)
-
-
-def cv_round(v):
-    """cvRound: round half to even"""
-    return int(np.rint(np.float64(v)))
-
-
-def ic_angle_definitional(img, x, y):
-    cx, cy = cv_round(x), cv_round(y)
-    m01 = m10 = 0
-    for v in range(-15, 16):
-        d = UMAX[abs(v)]
-        rowv = img[cy + v, cx - d:cx + d + 1].astype(np.int64)
-        m10 += int((np.arange(-d, d + 1) * rowv).sum())
-        m01 += v * int(rowv.sum())
-    return fast_atan2_f32(F(m01), F(m10))
-
-
-def load_pattern():
-    txt = open(os.path.join(os.path.dirname(__file__), "..", "oracle", "orb_pattern_31.inc")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    vals = [int(t) for t in re.findall(r"-?\d+", txt)]
-    assert len(vals) == 1024
-    return np.array(vals, np.int32).reshape(256, 4)
-
-
-def descriptor_definitional(blur, x, y, angle_deg, pattern):
-    factor_pi = F(math.pi / F(180.0))               # (float)(CV_PI / 180.f)
-    ang = F(angle_deg) * factor_pi
-    a, b = F(math.cos(float(ang))), F(math.sin(float(ang)))
-    cx, cy = cv_round(x), cv_round(y)
-
-    def value(px, py):
-        px, py = F(px), F(py)
-        return int(blur[cy + cv_round(px * b + py * a), cx + cv_round(px * a - py * b)])
-    bits = np.zeros(256, np.uint8)
-    for i, (x0, y0, x1, y1) in enumerate(pattern):
-        bits[i] = value(x0, y0) < value(x1, y1)
-    return np.packbits(bits, bitorder="little")
+# ---- float32 restatements (numpy float32 scalars: every operation rounds to float32, nothing is contracted): shared with the
+# tests of the device kernel, tests/orient_desc_reference.py ----
+from orient_desc_reference import F, cv_round, descriptor_definitional, fast_atan2_f32, ic_angle_definitional, load_pattern  # noqa: E402,F401
 
 
 def test_fast_atan2_restatement_matches_the_oracle(oracle):

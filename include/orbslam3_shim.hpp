@@ -305,17 +305,10 @@ public:
     int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono)
     {
         if (CurrentFrame.Nleft != -1 || LastFrame.Nleft != -1) return ORBmatcher(mfNNratio, mbCheckOrientation).SearchByProjection(CurrentFrame, LastFrame, th, bMono);
-        const int nL = LastFrame.N, nF = CurrentFrame.N;
+        const int nL = LastFrame.N;
         const Sophus::SE3f Tcw = CurrentFrame.GetPose();
-        const Eigen::Vector3f twc = Tcw.inverse().translation();                   // :1686-1693
-        const Sophus::SE3f Tlw = LastFrame.GetPose();
-        const Eigen::Vector3f tlc = Tlw * twc;
-        const bool bForward = tlc(2) > CurrentFrame.mb && !bMono;
-        const bool bBackward = -tlc(2) > CurrentFrame.mb && !bMono;
-        const int levelWindow = bForward ? ORBM_LEVELS_FORWARD : bBackward ? ORBM_LEVELS_BACKWARD : ORBM_LEVELS_AROUND;
-        std::vector<uint8_t> valid(nL, 0), hasObs(nL, 0), desc((size_t)nL * 32, 0), occ(nF);
-        std::vector<float> u(nL, 0.f), v(nL, 0.f), ur(nL, 0.f), ang(nL, 0.f);
-        std::vector<int32_t> oct(nL, 0), assign(nF, -2);      // -2 = untouched, -1 = nulled by the rotation check (:1878)
+        std::vector<uint8_t> valid(nL, 0);
+        std::vector<float> u(nL, 0.f), v(nL, 0.f), ur(nL, 0.f);
         for (int i = 0; i < nL; i++) {
             MapPoint* p = LastFrame.mvpMapPoints[i];
             if (!p || LastFrame.mvbOutlier[i]) continue;
@@ -324,12 +317,35 @@ public:
             if (invzc < 0) continue;
             const Eigen::Vector2f uv = CurrentFrame.mpCamera->project(x3Dc);
             valid[i] = 1; u[i] = uv(0); v[i] = uv(1); ur[i] = uv(0) - CurrentFrame.mbf * invzc;      // :1753
+        }
+        return SearchByProjectionProjected(CurrentFrame, LastFrame, th, bMono, valid.data(), u.data(), v.data(), ur.data());
+    }
+
+    // The same search with the projections of LastFrame's map points supplied (LastFrame.N entries; valid[i] = 0 where :1697-1711 skip
+    // entry i): what orbm_project_last_batch returns (orbslam3_shim_track_project.hpp).  Conventional frames only.
+    int SearchByProjectionProjected(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono,
+                                    const uint8_t* valid, const float* u, const float* v, const float* ur)
+    {
+        const int nL = LastFrame.N, nF = CurrentFrame.N;
+        const Sophus::SE3f Tcw = CurrentFrame.GetPose();
+        const Eigen::Vector3f twc = Tcw.inverse().translation();                   // :1686-1693
+        const Sophus::SE3f Tlw = LastFrame.GetPose();
+        const Eigen::Vector3f tlc = Tlw * twc;
+        const bool bForward = tlc(2) > CurrentFrame.mb && !bMono;
+        const bool bBackward = -tlc(2) > CurrentFrame.mb && !bMono;
+        const int levelWindow = bForward ? ORBM_LEVELS_FORWARD : bBackward ? ORBM_LEVELS_BACKWARD : ORBM_LEVELS_AROUND;
+        std::vector<uint8_t> hasObs(nL, 0), desc((size_t)nL * 32, 0), occ(nF);
+        std::vector<float> ang(nL, 0.f);
+        std::vector<int32_t> oct(nL, 0), assign(nF, -2);      // -2 = untouched, -1 = nulled by the rotation check (:1878)
+        for (int i = 0; i < nL; i++) {
+            if (!valid[i]) continue;
+            MapPoint* p = LastFrame.mvpMapPoints[i];
             oct[i] = LastFrame.mvKeys[i].octave; ang[i] = LastFrame.mvKeysUn[i].angle; hasObs[i] = p->Observations() > 0;
             const cv::Mat d = p->GetDescriptor();
             std::memcpy(&desc[(size_t)i * 32], d.data, 32);
         }
         OrbmFrame f = frameView(CurrentFrame, occ);
-        const int n = orbslam3_hip::check(orbm_search_by_projection_last(m_, &f, nL, valid.data(), u.data(), v.data(), ur.data(), oct.data(), ang.data(),
+        const int n = orbslam3_hip::check(orbm_search_by_projection_last(m_, &f, nL, valid, u, v, ur, oct.data(), ang.data(),
                                                                           desc.data(), hasObs.data(), th, levelWindow, mbCheckOrientation,
                                                                           assign.data(), occ.data()));
         for (int i = 0; i < nF; i++) {

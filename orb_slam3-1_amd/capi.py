@@ -334,6 +334,42 @@ def _fv(fv):
     return s
 
 
+class FramePose(C.Structure):
+    """OrbmFramePose (include/orbslam3_hip_track_project.h): 19 floats"""
+    _fields_ = [("q", C.c_float * 4), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)]
+
+
+class TrackCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
+class LocalPoints(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("normal", C.c_void_p), ("min_distance", C.c_void_p), ("max_distance", C.c_void_p),
+                ("skip", C.c_void_p), ("bad", C.c_void_p), ("n", C.c_void_p), ("pcap", C.c_int32)]
+
+
+class FrustumOut(C.Structure):
+    _fields_ = [("valid", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("octave", C.c_void_p), ("view_cos", C.c_void_p),
+                ("track_depth", C.c_void_p), ("proj_ur", C.c_void_p), ("n_to_match", C.c_void_p)]
+
+
+class LastProjOut(C.Structure):
+    _fields_ = [("valid", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("proj_ur", C.c_void_p)]
+
+
+TRACK_MAX_BATCH, TRACK_MAX_LEVELS = 65535, 16
+
+
+def track_project_check(cam, poses, pts, out, batch):
+    """orbm_track_project_check (host only): cam / pts / out are TrackCamera / LocalPoints / FrustumOut or None, poses an address or
+    None.  Returns the code (ORBX_OK, ORBX_ERR_ARG = -3, ORBX_ERR_CAPACITY = -2)."""
+    lib.orbm_track_project_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    ref = lambda s: C.cast(C.pointer(s), C.c_void_p) if s is not None else None
+    return lib.orbm_track_project_check(ref(cam), C.c_void_p(poses) if poses else None, ref(pts), ref(out), int(batch))
+
+
 class Matcher:
     """ORB_SLAM3::ORBmatcher (reference include/ORBmatcher.h:40-106): ORBmatcher(nnratio=0.6, checkOri=true)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
@@ -540,6 +576,70 @@ class Matcher:
         lib.orbm_search_by_projection_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _check(lib.orbm_search_by_projection_batch_device(self._h, C.byref(cf), C.byref(lp), C.byref(ex), int(batch), C.c_float(th),
                                                           C.c_void_p(d_assign), C.c_void_p(d_occupied), C.c_void_p(d_n_matches), C.c_void_p(stream or 0)))
+
+    # ---- include/orbslam3_hip_track_project.h: the projections in front of the two searches above ----
+    @staticmethod
+    def _track_camera(cam):
+        return TrackCamera(*[float(cam[k]) for k in ("fx", "fy", "cx", "cy", "bf", "min_x", "min_y", "max_x", "max_y", "log_scale_factor")], int(cam["n_levels"]))
+
+    def frame_pose_batch_device(self, d_pose, batch, normalise, d_frame_pose, stream=None):
+        """orbm_frame_pose_batch_device: d_pose [batch][7] double -> d_frame_pose [batch] FramePose records.  Only enqueues."""
+        lib.orbm_frame_pose_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _check(lib.orbm_frame_pose_batch_device(self._h, C.c_void_p(d_pose), int(batch), int(normalise), C.c_void_p(d_frame_pose), C.c_void_p(stream or 0)))
+
+    def frustum_batch_device(self, cam, d_frame_pose, pts, cos_limit, out, batch, stream=None):
+        """orbm_frustum_batch_device: cam a dict as synth_track.camera(); pts = (d_xyz, d_normal, d_min_distance, d_max_distance, d_skip,
+        d_bad, d_n, pcap); out = (d_valid, d_u, d_v, d_octave, d_view_cos, d_track_depth, d_proj_ur, d_n_to_match).  Only enqueues."""
+        lib.orbm_frustum_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        c, p, o = self._track_camera(cam), LocalPoints(*pts[:7], int(pts[7])), FrustumOut(*out)
+        _check(lib.orbm_frustum_batch_device(self._h, C.byref(c), C.c_void_p(d_frame_pose), C.byref(p), C.c_float(cos_limit), C.byref(o), int(batch), C.c_void_p(stream or 0)))
+
+    def project_last_batch_device(self, cam, d_frame_pose, d_mp_xyz, d_has_point, d_n, cap, out, batch, stream=None):
+        """orbm_project_last_batch_device: out = (d_valid, d_u, d_v, d_proj_ur).  Only enqueues."""
+        lib.orbm_project_last_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        c, o = self._track_camera(cam), LastProjOut(*out)
+        _check(lib.orbm_project_last_batch_device(self._h, C.byref(c), C.c_void_p(d_frame_pose), C.c_void_p(d_mp_xyz), C.c_void_p(d_has_point), C.c_void_p(d_n),
+                                                  int(cap), C.byref(o), int(batch), C.c_void_p(stream or 0)))
+
+    def track_handover_batch_device(self, d_assign, d_outlier, d_n_cur, cap, d_last_local, last_cap, d_bad, d_has_obs, pcap,
+                                    d_assign_local, d_occupied, d_skip, d_n_dropped, batch, stream=None):
+        """orbm_track_handover_batch_device.  Only enqueues."""
+        lib.orbm_track_handover_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(lib.orbm_track_handover_batch_device(self._h, C.c_void_p(d_assign), C.c_void_p(d_outlier), C.c_void_p(d_n_cur), int(cap), C.c_void_p(d_last_local),
+                                                    int(last_cap), C.c_void_p(d_bad), C.c_void_p(d_has_obs), int(pcap), C.c_void_p(d_assign_local),
+                                                    C.c_void_p(d_occupied), C.c_void_p(d_skip), C.c_void_p(d_n_dropped), int(batch), C.c_void_p(stream or 0)))
+
+    def frustum_batch(self, case, frame_poses):
+        """orbm_frustum_batch on host arrays: case as synth_track.make_local_map_case, frame_poses [batch][19] float32 FramePose records.
+        Returns dict(valid, u, v, octave, view_cos, track_depth, proj_ur, n_to_match)."""
+        lib.orbm_frustum_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int]
+        B, pcap = case["skip"].shape
+        fp = np.ascontiguousarray(frame_poses, np.float32).reshape(B, 19)
+        keep = [np.ascontiguousarray(case[k], np.float32) for k in ("xyz", "normal", "min_distance", "max_distance")] + \
+               [np.ascontiguousarray(case[k], np.uint8) for k in ("skip", "bad")] + [np.ascontiguousarray(case["n"], np.int32)]
+        res = dict(valid=np.zeros((B, pcap), np.uint8), u=np.zeros((B, pcap), np.float32), v=np.zeros((B, pcap), np.float32), octave=np.zeros((B, pcap), np.int32),
+                   view_cos=np.zeros((B, pcap), np.float32), track_depth=np.zeros((B, pcap), np.float32), proj_ur=np.zeros((B, pcap), np.float32),
+                   n_to_match=np.zeros(B, np.int32))
+        c, p, o = self._track_camera(case["cam"]), LocalPoints(*[a.ctypes.data for a in keep], pcap), FrustumOut(*[a.ctypes.data for a in res.values()])
+        _check(lib.orbm_frustum_batch(self._h, C.byref(c), _p(fp), C.byref(p), C.c_float(case["cos_limit"]), C.byref(o), B))
+        return res
+
+    def project_last_batch(self, case, frame_poses):
+        """orbm_project_last_batch on host arrays: case as synth_track.make_last_frame_case.  Returns dict(valid, u, v, proj_ur)."""
+        lib.orbm_project_last_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        B, cap = case["has_point"].shape
+        fp = np.ascontiguousarray(frame_poses, np.float32).reshape(B, 19)
+        xyz, has, n = np.ascontiguousarray(case["xyz"], np.float32), np.ascontiguousarray(case["has_point"], np.uint8), np.ascontiguousarray(case["n"], np.int32)
+        res = dict(valid=np.zeros((B, cap), np.uint8), u=np.zeros((B, cap), np.float32), v=np.zeros((B, cap), np.float32), proj_ur=np.zeros((B, cap), np.float32))
+        c, o = self._track_camera(case["cam"]), LastProjOut(*[a.ctypes.data for a in res.values()])
+        _check(lib.orbm_project_last_batch(self._h, C.byref(c), _p(fp), _p(xyz), _p(has), _p(n), cap, C.byref(o), B))
+        return res
+
+    def track_project_last_kernel_ms(self):
+        lib.orbm_track_project_last_kernel_ms.restype = C.c_float
+        lib.orbm_track_project_last_kernel_ms.argtypes = [C.c_void_p]
+        return float(lib.orbm_track_project_last_kernel_ms(self._h))
 
     class _TriSide(C.Structure):
         _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("has_mp", C.c_void_p), ("stereo", C.c_void_p), ("x", C.c_void_p),

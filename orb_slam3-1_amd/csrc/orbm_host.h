@@ -90,6 +90,7 @@ struct orbm_matcher {
     KernelTimer rig_nmp_timer;          // orbm_create_new_map_points_rig: k_new_map_points_rig, once per segment
     float rig_nmp_ms = 0.f;             // ... summed over the segments of the last call
     int rig_nmp_launches = 0;
+    KernelTimer tp_timer;               // orbm_frustum_batch / orbm_project_last_batch: their one kernel
 
     int ensure(size_t bytes)
     {

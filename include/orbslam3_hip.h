@@ -131,6 +131,15 @@ int orbx_debug_set_tail_delay(orbx_extractor* h, int microseconds);
  * LDS, 2 keys in the L2-resident scratch, 3 per level and frame: keys in LDS when the level's candidates fit), 4 two octree launches, 8 level-0 octree started early, 16 level 0 read in place,
  * 32 resize tail on the side stream, 64 the whole resize chain on the side stream beside FAST on level 0. */
 int orbx_debug_last_schedule(orbx_extractor* h);
+/* Test hook: the stream hand-offs the LAST extract call used (large batches only, 0 otherwise) -- bit 0 the blur in two launches by
+ * level range, the tail's levels on the resize tail's own queue behind FAST on them (ORBX_BLUR_SPLIT = 0 | 1); bit 1 events recorded as the stop event of the launch they follow (ORBX_BIND_RECORDS = 0 | 1);
+ * bit 2 the status words cleared by the first FAST launch instead of a fill (ORBX_STATUS_IN_FAST = 0 | 1); bit 3 reserved (the upper
+ * levels' octree started behind FAST on them: not built).  The switches are read at construction; 0 restores the schedule without. */
+int orbx_debug_last_handoffs(orbx_extractor* h);
+/* Host only (no device): the levels of the blur's tiles for a width x height image, in launch order, and *split, the first tile of
+ * `level` -- the cut between the blur's two launches.  Returns the number of tiles, ORBX_ERR_INTERNAL when tiles[0, *split) and
+ * tiles[*split, n) are not exactly the levels below `level` and the levels from it on. */
+int orbx_debug_blur_tile_split(float scale_factor, int nlevels, int width, int height, int level, int16_t* tile_levels, int cap, int* split);
 /* Test hook: the waves per workgroup (1, 2 or 4) of the LAST extract call's octree launches -- launch 0 level 0 started early, 1 the
  * lower levels (or all levels, when there is one launch), 2 the upper levels; 0 when the call had no such launch.  ORBX_OCT_WAVES =
  * 1 | 2 | 4 (read at construction) forces the value for every launch. */

@@ -84,6 +84,8 @@ lib.orbx_debug_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, 
 lib.orbx_debug_level_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
 lib.orbx_debug_set_tail_delay.argtypes = [C.c_void_p, C.c_int]
 lib.orbx_debug_last_schedule.argtypes = [C.c_void_p]
+lib.orbx_debug_last_handoffs.argtypes = [C.c_void_p]
+lib.orbx_debug_blur_tile_split.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
 lib.orbx_debug_octree_waves.argtypes = [C.c_void_p, C.c_int]
 lib.orbx_debug_octree_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int]
 lib.orbx_debug_resize_bands.argtypes = [C.c_void_p]
@@ -265,6 +267,11 @@ class Extractor:
         """bits: 0-1 octree instantiation (0 node pool in HBM, 1 keys + nodes in LDS, 2 keys in the scratch), 4 two octree launches,
         8 level-0 octree early, 16 level 0 read in place, 32 resize tail on the side stream"""
         return int(lib.orbx_debug_last_schedule(self._h))
+
+    def debug_last_handoffs(self):
+        """bits: 1 the blur in two launches by level range, 2 events bound to the launches they follow, 4 status cleared by the first
+        FAST launch (large batches; 0 otherwise)"""
+        return int(lib.orbx_debug_last_handoffs(self._h))
 
     def debug_octree_waves(self, launch):
         """waves per workgroup of the last call's octree launch: 0 level 0 started early, 1 the lower (or all) levels, 2 the upper

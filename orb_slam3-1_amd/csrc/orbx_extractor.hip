@@ -4,6 +4,7 @@
 // constructor tables on the host (E0), then one fixed sequence of kernel launches per batch of
 // frames (orbx_kernels.hip).  No CPU compute path exists: without a HIP device every entry point fails.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cmath>
@@ -115,6 +116,29 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// the blur's tiles of a w x h level, appended in row-major order (k_blur: kBlurTW x kBlurTH outputs per workgroup)
+static void append_blur_tiles(int level, int w, int h, std::vector<TileDesc>& tiles)
+{
+    for (int y0 = 0; y0 < h; y0 += kBlurTH)
+        for (int x0 = 0; x0 < w; x0 += kBlurTW) {
+            TileDesc t; t.level = (int16_t)level; t.x0 = (int16_t)x0; t.y0 = (int16_t)y0;
+            // (the 7 taps of the tile's last column, x0 + 63, reach column x0 + 66)
+            t.edge = (int16_t)((x0 == 0 ? 1 : 0) | (w <= x0 + kBlurTW + 2 ? 2 : 0));
+            tiles.push_back(t);
+        }
+}
+
+// Two blur launches by level range: tiles[0, *split) must be exactly the tiles of the levels below `level` and tiles[*split, n) exactly
+// those from `level` on.  False when the list is not in level order (no such cut exists).
+static bool blur_tile_split(const std::vector<TileDesc>& tiles, int level, int* split)
+{
+    size_t t = 0;
+    while (t < tiles.size() && tiles[t].level < level) t++;
+    *split = (int)t;
+    for (; t < tiles.size(); t++) if (tiles[t].level < level) return false;
+    return true;
+}
+
 }  // namespace orbx
 
 using namespace orbx;
@@ -200,7 +224,7 @@ struct orbx_extractor {
     // second stream for the octree of the upper pyramid levels (their node pools are small: own launch, own LDS size)
     hipStream_t oct_stream = nullptr;
     hipEvent_t ev_oct_join = nullptr, ev_fast0 = nullptr, ev_resize = nullptr;
-    hipEvent_t ev_tail = nullptr;        // the resize tail's levels are written (the blur on the launch stream reads them)
+    hipEvent_t ev_tail = nullptr;        // the resize tail's levels are written (a blur of every level on the launch stream reads them: ORBX_BLUR_SPLIT=0)
     int dbg_tail_delay_us = 0;           // tests: a spin kernel in front of the resize tail (orbx_debug_set_tail_delay)
     int last_octree_variant = 0;         // which k_octree instantiation / schedule the last enqueue used (orbx_debug_last_schedule)
     int oct_split = 0, oct_pool_hi = 0;  // levels [oct_split, nlevels) go to the second launch with a pool of oct_pool_hi nodes (0: one launch)
@@ -228,6 +252,14 @@ struct orbx_extractor {
     int last_oct_waves[3] = {0, 0, 0};    // W of the last enqueue's launches, same order; 0: no such launch (orbx_debug_octree_waves)
     int oct_dyn_keys_beside = 6144;      // LDS keys per workgroup when the blur runs beside the octree (batches of 32 frames and more)
     bool resize_beside = true;           // the whole resize chain on the side stream beside FAST on level 0 (ORBX_RESIZE_BESIDE=0: in front of it)
+    // Hand-offs of the large-batch schedule (run_range with a blur stream; see the comment there).  Each has a switch, 0 restores
+    // the schedule without it:
+    bool blur_split = true;              // ORBX_BLUR_SPLIT: the blur in two launches by level range, the tail's levels on the tail's queue
+                                         // behind FAST on them; no wait for the resize tail on the launch stream
+    bool bind_records = true;            // ORBX_BIND_RECORDS: an event that follows a launch is that launch's stop event, not a marker of its own
+    bool status_in_fast = true;          // ORBX_STATUS_IN_FAST: the first FAST launch clears the status words, no fill kernel in front of it
+    int blur_split_tile = 0;             // first blur tile of level resize_tail_first (setup_geometry; tiles are in level order)
+    int last_handoffs = 0;               // which of them the last enqueue used (orbx_debug_last_handoffs)
     std::vector<hipStream_t> aux_streams;
     hipEvent_t ev_parts_fork = nullptr;
     std::vector<hipEvent_t> ev_parts_join;
@@ -386,13 +418,7 @@ int orbx_extractor::setup_geometry(int w, int h)
             c0 = c1;
         }
         // blur tiles
-        for (int y0 = 0; y0 < L.h; y0 += kBlurTH)
-            for (int x0 = 0; x0 < L.w; x0 += kBlurTW) {
-                TileDesc t; t.level = (int16_t)l; t.x0 = (int16_t)x0; t.y0 = (int16_t)y0;
-                // (the 7 taps of the tile's last column, x0 + 63, reach column x0 + 66)
-                t.edge = (int16_t)((x0 == 0 ? 1 : 0) | (L.w <= x0 + kBlurTW + 2 ? 2 : 0));
-                tiles.push_back(t);
-            }
+        append_blur_tiles(l, L.w, L.h, tiles);
         // resize tables (cv::resize INTER_LINEAR 8UC1); level l is made from level l-1
         if (l > 0) {
             const LevelDesc& P = levels[l - 1];
@@ -607,6 +633,10 @@ int orbx_extractor::setup_geometry(int w, int h)
     int r;
     if ((r = d_oct_tabs.upload(oct_tabs)) || (r = d_oct_bounds.upload(oct_bounds)) || (r = d_oct_maps.upload(oct_maps))) return r;
     if ((r = d_levels.upload(levels)) || (r = d_cells.upload(cells)) || (r = d_tiles.upload(tiles)) || (r = d_strips.upload(strip_recs))) return r;
+    // the blur by level range (enqueue): the tiles of the levels before the resize tail and those of the tail's levels
+    blur_split_tile = (int)tiles.size();
+    if (resize_tail_first >= 2 && resize_tail_first < nlevels && !blur_tile_split(tiles, resize_tail_first, &blur_split_tile))
+        return fail(ORBX_ERR_INTERNAL, "the blur tiles of levels %d.. are not one range of the tile list", resize_tail_first);
     geo_w = w; geo_h = h;
     batch_cap = 0;      // scratch must be re-sized for the new geometry
     return ORBX_OK;
@@ -676,7 +706,6 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
                             hipStream_t st)
 {
     const int B = batch;
-    ORBX_HIP(hipMemsetAsync(o_status, 0, sizeof(int) * B, st));
     // optional per-stage timing with HIP events on the launch stream (bench.py roofline leg)
     int mark_i = 0;
     auto mark = [&]() { if (profile && mark_i < kProfEvents) (void)hipEventRecord(prof_ev[mark_i++], st); };
@@ -688,6 +717,34 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
     // (... and when a tile's rows are within 32-bit offsets of its first one, as k_fast_strips addresses them)
     const bool in_place = !level0_ready && ((uintptr_t)d_imgs % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0) && row_stride < (1 << 23);
     const int n_cells = (int)cells.size();
+    // Optionally (ORBX_SPLIT=2..4) a large batch is cut into ranges, each on a stream of its own, so that one range's latency-bound
+    // stages (octree, the dependent resize launches) could hide behind the others' FAST / blur / descriptors.  Measured on MI355X
+    // (B = 256, round 2): 1 range 1.344 ms per step, 2 ranges 1.348, 3 ranges 1.637, 4 ranges 1.649 -- the blur beside the octree
+    // already fills the idle chip and whole-chip kernels of different streams do not co-run, so the default stays ONE range.
+    int parts = 1;
+    if (!profile && split_parts > 1 && B >= 32 * split_parts) parts = std::min(split_parts, 1 + (int)aux_streams.size());
+    // (small batches: the blur is a few microseconds, less than the fork / join across streams costs)
+    hipStream_t side_q = (parts == 1 && !profile && !serial_schedule && side_stream && B >= 32) ? side_stream : nullptr;
+    // first level of the fused resize tail for a range of nB frames (nlevels: none), and the first FAST strip of its levels
+    // (resize_tail_first: the levels from there on are one launch, a workgroup per frame -- k_resize_tail)
+    // (only with many frames: a single workgroup walks a small batch's levels slower than one wide launch per level does)
+    auto tail_plan = [&](int nB, int& l_tail, int& tail_strip) {
+        l_tail = (nB >= 64 && resize_tail_first >= 2 && resize_tail_first < nlevels) ? resize_tail_first : nlevels;
+        for (int l = l_tail; l < nlevels; l++) if (resize_generic[l]) l_tail = nlevels;      // (the fused tail only knows the table-driven kernel)
+        tail_strip = (int)strips.size();        // (the strips are in level order)
+        for (int si = (int)strips.size() - 1; si >= 0 && strips[si].level >= l_tail; si--) tail_strip = si;
+    };
+    // The status words are cleared by the first kernel of the launch stream where that is FAST on the lowest levels: the large-batch
+    // schedule with the resize tail beside it (run_range below), level 0 in place.  Every writer of a non-zero status (k_octree,
+    // k_index) runs behind an event recorded after that launch or after a later one of the launch stream.  Elsewhere: a fill.
+    bool status_by_fast = false;
+    if (status_in_fast && side_q && oct_stream && n_cells > 0 && (level0_ready || in_place)) {
+        int lt, ts;
+        tail_plan(B, lt, ts);
+        status_by_fast = lt < nlevels && ts > 0;
+    }
+    if (!status_by_fast) ORBX_HIP(hipMemsetAsync(o_status, 0, sizeof(int) * B, st));
+    int handoffs = status_by_fast ? 4 : 0;
 
     // One range of frames [f0, f0 + nB) through the whole pipeline on stream `s`; the blur either on `blur_s` beside the octree
     // (a single range: the octree is one wave per frame and level and leaves most of the chip idle) or on `s` itself.
@@ -705,10 +762,22 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             ORBX_LAUNCHED("k_copy_level0");
         }
         if (marks) mark();
-        // (resize_tail_first: the levels from there on are one launch, a workgroup per frame -- k_resize_tail)
-        // (only with many frames: a single workgroup walks a small batch's levels slower than one wide launch per level does)
-        int l_tail = (nB >= 64 && resize_tail_first >= 2 && resize_tail_first < nlevels) ? resize_tail_first : nlevels;
-        for (int l = l_tail; l < nlevels; l++) if (resize_generic[l]) l_tail = nlevels;      // (the fused tail only knows the table-driven kernel)
+        int l_tail, tail_strip;
+        tail_plan(nB, l_tail, tail_strip);
+        // Launches `kern` on queue `q` and, with `ev`, records `ev` behind it.  Such a record publishes nothing but "this kernel has
+        // finished", so the event is made the launch's own stop event (hipExtLaunchKernelGGL) and no marker packet is enqueued.
+        // (Measured, DESIGN.md 5i: the next kernel of the queue starts 5.5 us behind a kernel that carries an event instead of 7 us
+        // behind the marker -- most of the hand-off is the completion signal, not the packet -- and the step gains 7 us over its
+        // six records, the largest share of the three hand-off changes.)
+        auto launch_ev = [&](hipEvent_t ev, auto kern, dim3 grid, dim3 block, size_t lds, hipStream_t q, auto... args) -> hipError_t {
+            if (ev && bind_records) {
+                hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, q, nullptr, ev, 0, args...);
+                handoffs |= 2;
+                return hipSuccess;
+            }
+            hipLaunchKernelGGL(kern, grid, block, lds, q, args...);
+            return ev ? hipEventRecord(ev, q) : hipSuccess;
+        };
         // FAST on level 0 needs no resized level, so the whole resize chain (levels 1 .. and the tail) runs on the side stream beside
         // it; `s` waits for the levels before the tail (ev_resize) in front of FAST on levels 1 ..  (1.005 -> 0.991 ms per 256-frame
         // step.  Measured and dropped in the same session: the blur on a stream of its own right behind the resize chain, beside
@@ -724,16 +793,17 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             SrcImage src;
             src.base = pyr + P.off; src.frame_stride = pyr_frame_bytes; src.stride = P.stride; src.w = P.w; src.h = P.h;
             if (l == 1 && in_place) src = lvl0;
+            const hipEvent_t ev = (chain_beside && l == l_tail - 1) ? ev_resize : nullptr;      // the chain's last launch: the levels before the tail are written
             if (resize_generic[l]) {
-                hipLaunchKernelGGL(k_resize_generic, dim3((D.w + 255) / 256, D.h, nB), dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
-                                   d_xofs[l].p, d_ialpha[l].p, d_yofs[l].p, d_ibeta[l].p);
+                ORBX_HIP(launch_ev(ev, k_resize_generic, dim3((D.w + 255) / 256, D.h, nB), dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
+                                   d_xofs[l].p, d_ialpha[l].p, d_yofs[l].p, d_ibeta[l].p));
                 ORBX_LAUNCHED("k_resize_generic");
                 continue;
             }
             if (nB < resize_band_min) {          // few frames: short waves, a workgroup per tile and frame
                 dim3 g(xcd_grid(((D.w + kResizeTileW - 1) / kResizeTileW) * ((D.h + kResizeRows - 1) / kResizeRows)), nB);
-                hipLaunchKernelGGL(resize_sat[l] ? k_resize_tiles<true> : k_resize_tiles<false>, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
-                                   d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
+                ORBX_HIP(launch_ev(ev, resize_sat[l] ? k_resize_tiles<true> : k_resize_tiles<false>, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D,
+                                   d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p));
                 ORBX_LAUNCHED("k_resize_tiles");
                 continue;
             }
@@ -742,11 +812,10 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
             const int F = (nB >= 4 && resize_frames_fit(src.frame_stride) && resize_frames_fit(pyr_frame_bytes)) ? kResizeFrames : 1;
             dim3 g(xcd_grid(((D.w + resize_strip_w(F) - 1) / resize_strip_w(F)) * ((D.h + kResizeRows - 1) / kResizeRows)), (nB + F - 1) / F);
             auto kern = F == 1 ? (resize_sat[l] ? k_resize<1, true> : k_resize<1, false>) : (resize_sat[l] ? k_resize<kResizeFrames, true> : k_resize<kResizeFrames, false>);
-            hipLaunchKernelGGL(kern, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D, nB, d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p);
+            ORBX_HIP(launch_ev(ev, kern, g, dim3(256), 0, rs, src, pyr, pyr_frame_bytes, D, nB, d_qsx0[l].p, d_qsel[l].p, d_qalpha[l].p, d_rows[l].p));
             resize_bands = true;
             ORBX_LAUNCHED("k_resize");
         }
-        if (chain_beside) ORBX_HIP(hipEventRecord(ev_resize, rs));
         // The octree is one wave per (level, frame).  With few frames the chip is empty anyway and a wave's latency is the
         // whole stage: keep the ping-pong key buffers in LDS (no L2 round trip per DivideNode).  With many frames the larger
         // LDS footprint would halve the resident waves, and the L2-resident scratch wins.
@@ -767,132 +836,155 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
         // `which`: 0 level 0 started early, 1 the lower levels (or all of them), 2 the upper levels
         const bool oct_beside = B > 64;                  // the launch shares a full chip: with FAST / the blur, or with its own 2 000 workgroups
         last_oct_waves[0] = last_oct_waves[1] = last_oct_waves[2] = 0;
-        auto launch_octree = [&](hipStream_t qs, int lv0, int lv1, size_t lds, int pool, int keys, int which) {
+        // (the launches below take an event to record behind them, see launch_ev; a launch of nothing still records it)
+        auto launch_octree = [&](hipStream_t qs, int lv0, int lv1, size_t lds, int pool, int keys, int which, hipEvent_t ev) -> hipError_t {
             const int W = oct_waves_env ? oct_waves_env : (oct_beside ? oct_waves_beside[which] : 4);
-            if (lv1 > lv0) last_oct_waves[which] = W;
-            if (lv1 > lv0)
-                hipLaunchKernelGGL(oct_kernel, dim3(lv1 - lv0, nB), dim3(64 * W), lds, qs, d_levels.p, d_cells.p, d_cand.p + (size_t)f0 * cand_frame_entries, (size_t)cand_frame_entries,
-                                   d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1), n_cells, d_scratch.p + (size_t)f0 * 2 * cand_frame_entries, (size_t)2 * cand_frame_entries, pool, keys,
-                                   sel, sel_frame_entries, sel_cnt, nlevels, o_status + f0,
-                                   d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0, W > 1 ? oct_small_max_waves : 32,
-                                   d_oct_tabs.p, d_oct_maps.p, d_oct_prefix.p + (size_t)f0 * oct_prefix_frame, oct_prefix_frame);
+            if (lv1 <= lv0) return ev ? hipEventRecord(ev, qs) : hipSuccess;
+            last_oct_waves[which] = W;
+            return launch_ev(ev, oct_kernel, dim3(lv1 - lv0, nB), dim3(64 * W), lds, qs, d_levels.p, d_cells.p, d_cand.p + (size_t)f0 * cand_frame_entries, (size_t)cand_frame_entries,
+                             d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1), n_cells, d_scratch.p + (size_t)f0 * 2 * cand_frame_entries, (size_t)2 * cand_frame_entries, pool, keys,
+                             sel, sel_frame_entries, sel_cnt, nlevels, o_status + f0,
+                             d_oct_nodes.p ? d_oct_nodes.p + (size_t)f0 * nlevels * oct_node_stride : nullptr, oct_node_stride, lv0, W > 1 ? oct_small_max_waves : 32,
+                             d_oct_tabs.p, d_oct_maps.p, d_oct_prefix.p + (size_t)f0 * oct_prefix_frame, oct_prefix_frame);
         };
-        auto launch_blur = [&](hipStream_t bs) {
-            hipLaunchKernelGGL(k_blur, dim3(xcd_grid((int)tiles.size()), nB), dim3(256), 0, bs, lvl0, pyr, in_place ? pyr : nullptr, blr, pyr_frame_bytes,
-                               d_levels.p, d_tiles.p, (int)tiles.size(), taps[0], taps[1], taps[2], taps[3]);
+        // the blur of tiles [t0, t1): a range of levels (the tiles are in level order).  The launch that blurs level 0 also leaves its
+        // in-place copy in the pyramid.
+        auto launch_blur = [&](hipStream_t bs, int t0, int t1, hipEvent_t ev) -> hipError_t {
+            if (t1 <= t0) return ev ? hipEventRecord(ev, bs) : hipSuccess;
+            return launch_ev(ev, k_blur, dim3(xcd_grid(t1 - t0), nB), dim3(256), 0, bs, lvl0, pyr, (in_place && t0 == 0) ? pyr : nullptr, blr, pyr_frame_bytes,
+                             d_levels.p, d_tiles.p + t0, t1 - t0, taps[0], taps[1], taps[2], taps[3]);
         };
+        const int n_tiles = (int)tiles.size();
         bool oct0_early = false;            // level 0's octree already runs beside FAST on the levels above it (below)
-        bool tail_beside = false;           // the resize tail ran on oct_stream: ev_tail orders its levels before the blur
+        bool tail_beside = false;           // the resize tail ran on oct_stream: its levels are ordered before their blur (below)
         uint32_t* cand = d_cand.p + (size_t)f0 * cand_frame_entries;
         int* cell_cnt = d_cell_count.p + (size_t)f0 * std::max<size_t>(cells.size(), 1);
-        auto launch_fast = [&](hipStream_t fs, int s0, int s1) {
-            if (s1 > s0)
-                hipLaunchKernelGGL(k_fast_strips, dim3(xcd_grid(s1 - s0), nB), dim3(256), fast_lds, fs, lvl0, pyr, pyr_frame_bytes,
-                                   d_strips.p + s0, s1 - s0, n_cells, ini_th, min_th, fast_layout, cand, (size_t)cand_frame_entries, cell_cnt);
+        bool clear_pending = status_by_fast;        // the first FAST launch of the launch stream clears the status words
+        auto launch_fast = [&](hipStream_t fs, int s0, int s1, hipEvent_t ev) -> hipError_t {
+            if (s1 <= s0) return ev ? hipEventRecord(ev, fs) : hipSuccess;
+            int* clear = (clear_pending && fs == s) ? o_status + f0 : nullptr;
+            if (clear) clear_pending = false;
+            return launch_ev(ev, k_fast_strips, dim3(xcd_grid(s1 - s0), nB), dim3(256), fast_lds, fs, lvl0, pyr, pyr_frame_bytes,
+                             d_strips.p + s0, s1 - s0, n_cells, ini_th, min_th, fast_layout, cand, (size_t)cand_frame_entries, cell_cnt, clear);
         };
-        // first strip of the levels the resize tail produces (the strips are in level order)
-        int tail_strip = (int)strips.size();
-        for (int si = (int)strips.size() - 1; si >= 0 && strips[si].level >= l_tail; si--) tail_strip = si;
+        // With side streams the resize tail -- one latency-bound workgroup per frame -- and FAST on its levels run BESIDE FAST on the
+        // lower levels (which only need the levels before the tail) instead of in front of it.
+        const bool beside = l_tail < nlevels && blur_s && oct_stream && n_cells > 0 && tail_strip > 0;
+        // The blur in two launches by level range (ORBX_BLUR_SPLIT): the levels before the tail on the launch stream directly behind
+        // FAST -- which has waited for them (ev_resize) --, the tail's levels on the tail's own queue behind FAST on them, where queue
+        // order puts them behind k_resize_tail: that queue idles there while FAST on the lower levels finishes.  The launch stream
+        // then never waits for the tail.  k_orient_desc is ordered behind the second launch by the join that FAST on the tail's levels
+        // already has: blur (oct_stream) -> the first ev_oct_join -> blur_s waits for it in front of its octree and of k_index ->
+        // k_index -> ev_join -> s waits for it in front of k_orient_desc.
+        // (Measured and dropped: the second launch behind the upper levels' octree, the phase in which the one blur runs -- k_index then
+        // starts behind it and ends after the launch stream's blur, the join moves back; slower than one blur)
+        const bool blur_ranges = blur_split && beside && l_tail == resize_tail_first && blur_split_tile > 0 && blur_split_tile < n_tiles;
+        bool fork_recorded = false;         // ev_fork already follows the launch stream's last FAST launch
         if (l_tail < nlevels) {
             ResizeTables T;
             std::memset(&T, 0, sizeof(T));
             for (int l = l_tail; l < nlevels; l++) { T.q_sx0[l] = d_qsx0[l].p; T.q_sel[l] = d_qsel[l].p; T.q_alpha[l] = d_qalpha[l].p; T.rows[l] = d_rows[l].p; }
-            // With side streams the tail -- one latency-bound workgroup per frame -- and FAST on its levels run BESIDE FAST on the
-            // lower levels (which only need the levels before the tail) instead of in front of it.
-            const bool beside = blur_s && oct_stream && n_cells > 0 && tail_strip > 0;
             hipStream_t ts = beside ? oct_stream : s;
             if (beside && !chain_beside) { ORBX_HIP(hipEventRecord(ev_fork, s)); ORBX_HIP(hipStreamWaitEvent(ts, ev_fork, 0)); }
             if (dbg_tail_delay_us > 0) hipLaunchKernelGGL(k_debug_spin, dim3(1), dim3(64), 0, ts, (long long)dbg_tail_delay_us * 100);
             bool tail_sat = false;
             for (int l = l_tail; l < nlevels; l++) tail_sat = tail_sat || resize_sat[l];
-            hipLaunchKernelGGL(tail_sat ? k_resize_tail<true> : k_resize_tail<false>, dim3(nB), dim3(1024), 0, ts, pyr, pyr_frame_bytes, d_levels.p, T, l_tail, nlevels);
+            // one blur on `s` reads EVERY level: it has to wait for the tail's levels (ev_tail; FAST on them may still run).  With the
+            // blur by level range nobody outside this queue reads them before the join.
+            ORBX_HIP(launch_ev((beside && !blur_ranges) ? ev_tail : nullptr, tail_sat ? k_resize_tail<true> : k_resize_tail<false>, dim3(nB), dim3(1024), 0, ts,
+                               pyr, pyr_frame_bytes, d_levels.p, T, l_tail, nlevels));
             ORBX_LAUNCHED("k_resize_tail");
             if (beside) {
-                // the blur runs on `s` and reads EVERY level: it has to wait for the tail's levels (FAST on them may still run)
-                ORBX_HIP(hipEventRecord(ev_tail, ts));
                 tail_beside = true;
-                launch_fast(ts, tail_strip, (int)strips.size());
-                ORBX_HIP(hipEventRecord(ev_oct_join, ts));
+                ORBX_HIP(launch_fast(ts, tail_strip, (int)strips.size(), blur_ranges ? nullptr : ev_oct_join));
+                if (blur_ranges) ORBX_HIP(launch_blur(ts, blur_split_tile, n_tiles, ev_oct_join));
                 // FAST on level 0 first; its octree -- the longest chain of the stage -- then runs beside FAST on levels 1..
                 // (a launch per level with every level's octree started early was measured too: the extra launch tails cost
                 // FAST 40 us, more than the octrees gain)
+                // The launch stream's last FAST launch carries ev_fork, which starts the octrees.
                 int l1_strip = tail_strip;
                 for (int si = tail_strip - 1; si >= 0 && strips[si].level >= 1; si--) l1_strip = si;
                 if (two_launches && oct_split > 1 && l1_strip > 0 && l1_strip < tail_strip) {
-                    launch_fast(s, 0, l1_strip);
-                    ORBX_HIP(hipEventRecord(ev_fast0, s));
+                    ORBX_HIP(launch_fast(s, 0, l1_strip, ev_fast0));
                     ORBX_HIP(hipStreamWaitEvent(blur_s, ev_fast0, 0));
-                    launch_octree(blur_s, 0, 1, o_lds, oct_pool, o_keys, 0);
+                    ORBX_HIP(launch_octree(blur_s, 0, 1, o_lds, oct_pool, o_keys, 0, nullptr));
                     oct0_early = true;
                     if (chain_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_resize, 0));
-                    launch_fast(s, l1_strip, tail_strip);
+                    ORBX_HIP(launch_fast(s, l1_strip, tail_strip, ev_fork));
                 } else if (chain_beside && l1_strip > 0 && l1_strip < tail_strip) {
-                    launch_fast(s, 0, l1_strip);
+                    ORBX_HIP(launch_fast(s, 0, l1_strip, nullptr));
                     ORBX_HIP(hipStreamWaitEvent(s, ev_resize, 0));
-                    launch_fast(s, l1_strip, tail_strip);
+                    ORBX_HIP(launch_fast(s, l1_strip, tail_strip, ev_fork));
                 } else {
                     if (chain_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_resize, 0));
-                    launch_fast(s, 0, tail_strip);
+                    ORBX_HIP(launch_fast(s, 0, tail_strip, ev_fork));
                 }
+                fork_recorded = true;
                 ORBX_HIP(hipStreamWaitEvent(blur_s, ev_oct_join, 0));
             } else {
                 if (marks) mark();
-                if (n_cells > 0) launch_fast(s, 0, (int)strips.size());
+                if (n_cells > 0) ORBX_HIP(launch_fast(s, 0, (int)strips.size(), nullptr));
             }
         } else {
             if (marks) mark();
-            if (n_cells > 0) launch_fast(s, 0, (int)strips.size());
+            if (n_cells > 0) ORBX_HIP(launch_fast(s, 0, (int)strips.size(), nullptr));
         }
         ORBX_LAUNCHED("k_fast_strips");
+        if (clear_pending) return fail(ORBX_ERR_INTERNAL, "no FAST launch on the launch stream took the status clear");
         if (marks) mark();
         // With a side stream the throughput-bound blur stays on the launch stream (it starts the moment FAST ends) and the
         // latency-bound octree + index go beside it: octree of the lower levels and the index on `blur_s`, the upper levels'
         // octree on `oct_stream`.  Without one (profiling) everything is serial on `s`.
+        // The queues of the large-batch schedule, and what orders them (a hand-off between queues costs the waiting queue 5 - 13 us
+        // also when the event completed long ago, so the launch stream -- the queue the caller waits on -- takes as few as it can):
+        //   s           [status fill, unless FAST clears it] ev_fork | FAST level 0 +ev_fast0 | wait ev_resize | FAST levels 1 .. tail
+        //               +ev_fork | blur of the levels before the tail | wait ev_join | k_orient_desc
+        //   oct_stream  wait ev_fork | k_resize x (tail - 1) +ev_resize | k_resize_tail | FAST on the tail's levels | blur of the tail's
+        //               levels +ev_oct_join | wait ev_fork | octree of the upper levels +ev_oct_join
+        //   blur_s      wait ev_fast0 | octree of level 0 | wait ev_oct_join (FAST and blur of the tail's levels) | wait ev_fork |
+        //               octree of the lower levels | wait ev_oct_join | k_index +ev_join
+        // "+ev": the event is the stop event of that launch (launch_ev).
         hipStream_t os = blur_s ? blur_s : s;
         if (blur_s) {
-            ORBX_HIP(hipEventRecord(ev_fork, s));
+            if (!fork_recorded) ORBX_HIP(hipEventRecord(ev_fork, s));
             ORBX_HIP(hipStreamWaitEvent(blur_s, ev_fork, 0));
         }
         if (two_launches) {
             ORBX_HIP(hipStreamWaitEvent(oct_stream, ev_fork, 0));
             {   // (dynamic LDS keys: the upper levels hold fewer candidates -- half the allotment)
                 const int k_hi = dyn_keys ? std::max(64, o_keys / 2) : 0;
-                launch_octree(oct_stream, oct_split, nlevels, oct_lds_hi + 8 * (size_t)k_hi, oct_pool_hi, k_hi, 2);
+                ORBX_HIP(launch_octree(oct_stream, oct_split, nlevels, oct_lds_hi + 8 * (size_t)k_hi, oct_pool_hi, k_hi, 2, ev_oct_join));
             }
-            ORBX_HIP(hipEventRecord(ev_oct_join, oct_stream));
         }
-        launch_octree(os, oct0_early ? 1 : 0, lv_lo, o_lds, oct_pool, o_keys, 1);
+        ORBX_HIP(launch_octree(os, oct0_early ? 1 : 0, lv_lo, o_lds, oct_pool, o_keys, 1, nullptr));
         if (blur_s) {
-            if (tail_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_tail, 0));
-            launch_blur(s);
+            if (blur_ranges) ORBX_HIP(launch_blur(s, 0, blur_split_tile, nullptr));
+            else {
+                if (tail_beside) ORBX_HIP(hipStreamWaitEvent(s, ev_tail, 0));
+                ORBX_HIP(launch_blur(s, 0, n_tiles, nullptr));
+            }
         }
+        if (blur_ranges) handoffs |= 1;
         last_octree_variant = (oct_nodes_hbm ? 0 : (dyn_keys ? 3 : (o_keys > 0 ? 1 : 2))) | (two_launches ? 4 : 0) | (oct0_early ? 8 : 0) | (in_place ? 16 : 0) | (tail_beside ? 32 : 0) | (chain_beside ? 64 : 0);
         last_resize_bands = resize_bands;
         if (two_launches) ORBX_HIP(hipStreamWaitEvent(os, ev_oct_join, 0));
         ORBX_LAUNCHED("k_octree / k_blur");
         if (marks) mark();
-        hipLaunchKernelGGL(k_index, dim3(nB), dim3(64), 0, os, d_levels.p, nlevels, sel, sel_frame_entries, sel_cnt,
-                           lap0, lap1, cap, kp_dst, sel_frame_entries, o_n + f0, o_mono + f0, o_status + f0);
+        ORBX_HIP(launch_ev(blur_s ? ev_join : nullptr, k_index, dim3(nB), dim3(64), 0, os, d_levels.p, nlevels, sel, sel_frame_entries, sel_cnt,
+                           lap0, lap1, cap, kp_dst, sel_frame_entries, o_n + f0, o_mono + f0, o_status + f0));
         ORBX_LAUNCHED("k_index");
         if (marks) mark();
-        if (blur_s) { ORBX_HIP(hipEventRecord(ev_join, blur_s)); ORBX_HIP(hipStreamWaitEvent(s, ev_join, 0)); }
-        else launch_blur(s);
+        if (blur_s) ORBX_HIP(hipStreamWaitEvent(s, ev_join, 0));
+        else ORBX_HIP(launch_blur(s, 0, n_tiles, nullptr));
         if (marks) mark();
         if (const int lr = launch_orient_desc(f0, nB, s, o_kps, o_desc, cap)) return lr;
         if (marks) mark();
         return ORBX_OK;
     };
 
-    // Optionally (ORBX_SPLIT=2..4) a large batch is cut into ranges, each on a stream of its own, so that one range's latency-bound
-    // stages (octree, the dependent resize launches) could hide behind the others' FAST / blur / descriptors.  Measured on MI355X
-    // (B = 256, round 2): 1 range 1.344 ms per step, 2 ranges 1.348, 3 ranges 1.637, 4 ranges 1.649 -- the blur beside the octree
-    // already fills the idle chip and whole-chip kernels of different streams do not co-run, so the default stays ONE range.
-    int parts = 1;
-    if (!profile && split_parts > 1 && B >= 32 * split_parts) parts = std::min(split_parts, 1 + (int)aux_streams.size());
     int r;
     if (parts == 1) {
-        // (small batches: the blur is a few microseconds, less than the fork / join across streams costs)
-        if ((r = run_range(0, B, st, (!profile && !serial_schedule && side_stream && B >= 32) ? side_stream : nullptr, true))) return r;
+        if ((r = run_range(0, B, st, side_q, true))) return r;
     } else {
         ORBX_HIP(hipEventRecord(ev_parts_fork, st));
         for (int p = 0; p < parts; p++) {
@@ -907,6 +999,7 @@ int orbx_extractor::enqueue(const uint8_t* d_imgs, bool level0_ready, int batch,
     prof_stream = st;
     ORBX_HIP(hipGetLastError());
     last_batch = B;
+    last_handoffs = handoffs;
     return ORBX_OK;
 }
 
@@ -975,6 +1068,9 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
     if (const char* env = getenv("ORBX_RESIZE_TAIL")) e->resize_tail_first = atoi(env);
     if (const char* env = getenv("ORBX_RESIZE_BAND_MIN")) e->resize_band_min = std::max(atoi(env), 1);
     if (const char* env = getenv("ORBX_RESIZE_BESIDE")) e->resize_beside = atoi(env) != 0;
+    if (const char* env = getenv("ORBX_BLUR_SPLIT")) e->blur_split = atoi(env) != 0;
+    if (const char* env = getenv("ORBX_BIND_RECORDS")) e->bind_records = atoi(env) != 0;
+    if (const char* env = getenv("ORBX_STATUS_IN_FAST")) e->status_in_fast = atoi(env) != 0;
     if (const char* env = getenv("ORBX_OCT_DYN")) e->oct_dyn_off = atoi(env) == 0;
     if (const char* env = getenv("ORBX_OCT_DYN_MAXB")) e->oct_dyn_max_batch = atoi(env);
     if (const char* env = getenv("ORBX_OCT_WAVES")) { const int wv = atoi(env); if (wv == 1 || wv == 2 || wv == 4) e->oct_waves_env = wv; }
@@ -1265,6 +1361,29 @@ int orbx_debug_last_schedule(orbx_extractor* e)
 {
     if (!e) return fail(ORBX_ERR_ARG, "NULL handle");
     return e->last_octree_variant;
+}
+
+int orbx_debug_last_handoffs(orbx_extractor* e)
+{
+    if (!e) return fail(ORBX_ERR_ARG, "NULL handle");
+    return e->last_handoffs;
+}
+
+// host only: the blur's tile list of a width x height image and its cut in front of `level`, as setup_geometry makes them
+int orbx_debug_blur_tile_split(float scale_factor, int nlevels, int width, int height, int level, int16_t* tile_levels, int cap, int* split)
+{
+    if (!tile_levels || !split || nlevels < 1 || nlevels > kMaxLevels || !(scale_factor > 1.0f) || width < 1 || height < 1)
+        return fail(ORBX_ERR_ARG, "bad tile split request");
+    orbx_extractor e;
+    e.nfeatures = 1; e.nlevels = nlevels; e.scale_factor_f = scale_factor; e.scale_factor_d = (double)scale_factor;
+    build_tables(&e);
+    std::vector<TileDesc> tiles;
+    for (int l = 0; l < nlevels; l++)
+        append_blur_tiles(l, (int)std::nearbyintf((float)width * e.inv_scale[l]), (int)std::nearbyintf((float)height * e.inv_scale[l]), tiles);
+    if ((int)tiles.size() > cap) return fail(ORBX_ERR_CAPACITY, "%d tiles, room for %d", (int)tiles.size(), cap);
+    for (size_t t = 0; t < tiles.size(); t++) tile_levels[t] = tiles[t].level;
+    if (!blur_tile_split(tiles, level, split)) return fail(ORBX_ERR_INTERNAL, "the blur tiles of levels %d.. are not one range of the tile list", level);
+    return (int)tiles.size();
 }
 
 int orbx_debug_set_fast_corner_cap(orbx_extractor* e, int cap)

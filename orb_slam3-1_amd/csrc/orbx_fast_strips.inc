@@ -170,7 +170,8 @@ __device__ unsigned long long d_fast_prof[16];
 __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_t* __restrict__ pyr, size_t frame_stride,
                                                      const StripRec* __restrict__ recs, int n_strips, int n_cells,
                                                      int ini_th, int min_th, FastLds Z,
-                                                     uint32_t* __restrict__ cand, size_t cand_frame_stride, int* __restrict__ cell_count)
+                                                     uint32_t* __restrict__ cand, size_t cand_frame_stride, int* __restrict__ cell_count,
+                                                     int* __restrict__ status_clear)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ StripTab s_tab;
@@ -181,6 +182,9 @@ __global__ __launch_bounds__(256) void k_fast_strips(SrcImage lvl0, const uint8_
     int fallback_slot = 0;
 #endif
 
+    // the first launch of a batch clears the frames' status words (enqueue(): every writer of a non-zero status is ordered behind
+    // this launch); one thread per frame, in a workgroup that every grid has
+    if (status_clear != nullptr && blockIdx.x == 0 && threadIdx.x == 0) status_clear[blockIdx.y] = 0;
     const int strip_idx = xcd_remap(blockIdx.x, gridDim.x, blockIdx.y);
     if (strip_idx >= n_strips) return;
     const StripRec* S = recs + strip_idx;

@@ -47,8 +47,9 @@ def _host_batch(pkg, refs, what, min_kps):
         ex.close()
 
 
-def _device_batch(pkg, refs, B, what, min_kps, row_pad=0, frame_pad=0, misalign=0):
-    """B frames (refs in turn) through extract_batch_device; returns the schedule bits"""
+def _device_batch(pkg, refs, B, what, min_kps, row_pad=0, frame_pad=0, misalign=0, corner_cap=None):
+    """B frames (refs in turn) through extract_batch_device; returns the schedule bits.  corner_cap: the FAST kernel's corner lists
+    shrunk to that many entries (its overflow path)"""
     import torch
     args = refs[0]["args"]
     h, w = refs[0]["img"].shape
@@ -62,6 +63,8 @@ def _device_batch(pkg, refs, B, what, min_kps, row_pad=0, frame_pad=0, misalign=
     d_img = torch.from_numpy(host).to(dev)
     ex = pkg.Extractor(*args)
     try:
+        if corner_cap is not None:
+            ex.debug_set_fast_corner_cap(corner_cap)
         cap = max(ex.max_keypoints, ex.max_keypoints_for(w, h))
         d_kps = torch.zeros(B * cap * 28, dtype=torch.uint8, device=dev); d_desc = torch.zeros(B * cap * 32, dtype=torch.uint8, device=dev)
         d_n = torch.zeros(B, dtype=torch.int32, device=dev); d_mono = torch.zeros(B, dtype=torch.int32, device=dev)

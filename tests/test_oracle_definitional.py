@@ -17,35 +17,8 @@ goes through restatements written from the DEFINITIONS, sharing no code and no e
 import numpy as np
 import pytest
 
-RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-
-
-def fast_definitional(img, t, want_map=False):
-    """(x, y, score) of FAST-9/16 corners at threshold t with 3x3 NMS, row-major, straight from the definition"""
-    h, w = img.shape
-    v = img.astype(np.int32)
-    H, W = h - 6, w - 6
-    c = v[3:h - 3, 3:w - 3]
-    d = np.stack([v[3 + dy:3 + dy + H, 3 + dx:3 + dx + W] - c for (dx, dy) in RING])       # ring - centre, [16, H, W]
-    best = np.full((H, W), -1 << 20, np.int32)
-    for k in range(16):
-        arc = d[[(k + i) % 16 for i in range(9)]]
-        best = np.maximum(best, np.maximum(arc.min(0), (-arc).min(0)))      # brighter arc / darker arc
-    score = np.zeros((h, w), np.int32)
-    sc = best - 1                       # largest threshold at which the pixel is a corner
-    score[3:h - 3, 3:w - 3] = np.where(best > t, sc, 0)
-    if want_map:
-        return score
-    out = []
-    for y in range(3, h - 3):
-        row = score[y]
-        for x in np.nonzero(row[3:w - 3])[0] + 3:
-            s = row[x]
-            nb = score[y - 1:y + 2, x - 1:x + 2].copy()
-            nb[1, 1] = -1
-            if (s > nb).all():
-                out.append((x, y, s))
-    return out
+# the FAST restatement is shared with the tests of the device kernel's cells, tests/fast_cells_reference.py
+from fast_cells_reference import RING, fast_definitional  # noqa: E402,F401
 
 
 @pytest.mark.parametrize("seed,t", [(0, 20), (1, 20), (2, 7), (3, 7), (4, 12), (5, 40)])

@@ -42,4 +42,41 @@ inline int rig_from_abi(const OrbxKB8Rig* rig, Rig* out)
     return ORBX_OK;
 }
 
+// The camera of a solver handle: pinhole (the figures every problem brings) until a setter names a fisheye camera or a rig of two.
+// NULL resets to pinhole, the last setter wins, a refused argument leaves the choice as it was.
+struct CameraChoice {
+    enum Kind { kPinhole, kFisheye, kRig } kind = kPinhole;
+    Cam cam;
+    Rig rig;        // (rig.kind / rig.kind_tab: the per-edge cameras of an LBA window, filled in by its shard / its batch)
+    int set(const OrbxKB8* a)
+    {
+        if (!a) { kind = kPinhole; return ORBX_OK; }
+        if (!(a->fx > 0) || !(a->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
+        cam_from_abi(*a, &cam);
+        kind = kFisheye;
+        return ORBX_OK;
+    }
+    int set(const OrbxKB8Rig* a)
+    {
+        if (!a) { kind = kPinhole; return ORBX_OK; }
+        Rig g;
+        if (int r = rig_from_abi(a, &g)) return r;
+        rig = g;
+        kind = kRig;
+        return ORBX_OK;
+    }
+};
+
+// f() for the pinhole camera, f(cam) for the fisheye one, f(rig) for the rig: a launch site passes a generic lambda over a pack,
+// [&](auto... cam) { hipLaunchKernelGGL((k<decltype(cam)...>), ..., cam..., ...); }
+template <class F>
+inline void with_camera(const CameraChoice& c, F&& f)
+{
+    switch (c.kind) {
+    case CameraChoice::kFisheye: f(c.cam); break;
+    case CameraChoice::kRig: f(c.rig); break;
+    default: f();
+    }
+}
+
 }  // namespace kb8

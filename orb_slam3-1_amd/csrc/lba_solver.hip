@@ -81,9 +81,12 @@ __device__ __forceinline__ void edge_residual(const Cam& c, const double* Xc, co
 // the same edge with pCamera = KannalaBrandt8 (lba_set_camera_kb8): obs - project(Xc); such a window has no stereo edge.
 // The edge bodies below take their camera as a template parameter: ProblemCam (the pinhole figures of the window's own Dev, read
 // exactly where they were read before the parameter existed -- handing the bodies a reference to d.cam instead made k_lin_all
-// spill its whole Dev to scratch) or a kb8::Cam, which the _kb8 kernels receive by value.
+// spill its whole Dev to scratch), a kb8::Cam or a kb8::Rig (which finds the camera of edge e in its own array: RigEdge).
+// The kernels of these bodies are templates over a pack CamT...: empty for the pinhole camera, whose kernels have no camera argument,
+// else the one kb8::Cam / kb8::Rig the kernel receives by value in that place (launched through kb8::with_camera).
 struct ProblemCam {};
-// (a kb8::Rig, which the _rig kernels receive by value, finds the camera of edge e in its own array: RigEdge)
+__device__ __forceinline__ ProblemCam camera_arg() { return ProblemCam(); }
+template <class C> __device__ __forceinline__ const C& camera_arg(const C& c) { return c; }
 __device__ __forceinline__ const Cam& camera(const Dev& d, const ProblemCam&, int) { return d.cam; }
 __device__ __forceinline__ const kb8::Cam& camera(const Dev&, const kb8::Cam& c, int) { return c; }
 __device__ __forceinline__ kb8::RigEdge camera(const Dev&, const kb8::Rig& g, int e) { return kb8::RigEdge{g, g.kind[e] != 0}; }
@@ -217,18 +220,10 @@ __device__ __forceinline__ void errors_body(Dev d, const CamT& cam, const double
     d.err[3 * (size_t)e] = r[0]; d.err[3 * (size_t)e + 1] = r[1]; d.err[3 * (size_t)e + 2] = r[2];
     d.rho0[e] = rho0;
 }
-__global__ __launch_bounds__(256) void k_errors(Dev d, const double* __restrict__ poses, const double* __restrict__ pts)
+template <class... CamT>
+__global__ __launch_bounds__(256) void k_errors(Dev d, CamT... cam, const double* __restrict__ poses, const double* __restrict__ pts)
 {
-    errors_body(d, ProblemCam(), poses, pts, (int)blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_errors_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts)
-{
-    errors_body(d, cam, poses, pts, (int)blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void k_errors_rig(Dev d, kb8::Rig rig, const double* __restrict__ poses, const double* __restrict__ pts)
-{
-    errors_body(d, rig, poses, pts, (int)blockIdx.x);
+    errors_body(d, camera_arg(cam...), poses, pts, (int)blockIdx.x);
 }
 
 // ---- buildSystem, landmark side: Hll, bl and the Hpl blocks W_e = B^T (rho1 Omega) A (6x3) ----
@@ -393,18 +388,10 @@ __device__ __forceinline__ void lin_all_body(Dev d, const CamT& cam, const doubl
         }
     }
 }
-__global__ __launch_bounds__(256) void k_lin_all(Dev d, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
+template <class... CamT>
+__global__ __launch_bounds__(256) void k_lin_all(Dev d, CamT... cam, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
 {
-    lin_all_body(d, ProblemCam(), poses, pts, lambda, (int)blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_lin_all_kb8(Dev d, kb8::Cam cam, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
-{
-    lin_all_body(d, cam, poses, pts, lambda, (int)blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void k_lin_all_rig(Dev d, kb8::Rig rig, const double* __restrict__ poses, const double* __restrict__ pts, double lambda)
-{
-    lin_all_body(d, rig, poses, pts, lambda, (int)blockIdx.x);
+    lin_all_body(d, camera_arg(cam...), poses, pts, lambda, (int)blockIdx.x);
 }
 
 // ---- deterministic scalar reductions (single workgroup) ----
@@ -698,20 +685,11 @@ __device__ __forceinline__ void update_errors_body(const Dev& d, const CamT& cam
         }
     }
 }
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors(Dev d, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
+template <class... CamT>
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors(Dev d, CamT... cam, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
                                                                double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
 {
-    update_errors_body(d, ProblemCam(), lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
-}
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors_kb8(Dev d, kb8::Cam cam, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
-                                                                   double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
-{
-    update_errors_body(d, cam, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
-}
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors_rig(Dev d, kb8::Rig rig, double lambda, const double* __restrict__ pts, const double* __restrict__ poses_new,
-                                                                   double* __restrict__ pts_new, double* __restrict__ hmap, unsigned long long seq)
-{
-    update_errors_body(d, rig, lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
+    update_errors_body(d, camera_arg(cam...), lambda, pts, poses_new, pts_new, hmap, seq, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -734,63 +712,34 @@ struct BDyn { double lambda, hint; unsigned long long seq; int cur, flags; };
 struct BDynAll { BDyn w[kMaxBatch]; };
 enum { kBwErrors = 1, kBwLin = 2, kBwReduce0 = 4, kBwTrial = 8, kBwSchurLm = 16 };
 
-__global__ __launch_bounds__(256) void k_errors_b(const BWin* __restrict__ wins, BDynAll dyn, int trial_state)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & (trial_state ? kBwTrial : kBwErrors))) return;
-    const BWin& w = wins[blockIdx.y];
-    if ((int)blockIdx.x * 256 >= w.d.nE) return;
-    const int st = trial_state ? 1 - y.cur : y.cur;
-    errors_body(w.d, ProblemCam(), w.poses[st], w.pts[st], (int)blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_errors_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, int trial_state, kb8::Cam cam)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & (trial_state ? kBwTrial : kBwErrors))) return;
-    const BWin& w = wins[blockIdx.y];
-    if ((int)blockIdx.x * 256 >= w.d.nE) return;
-    const int st = trial_state ? 1 - y.cur : y.cur;
-    errors_body(w.d, cam, w.poses[st], w.pts[st], (int)blockIdx.x);
-}
-// (the rig of a batch is one for all windows; each window's edge kinds are found through the pointer table the rig carries)
-__device__ __forceinline__ kb8::Rig rig_of_window(const kb8::Rig& rig, int w)
+// the camera of window w of a batch: the one camera of the call; the rig of a batch is one for all windows too, and each window's
+// edge kinds are found through the pointer table the rig carries
+__device__ __forceinline__ ProblemCam window_camera(int) { return ProblemCam(); }
+__device__ __forceinline__ const kb8::Cam& window_camera(int, const kb8::Cam& c) { return c; }
+__device__ __forceinline__ kb8::Rig window_camera(int w, const kb8::Rig& rig)
 {
     kb8::Rig g = rig;
     g.kind = rig.kind_tab[w];
     return g;
 }
-__global__ __launch_bounds__(256) void k_errors_b_rig(const BWin* __restrict__ wins, BDynAll dyn, int trial_state, kb8::Rig rig)
+template <class... CamT>
+__global__ __launch_bounds__(256) void k_errors_b(const BWin* __restrict__ wins, BDynAll dyn, int trial_state, CamT... cam)
 {
     const BDyn y = dyn.w[blockIdx.y];
     if (!(y.flags & (trial_state ? kBwTrial : kBwErrors))) return;
     const BWin& w = wins[blockIdx.y];
     if ((int)blockIdx.x * 256 >= w.d.nE) return;
     const int st = trial_state ? 1 - y.cur : y.cur;
-    errors_body(w.d, rig_of_window(rig, (int)blockIdx.y), w.poses[st], w.pts[st], (int)blockIdx.x);
+    errors_body(w.d, window_camera((int)blockIdx.y, cam...), w.poses[st], w.pts[st], (int)blockIdx.x);
 }
-__global__ __launch_bounds__(256) void k_lin_all_b(const BWin* __restrict__ wins, BDynAll dyn)
+template <class... CamT>
+__global__ __launch_bounds__(256) void k_lin_all_b(const BWin* __restrict__ wins, BDynAll dyn, CamT... cam)
 {
     const BDyn y = dyn.w[blockIdx.y];
     if (!(y.flags & kBwLin)) return;
     const BWin& w = wins[blockIdx.y];
     if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
-    lin_all_body(w.d, ProblemCam(), w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_lin_all_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, kb8::Cam cam)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & kBwLin)) return;
-    const BWin& w = wins[blockIdx.y];
-    if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
-    lin_all_body(w.d, cam, w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_lin_all_b_rig(const BWin* __restrict__ wins, BDynAll dyn, kb8::Rig rig)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & kBwLin)) return;
-    const BWin& w = wins[blockIdx.y];
-    if ((int)blockIdx.x >= w.d.nP + (w.d.nL + 31) / 32) return;
-    lin_all_body(w.d, rig_of_window(rig, (int)blockIdx.y), w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
+    lin_all_body(w.d, window_camera((int)blockIdx.y, cam...), w.poses[y.cur], w.pts[y.cur], y.hint, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(1024) void k_reduce_b(const BWin* __restrict__ wins, BDynAll dyn, int mode)
 {
@@ -843,15 +792,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (w.d.n <= 0 || (int)blockIdx.x >= w.nblk * (w.nblk + 1) / 2) return;
     chol::chol_flow_body(w.S, w.Lp, w.d.n, w.nblk, w.Linv, w.d.scal, w.flow, (unsigned)y.seq, (int)blockIdx.x, sm_step);
 }
-__global__ __launch_bounds__(1024) void k_chol_solve_b(const BWin* __restrict__ wins, BDynAll dyn)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & kBwTrial)) return;
-    const BWin& w = wins[blockIdx.y];
-    const int n = w.d.n;
-    if (n <= 0) return;
-    chol::chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, chol::sm_solve);
-}
 __global__ __launch_bounds__(1024) void k_chol_solve_update_b(const BWin* __restrict__ wins, BDynAll dyn)
 {
     const BDyn y = dyn.w[blockIdx.y];
@@ -861,32 +801,15 @@ __global__ __launch_bounds__(1024) void k_chol_solve_update_b(const BWin* __rest
     if (n > 0) chol::chol_solve_body<true>(w.Lp, n, w.Linv, w.Lp + (size_t)n * n, w.bs, w.d.x, w.d.scal, 1, 0, chol::sm_solve);
     pose_update_tail(w.d, y.lambda, w.bpf, w.poses[y.cur], w.poses[1 - y.cur]);
 }
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b(const BWin* __restrict__ wins, BDynAll dyn)
+template <class... CamT>
+__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b(const BWin* __restrict__ wins, BDynAll dyn, CamT... cam)
 {
     const BDyn y = dyn.w[blockIdx.y];
     if (!(y.flags & kBwTrial)) return;
     const BWin& w = wins[blockIdx.y];
     const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
     if ((int)blockIdx.x >= nb) return;
-    update_errors_body(w.d, ProblemCam(), y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
-}
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b_kb8(const BWin* __restrict__ wins, BDynAll dyn, kb8::Cam cam)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & kBwTrial)) return;
-    const BWin& w = wins[blockIdx.y];
-    const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
-    if ((int)blockIdx.x >= nb) return;
-    update_errors_body(w.d, cam, y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
-}
-__global__ __launch_bounds__(kUpdThreads) void k_update_errors_b_rig(const BWin* __restrict__ wins, BDynAll dyn, kb8::Rig rig)
-{
-    const BDyn y = dyn.w[blockIdx.y];
-    if (!(y.flags & kBwTrial)) return;
-    const BWin& w = wins[blockIdx.y];
-    const int nb = max((w.d.nL + kUpdLandmarks - 1) / kUpdLandmarks, 1);
-    if ((int)blockIdx.x >= nb) return;
-    update_errors_body(w.d, rig_of_window(rig, (int)blockIdx.y), y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
+    update_errors_body(w.d, window_camera((int)blockIdx.y, cam...), y.lambda, w.pts[y.cur], w.poses[1 - y.cur], w.pts[1 - y.cur], w.hmap, y.seq, (int)blockIdx.x, nb);
 }
 
 __global__ __launch_bounds__(256) void k_epilogue(Dev d, const double* __restrict__ poses, const double* __restrict__ pts,
@@ -920,6 +843,17 @@ __global__ __launch_bounds__(256) void k_epilogue_rig(Dev d, kb8::Rig rig, const
     depth_pos[e] = Xp[2] > 0.0;
 }
 
+// (host) the epilogue of a window's camera; the pinhole and the fisheye windows share the first
+template <class... CamT>
+inline void launch_epilogue(hipStream_t st, const Dev& d, const double* poses, const double* pts, double* chi2, uint8_t* depth_pos, const CamT&...)
+{
+    hipLaunchKernelGGL(k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, st, d, poses, pts, chi2, depth_pos);
+}
+inline void launch_epilogue(hipStream_t st, const Dev& d, const double* poses, const double* pts, double* chi2, uint8_t* depth_pos, const kb8::Rig& rig)
+{
+    hipLaunchKernelGGL(k_epilogue_rig, dim3((d.nE + 255) / 256), dim3(256), 0, st, d, rig, poses, pts, chi2, depth_pos);
+}
+
 __global__ void k_normalize_poses(double* poses, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -940,10 +874,7 @@ struct lba_shard {
     int device = 0;
     hipStream_t stream = nullptr;
     lba::Dev d;
-    bool kb8_on = false;        // the window's camera is the fisheye one of its solver handle (lba_set_camera_kb8): the _kb8 kernels run
-    kb8::Cam kb8;
-    bool rig_on = false;        // ... or the rig of two (lba_set_rig_kb8): the _rig kernels run, rig.kind = this window's per-edge cameras
-    kb8::Rig rig;
+    kb8::CameraChoice camera;   // the window's camera is that of its solver handle (lba_set_camera_kb8, lba_set_rig_kb8); rig.kind = this window's per-edge cameras
     int nblk = 0;
     std::vector<void*> allocs;
     double *poses[2] = {nullptr, nullptr}, *pts[2] = {nullptr, nullptr};
@@ -1079,14 +1010,6 @@ static int rig_reject_kinds(const LbaProblem* p)
     return ORBX_OK;
 }
 
-static int kb8_from_abi(const OrbxKB8* cam, kb8::Cam* out)
-{
-    if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
-    out->fx = cam->fx; out->fy = cam->fy; out->cx = cam->cx; out->cy = cam->cy;
-    for (int k = 0; k < 4; k++) out->k[k] = cam->k[k];
-    return ORBX_OK;
-}
-
 struct lba_solver {                 // also a window slot of an lba_batch, with the batch's stream and a view of its scalars
     int device = 0;
     uint8_t* arena = nullptr;
@@ -1095,10 +1018,7 @@ struct lba_solver {                 // also a window slot of an lba_batch, with 
     stage::HostScalars hs;
     uint8_t* stage = nullptr;       // pinned mirror of the arena prefix that holds the uploaded arrays
     size_t stage_cap = 0;
-    bool kb8_on = false;            // lba_set_camera_kb8
-    kb8::Cam kb8;
-    bool rig_on = false;            // lba_set_rig_kb8
-    kb8::Rig rig;
+    kb8::CameraChoice camera;       // lba_set_camera_kb8, lba_set_rig_kb8
     ~lba_solver()
     {
         if (arena) (void)hipFree(arena);
@@ -1131,15 +1051,14 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     if (!out) return fail(ORBX_ERR_ARG, "out is NULL");
     *out = nullptr;
     int r = shard_validate(p);
-    if (!r && owner && owner->kb8_on) r = kb8_reject_stereo(p);
-    if (!r && owner && owner->rig_on) r = rig_reject_kinds(p);
+    if (!r && owner && owner->camera.kind == kb8::CameraChoice::kFisheye) r = kb8_reject_stereo(p);
+    if (!r && owner && owner->camera.kind == kb8::CameraChoice::kRig) r = rig_reject_kinds(p);
     if (r || (r = stage::check_device(device))) return r;
     ORBX_HIP(hipSetDevice(device));
     lba_shard* s = new lba_shard();
     s->device = device;
     if (owner) {
-        s->kb8_on = owner->kb8_on; s->kb8 = owner->kb8;
-        s->rig_on = owner->rig_on; s->rig = owner->rig;
+        s->camera = owner->camera;
         s->arena = owner->arena; s->arena_cap = owner->arena_cap;
         s->stream = owner->stream; s->owns_stream = false;
         s->hs = owner->hs.view();
@@ -1252,11 +1171,11 @@ static int shard_create_impl(int device, const LbaProblem* p, lba_shard** out, l
     LBA_TRY(s->upload_raw(&d.e_point, p->edge_point, (size_t)d.nE)); LBA_TRY(s->upload_raw(&d.e_pose, p->edge_pose, (size_t)d.nE));
     LBA_TRY(s->upload_raw(&d.e_obs, p->edge_obs, 3 * (size_t)d.nE));
     LBA_TRY(s->upload_raw(&d.e_w, p->edge_inv_sigma2, (size_t)d.nE)); 
-    if (!s->rig_on) LBA_TRY(s->upload_raw(&d.e_stereo, p->edge_stereo, (size_t)d.nE));
+    if (s->camera.kind != kb8::CameraChoice::kRig) LBA_TRY(s->upload_raw(&d.e_stereo, p->edge_stereo, (size_t)d.nE));
     else {      // a rig edge has two residual rows: the kernels' "third row" flag is 0, the camera of an edge travels in an array of its own
         const std::vector<uint8_t> zeros((size_t)d.nE, 0);
         LBA_TRY(s->upload(&d.e_stereo, zeros));
-        LBA_TRY(s->upload_raw(&s->rig.kind, p->edge_stereo, (size_t)d.nE));
+        LBA_TRY(s->upload_raw(&s->camera.rig.kind, p->edge_stereo, (size_t)d.nE));
     }
     LBA_TRY(s->upload(&d.l_off, l_off)); LBA_TRY(s->upload(&d.l_edge, l_edge)); LBA_TRY(s->upload(&d.p_off, p_off)); LBA_TRY(s->upload(&d.p_edge, p_edge));
     LBA_TRY(s->upload(&d.b_i, b_i)); LBA_TRY(s->upload(&d.b_j, b_j)); LBA_TRY(s->upload(&d.b_off, b_off)); LBA_TRY(s->upload(&d.b_pair, pairs));
@@ -1335,6 +1254,23 @@ extern "C" int lba_debug_tile_prof(unsigned long long* out8)
 extern "C" int lba_shard_create(int device, const LbaProblem* p, lba_shard** out) { return shard_create_impl(device, p, out, nullptr); }
 
 extern "C" {
+
+// The accepted state of a window on its way to the host, on the shard's stream: the epilogue kernel if chi2 or the depth signs are
+// wanted, then the poses ([nPoses][7]) and whichever of the three other arrays has a destination.  The caller synchronises.
+static int shard_enqueue_results(lba_shard* s, void* poses7, void* points, void* chi2_per_edge, void* depth_positive)
+{
+    const lba::Dev& d = s->d;
+    const double *P = s->poses[s->cur], *X = s->pts[s->cur];
+    if (d.nE > 0 && (chi2_per_edge || depth_positive))
+        kb8::with_camera(s->camera, [&](const auto&... cam) { lba::launch_epilogue(s->stream, d, P, X, s->d_chi2, s->d_depth, cam...); });
+    int r = ORBX_OK;
+    ORBX_HIP_FIRST(r, hipGetLastError());
+    ORBX_HIP_FIRST(r, hipMemcpyAsync(poses7, P, 7 * (size_t)d.nPoses * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (points && d.nL > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(points, X, 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (chi2_per_edge && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(chi2_per_edge, s->d_chi2, (size_t)d.nE * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (depth_positive && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(depth_positive, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, s->stream));
+    return r;
+}
 
 // restore the initial estimates (lets a benchmark re-run the optimisation without re-uploading the problem)
 int lba_shard_reset(lba_shard* s)
@@ -1470,19 +1406,13 @@ int lba_shard_linearize(lba_shard* s, double* chi2_local, double* max_diag_poses
     // synchronising path (they are needed for lambda initialisation at the first iteration only).
     const bool reuse = s->err_current;
     s->mark(lba::kStageLinearize);
-    if (!reuse && d.nE > 0) {
-        if (s->rig_on) hipLaunchKernelGGL(lba::k_errors_rig, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->rig, P, X);
-        else if (s->kb8_on) hipLaunchKernelGGL(lba::k_errors_kb8, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->kb8, P, X);
-        else hipLaunchKernelGGL(lba::k_errors, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, P, X);
-    }
+    if (!reuse && d.nE > 0)
+        kb8::with_camera(s->camera, [&](auto... cam) { hipLaunchKernelGGL((lba::k_errors<decltype(cam)...>), dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, cam..., P, X); });
     // one launch for both sides; with a lambda hint (lba_shard_hint_lambda) the landmark workgroups also do their part of the Schur complement
     const double hint = s->hint_lambda;
     s->hint_lambda = -1.0;
-    if (d.nP + d.nL > 0) {
-        if (s->rig_on) hipLaunchKernelGGL(lba::k_lin_all_rig, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->rig, P, X, hint);
-        else if (s->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_kb8, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, s->kb8, P, X, hint);
-        else hipLaunchKernelGGL(lba::k_lin_all, dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, P, X, hint);
-    }
+    if (d.nP + d.nL > 0)
+        kb8::with_camera(s->camera, [&](auto... cam) { hipLaunchKernelGGL((lba::k_lin_all<decltype(cam)...>), dim3(d.nP + (d.nL + 31) / 32), dim3(256), 0, s->stream, d, cam..., P, X, hint); });
     s->schur_lambda = hint;
     s->mark(lba::kStageIdle);
     if (!reuse) {
@@ -1556,9 +1486,9 @@ int lba_shard_finish(lba_shard* s, double lambda, double* chi2_local_new, double
     }
     s->mark(lba::kStageUpdate);
     const dim3 upd_grid(std::max((d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks, 1));
-    if (s->rig_on) hipLaunchKernelGGL(lba::k_update_errors_rig, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->rig, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
-    else if (s->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_kb8, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, s->kb8, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
-    else hipLaunchKernelGGL(lba::k_update_errors, upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    kb8::with_camera(s->camera, [&](auto... cam) {
+        hipLaunchKernelGGL((lba::k_update_errors<decltype(cam)...>), upd_grid, dim3(lba::kUpdThreads), 0, s->stream, d, cam..., lambda, X, (const double*)Pn, Xn, s->hs.d, ++s->hs.seq);
+    });
     s->mark(lba::kStageIdle);
     ORBX_HIP(hipGetLastError());
     int r = s->hs.wait(s->stream);
@@ -1591,19 +1521,10 @@ int lba_shard_download(lba_shard* s, double* pose_q, double* pose_t, double* poi
 {
     if (!s) return fail(ORBX_ERR_ARG, "NULL shard");
     ORBX_HIP(hipSetDevice(s->device));
-    const lba::Dev& d = s->d;
-    if (d.nE > 0 && s->rig_on)
-        hipLaunchKernelGGL(lba::k_epilogue_rig, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, s->rig, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-    else if (d.nE > 0)
-        hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, s->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-    ORBX_HIP(hipGetLastError());
-    std::vector<double> poses(7 * (size_t)d.nPoses);
-    ORBX_HIP(hipMemcpyAsync(poses.data(), s->poses[s->cur], poses.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (points && d.nL > 0) ORBX_HIP(hipMemcpyAsync(points, s->pts[s->cur], 3 * (size_t)d.nL * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (chi2_per_edge && d.nE > 0) ORBX_HIP(hipMemcpyAsync(chi2_per_edge, s->d_chi2, (size_t)d.nE * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (depth_positive && d.nE > 0) ORBX_HIP(hipMemcpyAsync(depth_positive, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, s->stream));
+    std::vector<double> poses(7 * (size_t)s->d.nPoses);
+    if (int r = shard_enqueue_results(s, poses.data(), points, chi2_per_edge, depth_positive)) return r;
     ORBX_HIP(hipStreamSynchronize(s->stream));
-    stage::split_poses7(poses.data(), d.nPoses, pose_q, pose_t);
+    stage::split_poses7(poses.data(), s->d.nPoses, pose_q, pose_t);
     return ORBX_OK;
 }
 
@@ -1720,25 +1641,8 @@ void lba_destroy(lba_solver* s)
     delete s;
 }
 
-int lba_set_camera_kb8(lba_solver* s, const OrbxKB8* cam)
-{
-    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!cam) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
-    kb8::Cam c;
-    if (int r = kb8_from_abi(cam, &c)) return r;
-    s->kb8 = c; s->kb8_on = true; s->rig_on = false;        // the last setter wins
-    return ORBX_OK;
-}
-
-int lba_set_rig_kb8(lba_solver* s, const OrbxKB8Rig* rig)
-{
-    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!rig) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
-    kb8::Rig g;
-    if (int r = kb8::rig_from_abi(rig, &g)) return r;
-    s->rig = g; s->rig_on = true; s->kb8_on = false;
-    return ORBX_OK;
-}
+int lba_set_camera_kb8(lba_solver* s, const OrbxKB8* cam) { return s ? s->camera.set(cam) : fail(ORBX_ERR_ARG, "NULL solver"); }
+int lba_set_rig_kb8(lba_solver* s, const OrbxKB8Rig* rig) { return s ? s->camera.set(rig) : fail(ORBX_ERR_ARG, "NULL solver"); }
 
 int lba_solve(lba_solver* sv, const LbaProblem* problem, const volatile uint8_t* stop_flag, int max_iters, double lambda_init,
               double* pose_q_out, double* pose_t_out, double* points_out,
@@ -1783,10 +1687,7 @@ struct lba_batch : stage::Batch {       // its stream, the two events around the
     lba::BWin* d_wins = nullptr;
     stage::HostScalars hs;              // 16 doubles per slot
     double last_device_ms = 0.0;
-    bool kb8_on = false;                // lba_batch_set_camera_kb8: one fisheye camera for every window of a call
-    kb8::Cam kb8;
-    bool rig_on = false;                // lba_batch_set_rig_kb8: one rig for every window of a call
-    kb8::Rig rig;
+    kb8::CameraChoice camera;           // lba_batch_set_camera_kb8, lba_batch_set_rig_kb8: one camera for every window of a call
     const uint8_t** d_kinds = nullptr;  // [kMaxBatch] the per-edge camera array of each window of a rig call (kb8::Rig::kind_tab)
     stage::PinnedOut out;               // the results of all windows (one synchronisation per call)
     ~lba_batch()
@@ -1818,25 +1719,8 @@ void lba_batch_destroy(lba_batch* b) { stage::close(b); }
 
 double lba_batch_last_device_ms(const lba_batch* b) { return b ? b->last_device_ms : 0.0; }
 
-int lba_batch_set_camera_kb8(lba_batch* b, const OrbxKB8* cam)
-{
-    if (!b) return fail(ORBX_ERR_ARG, "NULL batch");
-    if (!cam) { b->kb8_on = false; b->rig_on = false; return ORBX_OK; }
-    kb8::Cam c;
-    if (int r = kb8_from_abi(cam, &c)) return r;
-    b->kb8 = c; b->kb8_on = true; b->rig_on = false;        // the last setter wins
-    return ORBX_OK;
-}
-
-int lba_batch_set_rig_kb8(lba_batch* b, const OrbxKB8Rig* rig)
-{
-    if (!b) return fail(ORBX_ERR_ARG, "NULL batch");
-    if (!rig) { b->kb8_on = false; b->rig_on = false; return ORBX_OK; }
-    kb8::Rig g;
-    if (int r = kb8::rig_from_abi(rig, &g)) return r;
-    b->rig = g; b->rig_on = true; b->kb8_on = false;
-    return ORBX_OK;
-}
+int lba_batch_set_camera_kb8(lba_batch* b, const OrbxKB8* cam) { return b ? b->camera.set(cam) : fail(ORBX_ERR_ARG, "NULL batch"); }
+int lba_batch_set_rig_kb8(lba_batch* b, const OrbxKB8Rig* rig) { return b ? b->camera.set(rig) : fail(ORBX_ERR_ARG, "NULL batch"); }
 
 int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* outputs, int n_windows,
                     const volatile uint8_t* const* stop_flags, int max_iters, double lambda_init, LbaStats* stats_out)
@@ -1844,25 +1728,20 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     if (!b || !problems || n_windows < 0) return fail(ORBX_ERR_ARG, "NULL argument");
     if (n_windows > lba::kMaxBatch) return fail(ORBX_ERR_CAPACITY, "at most %d windows per call", lba::kMaxBatch);
     if (n_windows == 0) return ORBX_OK;
-    if (b->kb8_on)          // every window's check before the first one touches the device
-        for (int i = 0; i < n_windows; i++) {
-            int rc = shard_validate(&problems[i]);
-            if (rc || (rc = kb8_reject_stereo(&problems[i]))) return rc;
-        }
-    if (b->rig_on)
-        for (int i = 0; i < n_windows; i++) {
-            int rc = shard_validate(&problems[i]);
-            if (rc || (rc = rig_reject_kinds(&problems[i]))) return rc;
-        }
+    const bool fisheye = b->camera.kind == kb8::CameraChoice::kFisheye, rig = b->camera.kind == kb8::CameraChoice::kRig;
+    for (int i = 0; i < n_windows && (fisheye || rig); i++) {       // every window's check before the first one touches the device
+        int rc = shard_validate(&problems[i]);
+        if (rc || (rc = fisheye ? kb8_reject_stereo(&problems[i]) : rig_reject_kinds(&problems[i]))) return rc;
+    }
     ORBX_HIP(hipSetDevice(b->device));
-    if (b->rig_on && !b->d_kinds) ORBX_HIP(hipMalloc((void**)&b->d_kinds, lba::kMaxBatch * sizeof(const uint8_t*)));
+    if (rig && !b->d_kinds) ORBX_HIP(hipMalloc((void**)&b->d_kinds, lba::kMaxBatch * sizeof(const uint8_t*)));
     const int W = n_windows;
     while ((int)b->slots.size() < W) {
         lba_solver* sv = new lba_solver();
         sv->device = b->device; sv->stream = b->stream; sv->hs = b->hs.view((int)b->slots.size());
         b->slots.push_back(sv);
     }
-    for (int i = 0; i < W; i++) { b->slots[i]->kb8_on = b->kb8_on; b->slots[i]->kb8 = b->kb8; b->slots[i]->rig_on = b->rig_on; b->slots[i]->rig = b->rig; }
+    for (int i = 0; i < W; i++) b->slots[i]->camera = b->camera;
     std::vector<lba_shard*> sh((size_t)W, nullptr);
     std::vector<size_t> wanted((size_t)W, 0), wanted_stage((size_t)W, 0);
     int r = ORBX_OK;
@@ -1887,7 +1766,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         lba::BWin& w = hw[i];
         w.d = s->d; w.poses[0] = s->poses[0]; w.poses[1] = s->poses[1]; w.pts[0] = s->pts[0]; w.pts[1] = s->pts[1];
         w.S = s->S(); w.bs = s->bs(); w.bpf = s->bpf(); w.diag = s->diag(); w.Lp = s->Lp; w.Linv = s->Linv; w.hmap = s->hs.d; w.flow = s->flow; w.nblk = s->nblk;
-        hkinds[i] = s->rig.kind;
+        hkinds[i] = s->camera.rig.kind;
         const lba::Dev& d = s->d;
         max_lin = std::max(max_lin, d.nP + (d.nL + 31) / 32); max_e = std::max(max_e, (d.nE + 255) / 256); max_lm = std::max(max_lm, (d.nL + 7) / 8);
         max_sb = std::max(max_sb, d.nBlocks + d.nP); max_nblk = std::max(max_nblk, s->nblk); max_upd = std::max(max_upd, (d.nL + lba::kUpdLandmarks - 1) / lba::kUpdLandmarks);
@@ -1898,12 +1777,12 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
     if (chol::allow_lds(lba::k_chol_step_b, chol::kStepLds) || chol::allow_lds(lba::k_chol_flow_b, chol::kStepLds) ||
         chol::allow_lds(lba::k_chol_solve_update_b, chol::kFusedSolveLds) ||
         hipMemcpyAsync(b->d_wins, hw.data(), (size_t)W * sizeof(lba::BWin), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
-        (b->rig_on && hipMemcpyAsync(b->d_kinds, hkinds.data(), (size_t)W * sizeof(const uint8_t*), hipMemcpyHostToDevice, b->stream) != hipSuccess)) {
+        (rig && hipMemcpyAsync(b->d_kinds, hkinds.data(), (size_t)W * sizeof(const uint8_t*), hipMemcpyHostToDevice, b->stream) != hipSuccess)) {
         cleanup();
         return fail(ORBX_ERR_HIP, "batch setup failed");
     }
-    kb8::Rig brig = b->rig;
-    brig.kind = nullptr; brig.kind_tab = b->d_kinds;
+    kb8::CameraChoice bcam = b->camera;         // (the rig of the launches: no edge kinds of its own, the table of the windows')
+    bcam.rig.kind = nullptr; bcam.rig.kind_tab = b->d_kinds;
     (void)hipEventRecord(b->ev0, b->stream);
 
     // ---- one Levenberg controller per window (the control flow of lba_shard_optimize, cut at the points where it waits for the device);
@@ -1938,16 +1817,10 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
         }
         if (!any_lin && !any_trial) break;
         hipStream_t st = b->stream;
-        if (any_err) {
-            if (b->rig_on) hipLaunchKernelGGL(lba::k_errors_b_rig, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, brig);
-            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_errors_b_kb8, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, b->kb8);
-            else hipLaunchKernelGGL(lba::k_errors_b, dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
-        }
-        if (any_lin) {
-            if (b->rig_on) hipLaunchKernelGGL(lba::k_lin_all_b_rig, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, brig);
-            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_lin_all_b_kb8, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
-            else hipLaunchKernelGGL(lba::k_lin_all_b, dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn);
-        }
+        if (any_err)
+            kb8::with_camera(bcam, [&](auto... cam) { hipLaunchKernelGGL((lba::k_errors_b<decltype(cam)...>), dim3(max_e, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, 0, cam...); });
+        if (any_lin)
+            kb8::with_camera(bcam, [&](auto... cam) { hipLaunchKernelGGL((lba::k_lin_all_b<decltype(cam)...>), dim3(max_lin, W), dim3(256), 0, st, (const lba::BWin*)b->d_wins, dyn, cam...); });
         if (any_err) hipLaunchKernelGGL(lba::k_reduce_b, dim3(1, W), dim3(1024), 0, st, (const lba::BWin*)b->d_wins, dyn, 0);
         if (any_trial) {
             if (any_lm) hipLaunchKernelGGL(lba::k_schur_landmarks_b, dim3(max_lm, W), dim3(64), 0, st, (const lba::BWin*)b->d_wins, dyn);
@@ -1965,9 +1838,9 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
                 }
             }
             hipLaunchKernelGGL(lba::k_chol_solve_update_b, dim3(1, W), dim3(1024), solve_lds, st, (const lba::BWin*)b->d_wins, dyn);
-            if (b->rig_on) hipLaunchKernelGGL(lba::k_update_errors_b_rig, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, brig);
-            else if (b->kb8_on) hipLaunchKernelGGL(lba::k_update_errors_b_kb8, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, b->kb8);
-            else hipLaunchKernelGGL(lba::k_update_errors_b, dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn);
+            kb8::with_camera(bcam, [&](auto... cam) {
+                hipLaunchKernelGGL((lba::k_update_errors_b<decltype(cam)...>), dim3(max_upd, W), dim3(lba::kUpdThreads), 0, st, (const lba::BWin*)b->d_wins, dyn, cam...);
+            });
         }
         if (hipGetLastError() != hipSuccess) { r = fail(ORBX_ERR_HIP, "batched launch failed"); break; }
         // results of the round: every window that ran a reduction publishes its sequence number last
@@ -2016,14 +1889,7 @@ int lba_solve_batch(lba_batch* b, const LbaProblem* problems, const LbaOutputs* 
             const lba::Dev& d = s->d;
             const LbaOutputs& o = outputs[i];
             const stage::PinnedOut::Slice h = po.slice(po.h + po.off[i], 7 * (size_t)d.nPoses * 8, d.nL, d.nE);
-            if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive) && s->rig_on)
-                hipLaunchKernelGGL(lba::k_epilogue_rig, dim3((d.nE + 255) / 256), dim3(256), 0, b->stream, d, s->rig, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-            else if (d.nE > 0 && (o.chi2_per_edge || o.depth_positive))
-                hipLaunchKernelGGL(lba::k_epilogue, dim3((d.nE + 255) / 256), dim3(256), 0, b->stream, d, (const double*)s->poses[s->cur], (const double*)s->pts[s->cur], s->d_chi2, s->d_depth);
-            ORBX_HIP_FIRST(r, hipMemcpyAsync(h.state, s->poses[s->cur], 7 * (size_t)d.nPoses * 8, hipMemcpyDeviceToHost, b->stream));
-            if (o.points && d.nL > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.points, s->pts[s->cur], 3 * (size_t)d.nL * 8, hipMemcpyDeviceToHost, b->stream));
-            if (o.chi2_per_edge && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.chi2, s->d_chi2, (size_t)d.nE * 8, hipMemcpyDeviceToHost, b->stream));
-            if (o.depth_positive && d.nE > 0) ORBX_HIP_FIRST(r, hipMemcpyAsync(h.depth, s->d_depth, (size_t)d.nE, hipMemcpyDeviceToHost, b->stream));
+            r = shard_enqueue_results(s, h.state, o.points ? h.points : nullptr, o.chi2_per_edge ? h.chi2 : nullptr, o.depth_positive ? h.depth : nullptr);
         }
         if (!r) {
             ORBX_HIP_FIRST(r, hipStreamSynchronize(b->stream));

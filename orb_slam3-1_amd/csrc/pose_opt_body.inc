@@ -1,7 +1,7 @@
-// pose_opt_body.inc -- the body of k_pose_opt (pose_solver.hip), included once per camera: the text of a kernel, not a function.
+// pose_opt_body.inc -- the body of the kernel template k_pose_opt (pose_solver.hip): the text of a kernel, not a function.
 // Expects: problems (const ProblemDev*), cam (a camera policy: Pinhole, Fisheye or RigCam), STEREO (bool constant), kRegEdges (int constant).
-// (As a __device__ function template shared by the two kernels the same statements compiled to other code for the pinhole kernels:
-// other register allocation throughout, DESIGN.md 4f / 4g.  Included as text, the pinhole kernels are the ones they were.)
+// (As a __device__ function template called by the kernels the same statements compiled to other code for the pinhole kernels:
+// other register allocation throughout, DESIGN.md 4f / 4g.  As the text of one templated kernel every instantiation is what it was, 4j.1.)
     __shared__ double s_acc[28][kAccRow];       // per-thread partials of H (21), b (6), chi2 (1), transposed
     __shared__ double s_out[28];
     __shared__ double s_red[4];

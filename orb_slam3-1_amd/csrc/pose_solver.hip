@@ -189,24 +189,16 @@ constexpr int kAccRow = 264;        // 256 partials + one pad per 32 (bank sprea
 // The Levenberg state (pose, lambda, chi2, counters) and the 6x6 solve are REPLICATED in every thread: all lanes run the
 // same scalar code on the same reduced values, so no broadcast barriers sit between the solve, the trial pass and the
 // accept / reject decision -- the only synchronisation left is inside the two block reductions.
-template <bool STEREO, int kRegEdges>
-__global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__ problems)
+// The camera is a pack: empty for the pinhole kernels (no camera argument), else the one Fisheye / RigCam the kernel receives by value
+// (monocular edges only, or left and right fisheye edges interleaved with the kind of an edge in the problem's stereo byte: kStereo is
+// false in both).
+__device__ __forceinline__ Pinhole camera_arg() { return Pinhole(); }
+template <class C> __device__ __forceinline__ const C& camera_arg(const C& c) { return c; }
+template <bool kStereo, int kRegEdges, class... CamT>
+__global__ __launch_bounds__(256) void k_pose_opt(const ProblemDev* __restrict__ problems, CamT... cam_arg)
 {
-    const Pinhole cam;
-#include "pose_opt_body.inc"
-}
-// the fisheye instantiation: monocular edges only, the camera of the handle by value
-template <int kRegEdges>
-__global__ __launch_bounds__(256) void k_pose_opt_kb8(const ProblemDev* __restrict__ problems, const Fisheye cam)
-{
-    constexpr bool STEREO = false;
-#include "pose_opt_body.inc"
-}
-// the rig instantiation: left and right fisheye edges interleaved, the kind of an edge in the problem's stereo byte
-template <int kRegEdges>
-__global__ __launch_bounds__(256) void k_pose_opt_rig(const ProblemDev* __restrict__ problems, const RigCam cam)
-{
-    constexpr bool STEREO = false;
+    constexpr bool STEREO = kStereo;
+    const auto& cam = camera_arg(cam_arg...);
 #include "pose_opt_body.inc"
 }
 
@@ -318,40 +310,38 @@ __global__ __launch_bounds__(256) void k_kb8_project(kb8::Cam c, const double* _
 struct pose_solver : stage::Batch {
     uint8_t* d_dev = nullptr;       // arena of the device-resident entry (edge slots, problem descriptors, results)
     size_t dev_cap = 0;
-    bool kb8_on = false;            // pose_set_camera_kb8: the fisheye camera replaces fx .. bf of every problem
-    poseopt::Fisheye kb8;
-    bool rig_on = false;            // pose_set_rig_kb8: two fisheye cameras, the stereo byte of an edge names its camera
-    poseopt::RigCam rig;
+    kb8::CameraChoice camera;       // pose_set_camera_kb8: the fisheye camera replaces fx .. bf of every problem; pose_set_rig_kb8: two of them,
+                                    // the stereo byte of an edge names its camera
     ~pose_solver() { if (d_dev) (void)hipFree(d_dev); }
 };
 
 namespace {
-inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p, const poseopt::Fisheye* kb8 = nullptr,
-                        const poseopt::RigCam* rig = nullptr)
+inline poseopt::Fisheye policy(const kb8::Cam& c) { return poseopt::Fisheye{c}; }
+inline poseopt::RigCam policy(const kb8::Rig& g) { return poseopt::RigCam{g}; }
+
+// cam: nothing (pinhole; the stereo instantiation if the batch holds a stereo edge), or the Fisheye / RigCam of the handle
+template <class... CamT>
+inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, const poseopt::ProblemDev* p, const CamT&... cam)
 {
-    if (rig) {
-        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt_rig<4>), dim3(n), dim3(256), 0, st, p, *rig);
-        else hipLaunchKernelGGL((poseopt::k_pose_opt_rig<2>), dim3(n), dim3(256), 0, st, p, *rig);
-    } else if (kb8) {
-        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<4>), dim3(n), dim3(256), 0, st, p, *kb8);
-        else hipLaunchKernelGGL((poseopt::k_pose_opt_kb8<2>), dim3(n), dim3(256), 0, st, p, *kb8);
-    } else if (stereo) {
-        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<true, 4>), dim3(n), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((poseopt::k_pose_opt<true, 2>), dim3(n), dim3(256), 0, st, p);
-    } else {
-        if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<false, 4>), dim3(n), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((poseopt::k_pose_opt<false, 2>), dim3(n), dim3(256), 0, st, p);
+    if constexpr (sizeof...(CamT) == 0) {
+        if (stereo) {
+            if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<true, 4>), dim3(n), dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((poseopt::k_pose_opt<true, 2>), dim3(n), dim3(256), 0, st, p);
+            return;
+        }
     }
+    if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<false, 4, CamT...>), dim3(n), dim3(256), 0, st, p, cam...);
+    else hipLaunchKernelGGL((poseopt::k_pose_opt<false, 2, CamT...>), dim3(n), dim3(256), 0, st, p, cam...);
 }
 
 int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
 {
     if (!s || !problems || !results || n_problems < 1) return fail(ORBX_ERR_ARG, "bad arguments");
-    if (s->kb8_on)          // a fisheye frame is monocular (or a two-camera rig, which this library does not take): before any device work
+    if (s->camera.kind == kb8::CameraChoice::kFisheye)          // a fisheye frame is monocular (or a two-camera rig, which this library does not take): before any device work
         for (int i = 0; i < n_problems; i++)
             for (int k = 0; k < problems[i].n && problems[i].stereo; k++)
                 if (problems[i].stereo[k]) return fail(ORBX_ERR_ARG, "problem %d: edge %d is stereo, the handle's camera is KannalaBrandt8", i, k);
-    if (s->rig_on)          // a rig frame holds left (0) and right (ORBX_EDGE_RIGHT) edges only: before any device work
+    if (s->camera.kind == kb8::CameraChoice::kRig)          // a rig frame holds left (0) and right (ORBX_EDGE_RIGHT) edges only: before any device work
         for (int i = 0; i < n_problems; i++)
             for (int k = 0; k < problems[i].n && problems[i].stereo; k++)
                 if (problems[i].stereo[k] != 0 && problems[i].stereo[k] != ORBX_EDGE_RIGHT)
@@ -407,9 +397,9 @@ int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, 
         d.result = (PoseResult*)(base + res_off) + i;
         descs[i] = d;
     }
-    const int rr = stage::run(*s, up_bytes, res_off, down_end,
-                              [&] { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base, s->kb8_on ? &s->kb8 : nullptr,
-                                                 s->rig_on ? &s->rig : nullptr); });
+    const int rr = stage::run(*s, up_bytes, res_off, down_end, [&] {
+        kb8::with_camera(s->camera, [&](const auto&... cam) { pose_launch(any_stereo, n_max > 512, n_problems, s->stream, (const poseopt::ProblemDev*)base, policy(cam)...); });
+    });
     if (rr != ORBX_OK) return rr;
     std::memcpy(results, s->h_blob + res_off, sizeof(PoseResult) * (size_t)n_problems);
     if (outlier_out)
@@ -436,8 +426,8 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
                                uint8_t* d_outlier, PoseResult* d_results, void* stream)
 {
     if (!s || !f || batch < 1) return fail(ORBX_ERR_ARG, "bad arguments");
-    if (s->rig_on) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 rig path: reset the camera (pose_set_rig_kb8(s, NULL)) or use pose_optimize_batch");
-    if (s->kb8_on) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 path: reset the camera (pose_set_camera_kb8(s, NULL)) or use pose_optimize_batch");
+    if (s->camera.kind == kb8::CameraChoice::kRig) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 rig path: reset the camera (pose_set_rig_kb8(s, NULL)) or use pose_optimize_batch");
+    if (s->camera.kind == kb8::CameraChoice::kFisheye) return fail(ORBX_ERR_ARG, "pose_optimize_batch_device has no KannalaBrandt8 path: reset the camera (pose_set_camera_kb8(s, NULL)) or use pose_optimize_batch");
     if (!f->d_kps || !f->d_n || !f->d_assign || !f->d_mp_xyz || !f->d_pose || !f->inv_level_sigma2) return fail(ORBX_ERR_ARG, "NULL arrays");
     if (f->cap < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap / mp_cap / n_levels");
     ORBX_HIP(hipSetDevice(s->device));
@@ -481,27 +471,8 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
     return ORBX_OK;
 }
 
-int pose_set_camera_kb8(pose_solver* s, const OrbxKB8* cam)
-{
-    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!cam) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
-    if (!(cam->fx > 0) || !(cam->fy > 0)) return fail(ORBX_ERR_ARG, "KannalaBrandt8 focal lengths must be positive");
-    s->kb8.c.fx = cam->fx; s->kb8.c.fy = cam->fy; s->kb8.c.cx = cam->cx; s->kb8.c.cy = cam->cy;
-    for (int k = 0; k < 4; k++) s->kb8.c.k[k] = cam->k[k];
-    s->kb8_on = true; s->rig_on = false;        // the last setter wins
-    return ORBX_OK;
-}
-
-int pose_set_rig_kb8(pose_solver* s, const OrbxKB8Rig* rig)
-{
-    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
-    if (!rig) { s->kb8_on = false; s->rig_on = false; return ORBX_OK; }
-    kb8::Rig g;
-    if (int r = kb8::rig_from_abi(rig, &g)) return r;
-    s->rig.g = g;
-    s->rig_on = true; s->kb8_on = false;
-    return ORBX_OK;
-}
+int pose_set_camera_kb8(pose_solver* s, const OrbxKB8* cam) { return s ? s->camera.set(cam) : fail(ORBX_ERR_ARG, "NULL solver"); }
+int pose_set_rig_kb8(pose_solver* s, const OrbxKB8Rig* rig) { return s ? s->camera.set(rig) : fail(ORBX_ERR_ARG, "NULL solver"); }
 
 // diagnostic: the two device functions of camera_kb8.h on n points
 int orbx_kb8_project(int device, const OrbxKB8* cam, const double* Xc, int n, double* uv, double* jac)
@@ -512,8 +483,7 @@ int orbx_kb8_project(int device, const OrbxKB8* cam, const double* Xc, int n, do
     if (n == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(device));
     kb8::Cam c;
-    c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
-    for (int k = 0; k < 4; k++) c.k[k] = cam->k[k];
+    kb8::cam_from_abi(*cam, &c);
     double* d = nullptr;
     const size_t N = (size_t)n;
     ORBX_HIP(hipMalloc((void**)&d, 11 * N * sizeof(double)));          // [X 3n | uv 2n | jac 6n]

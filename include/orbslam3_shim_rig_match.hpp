@@ -72,9 +72,8 @@ public:
         const bool bBackward = -tlc(2) > CurrentFrame.mb && !bMono;
         const int levelWindow = bForward ? ORBM_LEVELS_FORWARD : bBackward ? ORBM_LEVELS_BACKWARD : ORBM_LEVELS_AROUND;
         const Sophus::SE3f Trl = CurrentFrame.GetRelativePoseTrl();
-        std::vector<uint8_t> valid(nL, 0), hasObs(nL, 0), desc((size_t)nL * 32, 0);
-        std::vector<float> u(nL, 0.f), v(nL, 0.f), uR(nL, 0.f), vR(nL, 0.f), ang(nL, 0.f);
-        std::vector<int32_t> oct(nL, 0);
+        std::vector<uint8_t> valid(nL, 0);
+        std::vector<float> u(nL, 0.f), v(nL, 0.f), uR(nL, 0.f), vR(nL, 0.f);
         for (int i = 0; i < nL; i++) {
             MapPoint* p = LastFrame.mvpMapPoints[i];
             if (!p || LastFrame.mvbOutlier[i]) continue;
@@ -85,6 +84,23 @@ public:
             const Eigen::Vector3f x3Dr = Trl * x3Dc;                               // :1795
             const Eigen::Vector2f uvr = CurrentFrame.mpCamera->project(x3Dr);      // :1796: mpCamera, not mpCamera2
             valid[i] = 1; u[i] = uv(0); v[i] = uv(1); uR[i] = uvr(0); vR[i] = uvr(1);
+        }
+        return SearchByProjectionProjected(CurrentFrame_, LastFrame_, th, levelWindow, valid.data(), u.data(), v.data(), uR.data(), vR.data());
+    }
+
+    // The last-frame search of a rig frame behind its projection loop: valid / proj_u / proj_v / proj_u_r / proj_v_r [LastFrame.N] as
+    // that loop (or orbm_project_last_rig_batch, through TrackProjectRigHIP) left them; level_window is one of ORBM_LEVELS_*.
+    int SearchByProjectionProjected(Frame& CurrentFrame_, const Frame& LastFrame, const float th, const int levelWindow,
+                                    const uint8_t* valid, const float* u, const float* v, const float* uR, const float* vR)
+    {
+        FrameT& CurrentFrame = static_cast<FrameT&>(CurrentFrame_);
+        const int nL = LastFrame.N;
+        std::vector<uint8_t> hasObs(nL, 0), desc((size_t)nL * 32, 0);
+        std::vector<float> ang(nL, 0.f);
+        std::vector<int32_t> oct(nL, 0);
+        for (int i = 0; i < nL; i++) {
+            if (!valid[i]) continue;
+            MapPoint* p = LastFrame.mvpMapPoints[i];
             const bool lastRight = LastFrame.Nleft != -1 && i >= LastFrame.Nleft;
             if (lastRight) { const cv::KeyPoint& kp = LastFrame.mvKeysRight[i - LastFrame.Nleft]; oct[i] = kp.octave; ang[i] = kp.angle; }    // :1720-1721, :1777-1779
             else { oct[i] = LastFrame.mvKeys[i].octave; ang[i] = LastFrame.Nleft == -1 ? LastFrame.mvKeysUn[i].angle : LastFrame.mvKeys[i].angle; }
@@ -95,7 +111,7 @@ public:
         RigView view(CurrentFrame);
         OrbmRigLastPoints pts;
         pts.n = nL;
-        pts.valid = valid.data(); pts.proj_u = u.data(); pts.proj_v = v.data(); pts.proj_u_r = uR.data(); pts.proj_v_r = vR.data();
+        pts.valid = valid; pts.proj_u = u; pts.proj_v = v; pts.proj_u_r = uR; pts.proj_v_r = vR;
         pts.octave = oct.data(); pts.angle = ang.data(); pts.has_obs = hasObs.data(); pts.desc = desc.data();
         const int n = orbslam3_hip::check(orbm_search_by_projection_last_rig(m_, &view.rig, &pts, th, levelWindow, mbCheckOrientation, view.assign.data(), view.occ.data()));
         for (size_t s = 0; s < view.assign.size(); s++) {

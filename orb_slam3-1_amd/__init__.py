@@ -26,4 +26,5 @@ def build(verbose=False):
 
 from .capi import (OrbxKB8, OrbxKB8Rig, EDGE_RIGHT, kb8_project, OrbxFisheyeRig, fisheye_rig, kb8_triangulate_matches, stereo_fisheye_check, ORBM_FISHEYE_KNN_CHUNK, Extractor, Matcher, LbaSolver, LbaShard, LbaBatch, PoseSolver, Vocabulary, DeviceBowPlan, PacketCodec, InertialSolver, LibaBatch, Sim3Solver, EssentialGraph, ImuInit, FullInertialBA, ImuPreintegrator, sim3_draw_triples, ORBM_MAX_NEIGHBOURS, IMU_DTYPE, lib, KP_DTYPE, OrbxError, hamming,  # noqa: E402,F401
                    device_count, create_new_map_points_rig_check,
-                   FramePose, TrackCamera, LocalPoints, FrustumOut, LastProjOut, TRACK_MAX_BATCH, TRACK_MAX_LEVELS, track_project_check)
+                   FramePose, TrackCamera, LocalPoints, FrustumOut, LastProjOut, TRACK_MAX_BATCH, TRACK_MAX_LEVELS, track_project_check,
+                   TrackRigCamera, RigFramePose, RigFrustumOut, RigLastProjOut, track_rig_camera, track_project_rig_check)

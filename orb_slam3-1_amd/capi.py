@@ -377,6 +377,53 @@ def track_project_check(cam, poses, pts, out, batch):
     return lib.orbm_track_project_check(ref(cam), C.c_void_p(poses) if poses else None, ref(pts), ref(out), int(batch))
 
 
+class TrackRigCamera(C.Structure):
+    """OrbmTrackRigCamera (include/orbslam3_hip_track_project_rig.h)"""
+    _fields_ = [("left", C.c_float * 8), ("right", C.c_float * 8), ("Rrl", C.c_float * 9), ("trl", C.c_float * 3), ("tlr", C.c_float * 3),
+                ("q_rl", C.c_float * 4), ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
+class RigFramePose(C.Structure):
+    """OrbmRigFramePose: 43 floats"""
+    _fields_ = [("left", FramePose), ("Rwc", C.c_float * 9), ("R_r", C.c_float * 9), ("t_r", C.c_float * 3), ("Ow_r", C.c_float * 3)]
+
+
+class RigFrustumOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("in_view", "proj_u", "proj_v", "pred_level", "view_cos", "in_view_r", "proj_u_r", "proj_v_r", "pred_level_r",
+                                          "view_cos_r", "track_depth", "track_depth_r", "n_to_match")]
+
+
+class RigLastProjOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("valid", "proj_u", "proj_v", "proj_u_r", "proj_v_r")]
+
+
+RIG_FRUSTUM_DTYPES = dict(in_view=np.uint8, proj_u=np.float32, proj_v=np.float32, pred_level=np.int32, view_cos=np.float32, in_view_r=np.uint8,
+                          proj_u_r=np.float32, proj_v_r=np.float32, pred_level_r=np.int32, view_cos_r=np.float32, track_depth=np.float32,
+                          track_depth_r=np.float32)
+RIG_LAST_DTYPES = dict(valid=np.uint8, proj_u=np.float32, proj_v=np.float32, proj_u_r=np.float32, proj_v_r=np.float32)
+
+
+def track_rig_camera(cam):
+    """a rig camera dict (synth_track.rig_camera) -> TrackRigCamera"""
+    c = TrackRigCamera()
+    for k in ("left", "right", "Rrl", "trl", "tlr", "q_rl"):
+        a = np.asarray(cam[k], np.float32).reshape(-1)
+        getattr(c, k)[:] = [float(v) for v in a]
+    for k in ("min_x", "min_y", "max_x", "max_y", "log_scale_factor"):
+        setattr(c, k, float(cam[k]))
+    c.n_levels = int(cam["n_levels"])
+    return c
+
+
+def track_project_rig_check(cam, poses, pts, out, batch):
+    """orbm_track_project_rig_check (host only): cam / pts / out are TrackRigCamera / LocalPoints / RigFrustumOut or None, poses an
+    address or None.  Returns the code."""
+    lib.orbm_track_project_rig_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    ref = lambda s: C.cast(C.pointer(s), C.c_void_p) if s is not None else None
+    return lib.orbm_track_project_rig_check(ref(cam), C.c_void_p(poses) if poses else None, ref(pts), ref(out), int(batch))
+
+
 class Matcher:
     """ORB_SLAM3::ORBmatcher (reference include/ORBmatcher.h:40-106): ORBmatcher(nnratio=0.6, checkOri=true)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
@@ -647,6 +694,73 @@ class Matcher:
         lib.orbm_track_project_last_kernel_ms.restype = C.c_float
         lib.orbm_track_project_last_kernel_ms.argtypes = [C.c_void_p]
         return float(lib.orbm_track_project_last_kernel_ms(self._h))
+
+    # ---- include/orbslam3_hip_track_project_rig.h: the same projections for two-camera fisheye rig frames ----
+    def rig_frame_pose_batch_device(self, cam, d_pose, batch, normalise, d_rig_pose, stream=None):
+        """orbm_rig_frame_pose_batch_device: d_pose [batch][7] double -> d_rig_pose [batch] RigFramePose records.  Only enqueues."""
+        lib.orbm_rig_frame_pose_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        c = track_rig_camera(cam)
+        _check(lib.orbm_rig_frame_pose_batch_device(self._h, C.byref(c), C.c_void_p(d_pose), int(batch), int(normalise), C.c_void_p(d_rig_pose), C.c_void_p(stream or 0)))
+
+    def frustum_rig_batch_device(self, cam, d_rig_pose, pts, cos_limit, out, batch, stream=None):
+        """orbm_frustum_rig_batch_device: pts as frustum_batch_device; out = the 13 device addresses in the order of RigFrustumOut."""
+        lib.orbm_frustum_rig_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        c, p, o = track_rig_camera(cam), LocalPoints(*pts[:7], int(pts[7])), RigFrustumOut(*out)
+        _check(lib.orbm_frustum_rig_batch_device(self._h, C.byref(c), C.c_void_p(d_rig_pose), C.byref(p), C.c_float(cos_limit), C.byref(o), int(batch), C.c_void_p(stream or 0)))
+
+    def project_last_rig_batch_device(self, cam, d_rig_pose, d_mp_xyz, d_has_point, d_n, cap, out, batch, stream=None):
+        """orbm_project_last_rig_batch_device: out = (d_valid, d_proj_u, d_proj_v, d_proj_u_r, d_proj_v_r).  Only enqueues."""
+        lib.orbm_project_last_rig_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        c, o = track_rig_camera(cam), RigLastProjOut(*out)
+        _check(lib.orbm_project_last_rig_batch_device(self._h, C.byref(c), C.c_void_p(d_rig_pose), C.c_void_p(d_mp_xyz), C.c_void_p(d_has_point), C.c_void_p(d_n),
+                                                      int(cap), C.byref(o), int(batch), C.c_void_p(stream or 0)))
+
+    def unproject_stereo_fisheye_batch_device(self, d_rig_pose, d_points, d_valid, d_n, cap, d_world, batch, stream=None):
+        """orbm_unproject_stereo_fisheye_batch_device.  Only enqueues."""
+        lib.orbm_unproject_stereo_fisheye_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _check(lib.orbm_unproject_stereo_fisheye_batch_device(self._h, C.c_void_p(d_rig_pose), C.c_void_p(d_points), C.c_void_p(d_valid), C.c_void_p(d_n), int(cap),
+                                                              C.c_void_p(d_world), int(batch), C.c_void_p(stream or 0)))
+
+    def frustum_rig_batch(self, case, rig_poses, state):
+        """orbm_frustum_rig_batch on host arrays: case as synth_track.make_rig_local_map_case, rig_poses [batch][43] float32, state a
+        dict of the twelve [batch][pcap] arrays of RIG_FRUSTUM_DTYPES as the caller holds them (copied, not modified).  Returns
+        the arrays after the call plus n_to_match."""
+        lib.orbm_frustum_rig_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int]
+        B, pcap = case["skip"].shape
+        fp = np.ascontiguousarray(rig_poses, np.float32).reshape(B, 43)
+        keep = [np.ascontiguousarray(case[k], np.float32) for k in ("xyz", "normal", "min_distance", "max_distance")] + \
+               [np.ascontiguousarray(case[k], np.uint8) for k in ("skip", "bad")] + [np.ascontiguousarray(case["n"], np.int32)]
+        res = {k: np.array(state[k], dt, order="C").reshape(B, pcap) for k, dt in RIG_FRUSTUM_DTYPES.items()}
+        res["n_to_match"] = np.zeros(B, np.int32)
+        c, p, o = track_rig_camera(case["cam"]), LocalPoints(*[a.ctypes.data for a in keep], pcap), RigFrustumOut(*[a.ctypes.data for a in res.values()])
+        _check(lib.orbm_frustum_rig_batch(self._h, C.byref(c), _p(fp), C.byref(p), C.c_float(case["cos_limit"]), C.byref(o), B))
+        return res
+
+    def project_last_rig_batch(self, case, rig_poses):
+        """orbm_project_last_rig_batch on host arrays: case as synth_track.make_rig_last_frame_case"""
+        lib.orbm_project_last_rig_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        B, cap = case["has_point"].shape
+        fp = np.ascontiguousarray(rig_poses, np.float32).reshape(B, 43)
+        xyz, has, n = np.ascontiguousarray(case["xyz"], np.float32), np.ascontiguousarray(case["has_point"], np.uint8), np.ascontiguousarray(case["n"], np.int32)
+        res = {k: np.zeros((B, cap), dt) for k, dt in RIG_LAST_DTYPES.items()}
+        c, o = track_rig_camera(case["cam"]), RigLastProjOut(*[a.ctypes.data for a in res.values()])
+        _check(lib.orbm_project_last_rig_batch(self._h, C.byref(c), _p(fp), _p(xyz), _p(has), _p(n), cap, C.byref(o), B))
+        return res
+
+    def unproject_stereo_fisheye_batch(self, rig_poses, points, valid, n, world):
+        """orbm_unproject_stereo_fisheye_batch on host arrays; `world` [batch][cap][3] float32 is copied and returned"""
+        lib.orbm_unproject_stereo_fisheye_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        B, cap = np.asarray(valid).shape
+        fp = np.ascontiguousarray(rig_poses, np.float32).reshape(B, 43)
+        pts, val, nn = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(valid, np.uint8), np.ascontiguousarray(n, np.int32)
+        w = np.array(world, np.float32, order="C").reshape(B, cap, 3)
+        _check(lib.orbm_unproject_stereo_fisheye_batch(self._h, _p(fp), _p(pts), _p(val), _p(nn), cap, _p(w), B))
+        return w
+
+    def track_project_rig_last_kernel_ms(self):
+        lib.orbm_track_project_rig_last_kernel_ms.restype = C.c_float
+        lib.orbm_track_project_rig_last_kernel_ms.argtypes = [C.c_void_p]
+        return float(lib.orbm_track_project_rig_last_kernel_ms(self._h))
 
     class _TriSide(C.Structure):
         _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("has_mp", C.c_void_p), ("stereo", C.c_void_p), ("x", C.c_void_p),

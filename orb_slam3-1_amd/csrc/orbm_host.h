@@ -91,6 +91,7 @@ struct orbm_matcher {
     float rig_nmp_ms = 0.f;             // ... summed over the segments of the last call
     int rig_nmp_launches = 0;
     KernelTimer tp_timer;               // orbm_frustum_batch / orbm_project_last_batch: their one kernel
+    KernelTimer tpr_timer;              // the host-array rig projections (orbm_frustum_rig_batch and its kin): their one kernel
 
     int ensure(size_t bytes)
     {

@@ -918,6 +918,26 @@ class Matcher:
         _rig_match_argtypes()
         return float(lib.orbm_rig_search_last_kernel_ms(self._h))
 
+    # ---- the same two searches on device arrays (include/orbslam3_hip_rig_track_device.h) ----
+    def search_by_projection_last_rig_batch_device(self, frames, last, batch, th, d_assign, d_occupied, d_n_matches, d_n_slots=None, stream=None):
+        """orbm_search_by_projection_last_rig_batch_device.  frames / last: dicts keyed by the fields of OrbmDeviceRigFrames /
+        OrbmDeviceRigLastPoints (device addresses as ints; scale_factors a host float array; optional fields may be absent).
+        Only enqueues."""
+        _rig_track_device_argtypes()
+        f, keep = device_rig_frames(frames)
+        p = device_rig_points(OrbmDeviceRigLastPoints, last)
+        _check(lib.orbm_search_by_projection_last_rig_batch_device(self._h, C.byref(f), C.byref(p), int(batch), th, int(self.check_ori), d_assign, d_occupied,
+                                                                   d_n_matches, d_n_slots, stream))
+
+    def search_by_projection_rig_batch_device(self, frames, points, batch, th, d_assign, d_occupied, d_n_matches, d_n_slots=None, stream=None,
+                                              far_points=False, th_far=0.0):
+        """orbm_search_by_projection_rig_batch_device.  points: dict keyed by the array fields of OrbmDeviceRigMapPoints and cap; nnratio is
+        the handle's.  Only enqueues."""
+        _rig_track_device_argtypes()
+        f, keep = device_rig_frames(frames)
+        p = device_rig_points(OrbmDeviceRigMapPoints, dict(points, th_far=float(th_far), nnratio=self.nnratio, far_points=int(far_points)))
+        _check(lib.orbm_search_by_projection_rig_batch_device(self._h, C.byref(f), C.byref(p), int(batch), th, d_assign, d_occupied, d_n_matches, d_n_slots, stream))
+
 
     # ---- SearchByBoW and SearchForTriangulation for two-camera fisheye rigs (include/orbslam3_hip_rig_bow.h) ----
     def search_by_bow_rig(self, s):
@@ -1037,6 +1057,65 @@ def rig_search_check(rig, mp=None, last=None, assign=None, occupied=None):
     a = None if mp is None else C.byref(rig_map_points(mp))
     b = None if last is None else C.byref(rig_last_points(last))
     return int(lib.orbm_rig_search_check(r, a, b, _p(assign), _p(occupied)))
+
+
+# ---- include/orbslam3_hip_rig_track_device.h: the rig searches and the rig PoseOptimization on device arrays ----
+class OrbmDeviceRigFrames(C.Structure):
+    _fields_ = [("d_kps_l", C.c_void_p), ("d_desc_l", C.c_void_p), ("d_n_l", C.c_void_p), ("cap_l", C.c_int32),
+                ("d_kps_r", C.c_void_p), ("d_desc_r", C.c_void_p), ("d_n_r", C.c_void_p), ("cap_r", C.c_int32),
+                ("d_left_to_right", C.c_void_p), ("d_right_to_left", C.c_void_p),
+                ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float), ("grid_cols", C.c_int32), ("grid_rows", C.c_int32),
+                ("scale_factors", C.c_void_p), ("n_levels", C.c_int32), ("slot_cap", C.c_int32)]
+
+
+class OrbmDeviceRigLastPoints(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("d_valid", "d_u", "d_v", "d_u_r", "d_v_r", "d_octave", "d_angle", "d_has_obs", "d_desc", "d_n")] + \
+               [("cap", C.c_int32), ("d_level_window", C.c_void_p)]
+
+
+class OrbmDeviceRigMapPoints(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("d_in_view", "d_u", "d_v", "d_pred_level", "d_view_cos", "d_in_view_r", "d_u_r", "d_v_r", "d_pred_level_r",
+                                         "d_view_cos_r", "d_track_depth", "d_bad", "d_has_obs", "d_desc", "d_n")] + \
+               [("cap", C.c_int32), ("th_far", C.c_float), ("nnratio", C.c_float), ("far_points", C.c_int32)]
+
+
+class PoseDeviceRigFrames(C.Structure):
+    _fields_ = [("d_kps_l", C.c_void_p), ("d_n_l", C.c_void_p), ("cap_l", C.c_int32), ("d_kps_r", C.c_void_p), ("d_n_r", C.c_void_p), ("cap_r", C.c_int32),
+                ("d_assign", C.c_void_p), ("slot_cap", C.c_int32), ("d_mp_xyz", C.c_void_p), ("mp_cap", C.c_int32), ("d_pose", C.c_void_p),
+                ("inv_level_sigma2", C.c_void_p), ("n_levels", C.c_int32), ("huber_mono", C.c_double)]
+
+
+def _rig_track_device_argtypes():
+    P, I = C.c_void_p, C.c_int
+    lib.orbm_rig_search_device_check.argtypes = [P, P, P, I]
+    lib.orbm_search_by_projection_last_rig_batch_device.argtypes = [P, P, P, I, C.c_float, I, P, P, P, P, P]
+    lib.orbm_search_by_projection_rig_batch_device.argtypes = [P, P, P, I, C.c_float, P, P, P, P, P]
+    lib.pose_optimize_rig_batch_device.argtypes = [P, P, I, P, P, P, P, P]
+
+
+def device_rig_frames(fr):
+    """dict keyed by the fields of OrbmDeviceRigFrames -> (the struct, the host scale array it points to).  scale_factors is a host
+    float array (n_levels defaults to its length), grid_cols / grid_rows default to 64 x 48, slot_cap to cap_l + cap_r."""
+    sf = None if fr.get("scale_factors") is None else np.ascontiguousarray(fr["scale_factors"], np.float32)
+    v = dict(fr, scale_factors=_ptr(sf))
+    v.setdefault("n_levels", 0 if sf is None else len(sf))
+    v.setdefault("grid_cols", 64); v.setdefault("grid_rows", 48)
+    v.setdefault("slot_cap", int(fr.get("cap_l", 0)) + int(fr.get("cap_r", 0)))
+    return OrbmDeviceRigFrames(*[v.get(k, 0 if t is not C.c_void_p else None) for k, t in OrbmDeviceRigFrames._fields_]), sf
+
+
+def device_rig_points(cls, pts):
+    """dict keyed by the fields of OrbmDeviceRigLastPoints / OrbmDeviceRigMapPoints -> the struct; an absent address is NULL"""
+    return cls(*[pts.get(k, 0 if t is not C.c_void_p else None) for k, t in cls._fields_])
+
+
+def rig_search_device_check(frames, last=None, mp=None, batch=1):
+    """orbm_rig_search_device_check with the arguments as given (dicts or None): the code"""
+    _rig_track_device_argtypes()
+    f = None if frames is None else C.byref(device_rig_frames(frames)[0])
+    a = None if last is None else C.byref(device_rig_points(OrbmDeviceRigLastPoints, last))
+    b = None if mp is None else C.byref(device_rig_points(OrbmDeviceRigMapPoints, mp))
+    return int(lib.orbm_rig_search_device_check(f, a, b, int(batch)))
 
 
 class OrbmBowRigPair(C.Structure):
@@ -1857,6 +1936,17 @@ class PoseSolver:
                              float(cam["fx"]), float(cam["fy"]), float(cam["cx"]), float(cam["cy"]), float(cam.get("bf", 0.0)),
                              float(cam.get("huber_mono", np.float32(np.sqrt(5.991)))), float(cam.get("huber_stereo", np.float32(np.sqrt(7.815)))))
         _check(lib.pose_optimize_batch_device(self._h, C.byref(f), batch, d_pose_out, d_inliers, d_outlier, d_results, stream))
+
+    def optimize_rig_batch_device(self, frames, batch, d_pose_out=None, d_inliers=None, d_outlier=None, d_results=None, stream=None):
+        """pose_optimize_rig_batch_device on a handle with a rig set: frames a dict keyed by the fields of PoseDeviceRigFrames (device
+        addresses as ints; inv_level_sigma2 a host float array; huber_mono defaults to sqrt(5.991) as a float).  Only enqueues."""
+        _rig_track_device_argtypes()
+        isig = np.ascontiguousarray(frames["inv_level_sigma2"], np.float32)
+        v = dict(frames, inv_level_sigma2=isig.ctypes.data)
+        v.setdefault("n_levels", len(isig)); v.setdefault("huber_mono", float(np.float32(np.sqrt(5.991))))
+        v.setdefault("slot_cap", int(frames["cap_l"]) + int(frames["cap_r"]))
+        f = PoseDeviceRigFrames(*[v.get(k) for k, _ in PoseDeviceRigFrames._fields_])
+        _check(lib.pose_optimize_rig_batch_device(self._h, C.byref(f), int(batch), d_pose_out, d_inliers, d_outlier, d_results, stream))
 
     def last_kernel_ms(self):
         lib.pose_last_kernel_ms.restype = C.c_float

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "../../include/orbslam3_hip_rig_track_device.h"
 #include "hip_check.h"
 #include "orbm_host.h"
 
@@ -1662,6 +1663,29 @@ int launch_grid(hipStream_t st, const orbm::ProjArgs* jobs, int n_blocks, size_t
     return ORBX_OK;
 }
 
+// The workspace of the device-resident batch entries grows on demand: their only synchronising step.
+int reserve_workspace(orbm_matcher* m, size_t bytes)
+{
+    if (bytes <= m->ws_cap) return ORBX_OK;
+    if (m->d_ws) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(m->d_ws); }
+    m->d_ws = nullptr; m->ws_cap = 0;
+    ORBX_HIP(hipMalloc((void**)&m->d_ws, bytes + bytes / 4));
+    m->ws_cap = bytes + bytes / 4;
+    return ORBX_OK;
+}
+
+// The caller's host scale factors (at most 32) in m->d_scale; copied only when they differ from the last call's.
+int scale_factors_to_device(orbm_matcher* m, const float* scale_factors, int n_levels, hipStream_t st)
+{
+    if (!m->d_scale) ORBX_HIP(hipMalloc((void**)&m->d_scale, 32 * sizeof(float)));
+    if (std::memcmp(m->h_scale, scale_factors, sizeof(float) * n_levels) != 0) {      // (unchanged between the calls of a stream of frames)
+        ORBX_HIP(hipStreamSynchronize(st));                 // an earlier copy out of h_scale may still be in flight
+        std::memcpy(m->h_scale, scale_factors, sizeof(float) * n_levels);
+        ORBX_HIP(hipMemcpyAsync(m->d_scale, m->h_scale, sizeof(float) * n_levels, hipMemcpyHostToDevice, st));
+    }
+    return ORBX_OK;
+}
+
 // Which projection-search kernel a launch takes and its dynamic LDS.  k_proj_par (64 points at a time) keeps two int tables per
 // feature in LDS; frames too large for them keep the sequential k_proj -- where the entry has it (allow_sequential), else par comes
 // back false.  The frame is staged when all of it fits as well.
@@ -2182,18 +2206,8 @@ static int projection_batch_device(orbm_matcher* m, const OrbmDeviceFrames* cur,
     const size_t o_lf = off; off += al(B * pcap * 4);
     const size_t o_lb = off; off += al(B * pcap * 4);
     const size_t o_jobs = off; off += al(B * sizeof(orbm::ProjArgs));
-    if (off > m->ws_cap) {
-        if (m->d_ws) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(m->d_ws); }
-        m->d_ws = nullptr; m->ws_cap = 0;
-        ORBX_HIP(hipMalloc((void**)&m->d_ws, off + off / 4));
-        m->ws_cap = off + off / 4;
-    }
-    if (!m->d_scale) ORBX_HIP(hipMalloc((void**)&m->d_scale, 32 * sizeof(float)));
-    if (std::memcmp(m->h_scale, cur->scale_factors, sizeof(float) * cur->n_levels) != 0) {      // (unchanged between the calls of a stream of frames)
-        ORBX_HIP(hipStreamSynchronize(st));                 // an earlier copy out of h_scale may still be in flight
-        std::memcpy(m->h_scale, cur->scale_factors, sizeof(float) * cur->n_levels);
-        ORBX_HIP(hipMemcpyAsync(m->d_scale, m->h_scale, sizeof(float) * cur->n_levels, hipMemcpyHostToDevice, st));
-    }
+    if (int r = reserve_workspace(m, off)) return r;
+    if (int r = scale_factors_to_device(m, cur->scale_factors, cur->n_levels, st)) return r;
     const ProjLdsPlan plan = proj_lds_plan(cap, cells, false);         // (this entry has the block-parallel search only)
     if (!plan.par) return fail(ORBX_ERR_CAPACITY, "frames of %zu features exceed the search kernel's LDS tables", cap);
     orbm::ProjDevSetup P;

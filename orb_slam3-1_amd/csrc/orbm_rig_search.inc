@@ -1,5 +1,6 @@
 // orbm_rig_search.inc -- the two tracking searches for a two-camera fisheye rig frame (F.Nleft != -1): kernel, host driver and
-// the C ABI of include/orbslam3_hip_rig_match.h.  Included by orbm_matcher.hip (once, after its host helpers), whose
+// the C ABI of include/orbslam3_hip_rig_match.h, and the device-resident entries of include/orbslam3_hip_rig_track_device.h (k_rig_dev_setup
+// in front of the same k_grid and k_rig).  Included by orbm_matcher.hip (once, after its host helpers), whose
 // search_window, key helpers, rot_bin, three_maxima, ProjFrameDev, k_grid, check_frame, stage_frame and launch helpers it uses as they are.
 // Reference: src/ORBmatcher.cc:43-213 (Frame x map points) and :1676-1887 (last frame).  DESIGN.md 4k.
 namespace orbm {
@@ -271,6 +272,86 @@ __global__ __launch_bounds__(kRigThreads) void k_rig(const RigArgs* __restrict__
     for (int i = tid; i < nl + nr; i += kRigThreads) A.occupied[i] = s_occ[i];
 }
 
+// ---- device-resident batch of the two rig searches (include/orbslam3_hip_rig_track_device.h, DESIGN.md 4p) -----------------------
+// The rig twin of k_proj_dev_setup: the frames are what the two extractors and the rig's stereo step left in HBM.  One workgroup per
+// frame turns both sides' OrbxKeyPoint records into the SoA arrays and writes the frame's RigArgs and the two ProjArgs k_grid reads
+// ON THE DEVICE.  What the host entries refuse, this kernel clamps (the counts never visit the host): counts into [0, cap], partner
+// entries outside [-1, n_other) to -1, levels to the table (-1 stays on the right: no right pass).
+struct RigDevSide { const OrbxKeyPoint* kps; const uint8_t* desc; const int32_t* n; const int32_t* partner; int32_t cap;
+                    float* x; float* y; int32_t* oct; float* ang; int32_t* cell_off; int32_t* cell_feat; int32_t* partner_out; };
+struct RigDevSetup {
+    RigDevSide side[2];
+    // the points: fields of RigArgs, [batch][p_cap]
+    const uint8_t* p_valid; const float* p_u; const float* p_v; const int32_t* p_level; const float* p_vcos;
+    const uint8_t* p_valid_r; const float* p_u_r; const float* p_v_r; const int32_t* p_level_r; const float* p_vcos_r;
+    const float* p_depth; const uint8_t* p_bad; const float* p_angle; const uint8_t* p_desc; const uint8_t* p_obs; const int32_t* p_n; int32_t p_cap;
+    const int32_t* level_window;                        // [batch] or nullptr
+    int32_t* level; int32_t* level_r; uint8_t* obs_ones; int32_t* log_slot; int32_t* log_bin;      // scratch: [batch][p_cap], the logs [batch][2 * p_cap]
+    const float* scale; int32_t n_levels, cols, rows;
+    float min_x, min_y, max_x, max_y, th, th_far, nnratio;
+    int32_t far_points, check_ori, last_mode, slot_cap;
+    int32_t* assign; uint8_t* occupied; int32_t* n_matches; int32_t* n_slots;
+    RigArgs* jobs; ProjArgs* grids;                     // [batch], [2 * batch]: left side of frame b at 2b
+};
+__global__ __launch_bounds__(256) void k_rig_dev_setup(RigDevSetup P)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int n[2];
+    for (int s = 0; s < 2; s++) n[s] = min(max(P.side[s].n[b], 0), P.side[s].cap);
+    const int n_pts = min(max(P.p_n[b], 0), P.p_cap);
+    const size_t cells = (size_t)P.cols * P.rows, prow = (size_t)b * P.p_cap;
+    for (int s = 0; s < 2; s++) {
+        const RigDevSide& S = P.side[s];
+        const size_t row = (size_t)b * S.cap;
+        const int n_other = n[s ^ 1];
+        for (int i = tid; i < n[s]; i += 256) {
+            const OrbxKeyPoint k = S.kps[row + i];
+            S.x[row + i] = k.x; S.y[row + i] = k.y; S.oct[row + i] = k.octave; S.ang[row + i] = k.angle;
+            const int p = S.partner[row + i];
+            S.partner_out[row + i] = (p < -1 || p >= n_other) ? -1 : p;
+        }
+    }
+    for (int i = tid; i < n_pts; i += 256) {
+        P.level[prow + i] = min(max(P.p_level[prow + i], 0), P.n_levels - 1);
+        if (P.level_r) { const int l = P.p_level_r[prow + i]; P.level_r[prow + i] = l == -1 ? -1 : min(max(l, 0), P.n_levels - 1); }
+        if (P.obs_ones) P.obs_ones[prow + i] = 1;
+    }
+    if (tid == 0) {
+        RigArgs A;
+        for (int s = 0; s < 2; s++) {
+            const RigDevSide& S = P.side[s];
+            const size_t row = (size_t)b * S.cap;
+            ProjFrameDev& F = s ? A.R : A.L;
+            F.x = S.x + row; F.y = S.y + row; F.octave = S.oct + row; F.angle = S.ang + row; F.desc = S.desc + row * 32;
+            F.cell_off = S.cell_off + (size_t)b * (cells + 1); F.cell_feat = S.cell_feat + row;
+            F.scale_factors = P.scale;
+            F.min_x = P.min_x; F.min_y = P.min_y; F.max_x = P.max_x; F.max_y = P.max_y;
+            F.winv = (float)P.cols / (P.max_x - P.min_x); F.hinv = (float)P.rows / (P.max_y - P.min_y);        // mfGridElementWidthInv / HeightInv
+            F.n = n[s]; F.cols = P.cols; F.rows = P.rows; F.n_levels = P.n_levels; F.u_right = nullptr;
+            ProjArgs G = ProjArgs{};
+            G.F = F;
+            P.grids[2 * (size_t)b + s] = G;
+        }
+        A.l2r = P.side[0].partner_out + (size_t)b * P.side[0].cap; A.r2l = P.side[1].partner_out + (size_t)b * P.side[1].cap;
+        A.n_pts = n_pts;
+        A.valid = P.p_valid + prow; A.u = P.p_u + prow; A.v = P.p_v + prow; A.level = P.level + prow;
+        A.u_r = P.p_u_r + prow; A.v_r = P.p_v_r + prow;
+        A.view_cos = P.p_vcos ? P.p_vcos + prow : nullptr; A.valid_r = P.p_valid_r ? P.p_valid_r + prow : nullptr;
+        A.level_r = P.level_r ? P.level_r + prow : nullptr; A.view_cos_r = P.p_vcos_r ? P.p_vcos_r + prow : nullptr;
+        A.depth = P.p_depth ? P.p_depth + prow : nullptr; A.bad = P.p_bad ? P.p_bad + prow : nullptr;
+        A.angle = P.p_angle ? P.p_angle + prow : nullptr;
+        A.desc = P.p_desc + prow * 32; A.has_obs = P.p_obs ? P.p_obs + prow : P.obs_ones + prow;
+        A.th = P.th; A.th_far = P.th_far; A.nnratio = P.nnratio; A.far_points = P.far_points; A.check_ori = P.check_ori;
+        A.level_window = P.level_window ? P.level_window[b] : ORBM_LEVELS_AROUND;      // (k_rig takes anything else as _AROUND too)
+        A.last_mode = P.last_mode;
+        A.assign = P.assign + (size_t)b * P.slot_cap; A.occupied = P.occupied + (size_t)b * P.slot_cap;
+        A.log_slot = P.log_slot ? P.log_slot + 2 * prow : nullptr; A.log_bin = P.log_bin ? P.log_bin + 2 * prow : nullptr;
+        A.n_matches = P.n_matches + b;
+        P.jobs[b] = A;
+        if (P.n_slots) P.n_slots[b] = n[0] + n[1];
+    }
+}
+
 }  // namespace orbm
 
 // one rig search problem; host pointers
@@ -428,8 +509,114 @@ static int run_rig_jobs(orbm_matcher* m, RigJob* jobs, int n_jobs, int last_mode
     return ORBX_OK;
 }
 
+// ---- the device-resident entries: checks on the host, then setup + grid + search enqueued on the caller's stream ----
+static int rig_dev_check(const OrbmDeviceRigFrames* f, const OrbmDeviceRigLastPoints* last, const OrbmDeviceRigMapPoints* mp, int batch)
+{
+    if (!f) return fail(ORBX_ERR_ARG, "NULL rig frames");
+    if ((mp != nullptr) == (last != nullptr)) return fail(ORBX_ERR_ARG, "exactly one of the map points and the last-frame points is given");
+    if (batch < 1) return fail(ORBX_ERR_ARG, "batch %d", batch);
+    if (!f->d_kps_l || !f->d_desc_l || !f->d_n_l || !f->d_kps_r || !f->d_desc_r || !f->d_n_r || !f->d_left_to_right || !f->d_right_to_left || !f->scale_factors)
+        return fail(ORBX_ERR_ARG, "NULL rig frame arrays");
+    if (f->cap_l < 1 || f->cap_r < 1) return fail(ORBX_ERR_ARG, "capacities %d + %d", f->cap_l, f->cap_r);
+    if ((int64_t)f->slot_cap < (int64_t)f->cap_l + f->cap_r) return fail(ORBX_ERR_ARG, "slot_cap %d below cap_l + cap_r = %d + %d", f->slot_cap, f->cap_l, f->cap_r);
+    if (f->n_levels < 1 || f->n_levels > 32) return fail(ORBX_ERR_ARG, "n_levels %d outside [1, 32]", f->n_levels);
+    if (f->grid_cols < 1 || f->grid_rows < 1 || f->grid_cols * (int64_t)f->grid_rows > (1 << 20) || !(f->max_x > f->min_x) || !(f->max_y > f->min_y)) return fail(ORBX_ERR_ARG, "bad frame grid");
+    if (last) {
+        if (!last->d_valid || !last->d_u || !last->d_v || !last->d_u_r || !last->d_v_r || !last->d_octave || !last->d_desc || !last->d_n) return fail(ORBX_ERR_ARG, "NULL last-frame point arrays");
+        if (last->cap < 1) return fail(ORBX_ERR_ARG, "point capacity %d", last->cap);
+    } else {
+        if (!mp->d_in_view || !mp->d_u || !mp->d_v || !mp->d_pred_level || !mp->d_view_cos || !mp->d_in_view_r || !mp->d_u_r || !mp->d_v_r || !mp->d_pred_level_r ||
+            !mp->d_view_cos_r || !mp->d_track_depth || !mp->d_bad || !mp->d_has_obs || !mp->d_desc || !mp->d_n) return fail(ORBX_ERR_ARG, "NULL map point arrays");
+        if (mp->cap < 1) return fail(ORBX_ERR_ARG, "point capacity %d", mp->cap);
+    }
+    if (f->cap_l > 8192 || f->cap_r > 8192) return fail(ORBX_ERR_CAPACITY, "at most 8192 features per side (the grid is sorted in LDS)");
+    if ((size_t)f->cap_l + f->cap_r + 256 > dynamic_lds_budget<orbm::k_rig<true>, orbm::k_rig<false>>())
+        return fail(ORBX_ERR_CAPACITY, "rig frames of %d + %d features exceed the LDS occupancy table", f->cap_l, f->cap_r);
+    return ORBX_OK;
+}
+
+static int rig_search_batch_device(orbm_matcher* m, const OrbmDeviceRigFrames* f, const OrbmDeviceRigLastPoints* last, const OrbmDeviceRigMapPoints* mp, int batch,
+                                   float th, int check_ori, int32_t* d_assign, uint8_t* d_occupied, int32_t* d_n_matches, int32_t* d_n_slots, void* stream)
+{
+    if (int e = rig_dev_check(f, last, mp, batch)) return e;
+    if (!d_assign || !d_occupied || !d_n_matches) return fail(ORBX_ERR_ARG, "NULL assign / occupied / n_matches");
+    if (last && check_ori && !last->d_angle) return fail(ORBX_ERR_ARG, "check_orientation needs d_angle");
+    if (!m) return fail(ORBX_ERR_ARG, "NULL matcher");
+    ORBX_HIP(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = (size_t)batch, cap[2] = {(size_t)f->cap_l, (size_t)f->cap_r}, pcap = (size_t)(last ? last->cap : mp->cap);
+    const int ncell = f->grid_cols * f->grid_rows;
+    const bool ones = last && !last->d_has_obs;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    size_t o_x[2], o_y[2], o_oct[2], o_ang[2], o_coff[2], o_cfeat[2], o_partner[2];
+    for (int s = 0; s < 2; s++) {
+        o_x[s] = take(B * cap[s] * 4); o_y[s] = take(B * cap[s] * 4); o_oct[s] = take(B * cap[s] * 4); o_ang[s] = take(B * cap[s] * 4);
+        o_coff[s] = take(B * ((size_t)ncell + 1) * 4); o_cfeat[s] = take(B * cap[s] * 4); o_partner[s] = take(B * cap[s] * 4);
+    }
+    const size_t o_level = take(B * pcap * 4), o_level_r = take(mp ? B * pcap * 4 : 0), o_ones = take(ones ? B * pcap : 0);
+    const size_t o_ls = take(last ? 2 * B * pcap * 4 : 0), o_lb = take(last ? 2 * B * pcap * 4 : 0);
+    const size_t o_jobs = take(B * sizeof(orbm::RigArgs)), o_grids = take(2 * B * sizeof(orbm::ProjArgs));
+    if (int e = reserve_workspace(m, off)) return e;
+    if (int e = scale_factors_to_device(m, f->scale_factors, f->n_levels, st)) return e;
+    uint8_t* w = m->d_ws;
+    orbm::RigDevSetup P;
+    std::memset(&P, 0, sizeof(P));
+    const OrbxKeyPoint* kps[2] = {f->d_kps_l, f->d_kps_r}; const uint8_t* desc[2] = {f->d_desc_l, f->d_desc_r};
+    const int32_t* n[2] = {f->d_n_l, f->d_n_r}; const int32_t* partner[2] = {f->d_left_to_right, f->d_right_to_left};
+    for (int s = 0; s < 2; s++)
+        P.side[s] = orbm::RigDevSide{kps[s], desc[s], n[s], partner[s], (int32_t)cap[s], (float*)(w + o_x[s]), (float*)(w + o_y[s]), (int32_t*)(w + o_oct[s]),
+                                     (float*)(w + o_ang[s]), (int32_t*)(w + o_coff[s]), (int32_t*)(w + o_cfeat[s]), (int32_t*)(w + o_partner[s])};
+    if (last) {
+        P.p_valid = last->d_valid; P.p_u = last->d_u; P.p_v = last->d_v; P.p_u_r = last->d_u_r; P.p_v_r = last->d_v_r; P.p_level = last->d_octave;
+        P.p_angle = last->d_angle; P.p_desc = last->d_desc; P.p_obs = last->d_has_obs; P.p_n = last->d_n; P.level_window = last->d_level_window;
+        P.log_slot = (int32_t*)(w + o_ls); P.log_bin = (int32_t*)(w + o_lb);
+        if (ones) P.obs_ones = w + o_ones;
+    } else {
+        P.p_valid = mp->d_in_view; P.p_u = mp->d_u; P.p_v = mp->d_v; P.p_level = mp->d_pred_level; P.p_vcos = mp->d_view_cos;
+        P.p_valid_r = mp->d_in_view_r; P.p_u_r = mp->d_u_r; P.p_v_r = mp->d_v_r; P.p_level_r = mp->d_pred_level_r; P.p_vcos_r = mp->d_view_cos_r;
+        P.p_depth = mp->d_track_depth; P.p_bad = mp->d_bad; P.p_desc = mp->d_desc; P.p_obs = mp->d_has_obs; P.p_n = mp->d_n;
+        P.level_r = (int32_t*)(w + o_level_r);
+        P.th_far = mp->th_far; P.nnratio = mp->nnratio; P.far_points = mp->far_points;
+    }
+    P.p_cap = (int32_t)pcap; P.level = (int32_t*)(w + o_level);
+    P.scale = m->d_scale; P.n_levels = f->n_levels; P.cols = f->grid_cols; P.rows = f->grid_rows;
+    P.min_x = f->min_x; P.min_y = f->min_y; P.max_x = f->max_x; P.max_y = f->max_y; P.th = th;
+    P.check_ori = last && check_ori ? 1 : 0; P.last_mode = last ? 1 : 0; P.slot_cap = f->slot_cap;
+    P.assign = d_assign; P.occupied = d_occupied; P.n_matches = d_n_matches; P.n_slots = d_n_slots;
+    P.jobs = (orbm::RigArgs*)(w + o_jobs); P.grids = (orbm::ProjArgs*)(w + o_grids);
+    // staged or not by the capacities, with run_rig_jobs' arithmetic over the counts: every frame of the batch fits, or none is staged
+    const size_t slots = cap[0] + cap[1];
+    const size_t lds_occ = std::max((size_t)64, (slots + 63) & ~(size_t)63);
+    const size_t lds_full = ((slots + 15) & ~(size_t)15) + orbm::rig_side_bytes((int)cap[0], ncell) + orbm::rig_side_bytes((int)cap[1], ncell);
+    const bool stage = lds_full <= dynamic_lds_budget<orbm::k_rig<true>, orbm::k_rig<false>>();
+    hipLaunchKernelGGL(orbm::k_rig_dev_setup, dim3(batch), dim3(256), 0, st, P);
+    if (int e = launch_grid(st, P.grids, 2 * batch, std::max(cap[0], cap[1]))) return e;
+    if (int e = launch_staged(orbm::k_rig<true>, orbm::k_rig<false>, stage, batch, orbm::kRigThreads, stage ? lds_full : lds_occ, st, (const orbm::RigArgs*)P.jobs)) return e;
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
 
 extern "C" {
+
+int orbm_rig_search_device_check(const OrbmDeviceRigFrames* frames, const OrbmDeviceRigLastPoints* last, const OrbmDeviceRigMapPoints* mp, int batch)
+{
+    return rig_dev_check(frames, last, mp, batch);
+}
+
+int orbm_search_by_projection_last_rig_batch_device(orbm_matcher* m, const OrbmDeviceRigFrames* frames, const OrbmDeviceRigLastPoints* last, int batch,
+        float th, int check_orientation, int32_t* d_assign, uint8_t* d_occupied, int32_t* d_n_matches, int32_t* d_n_slots, void* stream)
+{
+    return rig_search_batch_device(m, frames, last, nullptr, batch, th, check_orientation, d_assign, d_occupied, d_n_matches, d_n_slots, stream);
+}
+
+int orbm_search_by_projection_rig_batch_device(orbm_matcher* m, const OrbmDeviceRigFrames* frames, const OrbmDeviceRigMapPoints* points, int batch,
+        float th, int32_t* d_assign, uint8_t* d_occupied, int32_t* d_n_matches, int32_t* d_n_slots, void* stream)
+{
+    return rig_search_batch_device(m, frames, nullptr, points, batch, th, 0, d_assign, d_occupied, d_n_matches, d_n_slots, stream);
+}
 
 int orbm_rig_search_check(const OrbmRigFrame* rig, const OrbmRigMapPoints* mp, const OrbmRigLastPoints* last, const int32_t* assign, const uint8_t* occupied)
 {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/orbslam3_hip.h"
+#include "../../include/orbslam3_hip_rig_track_device.h"
 #include "batch_stage.h"
 #include "camera_kb8.h"
 #include "camera_kb8_host.h"
@@ -267,6 +268,72 @@ __global__ __launch_bounds__(256) void k_pose_gather(GatherArgs A)
     }
 }
 
+// ---- device-resident entry for two-camera fisheye rig frames (pose_optimize_rig_batch_device) ----
+struct RigGatherArgs {
+    const OrbxKeyPoint* kps_l; const int32_t* n_l; const OrbxKeyPoint* kps_r; const int32_t* n_r; const int32_t* assign; const float* mp_xyz; const double* pose;
+    int32_t cap_l, cap_r, slot_cap, mp_cap, n_levels;
+    float inv_sigma2[16];
+    double huber_mono;
+    uint8_t* slots; size_t slot_bytes;              // per frame, as GatherArgs
+    size_t o_obs, o_w, o_err, o_idx, o_st, o_outl, o_act;
+    ProblemDev* problems; PoseResult* results;
+};
+
+// k_pose_gather over the SLOTS of a rig frame (mvpMapPoints[0 .. Nleft+Nright), right slot j at n_l + j): a slot below n_l that holds
+// a point becomes a left edge observing mvKeys[s], any other a right edge (ORBX_EDGE_RIGHT) observing mvKeysRight[s - n_l] -- the order
+// in which Optimizer::PoseOptimization walks a rig frame (:935-990)
+__global__ __launch_bounds__(256) void k_pose_gather_rig(RigGatherArgs A)
+{
+    __shared__ int s_wave[4];
+    __shared__ int s_base;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint8_t* slot = A.slots + (size_t)b * A.slot_bytes;
+    double* Xw = (double*)slot; double* obs = (double*)(slot + A.o_obs); double* w = (double*)(slot + A.o_w);
+    int32_t* idx = (int32_t*)(slot + A.o_idx); uint8_t* st = slot + A.o_st;
+    const int nl = min(max(A.n_l[b], 0), A.cap_l), nr = min(max(A.n_r[b], 0), A.cap_r), n = nl + nr;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        int j = -1;
+        if (i < n) { j = A.assign[(size_t)b * A.slot_cap + i]; if (j >= A.mp_cap) j = -1; }
+        const bool has = j >= 0;
+        const unsigned long long bal = __ballot(has);
+        const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int before = s_base;
+        for (int q = 0; q < wave; q++) before += s_wave[q];
+        if (has) {
+            const int e = before + in_wave;
+            const bool right = i >= nl;
+            const OrbxKeyPoint k = right ? A.kps_r[(size_t)b * A.cap_r + (i - nl)] : A.kps_l[(size_t)b * A.cap_l + i];
+            const float* X = A.mp_xyz + 3 * ((size_t)b * A.mp_cap + j);
+            Xw[3 * (size_t)e] = (double)X[0]; Xw[3 * (size_t)e + 1] = (double)X[1]; Xw[3 * (size_t)e + 2] = (double)X[2];
+            obs[3 * (size_t)e] = (double)k.x; obs[3 * (size_t)e + 1] = (double)k.y; obs[3 * (size_t)e + 2] = -1.0;
+            const int oc = min(max(k.octave, 0), A.n_levels - 1);
+            w[e] = (double)A.inv_sigma2[oc];
+            st[e] = right ? ORBX_EDGE_RIGHT : 0;
+            idx[e] = i;
+        }
+        __syncthreads();
+        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ProblemDev P;
+        for (int k = 0; k < 4; k++) P.q[k] = A.pose[7 * (size_t)b + k];
+        for (int k = 0; k < 3; k++) P.t[k] = A.pose[7 * (size_t)b + 4 + k];
+        P.n = s_base;
+        P.Xw = Xw; P.obs = obs; P.w = w; P.stereo = st;
+        P.fx = P.fy = P.cx = P.cy = P.bf = 0.0;          // the rig's cameras are the kernel's argument
+        P.huber_mono = A.huber_mono; P.huber_stereo = 0.0;
+        P.err = (double*)(slot + A.o_err); P.outlier = slot + A.o_outl; P.active = slot + A.o_act;
+        P.result = A.results + b;
+        A.problems[b] = P;
+    }
+}
+
 // results back into per-feature / per-frame arrays: mvbOutlier[i] (0 for a feature without a map point), the pose, the return value
 __global__ __launch_bounds__(256) void k_pose_scatter(const ProblemDev* __restrict__ problems, const uint8_t* __restrict__ slots, size_t slot_bytes, size_t o_idx,
                                                       int cap, double* __restrict__ pose_out, int32_t* __restrict__ inliers, uint8_t* __restrict__ outlier,
@@ -332,6 +399,39 @@ inline void pose_launch(bool stereo, bool many_edges, int n, hipStream_t st, con
     }
     if (many_edges) hipLaunchKernelGGL((poseopt::k_pose_opt<false, 4, CamT...>), dim3(n), dim3(256), 0, st, p, cam...);
     else hipLaunchKernelGGL((poseopt::k_pose_opt<false, 2, CamT...>), dim3(n), dim3(256), 0, st, p, cam...);
+}
+
+// The arena of the device-resident entries, sized by the capacity of a frame (features, or slots of a rig frame): per frame the edge
+// slots [Xw | obs | w | err | idx | stereo | outl | act], then the problem descriptors and the results.  Fills the layout fields of A
+// (GatherArgs / RigGatherArgs).  The arena grows on demand: the only synchronising step (first call / larger batch).
+template <class Args>
+int device_arena(pose_solver* s, size_t cap, int batch, Args& A)
+{
+    stage::Cursor slot;                 // Xw at 0
+    slot.take(24 * cap);
+    A.o_obs = slot.take(24 * cap);
+    A.o_w = slot.take(8 * cap);
+    A.o_err = slot.take(24 * cap);
+    A.o_idx = slot.take(4 * cap);
+    A.o_st = slot.take(cap);
+    A.o_outl = slot.take(cap);
+    A.o_act = slot.take(cap);
+    A.slot_bytes = slot.pos;
+    stage::Cursor arena;
+    arena.take(A.slot_bytes * (size_t)batch);
+    const size_t prob_off = arena.take(sizeof(poseopt::ProblemDev) * (size_t)batch);
+    const size_t res_off = arena.take(sizeof(PoseResult) * (size_t)batch);
+    const size_t total = arena.pos;
+    if (total > s->dev_cap) {
+        if (s->d_dev) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(s->d_dev); }
+        s->d_dev = nullptr; s->dev_cap = 0;
+        ORBX_HIP(hipMalloc((void**)&s->d_dev, total));
+        s->dev_cap = total;
+    }
+    A.slots = s->d_dev;
+    A.problems = (poseopt::ProblemDev*)(s->d_dev + prob_off);
+    A.results = (PoseResult*)(s->d_dev + res_off);
+    return ORBX_OK;
 }
 
 int optimize_batch(pose_solver* s, const PoseProblem* problems, int n_problems, PoseResult* results, uint8_t* const* outlier_out)
@@ -432,41 +532,43 @@ int pose_optimize_batch_device(pose_solver* s, const PoseDeviceFrames* f, int ba
     if (f->cap < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap / mp_cap / n_levels");
     ORBX_HIP(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t cap = (size_t)f->cap;
     poseopt::GatherArgs A;
     std::memset(&A, 0, sizeof(A));
-    stage::Cursor slot;                 // Xw at 0
-    slot.take(24 * cap);
-    A.o_obs = slot.take(24 * cap);
-    A.o_w = slot.take(8 * cap);
-    A.o_err = slot.take(24 * cap);
-    A.o_idx = slot.take(4 * cap);
-    A.o_st = slot.take(cap);
-    A.o_outl = slot.take(cap);
-    A.o_act = slot.take(cap);
-    A.slot_bytes = slot.pos;
-    stage::Cursor arena;
-    arena.take(A.slot_bytes * (size_t)batch);
-    const size_t prob_off = arena.take(sizeof(poseopt::ProblemDev) * (size_t)batch);
-    const size_t res_off = arena.take(sizeof(PoseResult) * (size_t)batch);
-    const size_t total = arena.pos;
-    if (total > s->dev_cap) {           // (first call / larger batch: the only synchronising step)
-        if (s->d_dev) { ORBX_HIP(hipDeviceSynchronize()); (void)hipFree(s->d_dev); }
-        s->d_dev = nullptr; s->dev_cap = 0;
-        ORBX_HIP(hipMalloc((void**)&s->d_dev, total));
-        s->dev_cap = total;
-    }
+    if (int r = device_arena(s, (size_t)f->cap, batch, A)) return r;
     A.kps = f->d_kps; A.n_kps = f->d_n; A.u_right = f->d_u_right; A.assign = f->d_assign; A.mp_xyz = f->d_mp_xyz; A.pose = f->d_pose;
     A.cap = f->cap; A.mp_cap = f->mp_cap; A.n_levels = f->n_levels;
     for (int l = 0; l < f->n_levels; l++) A.inv_sigma2[l] = f->inv_level_sigma2[l];
     A.fx = f->fx; A.fy = f->fy; A.cx = f->cx; A.cy = f->cy; A.bf = f->bf; A.huber_mono = f->huber_mono; A.huber_stereo = f->huber_stereo;
-    A.slots = s->d_dev;
-    A.problems = (poseopt::ProblemDev*)(s->d_dev + prob_off);
-    A.results = (PoseResult*)(s->d_dev + res_off);
     hipLaunchKernelGGL(poseopt::k_pose_gather, dim3(batch), dim3(256), 0, st, A);
     pose_launch(f->d_u_right != nullptr, f->cap > 512, batch, st, (const poseopt::ProblemDev*)A.problems);
     hipLaunchKernelGGL(poseopt::k_pose_scatter, dim3(batch), dim3(256), 0, st, (const poseopt::ProblemDev*)A.problems, (const uint8_t*)s->d_dev, A.slot_bytes, A.o_idx,
                        f->cap, d_pose_out, d_inliers, d_outlier, d_results);
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+int pose_optimize_rig_batch_device(pose_solver* s, const PoseDeviceRigFrames* f, int batch, double* d_pose_out, int32_t* d_inliers,
+                                   uint8_t* d_outlier, PoseResult* d_results, void* stream)
+{
+    if (!f || batch < 1) return fail(ORBX_ERR_ARG, "bad arguments");
+    if (!f->d_kps_l || !f->d_n_l || !f->d_kps_r || !f->d_n_r || !f->d_assign || !f->d_mp_xyz || !f->d_pose || !f->inv_level_sigma2) return fail(ORBX_ERR_ARG, "NULL arrays");
+    if (f->cap_l < 1 || f->cap_r < 1 || f->mp_cap < 1 || f->n_levels < 1 || f->n_levels > 16) return fail(ORBX_ERR_ARG, "bad cap_l / cap_r / mp_cap / n_levels");
+    if ((int64_t)f->slot_cap < (int64_t)f->cap_l + f->cap_r) return fail(ORBX_ERR_ARG, "slot_cap %d below cap_l + cap_r = %d + %d", f->slot_cap, f->cap_l, f->cap_r);
+    if (!s) return fail(ORBX_ERR_ARG, "NULL solver");
+    if (s->camera.kind != kb8::CameraChoice::kRig) return fail(ORBX_ERR_ARG, "pose_optimize_rig_batch_device needs a handle with a KannalaBrandt8 rig (pose_set_rig_kb8)");
+    ORBX_HIP(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    poseopt::RigGatherArgs A;
+    std::memset(&A, 0, sizeof(A));
+    if (int r = device_arena(s, (size_t)f->slot_cap, batch, A)) return r;
+    A.kps_l = f->d_kps_l; A.n_l = f->d_n_l; A.kps_r = f->d_kps_r; A.n_r = f->d_n_r; A.assign = f->d_assign; A.mp_xyz = f->d_mp_xyz; A.pose = f->d_pose;
+    A.cap_l = f->cap_l; A.cap_r = f->cap_r; A.slot_cap = f->slot_cap; A.mp_cap = f->mp_cap; A.n_levels = f->n_levels;
+    for (int l = 0; l < f->n_levels; l++) A.inv_sigma2[l] = f->inv_level_sigma2[l];
+    A.huber_mono = f->huber_mono;
+    hipLaunchKernelGGL(poseopt::k_pose_gather_rig, dim3(batch), dim3(256), 0, st, A);
+    kb8::with_camera(s->camera, [&](const auto&... cam) { pose_launch(false, f->slot_cap > 512, batch, st, (const poseopt::ProblemDev*)A.problems, policy(cam)...); });
+    hipLaunchKernelGGL(poseopt::k_pose_scatter, dim3(batch), dim3(256), 0, st, (const poseopt::ProblemDev*)A.problems, (const uint8_t*)s->d_dev, A.slot_bytes, A.o_idx,
+                       f->slot_cap, d_pose_out, d_inliers, d_outlier, d_results);
     ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
